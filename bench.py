@@ -13,18 +13,25 @@ generator is SURVEY.md section 8d's), fp64, x and y resident in HBM.  The matrix
 is FIXED and sharded by 1-D row blocks, so scaling is "strong".
 
 Metric (BASELINE.json): GFLOP/s = 2*nnz_full / t, the reference driver's own
-formula (bench/bench_spmv_mmf.cpp:168), with the achieved algorithmic GB/s of
-the dominant kernel against the 8 TB/s HBM3E peak in "roofline", and the CPU
-oracle (the reference's OpenMP conflict-free path, restated) timed on this
-box's host cores in "cpu_baseline" (rank 0, N = 1 only).
+formula (bench/bench_spmv_mmf.cpp:168); ms_per_step = wall time of the K timed
+steps / K.  A plain run sets up, warms up, times the K steps and prints the line.
+With --full the line also carries the achieved algorithmic GB/s of the dominant
+kernel against the 8 TB/s HBM3E peak in "roofline", and the CPU oracle (the
+reference's OpenMP conflict-free path, restated) timed on the host's cores in
+"cpu_baseline" (rank 0, N = 1 only), and the timed result is checked against
+the general CSR kernel.
+
+--dump-outputs DIR writes y of the last timed step as DIR/y.npy (y_rank<r>.npy
+per rank for N > 1; a fixed, seeded sample when it would exceed 64 MB).  The
+inputs are seeded: two runs with the same arguments multiply the same A and x.
 
 `python bench.py --gpus N` WITHOUT a torchrun environment (WORLD_SIZE unset) starts
 the N ranks itself: the parent never touches HIP, it spawns
 `python -m torch.distributed.run --nproc-per-node N ... bench.py <same args>` as a
 child process and exits with its code.  At N > 1 the line also carries
-`exchange_forms`: ms_per_step of the three forms of the off-block exchange (none =
-mirrored shards, all_to_all, reduce_scatter = the RCCL collective the north-star
-names), measured in the same run.
+`exchange_forms` (--full): ms_per_step of the three forms of the off-block exchange
+(none = mirrored shards, all_to_all, reduce_scatter = the RCCL collective the
+north-star names), measured in the same run.
 
 Only the cpu_baseline leg imports oracle/ -- as the reported baseline, never as
 the thing measured.
@@ -83,8 +90,41 @@ def parse():
                     help="untimed SpMVs before the W warm-up steps (set-up: clocks and power in the state "
                          "of a long run)")
     ap.add_argument("--event-every", type=int, default=4,
-                    help="bracket the tile kernel with HIP events on every n-th timed step")
-    return ap.parse_args()
+                    help="--full: bracket the tile kernel with HIP events on every n-th timed step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the kernel "
+                         "timings and roofline, the in-kernel clock, the self-check against the "
+                         "general CSR kernel, the cpu_baseline legs and (N > 1) the other exchange "
+                         "forms.  A plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write y of the last step as DIR/<name>.npy "
+                         "(y.npy; y_rank<r>.npy for N > 1), at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """write {name: tensor} as directory/<name>.npy (float32 / float64 as computed).  When
+    the arrays together exceed `limit` bytes, each is replaced by the same fixed, seeded
+    sample of its entries (sorted positions drawn with numpy's default_rng(0)), so two runs
+    with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if total > limit and a.size:
+            keep = max(1, int(a.size * limit // total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
 
 
 def host_cpus():
@@ -195,7 +235,7 @@ def bench_csr(args, cfs, lib, n, rp, ci, va, x_host, nnz_full, dev, t_dt, data_k
         return e
     K = args.steps
     every = max(1, min(args.event_every, K // 10 if K >= 10 else 1))
-    sampled = [i for i in range(K) if i % every == 0]
+    sampled = [i for i in range(K) if i % every == 0] if args.full else []
     ev0 = {i: new_event() for i in sampled}
     ev1 = {i: new_event() for i in sampled}
     t_pre = time.perf_counter()
@@ -216,6 +256,30 @@ def bench_csr(args, cfs, lib, n, rp, ci, va, x_host, nnz_full, dev, t_dt, data_k
             step()
     torch.cuda.synchronize()
     ms_per_step = (time.perf_counter() - t0) / K * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": y})
+    s_ = va.itemsize
+    form, meas = C.c_int(), C.c_int()
+    _lib.check(lib.cfs_hip_csr_kernel_form(A._h, C.byref(form), C.byref(meas)))
+    alg = int(nnz_full * (4 + s_) + n * (4 + 2 * s_))
+    out = {
+        "metric": f"fp{s_ * 8} general CSR SpMV GFLOP/s", "value": round(2.0 * nnz_full / (ms_per_step * 1e-3) / 1e9, 2),
+        "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": args.dtype, "data": data_kind,
+        "config": {"workload": f"{source}: n={n}, nnz_full={nnz_full}, general CSR SpMV y=Ax over every "
+                               f"stored entry (Format::csr)", "format": "csr",
+                   "algorithmic_bytes_per_spmv": alg,
+                   "effective_GBps_whole_step": round(alg / (ms_per_step * 1e-3) / 1e9, 1),
+                   "preproc_s": round(preproc, 2),
+                   "kernel_form": ("wave" if form.value == 1 else "block") +
+                                  (" (pinned by CFS_HIP_CSR_KERNEL)" if os.environ.get("CFS_HIP_CSR_KERNEL")
+                                   else " (the faster of the two forms, measured at the first SpMV)")},
+    }
+    if not args.full:
+        A.close()
+        print(json.dumps(out), flush=True)
+        return
     ms = C.c_float()
     tot = 0.0
     for i in sampled:
@@ -234,11 +298,7 @@ def bench_csr(args, cfs, lib, n, rp, ci, va, x_host, nnz_full, dev, t_dt, data_k
     S.close()
     if not err < (1e-9 if args.dtype == "f64" else 1e-3):
         raise SystemExit(f"self-check failed: max scaled |y_csr - y_sss| = {err}")
-    s_ = va.itemsize
-    form, meas = C.c_int(), C.c_int()
-    _lib.check(lib.cfs_hip_csr_kernel_form(A._h, C.byref(form), C.byref(meas)))
     kname = "cfs_csr_wave_kernel" if form.value == 1 else "cfs_csr_stream_kernel"
-    alg = int(nnz_full * (4 + s_) + n * (4 + 2 * s_))
     achieved = alg / (kern_ms * 1e-3) / 1e9
     streamed, narrow = C.c_int64(), C.c_int64()
     _lib.check(lib.cfs_hip_csr_stats(A._h, C.byref(streamed), C.byref(narrow)))
@@ -257,27 +317,13 @@ def bench_csr(args, cfs, lib, n, rp, ci, va, x_host, nnz_full, dev, t_dt, data_k
                                               "another run, not taken inside this run"}
     except Exception:
         traffic = None
-    out = {
-        "metric": f"fp{s_ * 8} general CSR SpMV GFLOP/s", "value": round(2.0 * nnz_full / (ms_per_step * 1e-3) / 1e9, 2),
-        "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": args.dtype, "data": data_kind,
-        "config": {"workload": f"{source}: n={n}, nnz_full={nnz_full}, general CSR SpMV y=Ax over every "
-                               f"stored entry (Format::csr)", "format": "csr",
-                   "algorithmic_bytes_per_spmv": alg,
-                   "effective_GBps_whole_step": round(alg / (ms_per_step * 1e-3) / 1e9, 1),
-                   "preproc_s": round(preproc, 2),
-                   "kernel_form": ("wave" if form.value == 1 else "block") +
-                                  (" (pinned by CFS_HIP_CSR_KERNEL)" if os.environ.get("CFS_HIP_CSR_KERNEL")
-                                   else " (the faster of the two forms, measured at the first SpMV)")},
-        "roofline": {"bound": "hbm", "kernel": kname,
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "kernel_ms": round(kern_ms, 5), "kernel_samples": len(sampled),
-                     "algorithmic_bytes_per_launch": alg,
-                     "bytes_streamed_by_format": streamed.value,
-                     "nnz_with_16bit_columns": narrow.value},
-    }
+    out["roofline"] = {"bound": "hbm", "kernel": kname,
+                       "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                       "kernel_ms": round(kern_ms, 5), "kernel_samples": len(sampled),
+                       "algorithmic_bytes_per_launch": alg,
+                       "bytes_streamed_by_format": streamed.value,
+                       "nnz_with_16bit_columns": narrow.value}
     r_ = out["roofline"]
     if traffic:
         wire = traffic / (kern_ms * 1e-3) / 1e9
@@ -531,9 +577,9 @@ def main():
     K = args.steps
     # the tile kernel is bracketed by HIP events on every n-th step of the timed
     # region only: an event between two kernels costs ~1-2 us of launch gap
-    # (a short run -- the driver's --steps 20 -- still gets ten samples)
+    # (a short run -- the driver's --steps 20 -- still gets ten samples); --full only
     every = max(1, min(args.event_every, K // 10 if K >= 10 else 1))
-    sampled = [i for i in range(K) if i % every == 0]
+    sampled = [i for i in range(K) if i % every == 0] if args.full else []
     ev0 = {i: new_event() for i in sampled}
     ev1 = {i: new_event() for i in sampled}
 
@@ -596,85 +642,92 @@ def main():
         elapsed = float(tmax.item())
     ms_per_step = elapsed / K * 1e3
 
-    # ---- roofline: average duration of the tile kernel over the timed region ----
-    tile_total = 0.0
-    ms = C.c_float()
-    for i in sampled:
-        _lib.check(lib.cfs_hip_event_elapsed_ms(ev0[i], ev1[i], C.byref(ms)))
-        tile_total += ms.value
-    tile_ms = tile_total / len(sampled)
-    for e in list(ev0.values()) + list(ev1.values()):
-        lib.cfs_hip_event_destroy(e)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y" if dist is None else f"y_rank{rank}": y},
+                     DUMP_LIMIT_BYTES // N)
 
-    # cross-check with the kernel's own clock (developer timeline build of the same
-    # launch: first workgroup start -> last workgroup end, 100 MHz wall clock).  A HIP
-    # event bracket also holds the dispatch latency around the kernel (~2-3 us: 2 % of
-    # a 110 us launch, 20 % of a 13 us one); rocprofv3's kernel duration is the
-    # counterpart of this number.
-    tl_ms = None
-    try:
-        tbuf = np.zeros(8 * 8192, dtype=np.uint64)
-        ng = C.c_int()
-        spans = []
-        for _ in range(5):
-            _lib.check(lib.cfs_hip_sym_debug_timeline(A._h, y.data_ptr(), x.data_ptr(),
-                                                      tbuf.ctypes.data, tbuf.size, C.byref(ng)))
-            tt = tbuf[:ng.value * 8].reshape(-1, 8).astype(np.int64)
-            spans.append((tt[:, 3].max() - tt[:, 0].min()) / 100.0 * 1e-3)
-        tl_ms = float(np.median(spans))
-        phases(3 if local_only else 1 | 4)  # y of a complete step again for the self-check
-        if not local_only:
-            sh.finish(y, x)
-        torch.cuda.synchronize()
-    except Exception:
+    # everything below the line's headline (kernel timings, roofline, self-check, the
+    # cpu_baseline legs, the other exchange forms) is measured with --full only
+    if args.full:
+        # ---- roofline: average duration of the tile kernel over the timed region ----
+        tile_total = 0.0
+        ms = C.c_float()
+        for i in sampled:
+            _lib.check(lib.cfs_hip_event_elapsed_ms(ev0[i], ev1[i], C.byref(ms)))
+            tile_total += ms.value
+        tile_ms = tile_total / len(sampled)
+        for e in list(ev0.values()) + list(ev1.values()):
+            lib.cfs_hip_event_destroy(e)
+
+        # cross-check with the kernel's own clock (developer timeline build of the same
+        # launch: first workgroup start -> last workgroup end, 100 MHz wall clock).  A HIP
+        # event bracket also holds the dispatch latency around the kernel (~2-3 us: 2 % of
+        # a 110 us launch, 20 % of a 13 us one); rocprofv3's kernel duration is the
+        # counterpart of this number.
         tl_ms = None
-
-    alg_bytes = st["bytes_algorithmic"]  # this rank's rows: nnz_low*(4+s) + rows*(4+3s)
-    achieved = alg_bytes / (tile_ms * 1e-3) / 1e9
-    # HBM bytes per launch from the PMC passes (profiles/hbm_traffic.json, written by
-    # tools/profile_round.sh): only quoted when the entry was measured on the SAME
-    # schedule that ran here (bytes the format streams, tiles, window, block) -- a
-    # stale entry reads null, never a number of another kernel
-    traffic = None
-    traffic_source = None
-    tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if os.path.exists(tpath):
         try:
-            with open(tpath) as f:
-                tj = json.load(f)
-            key = f"{args.matrix}:{args.scale}:{args.dtype}:{N}"
-            if args.shard_of > 1:
-                key += f":shard{args.shard_rank}of{args.shard_of}"
-            # (tune() keeps the faster of two window shapes, and boxes differ: a workload
-            # may hold one entry per schedule it was profiled on)
-            ents = tj.get(key, [])
-            for ent in (ents if isinstance(ents, list) else [ents]):
-                if all(ent.get(k) == st[k] for k in ("bytes_streamed", "lds_bytes", "block_threads")):
-                    traffic = ent.get("hbm_bytes_per_launch")
-                    traffic_source = {
-                        "file": "profiles/hbm_traffic.json", "key": key,
-                        "matched_on": {k: st[k] for k in ("bytes_streamed", "lds_bytes",
-                                                          "block_threads")},
-                        "measured_by": ent.get("source", "tools/profile_round.sh: two rocprofv3 "
-                                               "--pmc passes of this command (FETCH_SIZE, "
-                                               "WRITE_SIZE), 2 x FETCH + WRITE per launch"),
-                        "note": "a committed measurement of the SAME schedule on another run, "
-                                "not taken inside this run"}
+            tbuf = np.zeros(8 * 8192, dtype=np.uint64)
+            ng = C.c_int()
+            spans = []
+            for _ in range(5):
+                _lib.check(lib.cfs_hip_sym_debug_timeline(A._h, y.data_ptr(), x.data_ptr(),
+                                                          tbuf.ctypes.data, tbuf.size, C.byref(ng)))
+                tt = tbuf[:ng.value * 8].reshape(-1, 8).astype(np.int64)
+                spans.append((tt[:, 3].max() - tt[:, 0].min()) / 100.0 * 1e-3)
+            tl_ms = float(np.median(spans))
+            phases(3 if local_only else 1 | 4)  # y of a complete step again for the self-check
+            if not local_only:
+                sh.finish(y, x)
+            torch.cuda.synchronize()
         except Exception:
-            traffic = None
+            tl_ms = None
 
-    # quick self-check of the timed result against the plain-CSR row sums (GPU CSR
-    # kernel, not the oracle): guards against timing a broken kernel
-    G = cfs.CsrMatrix(n, n, rp, ci, va)
-    y2 = torch.empty(n, dtype=t_dt, device=dev)
-    G.dense_vector_multiply(y2, x)
-    torch.cuda.synchronize()
-    y2 = y2[st["row_begin"]:st["row_end"]]
-    scale = torch.maximum(y2.abs(), torch.tensor(1.0, dtype=t_dt, device=dev))
-    err = float(((y - y2).abs() / scale).max().item()) if rows else 0.0
-    G.close()
-    if not err < (1e-9 if args.dtype == "f64" else 1e-3):
-        raise SystemExit(f"rank {rank}: self-check failed: max scaled |y - y_csr| = {err}")
+        alg_bytes = st["bytes_algorithmic"]  # this rank's rows: nnz_low*(4+s) + rows*(4+3s)
+        achieved = alg_bytes / (tile_ms * 1e-3) / 1e9
+        # HBM bytes per launch from the PMC passes (profiles/hbm_traffic.json, written by
+        # tools/profile_round.sh): only quoted when the entry was measured on the SAME
+        # schedule that ran here (bytes the format streams, tiles, window, block) -- a
+        # stale entry reads null, never a number of another kernel
+        traffic = None
+        traffic_source = None
+        tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                with open(tpath) as f:
+                    tj = json.load(f)
+                key = f"{args.matrix}:{args.scale}:{args.dtype}:{N}"
+                if args.shard_of > 1:
+                    key += f":shard{args.shard_rank}of{args.shard_of}"
+                # (tune() keeps the faster of two window shapes, and machines differ: a workload
+                # may hold one entry per schedule it was profiled on)
+                ents = tj.get(key, [])
+                for ent in (ents if isinstance(ents, list) else [ents]):
+                    if all(ent.get(k) == st[k] for k in ("bytes_streamed", "lds_bytes", "block_threads")):
+                        traffic = ent.get("hbm_bytes_per_launch")
+                        traffic_source = {
+                            "file": "profiles/hbm_traffic.json", "key": key,
+                            "matched_on": {k: st[k] for k in ("bytes_streamed", "lds_bytes",
+                                                              "block_threads")},
+                            "measured_by": ent.get("source", "tools/profile_round.sh: two rocprofv3 "
+                                                   "--pmc passes of this command (FETCH_SIZE, "
+                                                   "WRITE_SIZE), 2 x FETCH + WRITE per launch"),
+                            "note": "a committed measurement of the SAME schedule on another run, "
+                                    "not taken inside this run"}
+            except Exception:
+                traffic = None
+
+        # quick self-check of the timed result against the plain-CSR row sums (GPU CSR
+        # kernel, not the oracle): guards against timing a broken kernel
+        G = cfs.CsrMatrix(n, n, rp, ci, va)
+        y2 = torch.empty(n, dtype=t_dt, device=dev)
+        G.dense_vector_multiply(y2, x)
+        torch.cuda.synchronize()
+        y2 = y2[st["row_begin"]:st["row_end"]]
+        scale = torch.maximum(y2.abs(), torch.tensor(1.0, dtype=t_dt, device=dev))
+        err = float(((y - y2).abs() / scale).max().item()) if rows else 0.0
+        G.close()
+        if not err < (1e-9 if args.dtype == "f64" else 1e-3):
+            raise SystemExit(f"rank {rank}: self-check failed: max scaled |y - y_csr| = {err}")
 
     # what one step multiplies: the whole matrix, or (--shard-of) the rows of one block
     shard_mode = args.shard_of > 1 and sh is None
@@ -711,7 +764,9 @@ def main():
                 "block_threads": st["block_threads"], "preproc_s": round(preproc, 2),
                 "tuning": args.tuning, "flags": args.flags,
             },
-            "roofline": {
+        }
+        if args.full:
+            out["roofline"] = {
                 "bound": "hbm", "kernel": "cfs_sym_tile_kernel",
                 "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
@@ -734,10 +789,9 @@ def main():
                                                  HBM_ACHIEVABLE_GBS, 4) if traffic else None),
                 "achievable_GBps": HBM_ACHIEVABLE_GBS,
                 "bytes_streamed_by_format": int(st["bytes_streamed"]),
-            },
-        }
+            }
 
-    if rank == 0 and N == 1 and not args.no_cpu_baseline and not shard_mode:
+    if args.full and rank == 0 and N == 1 and not args.no_cpu_baseline and not shard_mode:
         try:
             out["cpu_baseline"] = cpu_baseline(n, rp, ci, va, x_host, nnz_full, args.cpu_loops,
                                                ncpus, args.cpu_bind)
@@ -748,7 +802,7 @@ def main():
     # Measured LAST, under a watchdog: whatever happens to them (a collective that
     # hangs on some stack), the ONE line of the contract is printed -- and a hang ends
     # the run with a non-zero exit code (run_guarded).
-    if sh is not None and not args.no_exchange_forms:
+    if args.full and sh is not None and not args.no_exchange_forms:
         def on_timeout():
             if rank == 0:
                 out["exchange_forms"] = {args.exchange: round(ms_per_step, 5),

@@ -139,9 +139,43 @@ def exact_y(nrows, ncols, rc, val, x):
     return np.array([float(v) for v in y]), np.array([float(v) for v in ya])
 
 
+def stream_digest(rowcol, val64):
+    """sha256 of the one-based (row, col) int32 stream and of the fp64 values, in stored order"""
+    import hashlib
+    return (hashlib.sha256(np.ascontiguousarray(rowcol, np.int32).tobytes()).hexdigest(),
+            hashlib.sha256(np.ascontiguousarray(val64, np.float64).tobytes()).hexdigest())
+
+
+def record_reference(ref):
+    """the reference-derived records that let the tests run where the reference is absent
+    (lists of names and digests only, no reference source text):
+      reference_headers.txt          the headers the reference installs (include/**/*.hpp)
+      synth_pdb1HYS_0.05.ref.json    what the reference reader returns for the pdb1HYS
+                                     stand-in at scale 0.05: header + stream digests"""
+    import json
+    import tempfile
+    sys.path.insert(0, ROOT)
+    from cfs_spmv_amd import synth
+    inc = os.path.join(ref, "include")
+    hdrs = sorted(os.path.relpath(os.path.join(dp, f), inc)
+                  for dp, _, fs in os.walk(inc) for f in fs if f.endswith(".hpp"))
+    write(os.path.join(HERE, "reference_headers.txt"), "".join(h + "\n" for h in hdrs))
+    with tempfile.TemporaryDirectory() as td:
+        n, rp, ci, va, _ = synth.generate("pdb1HYS", 0.05)
+        p = os.path.join(td, "m.mtx")
+        synth.write_mtx(p, n, rp, ci, va)
+        h, rc, v = ref_dump(p, "f64")
+    d_rc, d_val = stream_digest(rc, v)
+    write(os.path.join(HERE, "synth_pdb1HYS_0.05.ref.json"),
+          json.dumps({"matrix": "pdb1HYS", "scale": 0.05, "header": [int(t) for t in h],
+                      "rowcol_sha256": d_rc, "val64_sha256": d_val}, indent=1) + "\n")
+
+
 def main():
     if not os.path.exists(DUMP):
         sys.exit("oracle/_ref/ref_mmf_dump missing: run `make -C oracle` with /root/reference present")
+    if "--reference-records" in sys.argv:
+        return record_reference(sys.argv[sys.argv.index("--reference-records") + 1])
     for name, text in make_files().items():
         path = os.path.join(HERE, name)
         write(path, text)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile: run on the GPU box (gpurun).  Produces, under gpurun_out/<tag>/:
-#   bench.json                 the contract line of `python bench.py <args>`
+#   bench.json                 the contract line of `python bench.py --full <args>`
 #   kernel_stats.csv           rocprofv3 --kernel-trace --stats of the same command
 #   pmc_fetch.csv, pmc_write.csv   separate --pmc passes (never combined with tracing)
 #   hbm_traffic.json           per-launch HBM bytes of the kernels:
@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 tag=$1; shift
 out=gpurun_out/$tag
 mkdir -p $out
-python3 bench.py "$@" > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -5 $out/bench.err; exit 1; }
+python3 bench.py --full "$@" > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -5 $out/bench.err; exit 1; }
 # the profiler passes run the window shape tune() kept in the bench run above (the two
 # shapes are within a few per cent of each other; under the profiler the clock may say otherwise)
 export CFS_HIP_SHAPE=$(python3 -c "import json,sys; print(json.load(open('$out/bench.json'))['config'].get('block_threads', 0))")
