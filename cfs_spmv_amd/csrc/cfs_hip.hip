@@ -1033,8 +1033,13 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
     combine_ok = P.chained_packets * 10 >= P.lane_packets && P.chained_packets > 0;
     combine = combine_ok && P.stream_len * (int64_t)sizeof(V) + P.slot_len * 2 >= (int64_t)200 * 1000 * 1000;
     combine_forced = false;
-    if (const char *e = getenv("CFS_HIP_COMBINE")) // developer knob: 2 = the combining kernel whatever the size
+    // developer knob CFS_HIP_COMBINE (read only when set; a forced choice skips choose_kernel):
+    // 0 = no sibling chains in the plan (to_opts), 2 = the combining kernel whatever the size
+    // (when the plan has enough chains), 3 = the chained plan but the plain kernel
+    if (const char *e = getenv("CFS_HIP_COMBINE")) {
       if (atoi(e) == 2) combine = combine_ok, combine_forced = true;
+      if (atoi(e) == 3) combine = false, combine_forced = true;
+    }
     mirror_entries = P.mirror_entries;
     stream_len = P.stream_len;
     slot_len = P.slot_len;
@@ -1066,6 +1071,9 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
     lds_bytes = (size_t)P.lds_slots * (size_t)cfs_plan::slot_lds_bytes<V>(P.deterministic);
     // the stream is cacheable across SpMVs only if it fits the 256 MiB Infinity Cache
     nt_stream = (stream_len * (int64_t)sizeof(V) + slot_len * 2) > (int64_t)240 * 1024 * 1024;
+    // developer knob CFS_HIP_NT=0|1 (read only when set): cacheable / non-temporal stream
+    // loads whatever the size, so that tests reach both instantiations at small sizes
+    if (const char *e = getenv("CFS_HIP_NT")) nt_stream = atoi(e) != 0;
     if (getenv("CFS_PLAN_VERBOSE"))
       fprintf(stderr, "[cfs_hip] handle: %s-built, %d tiles, window %d slots, %d threads x %d per CU, sibling chains %lld of %lld "
               "lane-packets -> %s kernel, %s stream loads\n", device_built ? "device" : "host", (int)P.tiles.size(),
@@ -1074,26 +1082,52 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
     return 0;
   }
 
-  // the instantiation of the tile kernel this handle launches
-  template <int BLOCK> static const void *pick_kernel(int mode, bool nt, bool offb, int u, bool det, bool comb) {
+  // the template arguments of the tile-kernel instantiation this handle launches
+  // (cfs_sym_tile_kernel<V, BLOCK, MODE, NT, OFFB, U, DET, COMB>): tile_kernel() launches
+  // what this says and cfs_hip_sym_debug_kernel reports it
+  struct TileVariant {
+    int block, mode;
+    bool nt, offb;
+    int u; // 3, 6 or kSlotsPerThread: the smallest bucket that covers the window
+    bool det, comb;
+  };
+  TileVariant tile_variant() const {
+    constexpr int UM = cfs_plan::kSlotsPerThread;
+    TileVariant t;
+    t.block = P.block_threads == 256 ? 256 : (P.block_threads == 512 ? 512 : 1024);
+    t.det = t.block != 256 && P.deterministic; // (to_opts: deterministic = 512 or 1 024 threads)
+    t.mode = !t.det && ablate_mode >= 1 && ablate_mode <= 4 ? ablate_mode : 0;
+    if (t.mode != 0) { // timing-only ablations: one instantiation each
+      t.nt = true, t.offb = false, t.u = UM, t.comb = true;
+      return t;
+    }
+    const int u = (P.lds_slots + P.block_threads - 1) / P.block_threads;
+    t.nt = nt_stream;
+    t.offb = offblock;
+    t.u = u <= 3 ? 3 : (u <= 6 ? 6 : UM);
+    t.comb = t.det || combine; // the deterministic instantiations always combine siblings
+    return t;
+  }
+  template <int BLOCK> static const void *pick_kernel(const TileVariant &t) {
 #define CFS_K(M, N, O, UU) ((const void *)cfs_sym_tile_kernel<V, BLOCK, M, N, O, UU>)
 #define CFS_KP(N, O, UU) ((const void *)cfs_sym_tile_kernel<V, BLOCK, 0, N, O, UU, false, false>)
 #define CFS_KDET(N, O, UU) ((const void *)cfs_sym_tile_kernel<V, (BLOCK < 512 ? 512 : BLOCK), 0, N, O, UU, true>)
     constexpr int UM = cfs_plan::kSlotsPerThread;
-    switch (mode) {
+    switch (t.mode) {
     case 1: return CFS_K(1, true, false, UM);
     case 2: return CFS_K(2, true, false, UM);
     case 3: return CFS_K(3, true, false, UM);
     case 4: return CFS_K(4, true, false, UM);
     default: break;
     }
-    if (det) { // CFS_HIP_FLAG_DETERMINISTIC: 512 or 1 024 threads (to_opts)
+    const int ui = t.u == 3 ? 0 : (t.u == 6 ? 1 : 2);
+    if (t.det) { // CFS_HIP_FLAG_DETERMINISTIC: 512 or 1 024 threads (to_opts)
       static const void *const dtab[2][2][3] = {
           {{CFS_KDET(false, false, 3), CFS_KDET(false, false, 6), CFS_KDET(false, false, UM)},
            {CFS_KDET(false, true, 3), CFS_KDET(false, true, 6), CFS_KDET(false, true, UM)}},
           {{CFS_KDET(true, false, 3), CFS_KDET(true, false, 6), CFS_KDET(true, false, UM)},
            {CFS_KDET(true, true, 3), CFS_KDET(true, true, 6), CFS_KDET(true, true, UM)}}};
-      return dtab[nt ? 1 : 0][offb ? 1 : 0][u <= 3 ? 0 : (u <= 6 ? 1 : 2)];
+      return dtab[t.nt ? 1 : 0][t.offb ? 1 : 0][ui];
     }
     static const void *const tab[2][2][3] = {
         {{CFS_K(0, false, false, 3), CFS_K(0, false, false, 6), CFS_K(0, false, false, UM)},
@@ -1108,16 +1142,14 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
 #undef CFS_K
 #undef CFS_KP
 #undef CFS_KDET
-    return (comb ? tab : ptab)[nt ? 1 : 0][offb ? 1 : 0][u <= 3 ? 0 : (u <= 6 ? 1 : 2)];
+    return (t.comb ? tab : ptab)[t.nt ? 1 : 0][t.offb ? 1 : 0][ui];
   }
-  const void *tile_kernel() {
-    const int u = (P.lds_slots + P.block_threads - 1) / P.block_threads;
-    switch (P.block_threads) {
-    case 256: return pick_kernel<256>(ablate_mode, nt_stream, offblock, u, false, combine);
-    case 512: return pick_kernel<512>(P.deterministic ? 0 : ablate_mode, nt_stream, offblock, u,
-                                      P.deterministic, combine);
-    default: return pick_kernel<1024>(P.deterministic ? 0 : ablate_mode, nt_stream, offblock, u, P.deterministic,
-                                      combine);
+  const void *tile_kernel() const {
+    const TileVariant t = tile_variant();
+    switch (t.block) {
+    case 256: return pick_kernel<256>(t);
+    case 512: return pick_kernel<512>(t);
+    default: return pick_kernel<1024>(t);
     }
   }
   int launch_tiles(V *y, const V *x, hipStream_t st) {
@@ -2468,6 +2500,18 @@ template <typename V> static int sym_digest(SymMatrix<V> *m, unsigned long long 
   }
   w[CFS_HIP_DIGEST_WORDS - 1] = m->device_built ? 1ull : 0ull;
   return 0;
+}
+template <typename V> static int sym_kernel(const SymMatrix<V> *m, int *w) {
+  const auto t = m->tile_variant();
+  const int v[CFS_HIP_KERNEL_WORDS] = {(int)sizeof(V), t.block, t.mode, t.nt, t.offb, t.u, t.det, t.comb};
+  for (int i = 0; i < CFS_HIP_KERNEL_WORDS; i++) w[i] = v[i];
+  return 0;
+}
+int cfs_hip_sym_debug_kernel(cfs_hip_sym_t h, int *words, int capacity_words) {
+  if (!h || !words || capacity_words < CFS_HIP_KERNEL_WORDS) return set_err(CFS_HIP_ERR_ARG, "bad argument");
+  if (auto *d = dynamic_cast<SymMatrix<double> *>(h)) return sym_kernel<double>(d, words);
+  if (auto *f = dynamic_cast<SymMatrix<float> *>(h)) return sym_kernel<float>(f, words);
+  return set_err(CFS_HIP_ERR_ARG, "no single tile kernel for a multi-device handle");
 }
 int cfs_hip_sym_debug_plan_note(cfs_hip_sym_t h, char *buf, int capacity) {
   if (!h || !buf || capacity < 1) return set_err(CFS_HIP_ERR_ARG, "bad argument");

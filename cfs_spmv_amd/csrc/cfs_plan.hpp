@@ -386,7 +386,8 @@ template <typename V> inline ChunkLayout chunk_layout(int rows, const Options &o
   int max_slots = opt.max_slots > 0 ? opt.max_slots : kDefaultSlots;
   if (opt.deterministic && opt.max_slots <= 0) // still two workgroups per CU
     max_slots = std::min(max_slots, (160 * 1024 / 2 - 64) / slot_bytes / 64 * 64);
-  max_slots = std::min(max_slots, (160 * 1024 - 64) / slot_bytes); // 16 B static LDS (tickets)
+  // 16 B static LDS (tickets); whole 64-slot steps: finish() rounds the window UP to 64
+  max_slots = std::min(max_slots, (160 * 1024 - 64) / slot_bytes / 64 * 64);
   max_slots = std::min(max_slots, 65536);
   max_slots = std::min(max_slots, kSlotsPerThread * std::max(L.block, 64));
   L.max_slots = std::max(max_slots, 64);

@@ -54,6 +54,8 @@ def _stream_ptr(stream=None):
 FLAG_SHARD_EXCHANGE = 64  # include/cfs_hip.h: CFS_HIP_FLAG_SHARD_EXCHANGE
 FLAG_KEEP_VALUE_MAP = 2048  # CFS_HIP_FLAG_KEEP_VALUE_MAP
 FLAG_HOST_PLAN = 4096  # CFS_HIP_FLAG_HOST_PLAN: build the schedule with the host builder
+# CFS_HIP_KERNEL_WORDS: cfs_sym_tile_kernel<V, BLOCK, MODE, NT, OFFB, U, DET, COMB> ("value_bytes" = sizeof(V))
+KERNEL_NAMES = ["value_bytes", "block", "mode", "nt", "offb", "u", "det", "comb"]
 DIGEST_WORDS = 28  # CFS_HIP_DIGEST_WORDS
 DIGEST_NAMES = ["tiles", "gfirst", "group_range", "slot_col", "rowinfo", "diag", "slice_meta", "leadlane",
                 "vals", "slots", "cvals", "crows", "ccols", "fold_rec", "fold_idx", "val_map", "cval_map",
@@ -181,6 +183,13 @@ class SymMatrix:
         w = (C.c_ulonglong * DIGEST_WORDS)()
         _lib.check(_lib.load().cfs_hip_sym_debug_digest(self._h, w, DIGEST_WORDS))
         return dict(zip(DIGEST_NAMES, [int(v) for v in w]))
+
+    def kernel_variant(self):
+        """developer / test: template arguments of the tile-kernel instantiation this handle
+        launches (cfs_hip_sym_debug_kernel)"""
+        w = (C.c_int * len(KERNEL_NAMES))()
+        _lib.check(_lib.load().cfs_hip_sym_debug_kernel(self._h, w, len(KERNEL_NAMES)))
+        return dict(zip(KERNEL_NAMES, [int(v) for v in w]))
 
     def plan_note(self):
         """why the device builder handed the schedule to the host builder ('' = it built it)"""

@@ -380,6 +380,15 @@ int cfs_hip_sym_debug_group_features(cfs_hip_sym_t h, long long *out, int capaci
  * on the GPU.                                                                           */
 #define CFS_HIP_DIGEST_WORDS 28
 int cfs_hip_sym_debug_digest(cfs_hip_sym_t h, unsigned long long *words, int capacity_words);
+/* developer / test: the instantiation of the tile kernel this handle launches,
+ * cfs_sym_tile_kernel<V, BLOCK, MODE, NT, OFFB, U, DET, COMB>, as CFS_HIP_KERNEL_WORDS ints:
+ * [0] value bytes (8 / 4), [1] BLOCK (256, 512, 1024), [2] MODE (0 = product, 1-4 = the
+ * timing-only ablations), [3] NT (non-temporal stream loads), [4] OFFB (mirrored shard:
+ * one-sided slots), [5] U (3, 6 or 10 slots a thread), [6] DET (fixed-point sums), [7] COMB
+ * (sibling-combined atomics; 1 for every deterministic handle).  The launch reads the same
+ * choice.  A multi-device handle returns CFS_HIP_ERR_ARG.                                  */
+#define CFS_HIP_KERNEL_WORDS 8
+int cfs_hip_sym_debug_kernel(cfs_hip_sym_t h, int *words, int capacity_words);
 /* why the device builder handed this handle's schedule to the host builder ("" = it built it) */
 int cfs_hip_sym_debug_plan_note(cfs_hip_sym_t h, char *buf, int capacity);
 

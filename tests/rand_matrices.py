@@ -64,3 +64,49 @@ def random_matrix(rng, n, kind):
         A.eliminate_zeros()
     A.sort_indices()
     return n, A
+
+
+def scattered_mesh(n_nodes, links, seed):
+    """mesh nodes of 1-4 unknowns, each coupled (dense dof x dof blocks) to a random number of
+    random earlier nodes, 0 .. 2 * links: the unknowns of a node are sibling rows with the same
+    columns, row lengths run from none to many packets, and -- no locality -- under
+    CFS_HIP_FLAG_NO_REORDER every coupling brings new halo slots, so tiles are cut full.
+    Signed values; returns (n, rowptr, colind, values) of the full symmetric CSR."""
+    rng = np.random.default_rng(seed)
+    dof = rng.integers(1, 5, n_nodes)
+    node = np.repeat(np.arange(n_nodes), dof)
+    n = int(node.size)
+    k = rng.integers(0, 2 * links + 1, n_nodes)
+    k[0] = 0
+    a = np.repeat(np.arange(n_nodes), k)
+    b = (rng.random(a.size) * a).astype(np.int64)
+    N = sp.coo_matrix((np.ones(a.size), (a, b)), shape=(n_nodes, n_nodes)) + sp.identity(n_nodes)
+    E = sp.coo_matrix((np.ones(n), (np.arange(n), node)), shape=(n, n_nodes)).tocsr()
+    L = sp.tril(E @ N.tocsr() @ E.T, k=-1).tocsr()
+    L.sort_indices()
+    L.data = rng.uniform(-1, 1, L.nnz)
+    L.data[L.data == 0] = 0.5
+    A = (L + L.T + sp.diags(rng.uniform(1, 2, n))).tocsr()
+    A.sort_indices()
+    return n, A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data
+
+
+def banded_mesh(n_nodes, links=3, dof=3):
+    """a chain of mesh nodes of `dof` unknowns, each coupled (dense dof x dof blocks) to the
+    `links` nodes before it: locality, so a tile holds as many rows as its window has slots,
+    sibling rows of `dof` lanes, and rows of links * dof + 0 .. dof - 1 lower entries (9 .. 11:
+    two packets and 1 .. 3 COO leftovers each).  Signed values; (n, rowptr, colind, values)."""
+    rng = np.random.default_rng(n_nodes)
+    n = n_nodes * dof
+    a = np.repeat(np.arange(n_nodes), links)
+    b = a - np.tile(np.arange(1, links + 1), n_nodes)
+    keep = b >= 0
+    N = sp.coo_matrix((np.ones(int(keep.sum())), (a[keep], b[keep])), shape=(n_nodes, n_nodes)) + sp.identity(n_nodes)
+    E = sp.coo_matrix((np.ones(n), (np.arange(n), np.arange(n) // dof)), shape=(n, n_nodes)).tocsr()
+    L = sp.tril(E @ N.tocsr() @ E.T, k=-1).tocsr()
+    L.sort_indices()
+    L.data = rng.uniform(-1, 1, L.nnz)
+    L.data[L.data == 0] = 0.5
+    A = (L + L.T + sp.diags(rng.uniform(1, 2, n))).tocsr()
+    A.sort_indices()
+    return n, A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data

@@ -145,7 +145,61 @@ def test_schedule_options(slots, block, flags):
     n, rp, ci, va, low = synth.generate("pwtk", 0.05)
     rep = cfs.plan_check(n, rp, ci, va, options=cfs.make_options(slots, 0, block, flags))
     assert rep["mismatches"] == 0 and rep["decoded"] == low
-    assert rep["lds_slots"] <= max(64, (min(slots, 10 * block) + 63) // 64 * 64)
+    # the window is what was asked for (rounded to 64) but never more than the LDS holds
+    assert rep["lds_slots"] <= max(64, min((min(slots, 10 * block) + 63) // 64 * 64, window_cap(16, block)))
+    assert rep["lds_slots"] * 16 <= LDS_DYNAMIC
+
+
+# dynamic LDS the tile kernel may use (raise_lds_limit: 160 KiB minus the static ticket counter)
+LDS_DYNAMIC = 160 * 1024 - 64
+
+
+def slot_bytes(dtype, det):
+    """cfs_plan::slot_lds_bytes: x window in V, y window fp64 (deterministic: two words + exponent)"""
+    return np.dtype(dtype).itemsize + (18 if det else 8)
+
+
+def window_cap(sb, block):
+    """the largest window a plan may use: whole 64-slot steps of the LDS, at most 10 slots a thread"""
+    return min(LDS_DYNAMIC // sb // 64 * 64, 10 * block)
+
+
+@pytest.fixture(scope="module")
+def halo_heavy():
+    """random columns, ~30 lower entries a row, no locality: under CFS_HIP_FLAG_NO_REORDER every
+    row brings about its length in new halo slots, so a chunk (~n / 256 rows) needs several
+    windows and its tiles are cut full -- to within one row of max_slots"""
+    import scipy.sparse as sp
+    n, per = 200000, 30
+    rng = np.random.default_rng(7)
+    r = np.repeat(np.arange(1, n), per)
+    c = (rng.random(r.size) * r).astype(np.int64)
+    L = sp.coo_matrix((rng.uniform(-1, 1, r.size), (r, c)), shape=(n, n)).tocsr()
+    L.sum_duplicates()
+    A = (L + L.T + sp.identity(n) * 2.0).tocsr()
+    A.sort_indices()
+    return n, A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data, L.nnz
+
+
+# (deterministic handles run 512 or 1 024 threads: 256 is raised to 512, the case of 512)
+@pytest.mark.parametrize("dtype,det,block", [(dt, det, b) for dt in (np.float64, np.float32)
+                                             for det in (False, True) for b in (256, 512, 1024)
+                                             if not (det and b == 256)])
+@pytest.mark.parametrize("which", ["cap", "cap-1", "above"])
+def test_window_fits_lds_at_the_slot_cap(halo_heavy, dtype, det, block, which):
+    """an explicit max_slots at (or above) what the LDS holds: the window the plan rounds up to
+    whole 64-slot steps must still fit the dynamic LDS the kernel is given"""
+    n, rp, ci, va, low = halo_heavy
+    sb = slot_bytes(dtype, det)
+    raw = min(LDS_DYNAMIC // sb, 10 * block)  # the capacity in slots, not rounded
+    slots = {"cap": raw, "cap-1": raw - 1, "above": 1 << 16}[which]
+    flags = 8 | (1024 if det else 0)  # CFS_HIP_FLAG_NO_REORDER (| CFS_HIP_FLAG_DETERMINISTIC)
+    rep = cfs.plan_check(n, rp, ci, va.astype(dtype), options=cfs.make_options(slots, 0, block, flags))
+    assert rep["mismatches"] == 0 and rep["decoded"] == low
+    # the matrix reaches the edge: some tile is within 64 slots of the cap
+    assert rep["lds_slots"] > min(raw, slots) - 64, rep
+    assert rep["lds_slots"] * sb <= LDS_DYNAMIC, (rep["lds_slots"], sb)
+    assert rep["lds_slots"] <= window_cap(sb, block)
 
 
 @pytest.mark.parametrize("n,avg,band", [(1, 0, None), (2, 1, None), (63, 2, None), (64, 5, None),

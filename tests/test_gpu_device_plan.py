@@ -66,6 +66,12 @@ def test_device_schedule_equals_host_schedule_on_stand_ins(name, scale, dtype):
     tol = 1e-12 if dtype == np.float64 else 1e-5
     scale_ = torch.maximum(yh.abs(), torch.tensor(1.0, dtype=x.dtype, device="cuda"))
     assert float(((yd - yh).abs() / scale_).max()) <= 10 * tol
+    # ... and both agree with the long-double oracle
+    from conftest import scaled_err
+    from oracle import oracle
+    y_ld, absrow = oracle.csr_spmv_ld(n, rp, ci, va, x.cpu().numpy())
+    assert scaled_err(yd.cpu().numpy(), y_ld, absrow) <= tol, D.kernel_variant()
+    assert scaled_err(yh.cpu().numpy(), y_ld, absrow) <= tol, H.kernel_variant()
     D.close()
     H.close()
 

@@ -1,5 +1,6 @@
-"""Parity at BASELINE.json's FULL sizes through size-independent properties
-(the CPU oracle would need minutes per case here):
+"""Parity at BASELINE.json's FULL sizes: y against the long-double oracle (oracle.csr_spmv_ld,
+OpenMP: seconds even for Queen_4147 -- the restated SymOracle would need minutes), and
+size-independent properties:
 
   * agreement with the general-CSR GPU kernel on the full (both-triangle) matrix
     -- an independent code path (cfs_csr_stream_kernel) and an independent
@@ -80,6 +81,13 @@ def test_full_size_properties(name, dtype, mode):
     y, yz = sym(x), sym(z)
     torch.cuda.synchronize()
     assert torch.isfinite(y).all() and torch.isfinite(yz).all()
+    # (0) the long-double oracle on the host copy of x; the message names the instantiation
+    from conftest import scaled_err
+    from oracle import oracle
+    variant = A.kernel_variant() if mode != "x4" else "multi-device"
+    y_ld, absrow = oracle.csr_spmv_ld(n, rp, ci, va, x.cpu().numpy())
+    e_ld = scaled_err(y.cpu().numpy(), y_ld, absrow)
+    assert e_ld <= tol, (e_ld, variant)
     scale = torch.maximum(csr(Gabs, x.abs()), y.abs()).clamp_min(1e-300).double()
     # (1) independent kernel + independent storage
     y_csr = csr(G, x)
