@@ -55,7 +55,7 @@ SYMBOLS = [
     "cfs_hip_comm_allgather", "cfs_hip_comm_wait_consumed", "cfs_hip_sym_num_gpus", "cfs_hip_sym_multi_set_xmode", "cfs_hip_sym_multi_devices", "cfs_hip_sym_balanced_splits", "cfs_hip_sym_destroy", "cfs_hip_sym_update_values_f64", "cfs_hip_sym_update_values_f32", "cfs_hip_sym_spmv",
     "cfs_hip_sym_spmv_async", "cfs_hip_sym_cg", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
     "cfs_hip_sym_shard_set_recv", "cfs_hip_sym_spmv_local_async",
-    "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
+    "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_fold_lists", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
     "cfs_hip_sym_plan_check_f32", "cfs_hip_sym_plan_send_info_f64", "cfs_hip_csr_create_f64", "cfs_hip_csr_create_f32",
     "cfs_hip_csr_spmv", "cfs_hip_csr_spmv_async", "cfs_hip_csr_destroy", "cfs_hip_csr_kernel_form", "cfs_hip_csr_stats",
     "cfs_hip_event_create", "cfs_hip_event_record", "cfs_hip_event_elapsed_ms",
@@ -136,6 +136,8 @@ def load():
         lib.cfs_hip_sym_debug_plan_note.argtypes = [vp, C.c_char_p, C.c_int]
     if hasattr(lib, "cfs_hip_sym_debug_kernel"):
         lib.cfs_hip_sym_debug_kernel.argtypes = [vp, ip, C.c_int]
+    if hasattr(lib, "cfs_hip_sym_debug_fold_lists"):
+        lib.cfs_hip_sym_debug_fold_lists.argtypes = [vp, C.c_int, vp, vp, C.c_int, ip]
     lib.cfs_hip_sym_debug_group_features.argtypes = [vp, vp, C.c_int, ip]
     lib.cfs_hip_csr_spmv.argtypes = [vp, vp, vp]
     lib.cfs_hip_csr_spmv_async.argtypes = [vp, vp, vp, vp]

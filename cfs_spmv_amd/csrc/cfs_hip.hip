@@ -2525,6 +2525,41 @@ int cfs_hip_sym_debug_digest(cfs_hip_sym_t h, unsigned long long *words, int cap
   if (auto *f = dynamic_cast<SymMatrix<float> *>(h)) return sym_digest<float>(f, words);
   return set_err(CFS_HIP_ERR_ARG, "no digest for a multi-device handle");
 }
+// developer / test: the lists cfs_fold_kernel walks, decoded from the device arrays (cfs_hip.h)
+template <typename V>
+static int sym_fold_lists(SymMatrix<V> *m, int which, int *dst, int *len, int capacity, int *count) {
+  DeviceGuard g(m->device);
+  HIPCHK(hipDeviceSynchronize());
+  const DevBuf &rb = which ? m->rfold_rec : m->fold_rec, &ib = which ? m->rfold_idx : m->fold_idx;
+  const int nf = which ? m->nrfold : m->nfold;
+  *count = nf;
+  if (nf == 0) return 0;
+  if (capacity < nf) return set_err(CFS_HIP_ERR_ARG, "buffer too small: one entry per fold destination");
+  std::vector<int4> rec((size_t)nf);
+  std::vector<int32_t> rest(ib.bytes / 4);
+  HIPCHK(hipMemcpy(rec.data(), rb.p, rec.size() * sizeof(int4), hipMemcpyDeviceToHost));
+  if (!rest.empty()) HIPCHK(hipMemcpy(rest.data(), ib.p, rest.size() * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < nf; i++) {
+    const int4 r = rec[(size_t)i];
+    dst[i] = r.x;
+    if (r.w >= -1) {
+      len[i] = 1 + (r.z >= 0) + (r.w >= 0);
+    } else { // e2 = -(offset + 2): [count, entries 2..] in the remainder list
+      const size_t off = (size_t)(-(r.w + 2));
+      if (off >= rest.size() || rest[off] < 0 || off + 1 + (size_t)rest[off] > rest.size())
+        return set_err(CFS_HIP_ERR_INTERNAL, "fold record " + std::to_string(i) + " points outside the remainder lists");
+      len[i] = 2 + rest[off];
+    }
+  }
+  return 0;
+}
+int cfs_hip_sym_debug_fold_lists(cfs_hip_sym_t h, int which, int *dst, int *len, int capacity, int *count) {
+  if (!h || !count || (which != 0 && which != 1) || capacity < 0 || (capacity > 0 && (!dst || !len)))
+    return set_err(CFS_HIP_ERR_ARG, "bad argument");
+  if (auto *d = dynamic_cast<SymMatrix<double> *>(h)) return sym_fold_lists<double>(d, which, dst, len, capacity, count);
+  if (auto *f = dynamic_cast<SymMatrix<float> *>(h)) return sym_fold_lists<float>(f, which, dst, len, capacity, count);
+  return set_err(CFS_HIP_ERR_ARG, "no fold lists for a multi-device handle");
+}
 
 // ---- host-only plan self-check (no device needed) -------------------------
 template <typename V>

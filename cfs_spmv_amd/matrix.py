@@ -191,6 +191,16 @@ class SymMatrix:
         _lib.check(_lib.load().cfs_hip_sym_debug_kernel(self._h, w, len(KERNEL_NAMES)))
         return dict(zip(KERNEL_NAMES, [int(v) for v in w]))
 
+    def fold_lists(self, which=0):
+        """developer / test: (dst, len) of the lists cfs_fold_kernel walks, in record order, decoded from
+        the device arrays (cfs_hip_sym_debug_fold_lists): which = 0 the local halo fold, 1 the receive
+        fold; dst = local rows"""
+        cap = max(1, self.row_end - self.row_begin)  # at most one list per owned row
+        dst, ln, cnt = np.zeros(cap, np.int32), np.zeros(cap, np.int32), C.c_int()
+        _lib.check(_lib.load().cfs_hip_sym_debug_fold_lists(self._h, int(which), dst.ctypes.data, ln.ctypes.data,
+                                                            cap, C.byref(cnt)))
+        return dst[:cnt.value].copy(), ln[:cnt.value].copy()
+
     def plan_note(self):
         """why the device builder handed the schedule to the host builder ('' = it built it)"""
         buf = C.create_string_buffer(256)

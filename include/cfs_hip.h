@@ -389,6 +389,12 @@ int cfs_hip_sym_debug_digest(cfs_hip_sym_t h, unsigned long long *words, int cap
  * choice.  A multi-device handle returns CFS_HIP_ERR_ARG.                                  */
 #define CFS_HIP_KERNEL_WORDS 8
 int cfs_hip_sym_debug_kernel(cfs_hip_sym_t h, int *words, int capacity_words);
+/* developer / test: the lists cfs_fold_kernel walks, decoded from the DEVICE arrays (records and remainder
+ * lists are copied back, so a device-built and a host-built schedule both report what the launch reads):
+ * which = 0 the local halo fold, 1 the receive fold; dst[i] = local row, len[i] = entries of its list,
+ * in record order (record i is read by thread i of the launch).  *count = number of lists; more than
+ * `capacity` of them, or a multi-device handle, returns CFS_HIP_ERR_ARG (*count is set first).        */
+int cfs_hip_sym_debug_fold_lists(cfs_hip_sym_t h, int which, int *dst, int *len, int capacity, int *count);
 /* why the device builder handed this handle's schedule to the host builder ("" = it built it) */
 int cfs_hip_sym_debug_plan_note(cfs_hip_sym_t h, char *buf, int capacity);
 

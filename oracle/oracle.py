@@ -198,3 +198,15 @@ def is_equal(a, b, dtype=np.float64):
     if np.dtype(dtype) == np.float64:
         return bool(lib().orc_is_equal_f64(float(a), float(b)))
     return bool(lib().orc_is_equal_f32(float(a), float(b)))
+
+
+def csr_spmv_ldx(n, rowptr, colind, values, x):
+    """the product in np.longdouble throughout (x may itself be long double): row sums of the CSR
+    as they are stored, for references that feed a product back as the next input (numpy only)"""
+    rowptr = np.asarray(rowptr, np.int64)
+    t = np.asarray(values, np.longdouble) * np.asarray(x, np.longdouble)[np.asarray(colind, np.int64)]
+    y = np.zeros(n, np.longdouble)
+    full = np.flatnonzero(rowptr[1:] > rowptr[:-1])  # (reduceat would hand an empty row its successor's first term)
+    if full.size:
+        y[full] = np.add.reduceat(t, rowptr[:-1][full])
+    return y

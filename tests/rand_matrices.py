@@ -110,3 +110,59 @@ def banded_mesh(n_nodes, links=3, dof=3):
     A = (L + L.T + sp.diags(rng.uniform(1, 2, n))).tocsr()
     A.sort_indices()
     return n, A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data
+
+
+# list lengths at which cfs_fold_kernel changes its path: the inline forms (1, 2, 3), the lane's 16 own
+# entries (every (L - 2) % 4, and the last of them, 18), and the wave-strided rest at 64-entry steps +- 1
+FOLD_LENGTHS = (1, 2, 3, 4, 5, 6, 7, 17, 18, 19, 20, 81, 82, 83, 145, 146, 147)
+
+
+def hub_columns(targets=FOLD_LENGTHS, spacing=1100, first=2000, band=3, tail=500, seed=0):
+    """a banded, strictly diagonally dominant SPD base (row i coupled to the `band` rows before it: it
+    schedules and clusters like a mesh) plus hub columns: hub k is row / column k, referenced by rows
+    first, first + spacing, ... -- targets[k] of them.  With `spacing` larger than a tile is tall (a
+    tile has at most max_slots rows) every such row lies in another tile under CFS_HIP_FLAG_NO_REORDER,
+    so the halo fold's list of destination k holds targets[k] strip entries (Format::hyb would take
+    them out of the strips: CFS_HIP_FLAG_NO_HYB).  Signed values, diagonal = 1 + the row's absolute
+    sum.  Returns (n, rowptr, colind, values, hub_rows, targets)."""
+    rng = np.random.default_rng(seed)
+    targets = np.asarray(targets, dtype=np.int64)
+    nh = int(targets.size)
+    assert first > nh + band and spacing > band
+    n = first + int(targets.max()) * spacing + tail
+    i = np.repeat(np.arange(1, n), band)
+    j = i - np.tile(np.arange(1, band + 1), n - 1)
+    keep = j >= 0
+    r, c = [i[keep]], [j[keep]]
+    for k in range(nh):
+        r.append(first + spacing * np.arange(targets[k]))
+        c.append(np.full(int(targets[k]), k))
+    r, c = np.concatenate(r), np.concatenate(c)
+    v = rng.uniform(0.25, 1.0, r.size) * rng.choice([-1.0, 1.0], r.size)
+    L = sp.coo_matrix((v, (r, c)), shape=(n, n)).tocsr()
+    S = (L + L.T).tocsr()
+    A = (S + sp.diags(1.0 + np.asarray(abs(S).sum(axis=1)).ravel())).tocsr()
+    A.sort_indices()
+    return n, A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data, np.arange(nh), targets
+
+
+def dominant(n, rowptr, colind, values):
+    """the same pattern and off-diagonal values with diagonal = 1 + the row's absolute off-diagonal sum:
+    strictly diagonally dominant, so symmetric positive definite and well conditioned"""
+    A = sp.csr_matrix((np.asarray(values, np.float64), colind, rowptr), shape=(n, n))
+    S = (A - sp.diags(A.diagonal())).tocsr()
+    S.eliminate_zeros()
+    A = (S + sp.diags(1.0 + np.asarray(abs(S).sum(axis=1)).ravel())).tocsr()
+    A.sort_indices()
+    return n, A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data
+
+
+def banded_spd(n, band=3, seed=0):
+    """row i coupled to the `band` rows before it, signed values, strictly diagonally dominant"""
+    rng = np.random.default_rng(seed)
+    i = np.repeat(np.arange(1, n), band)
+    j = i - np.tile(np.arange(1, band + 1), max(n - 1, 0))
+    keep = j >= 0
+    v = rng.uniform(0.25, 1.0, int(keep.sum())) * rng.choice([-1.0, 1.0], int(keep.sum()))
+    L = sp.coo_matrix((v, (i[keep], j[keep])), shape=(n, n)).tocsr()
+    return dominant(n, *(lambda A: (A.indptr, A.indices, A.data))((L + L.T + sp.identity(n)).tocsr()))
