@@ -410,12 +410,46 @@ struct cfs_hip_csr_s {
   int device = 0;
 };
 
+// Malformed input is refused on the host, before any device work: what is uploaded here is read on
+// the GPU without further checks (a column outside [0, ncols) gathers x out of bounds, a decreasing
+// rowptr gives negative counts).  One pass over rowptr, one -- parallel -- over colind; unsorted
+// columns and duplicates within a row are legal (no kernel needs an order).
+static int csr_validate(int nrows, int ncols, const int *rowptr, const int *colind, const void *values) {
+  if (ncols < 0) return set_err(CFS_HIP_ERR_ARG, "ncols is negative");
+  if (rowptr[0] != 0) return set_err(CFS_HIP_ERR_ARG, "row 0: rowptr[0] is " + std::to_string(rowptr[0]) + ", not 0");
+  for (int r = 0; r < nrows; r++)
+    if (rowptr[r + 1] < rowptr[r])
+      return set_err(CFS_HIP_ERR_ARG, "row " + std::to_string(r) + ": rowptr decreases (" + std::to_string(rowptr[r]) +
+                                          " -> " + std::to_string(rowptr[r + 1]) + ")");
+  if (rowptr[nrows] > 0 && (!colind || !values))
+    return set_err(CFS_HIP_ERR_ARG, std::string("row 0: ") + (!colind ? "colind" : "values") + " is NULL with " +
+                                        std::to_string(rowptr[nrows]) + " nonzeros");
+  int bad = nrows; // the first row with a column outside [0, ncols)
+#pragma omp parallel for schedule(static) reduction(min : bad) num_threads(cfs_plan::host_threads())
+  for (int r = 0; r < nrows; r++) {
+    if (r > bad) continue;
+    for (int j = rowptr[r]; j < rowptr[r + 1]; j++)
+      if ((unsigned)colind[j] >= (unsigned)ncols) {
+        bad = std::min(bad, r);
+        break;
+      }
+  }
+  if (bad < nrows) {
+    int j = rowptr[bad];
+    while ((unsigned)colind[j] < (unsigned)ncols) j++;
+    return set_err(CFS_HIP_ERR_ARG, "row " + std::to_string(bad) + ": column " + std::to_string(colind[j]) +
+                                        " outside [0, " + std::to_string(ncols) + ")");
+  }
+  return 0;
+}
+
 template <typename V>
 static int csr_create(int nrows, int ncols, const int *rowptr, const int *colind,
                       const V *values, cfs_hip_csr_t *out) {
   if (!out || !rowptr || nrows < 0) return set_err(CFS_HIP_ERR_ARG, "bad argument");
-  int rc = ensure_init();
+  int rc = csr_validate(nrows, ncols, rowptr, colind, (const void *)values);
   if (rc) return rc;
+  if ((rc = ensure_init())) return rc;
   int cur_dev = 0;
   HIPCHK(hipGetDevice(&cur_dev));
   auto *m = new cfs_hip_csr_s();
@@ -567,6 +601,13 @@ static int csr_choose_form(cfs_hip_csr_t h, void *y, const void *x, hipStream_t 
   return 0;
 }
 
+// workgroups of a block-form launch (and the blocks an XCD walks, 0 = no XCD map)
+static int csr_block_grid(const cfs_hip_csr_s *h, int *per_xcd) {
+  *per_xcd = h->xcd_map ? (h->nblocks + 7) / 8 : 0;
+  const int want = h->xcd_map ? *per_xcd * 8 : h->nblocks;
+  return want < h->block_grid ? want : h->block_grid;
+}
+
 static int csr_launch(cfs_hip_csr_t h, void *y, const void *x, hipStream_t st) {
   if (!h->block_form) {
     if (h->nchunks > 0) {
@@ -590,9 +631,8 @@ static int csr_launch(cfs_hip_csr_t h, void *y, const void *x, hipStream_t st) {
                            (const float *)h->values.p, (const float *)x, (float *)y);
     }
   } else if (h->nblocks > 0) {
-    const int per_xcd = h->xcd_map ? (h->nblocks + 7) / 8 : 0;
-    const int want = h->xcd_map ? per_xcd * 8 : h->nblocks;
-    const int grid = want < 256 * 8 ? want : 256 * 8;
+    int per_xcd = 0;
+    const int grid = csr_block_grid(h, &per_xcd);
 #define CFS_CSR_BLOCK(V, W)                                                                              \
   hipLaunchKernelGGL((cfs_csr_stream_kernel<V, W>), dim3(grid), dim3(256), 0, st, (const int32_t *)h->blk_row.p, \
                      h->nblocks, (const int32_t *)h->rowptr.p, (const int32_t *)h->colind.p,                \
@@ -612,3 +652,39 @@ static int csr_launch(cfs_hip_csr_t h, void *y, const void *x, hipStream_t st) {
   return 0;
 }
 
+// developer / test: how the handle was cut, decoded from the DEVICE arrays (cfs_hip.h)
+static int csr_debug_layout(cfs_hip_csr_t h, long long *w) {
+  DeviceGuard g(h->device);
+  HIPCHK(hipDeviceSynchronize());
+  for (int i = 0; i < CFS_HIP_CSR_LAYOUT_WORDS; i++) w[i] = 0;
+  const int nb = h->nblocks;
+  std::vector<int32_t> blk((size_t)nb + 1, 0), rp((size_t)h->nrows + 1, 0);
+  if (nb > 0) HIPCHK(hipMemcpy(blk.data(), h->blk_row.p, blk.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rp.data(), h->rowptr.p, rp.size() * 4, hipMemcpyDeviceToHost));
+  // (the launch hands the kernel no cbase with single-entry loads: every block reads in natural order)
+  const bool have = h->cbase.p && h->wide == 2;
+  std::vector<int4> cb(have ? (size_t)nb : 0);
+  if (!cb.empty()) HIPCHK(hipMemcpy(cb.data(), h->cbase.p, cb.size() * sizeof(int4), hipMemcpyDeviceToHost));
+  w[0] = nb;
+  for (int b = 0; b < nb; b++) {
+    if (blk[b] < 0 || blk[b + 1] > h->nrows || blk[b + 1] <= blk[b])
+      return set_err(CFS_HIP_ERR_INTERNAL, "row block " + std::to_string(b) + " is not a range of rows");
+    const int n = rp[blk[b + 1]] - rp[blk[b]];
+    if (n > kCsrNnz) w[4]++;
+    else if (n == 0) w[5]++;
+    else if (have && cb[b].x >= 0) w[1]++;
+    else if (have && cb[b].x == -2) w[2]++;
+    else w[3]++;
+  }
+  std::vector<int4> cd((size_t)h->nchunks);
+  if (!cd.empty()) HIPCHK(hipMemcpy(cd.data(), h->chunks.p, cd.size() * sizeof(int4), hipMemcpyDeviceToHost));
+  w[6] = h->nchunks;
+  for (const int4 &d : cd) w[7] += d.y > 0;
+  w[8] = h->nlong;
+  int per_xcd = 0;
+  w[9] = nb > 0 ? csr_block_grid(h, &per_xcd) : 0;
+  w[10] = h->nchunks > 0 ? h->wave_grid : 0;
+  w[11] = h->wide;
+  w[12] = h->xcd_map ? 1 : 0;
+  return 0;
+}

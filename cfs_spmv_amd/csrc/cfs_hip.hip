@@ -2835,6 +2835,11 @@ int cfs_hip_csr_stats(cfs_hip_csr_t h, int64_t *bytes_streamed, int64_t *narrow_
   return 0;
 }
 
+int cfs_hip_csr_debug_layout(cfs_hip_csr_t h, long long *words, int capacity_words) {
+  if (!h || !words || capacity_words < CFS_HIP_CSR_LAYOUT_WORDS) return set_err(CFS_HIP_ERR_ARG, "bad argument");
+  return csr_debug_layout(h, words);
+}
+
 int cfs_hip_csr_spmv(cfs_hip_csr_t h, void *y, const void *x) {
   if (!h || !y || !x) return set_err(CFS_HIP_ERR_ARG, "null argument");
   const size_t vb = (size_t)h->value_bytes;

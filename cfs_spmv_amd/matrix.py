@@ -324,6 +324,29 @@ class CsrMatrix:
     def dense_vector_multiply_host(self, y, x):
         _lib.check(_lib.load().cfs_hip_csr_spmv(self._h, _ptr(y), _ptr(x)))
 
+    # name order of cfs_hip_csr_debug_layout (CFS_HIP_CSR_LAYOUT_WORDS)
+    LAYOUT_KEYS = ("blocks", "blocks_col16", "blocks_lane32", "blocks_natural", "blocks_long_row",
+                   "blocks_empty", "descriptors", "chunks", "long_rows", "block_grid", "wave_grid",
+                   "lw", "xcd_map")
+
+    def layout(self):
+        """developer / test: how the handle was cut (cfs_hip_csr_debug_layout), as a dict"""
+        buf = (C.c_longlong * len(self.LAYOUT_KEYS))()
+        _lib.check(_lib.load().cfs_hip_csr_debug_layout(self._h, buf, len(buf)))
+        return dict(zip(self.LAYOUT_KEYS, (int(v) for v in buf)))
+
+    def kernel_form(self):
+        """(form, measured): 0 = block, 1 = wave; measured = the choice has been made"""
+        form, measured = C.c_int(), C.c_int()
+        _lib.check(_lib.load().cfs_hip_csr_kernel_form(self._h, C.byref(form), C.byref(measured)))
+        return form.value, measured.value
+
+    def narrow_nnz(self):
+        """nonzeros the kept form reads through 16-bit column codes (cfs_hip_csr_stats)"""
+        streamed, nar = C.c_int64(), C.c_int64()
+        _lib.check(_lib.load().cfs_hip_csr_stats(self._h, C.byref(streamed), C.byref(nar)))
+        return nar.value
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             _lib.load().cfs_hip_csr_destroy(self._h)

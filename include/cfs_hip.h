@@ -460,6 +460,19 @@ int cfs_hip_csr_kernel_form(cfs_hip_csr_t h, int *form, int *measured);
  * bytes_streamed = bytes one SpMV of the kept form reads from the handle's arrays;
  * narrow_nnz = nonzeros stored with 16-bit columns.                                          */
 int cfs_hip_csr_stats(cfs_hip_csr_t h, int64_t *bytes_streamed, int64_t *narrow_nnz);
+/* developer / test: how this handle was cut, as CFS_HIP_CSR_LAYOUT_WORDS words: [0] row blocks (at
+ * most 4 096 nonzeros and 1 024 rows each, a longer row alone); of these [1] stored with 16-bit
+ * column codes, [2] in lane order with 32-bit columns, [3] read in natural order through the
+ * product branch, [4] one long row (more than 4 096 nonzeros), [5] empty rows only -- [1]..[5]
+ * partition [0], decoded from the DEVICE array of window starts copied back, so they report what
+ * the launch reads (no such array, or single-entry loads: every block that is neither a long row
+ * nor empty counts under [3]); [6] chunk descriptors of the wave form, padding included, [7]
+ * descriptors with at least one row, [8] long rows of the wave form (more than 1 024 nonzeros);
+ * [9] / [10] workgroups of a block-form / wave-form launch (0: nothing to launch); [11] entries a
+ * lane loads at once (1 or 2, CFS_HIP_CSR_WIDE); [12] 1 if the XCD map is on.  Fewer than
+ * CFS_HIP_CSR_LAYOUT_WORDS words of capacity is CFS_HIP_ERR_ARG.                              */
+#define CFS_HIP_CSR_LAYOUT_WORDS 13
+int cfs_hip_csr_debug_layout(cfs_hip_csr_t h, long long *words, int capacity_words);
 
 /* ---- HIP-event timing on the stream the kernels run on (bench.py) --------- */
 int cfs_hip_event_create(void **ev);

@@ -166,3 +166,241 @@ def banded_spd(n, band=3, seed=0):
     v = rng.uniform(0.25, 1.0, int(keep.sum())) * rng.choice([-1.0, 1.0], int(keep.sum()))
     L = sp.coo_matrix((v, (i[keep], j[keep])), shape=(n, n)).tocsr()
     return dominant(n, *(lambda A: (A.indptr, A.indices, A.data))((L + L.T + sp.identity(n)).tocsr()))
+
+
+# ---- the general CSR path (cfs_csr.hpp): the two host cuts restated from their documented rules, and
+# ---- matrices designed so that a row count or nonzero count sits exactly on a structural constant
+CSR_BLOCK_NNZ, CSR_BLOCK_ROWS = 4096, 1024  # block form: nonzeros / rows of a row block
+CSR_CHUNK_NNZ, CSR_CHUNK_ROWS = 1024, 63    # wave form: nonzeros / rows of a chunk
+CSR_WINDOW, CSR_WINDOWS = 16384, 4          # 16-bit column codes: four windows of 16 384 columns
+CSR_BLOCK_GRID = 2048                       # workgroups of a block-form launch, at most
+
+
+def csr_block_cut(rowptr):
+    """the block cut: consecutive rows, greedily as many as keep the block within 4 096 nonzeros and
+    1 024 rows; a row longer than that is a block alone.  Returns the row boundaries (blocks + 1)."""
+    rowptr = np.asarray(rowptr, np.int64)
+    nrows = rowptr.size - 1
+    cut, r = [0], 0
+    while r < nrows:
+        # the last e with rowptr[e] - rowptr[r] <= 4 096 (rowptr does not decrease)
+        e = int(np.searchsorted(rowptr, rowptr[r] + CSR_BLOCK_NNZ, side="right")) - 1
+        e = max(min(e, r + CSR_BLOCK_ROWS, nrows), r + 1)
+        cut.append(e)
+        r = e
+    return np.asarray(cut, np.int64)
+
+
+def csr_chunk_cut(rowptr, xcd=True):
+    """the chunk cut: a row of more than 1 024 nonzeros is set aside as a long row; the others go,
+    greedily, into chunks of consecutive rows of at most 1 024 nonzeros and 63 rows (a long row ends
+    the chunk before it).  Under the XCD map the descriptor list is padded: workgroups of 4 waves,
+    `per` workgroups for each of 8 XCDs, per = ceil(ceil(chunks / 4) / 8), 32 * per descriptors.
+    Returns dict(chunks = (first row, rows, first nonzero, nonzeros) per chunk, long_rows,
+    descriptors)."""
+    rowptr = np.asarray(rowptr, np.int64)
+    nrows = rowptr.size - 1
+    chunks, long_rows, r = [], [], 0
+    while r < nrows:
+        if rowptr[r + 1] - rowptr[r] > CSR_CHUNK_NNZ:
+            long_rows.append(r)
+            r += 1
+            continue
+        e = int(np.searchsorted(rowptr, rowptr[r] + CSR_CHUNK_NNZ, side="right")) - 1
+        e = min(e, r + CSR_CHUNK_ROWS, nrows)
+        chunks.append((r, e - r, int(rowptr[r]), int(rowptr[e] - rowptr[r])))
+        r = e
+    nd = len(chunks)
+    if xcd and nd:
+        per = -(-(-(-nd // 4)) // 8)
+        nd = 32 * per
+    return dict(chunks=np.asarray(chunks, np.int64).reshape(-1, 4), long_rows=np.asarray(long_rows, np.int64),
+                descriptors=nd)
+
+
+def csr_block_windows(rowptr, colind, cut):
+    """windows of 16 384 columns that cover the columns of each block of `cut`, placed greedily (each
+    starts at the smallest column not yet covered); 0 for a block without entries"""
+    rowptr = np.asarray(rowptr, np.int64)
+    out = np.zeros(len(cut) - 1, np.int64)
+    for b in range(len(cut) - 1):
+        cols = np.unique(np.asarray(colind[rowptr[cut[b]]:rowptr[cut[b + 1]]], np.int64))
+        i = 0
+        while i < cols.size:
+            out[b] += 1
+            i = int(np.searchsorted(cols, cols[i] + CSR_WINDOW, side="left"))
+    return out
+
+
+def csr_expected_layout(rowptr, colind, col16=True, lane32=True, lw=2, xcd=True):
+    """what CsrMatrix.layout() has to report for this matrix (every word but the wave grid, which
+    depends on the device), from the restated cuts; plus narrow_nnz of cfs_hip_csr_stats"""
+    rowptr = np.asarray(rowptr, np.int64)
+    cut = csr_block_cut(rowptr)
+    n = rowptr[cut[1:]] - rowptr[cut[:-1]]
+    win = csr_block_windows(rowptr, colind, cut)
+    product = (n > 0) & (n <= CSR_BLOCK_NNZ)
+    coded = col16 and lw == 2 and rowptr[-1] > 0  # (no array of window starts otherwise)
+    narrow = product & (win <= CSR_WINDOWS) & coded
+    lane = product & (win > CSR_WINDOWS) & (coded and lane32)
+    ch = csr_chunk_cut(rowptr, xcd)
+    nb = len(cut) - 1
+    want = -(-nb // 8) * 8 if xcd else nb
+    return dict(blocks=nb, blocks_col16=int(narrow.sum()), blocks_lane32=int(lane.sum()),
+                blocks_natural=int((product & ~narrow & ~lane).sum()), blocks_long_row=int((n > CSR_BLOCK_NNZ).sum()),
+                blocks_empty=int((n == 0).sum()), descriptors=ch["descriptors"], chunks=len(ch["chunks"]),
+                long_rows=len(ch["long_rows"]), block_grid=min(want, CSR_BLOCK_GRID), lw=lw, xcd_map=int(xcd),
+                narrow_nnz=int(n[narrow].sum()))
+
+
+def csr_from_row_lengths(lengths, ncols, col_rule, rng):
+    """a CSR pattern (rowptr, colind as int32) with the given row lengths.  col_rule:
+    ("band", h): within h columns of the row's own position scaled to the column range;
+    ("windows", starts, width): in one of the ranges [s, s + width), s of `starts`;
+    ("anywhere",): any column.  Columns are neither sorted nor distinct within a row."""
+    lengths = np.asarray(lengths, np.int64)
+    rowptr = np.concatenate([[0], np.cumsum(lengths)])
+    nnz, nrows = int(rowptr[-1]), lengths.size
+    row = np.repeat(np.arange(nrows), lengths)
+    if col_rule[0] == "band":
+        centre = row * (ncols - 1) // max(nrows - 1, 1)
+        col = np.clip(centre + rng.integers(-col_rule[1], col_rule[1] + 1, nnz), 0, ncols - 1)
+    elif col_rule[0] == "windows":
+        starts = np.asarray(col_rule[1], np.int64)
+        col = starts[rng.integers(0, starts.size, nnz)] + rng.integers(0, col_rule[2], nnz)
+    else:
+        col = rng.integers(0, ncols, nnz)
+    assert nnz == 0 or (col.min() >= 0 and col.max() < ncols)
+    return rowptr.astype(np.int32), col.astype(np.int32)
+
+
+def odd_rows(total, part=5):
+    """`total` nonzeros as rows of odd lengths (`part`s, then ones): what follows starts at an odd position
+    whenever total is odd"""
+    return [part] * (total // part) + [1] * (total % part)
+
+
+def padded_block(lengths):
+    """row lengths of one block of exactly 1 024 rows: the given rows, then empty ones -- the row cap ends it"""
+    assert len(lengths) <= CSR_BLOCK_ROWS and sum(lengths) <= CSR_BLOCK_NNZ
+    return list(lengths) + [0] * (CSR_BLOCK_ROWS - len(lengths))
+
+
+# nonzeros of the blocks of csr_case("block_nnz") / rows of the chunks of csr_case("chunk_rows_*"),
+# in matrix order
+CSR_BLOCK_NNZ_LIST = (4095, 1, 2, 511, 512, 513, 4096, 4095, 4096)
+CSR_CHUNK_ROWS_LIST = (1, 2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 62, 63)
+# window layouts of csr_case("windows"): gaps before the 2nd, 3rd ... window of a block whose smallest
+# column is c0 > 0 (gap 0: the next window starts exactly at the previous start + 16 384)
+CSR_WINDOW_GAPS = ((), (0,), (0, 0), (0, 0, 0), (700,), (1, 16384), (40000, 5, 123), (0, 0, 0, 0), (9, 9, 9, 9))
+
+
+def csr_case(name, seed=0):
+    """the designed matrices of tests/test_gpu_csr_edges.py: (nrows, ncols, rowptr, colind).
+    tests/test_plan_random.py checks, without a GPU, that each reaches the edge it is named after."""
+    rng = np.random.default_rng(seed)
+    short = lambda k: [3, 1, 5, 0, 7][:] * (k // 5) + [3] * (k % 5)  # ragged short rows, one in five empty
+    if name == "block_nnz":  # blocks of exactly CSR_BLOCK_NNZ_LIST nonzeros in odd rows, then empty rows
+        lengths = sum((padded_block(odd_rows(t)) for t in CSR_BLOCK_NNZ_LIST), [])
+        # ... and two blocks ended by the nonzero cap, not the row cap: 4 096 exactly, then 4 095 + a row of 3
+        lengths += odd_rows(4096) + odd_rows(4095) + [3] * 11
+        return (len(lengths), len(lengths)) + csr_from_row_lengths(lengths, len(lengths), ("band", 2000), rng)
+    if name == "full_blocks":  # nine blocks of exactly 4 096 nonzeros in 512 odd rows: the nonzero cap alone ends them
+        lengths = [7, 9] * (256 * 9)
+        return (len(lengths), 6000) + csr_from_row_lengths(lengths, 6000, ("band", 900), rng)
+    if name == "long_rows":  # long-row branch first, between short rows and last; a one-row product block
+        lengths = [4097] + short(50) + [4096] + short(30) + [20000] + short(41) + [4096] + [4097]
+        return (len(lengths), 30000) + csr_from_row_lengths(lengths, 30000, ("anywhere",), rng)
+    if name == "row_cap":  # 1 024 one-entry rows bind the row cap twice, the 2 049th row goes on; a mixed block
+        lengths = [1] * 2049 + [3, 0, 0, 1, 0, 5, 0, 0, 0, 2] * 60
+        return (len(lengths), 5000) + csr_from_row_lengths(lengths, 5000, ("band", 300), rng)
+    if name == "empty_blocks":  # blocks of empty rows only at the start, in the middle and as the tail
+        lengths = [0] * 1024 + short(300) + [0] * 2500 + short(200) + [0] * 1500
+        return (len(lengths), 4000) + csr_from_row_lengths(lengths, 4000, ("band", 100), rng)
+    if name == "no_rows":
+        return (0, 10) + csr_from_row_lengths([], 10, ("anywhere",), rng)
+    if name == "no_entries":
+        return (1500, 10) + csr_from_row_lengths([0] * 1500, 10, ("anywhere",), rng)
+    if name.startswith("blocks_"):  # k blocks of 1 024 rows of one or two entries
+        k = int(name[7:])
+        lengths = [1, 2] * (512 * k)
+        return (len(lengths), len(lengths)) + csr_from_row_lengths(lengths, len(lengths), ("band", 500), rng)
+    if name == "windows":  # one block per entry of CSR_WINDOW_GAPS, smallest column c0 = 1000 + 37 b
+        lengths, cols = [], []
+        ncols = 400_000
+        for b, gaps in enumerate(CSR_WINDOW_GAPS):
+            starts = [1000 + 37 * b]
+            for g in gaps:
+                starts.append(starts[-1] + CSR_WINDOW + g)
+            rows = odd_rows(7 * 201 + b, 7)
+            k = sum(rows)
+            s = np.asarray(starts, np.int64)
+            # every window's first and last column, then columns anywhere inside the windows
+            c = s[rng.integers(0, s.size, k)] + rng.integers(0, CSR_WINDOW, k)
+            edge = np.concatenate([s, s + CSR_WINDOW - 1])
+            c[rng.choice(k, edge.size, replace=False)] = edge
+            cols.append(c)
+            lengths += padded_block(rows)
+        rowptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+        return len(lengths), ncols, rowptr, np.concatenate(cols).astype(np.int32)
+    if name == "wide_rect":  # ncols >> nrows, columns up to ncols - 1 > 65 536
+        lengths = short(300)
+        rp, ci = csr_from_row_lengths(lengths, 200_000, ("anywhere",), rng)
+        ci[-1] = 200_000 - 1
+        ci[0] = 0
+        return len(lengths), 200_000, rp, ci
+    if name == "tall_rect":  # ncols < nrows
+        lengths = short(5000)
+        return (len(lengths), 37) + csr_from_row_lengths(lengths, 37, ("anywhere",), rng)
+    if name == "one_column":
+        lengths = [1, 0, 2, 1, 3] * 600
+        return (len(lengths), 1) + csr_from_row_lengths(lengths, 1, ("anywhere",), rng)
+    if name in ("chunk_rows_equal", "chunk_rows_ragged"):  # chunks of exactly CSR_CHUNK_ROWS_LIST rows, a long row after each
+        lengths = []
+        for k in CSR_CHUNK_ROWS_LIST:
+            rows = [3] * k if name.endswith("equal") else [int(v) for v in rng.integers(0, 17, k)]
+            if not name.endswith("equal") and k > 2:
+                rows[k // 2] = 0  # an empty row inside the chunk
+            lengths += rows + [CSR_CHUNK_NNZ + 1]
+        return (len(lengths), 9000) + csr_from_row_lengths(lengths, 9000, ("band", 700), rng)
+    if name == "chunk_caps":  # 64 short rows split 63 + 1; a chunk of exactly 1 024; rows of 1 024 and 1 025
+        lengths = [1025] + [2] * 64 + [1025] + [32] * 32 + [1] + [1025] + [1024] + [5] + [1024]
+        return (len(lengths), 3000) + csr_from_row_lengths(lengths, 3000, ("anywhere",), rng)
+    if name == "only_long_rows":
+        lengths = [1025, 2000, 1500]
+        return (3, 2500) + csr_from_row_lengths(lengths, 2500, ("anywhere",), rng)
+    if name == "empty_chunks":  # chunks of empty rows only: at the start, in the middle, as the tail
+        lengths = [0] * 200 + short(100) + [0] * 130 + short(40) + [0] * 200
+        return (len(lengths), 800) + csr_from_row_lengths(lengths, 800, ("band", 60), rng)
+    if name.startswith("chunks_"):  # k chunks of 63 rows of two entries
+        k = int(name[7:])
+        lengths = [2] * (63 * k)
+        return (len(lengths), len(lengths)) + csr_from_row_lengths(lengths, len(lengths), ("band", 90), rng)
+    if name == "confine":
+        return csr_confinement_case(rng)[:4]
+    raise KeyError(name)
+
+
+def csr_confinement_case(rng, groups=12, rows=51, length=9):
+    """groups of `rows` rows of `length` entries, a long row (4 097) after each: every group is one
+    block of the block form AND one chunk of the wave form, of rows * length entries -- not a multiple
+    of 512, 64 or 2.  Group g's smallest column, 10 g, is referenced once, by its row 20; the column
+    of its last entry, 10 g + 5, once, by its last row; every other column is >= 1 000.  Even groups
+    fit one window of 16 384 columns (16-bit codes), odd ones spread over the whole range (lane-order
+    32-bit columns).  Returns (nrows, ncols, rowptr, colind, special columns, rows that reference them)."""
+    assert (rows * length) % 2 == 1 and rows * length <= CSR_CHUNK_NNZ and rows <= CSR_CHUNK_ROWS
+    ncols = 200_000
+    lengths, cols, special, owners = [], [], [], []
+    for g in range(groups):
+        k = rows * length
+        c = (1000 + 100 * g + rng.integers(0, 3000, k)) if g % 2 == 0 else rng.integers(1000, ncols, k)
+        c[20 * length + 4] = 10 * g
+        c[k - 1] = 10 * g + 5
+        r0 = len(lengths)
+        special += [10 * g, 10 * g + 5]
+        owners += [r0 + 20, r0 + rows - 1]
+        cols += [c, rng.integers(1000, ncols, CSR_BLOCK_NNZ + 1)]
+        lengths += [length] * rows + [CSR_BLOCK_NNZ + 1]
+    rowptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    return (len(lengths), ncols, rowptr, np.concatenate(cols).astype(np.int32),
+            np.asarray(special), np.asarray(owners))

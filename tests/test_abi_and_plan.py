@@ -55,6 +55,63 @@ def test_bad_arguments_return_error_codes():
         cfs.plan_check(n, rp, ci, va, options=opt)
 
 
+def _csr(rowptr, colind, values=None):
+    rp, ci = np.asarray(rowptr, np.int32), np.asarray(colind, np.int32)
+    return rp, ci, (np.ones(ci.size) if values is None else values)
+
+
+# (nrows, ncols, rowptr, colind, null colind?, null values?, what the message has to name)
+CSR_REFUSALS = {
+    "negative_ncols": (2, -1, [0, 0, 0], [], False, False, "ncols"),
+    "rowptr_not_from_zero": (2, 4, [1, 2, 3], [0, 1, 2], False, False, r"row 0\b.*rowptr\[0\]"),
+    "decreasing_rowptr": (4, 4, [0, 2, 3, 1, 3], [0, 1, 2], False, False, r"row 2\b.*decreases"),
+    "null_colind": (2, 4, [0, 1, 2], [0, 1], True, False, "colind is NULL"),
+    "null_values": (2, 4, [0, 1, 2], [0, 1], False, True, "values is NULL"),
+    "column_at_ncols": (5, 4, [0, 1, 2, 4, 5, 6], [0, 3, 1, 4, 4, 2], False, False, r"row 2\b.*column 4 outside \[0, 4\)"),
+    "negative_column": (3, 4, [0, 2, 3, 4], [0, 1, 2, -1], False, False, r"row 2\b.*column -1 outside"),
+}
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("case", sorted(CSR_REFUSALS))
+def test_csr_create_refuses_malformed_input(case, dtype):
+    """cfs_hip_csr_create checks its input on the host, BEFORE the runtime is initialised (this test
+    runs without a GPU and only ever calls create): CFS_HIP_ERR_ARG, the message names the first
+    offending row, and no handle comes back"""
+    lib = cfs.load()
+    nrows, ncols, rowptr, colind, no_ci, no_va, what = CSR_REFUSALS[case]
+    rp, ci, va = _csr(rowptr, colind)
+    va = va.astype(dtype)
+    h = C.c_void_p()
+    create = getattr(lib, "cfs_hip_csr_create_" + ("f64" if dtype == np.float64 else "f32"))
+    rc = create(nrows, ncols, rp.ctypes.data, None if no_ci else ci.ctypes.data,
+                None if no_va else va.ctypes.data, C.byref(h))
+    assert rc == -1  # CFS_HIP_ERR_ARG
+    assert not h.value
+    assert re.search(what, lib.cfs_hip_last_error().decode()), lib.cfs_hip_last_error().decode()
+
+
+def test_csr_create_names_the_first_offending_row_of_many():
+    """rows 700 and 90 000 of 100 000 hold a column out of range (the pass over colind is parallel:
+    the FIRST row is reported whatever thread finds which); unsorted columns and duplicates are legal"""
+    lib = cfs.load()
+    n = 100_000
+    rp = (np.arange(n + 1) * 3).astype(np.int32)
+    ci = np.tile(np.array([7, 2, 7], np.int32), n)  # unsorted, duplicated: legal
+    ci[3 * 90_000 + 1] = n
+    ci[3 * 700 + 2] = -5
+    va = np.ones(ci.size)
+    h = C.c_void_p()
+    assert lib.cfs_hip_csr_create_f64(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, C.byref(h)) == -1
+    assert re.search(r"row 700\b.*column -5", lib.cfs_hip_last_error().decode())
+
+
+def test_csr_debug_layout_refuses_bad_arguments():
+    lib = cfs.load()
+    buf = (C.c_longlong * 13)()
+    assert lib.cfs_hip_csr_debug_layout(None, buf, 13) == -1
+
+
 CASES = [("pdb1HYS", 0.1), ("pwtk", 0.05), ("ldoor", 0.02), ("Flan_1565", 0.02),
          ("Queen_4147", 0.005)]
 

@@ -197,6 +197,8 @@ def test_csr_block_form_with_narrow_and_wide_row_blocks(col16, monkeypatch):
     torch = _torch()
     monkeypatch.setenv("CFS_HIP_CSR_KERNEL", "block")
     monkeypatch.setenv("CFS_HIP_CSR_COL16", col16)
+    for k in ("CFS_HIP_CSR_LANE32", "CFS_HIP_CSR_WIDE"):  # (would change the layout asserted below)
+        monkeypatch.delenv(k, raising=False)
     rng = np.random.default_rng(5)
     n = 300_000
     ia = np.arange(200_000)  # stencil-like part: 5-9 entries within +-3000 columns of row - 40 000, row, row + 40 000
@@ -214,6 +216,9 @@ def test_csr_block_form_with_narrow_and_wide_row_blocks(col16, monkeypatch):
         v = A.data.astype(dtype)
         x = rng.standard_normal(n).astype(dtype)
         G = cfs.CsrMatrix(n, n, rp, ci, v)
+        lay = G.layout()  # both kinds of block are there (or, without the 16-bit array, neither)
+        assert (lay["blocks_col16"] > 0, lay["blocks_lane32"] > 0, lay["blocks_natural"] > 0) == \
+            ((True, True, False) if col16 == "1" else (False, False, True)), lay
         xd = torch.from_numpy(x).cuda()
         yd = torch.full((n,), float("nan"), dtype=xd.dtype, device="cuda")
         G.dense_vector_multiply(yd, xd)
@@ -235,6 +240,8 @@ def test_csr_column_code_window_boundaries(last_col, narrow, monkeypatch):
     from oracle import oracle
     torch = _torch()
     monkeypatch.setenv("CFS_HIP_CSR_KERNEL", "block")
+    for k in ("CFS_HIP_CSR_COL16", "CFS_HIP_CSR_LANE32", "CFS_HIP_CSR_WIDE"):  # (would change the layout asserted below)
+        monkeypatch.delenv(k, raising=False)
     n = 70_000
     cols = np.array([0, 16383, 16384, 32767, 32768, 49151, 49152, last_col])
     nrows_used = 40  # one block
@@ -250,6 +257,8 @@ def test_csr_column_code_window_boundaries(last_col, narrow, monkeypatch):
         streamed, nar = C.c_int64(), C.c_int64()
         _lib.check(_lib.load().cfs_hip_csr_stats(G._h, C.byref(streamed), C.byref(nar)))
         assert (nar.value == A.nnz) == narrow and nar.value in (0, A.nnz)
+        lay = G.layout()  # the one block with entries: 16-bit codes, or lane order with 32-bit columns
+        assert (lay["blocks_col16"], lay["blocks_lane32"], lay["blocks_natural"]) == ((1, 0, 0) if narrow else (0, 1, 0)), lay
         xd = torch.from_numpy(x).cuda()
         yd = torch.full((n,), float("nan"), dtype=xd.dtype, device="cuda")
         G.dense_vector_multiply(yd, xd)
