@@ -15,6 +15,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "cfs_hip.h"
@@ -759,6 +760,44 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// the diagonal of the rows a handle owns, out of its schedule (cfs_hip_sym_diagonal_async): a
+// workgroup per tile.  `diag` is per VIRTUAL row, in the tile's sorted order, and holds a_ii on the
+// first chunk of a row only -- the other chunks of a split row, and a row without a stored diagonal
+// entry, hold +0 -- so at most one virtual row of a local row carries a non-zero word: it is put
+// into the row's place of an LDS window of the tile's own rows (zeroed first: no two lanes write one
+// word, no atomics), and the window leaves through the own-row slots of slot_col, which name the
+// caller's row of every local row (consecutive in natural order: coalesced stores; a permutation
+// inside the tile's cluster otherwise).  Every owned row lies in exactly one tile (cfs_hip_sym_
+// plan_check_*), so every entry of `out` is written exactly once and nothing has to be zeroed first.
+template <typename V>
+__global__ void __launch_bounds__(256)
+    cfs_diag_gather_kernel(V *__restrict__ out, const Tile *__restrict__ tiles, int ntiles,
+                           const int32_t *__restrict__ slot_col, const uint32_t *__restrict__ rowinfo,
+                           const V *__restrict__ diag, int row_begin, int rows, int window) {
+  extern __shared__ __align__(16) unsigned char cfs_diag_smem[];
+  V *w = reinterpret_cast<V *>(cfs_diag_smem);
+  typedef typename std::conditional<sizeof(V) == 8, unsigned long long, unsigned>::type Bits;
+  for (int ti = blockIdx.x; ti < ntiles; ti += gridDim.x) {
+    const int nown = min(tiles[ti].nown, window), nvr = tiles[ti].nvrows, v0 = tiles[ti].vrow_off,
+              s0 = tiles[ti].slot_off;
+    for (int i = threadIdx.x; i < nown; i += 256) w[i] = V(0);
+    __syncthreads();
+    for (int v = threadIdx.x; v < nvr; v += 256) {
+      const V d = diag[v0 + v];
+      const int r = (int)(rowinfo[v0 + v] & 0xffffu);
+      Bits bits;
+      __builtin_memcpy(&bits, &d, sizeof bits);
+      if (bits != 0 && r < nown) w[r] = d; // (the bits, not the value: a stored -0 or NaN is copied too)
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nown; i += 256) {
+      const int o = slot_col[s0 + i] - row_begin;
+      if ((unsigned)o < (unsigned)rows) out[o] = w[i];
+    }
+    __syncthreads(); // the next tile zeroes the window
+  }
+}
+
 // pack contributions for rows owned by lower ranks: one value per remote row
 template <typename V>
 __global__ void __launch_bounds__(256)
@@ -906,6 +945,8 @@ struct cfs_hip_sym_s {
   virtual int group_features(long long *out, int cap, int *ngroups) = 0;
   // values_dev: the caller's full CSR value array (same pattern as at create), on this device
   virtual int update_values(const void *values_dev, long long nnz, hipStream_t st) = 0;
+  // d_dev[i - row_begin] = a_ii of the owned rows, from the device arrays (cfs_hip_sym_diagonal_async)
+  virtual int diagonal(void *d_dev, hipStream_t st) = 0;
   int device = 0; // the device this handle's arrays live on (current device at create)
   std::string plan_note; // why the device builder handed the schedule to the host builder ("" = it did not)
   HostStage stage; // host-pointer callers
@@ -1314,6 +1355,20 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
     go(cvals, cval_map);
     go(fvals, fval_map);
     go(diag, diag_map);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  int diagonal(void *d_dev, hipStream_t st) override {
+    const int T = (int)P.tiles.size();
+    if (T == 0) return 0;
+    int window = 1; // own rows of the tallest tile
+    for (const Tile &t : P.tiles) window = std::max(window, (int)t.nown);
+    const void *k = (const void *)cfs_diag_gather_kernel<V>;
+    int rc = raise_lds_limit(k, device); // (a window of 1 024-thread tiles can exceed the 64 KiB default)
+    if (rc) return rc;
+    hipLaunchKernelGGL((cfs_diag_gather_kernel<V>), dim3(std::min(T, 4096)), dim3(256), (size_t)window * sizeof(V), st,
+                       (V *)d_dev, dev.tiles, T, dev.slot_col, dev.rowinfo, dev.diag, (int)P.row_begin,
+                       (int)(P.row_end - P.row_begin), window);
     HIPCHK(hipGetLastError());
     return 0;
   }
@@ -2142,6 +2197,27 @@ struct MultiSym : cfs_hip_sym_s {
     }
     return 0;
   }
+  // every shard gathers its block on its own device and stream; the block comes home the way its
+  // y block does (a peer copy in the replicate modes, written in place otherwise)
+  int diagonal(void *d, hipStream_t st) override {
+    HIPCHK(hipEventRecord(start_, st));
+    for (size_t g = 0; g < shard.size(); g++) {
+      DeviceGuard dg(dev[g]);
+      HIPCHK(hipStreamWaitEvent(st_[g], start_, 0));
+      char *dg_home = (char *)d + (size_t)splits[g] * value_bytes;
+      const size_t bytes = (size_t)(splits[g + 1] - splits[g]) * value_bytes;
+      int rc;
+      if (copies(g)) {
+        if ((rc = ensure_copies(g)) || (rc = shard[g]->diagonal(yloc[g].p, st_[g]))) return rc;
+        if (bytes) HIPCHK(hipMemcpyPeerAsync(dg_home, device, yloc[g].p, dev[g], bytes, st_[g]));
+      } else if ((rc = shard[g]->diagonal(dg_home, st_[g]))) {
+        return rc;
+      }
+      HIPCHK(hipEventRecord(done_[g], st_[g]));
+    }
+    for (size_t g = 0; g < shard.size(); g++) HIPCHK(hipStreamWaitEvent(st, done_[g], 0));
+    return 0;
+  }
   int ngpus() const { return (int)shard.size(); }
 };
 
@@ -2337,6 +2413,37 @@ int cfs_hip_sym_cg(cfs_hip_sym_t h, void *u_dev, const void *b_dev, double tol, 
   if (h->value_bytes == 8)
     return cfs_solver::cg<double>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, (hipStream_t)stream);
   return cfs_solver::cg<float>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, (hipStream_t)stream);
+}
+
+int cfs_hip_sym_pcg(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int precond, double tol, int maxiter,
+                    int check_every, int *iterations, double *relres, void *stream) {
+  if (precond == CFS_HIP_PRECOND_NONE) // the plain iteration: the same code path, the same bits
+    return cfs_hip_sym_cg(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, stream);
+  if (!h || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (iterations) *iterations = 0;
+  if (relres) *relres = 0.0;
+  if (precond != CFS_HIP_PRECOND_JACOBI) return set_err(CFS_HIP_ERR_ARG, "pcg: unknown preconditioner " + std::to_string(precond));
+  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg: u and b must be different vectors");
+  if (!h->send_rows().empty())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg: a handle of the whole matrix, not a shard");
+  int rc = check_placement(h, u_dev, b_dev);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  DeviceGuard g(h->device);
+  if (h->value_bytes == 8)
+    return cfs_solver::cg<double, true>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, (hipStream_t)stream);
+  return cfs_solver::cg<float, true>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, (hipStream_t)stream);
+}
+
+int cfs_hip_sym_diagonal_async(cfs_hip_sym_t h, void *d_dev, void *stream) {
+  if (!h || !d_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  const cfs_rt::PtrInfo di = cfs_rt::classify(d_dev);
+  if (!di.device) return set_err(CFS_HIP_ERR_ARG, "cfs_hip_sym_diagonal_async needs a device pointer");
+  if (di.dev != h->device)
+    return set_err(CFS_HIP_ERR_ARG, "d lives on device " + std::to_string(di.dev) + ", the matrix on device " +
+                                        std::to_string(h->device));
+  DeviceGuard g(h->device);
+  return h->diagonal(d_dev, (hipStream_t)stream);
 }
 
 int cfs_hip_sym_spmv(cfs_hip_sym_t h, void *y, const void *x) {

@@ -19,6 +19,16 @@
 // the convergence flag every `check_every` iterations (one 8-byte copy + synchronisation);
 // kernels enqueued behind a converged iteration return at once.  cfs_hip_sym_cg recomputes the
 // true residual ||b - A u|| / ||b|| at the end.
+//
+// Jacobi (cfs_hip_sym_pcg, PRE = true below): the same five launches.  dinv_i = (V)(1 / a_ii) is
+// built once from the handle's own diagonal (cfs_diag_gather_kernel, then cg_dinv_kernel);
+// z = D^-1 r is never stored: z_i = (double)r_i * (double)dinv_i, with r_i the rounded value in
+// memory, is formed in fp64 where it is needed --
+//   cg_update_kernel<V, true>     u += (rz/pq) p;  r -= (rz/pq) q;  rz' = r . z;  rr' = r . r
+//   cg_direction_kernel<V, true>  p = dinv r + (rz'/rz) p;  converged?  (rr' <= stop: the
+//                                 unpreconditioned residual, the same rule as without)
+// r . z has two slots alternating with the parity of the iteration, like r . r.  The PRE = false
+// instantiations are the kernels of the plain iteration, operation for operation.
 #pragma once
 
 namespace cfs_solver {
@@ -28,7 +38,8 @@ namespace cfs_solver {
 // order would vary; a fixed grid and a fixed summation order make the scalars bit-reproducible)
 constexpr int kThreads = 256;
 constexpr int kGrid = 512;                                  // workgroups of every vector kernel
-enum Slot { P_RR0 = 0, P_RR1, P_PQ, P_BB, P_RES, P_COUNT }; // part[slot][kGrid]
+// part[slot][kGrid]; P_RZ0 / P_RZ1 (r . z) and P_BAD (diagonal entries that are not finite and > 0) only with Jacobi
+enum Slot { P_RR0 = 0, P_RR1, P_PQ, P_BB, P_RES, P_RZ0, P_RZ1, P_BAD, P_COUNT };
 enum Counter { I_ITER = 0, I_DONE, I_COUNT };
 
 // sum of v over the workgroup, returned to every thread (fixed order)
@@ -65,39 +76,69 @@ template <typename V> struct Vec16 {
   typedef V type __attribute__((ext_vector_type(16 / sizeof(V))));
 };
 
-// r = b - q;  p = r (when given);  part[slot_rr] <- r . r;  part[P_BB] <- b . b (when with_bb)
+// dinv = (V)(1 / d) in place over the gathered diagonal;  part[P_BAD] <- entries that are not finite and > 0
 template <typename V>
+__global__ void __launch_bounds__(kThreads) cg_dinv_kernel(V *__restrict__ d, long long n, double *__restrict__ part) {
+  double bad = 0.0;
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+    const double a = (double)d[i];
+    // (!(a > 0): a NaN counts too)
+    if (!(a > 0.0) || a * 0.0 != 0.0) bad += 1.0;
+    d[i] = (V)(1.0 / a);
+  }
+  bad = block_sum(bad);
+  if (threadIdx.x == 0) part[P_BAD * kGrid + blockIdx.x] = bad;
+}
+
+// r = b - q;  p = r (when given);  part[slot_rr] <- r . r;  part[P_BB] <- b . b (when with_bb)
+// PRE: p = z = dinv r instead, and part[P_RZ0] <- r . z
+template <typename V, bool PRE = false>
 __global__ void __launch_bounds__(kThreads)
     cg_residual_kernel(V *__restrict__ r, V *__restrict__ p, const V *__restrict__ b, const V *__restrict__ q,
-                       long long n, double *__restrict__ part, int slot_rr, int with_bb) {
+                       long long n, double *__restrict__ part, int slot_rr, int with_bb,
+                       const V *__restrict__ dinv = nullptr) {
   constexpr int W = Vec16<V>::W;
   typedef typename Vec16<V>::type VT;
   const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  double rr = 0.0, bb = 0.0;
+  double rr = 0.0, bb = 0.0, rz = 0.0;
   for (long long i = t0; i < nv; i += stride) {
     const VT bv = reinterpret_cast<const VT *>(b)[i], qv = reinterpret_cast<const VT *>(q)[i];
-    VT rv;
+    VT rv, zv;
+    if (PRE) zv = reinterpret_cast<const VT *>(dinv)[i];
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       rv[k] = bv[k] - qv[k];
       rr += (double)rv[k] * (double)rv[k];
       bb += (double)bv[k] * (double)bv[k];
+      if (PRE) {
+        const double z = (double)rv[k] * (double)zv[k];
+        rz += (double)rv[k] * z;
+        zv[k] = (V)z;
+      }
     }
     if (r) reinterpret_cast<VT *>(r)[i] = rv;
-    if (p) reinterpret_cast<VT *>(p)[i] = rv;
+    if (p) reinterpret_cast<VT *>(p)[i] = PRE ? zv : rv;
   }
   for (long long i = nv * W + t0; i < n; i += stride) {
     const V bi = b[i], ri = bi - q[i];
     if (r) r[i] = ri;
-    if (p) p[i] = ri;
+    if (PRE) {
+      const double z = (double)ri * (double)dinv[i];
+      rz += (double)ri * z;
+      if (p) p[i] = (V)z;
+    } else if (p) {
+      p[i] = ri;
+    }
     rr += (double)ri * (double)ri;
     bb += (double)bi * (double)bi;
   }
   rr = block_sum(rr);
   bb = block_sum(bb);
+  if (PRE) rz = block_sum(rz);
   if (threadIdx.x == 0) {
     part[slot_rr * kGrid + blockIdx.x] = rr;
     if (with_bb) part[P_BB * kGrid + blockIdx.x] = bb;
+    if (PRE) part[P_RZ0 * kGrid + blockIdx.x] = rz;
   }
 }
 
@@ -122,26 +163,31 @@ __global__ void __launch_bounds__(kThreads)
 }
 
 // alpha = rr / pq;  u += alpha p;  r -= alpha q;  part[rr of the next iteration] <- r . r
-template <typename V>
+// PRE: alpha = rz / pq, and part[rz of the next iteration] <- r . z with z = dinv r of the ROUNDED r
+template <typename V, bool PRE = false>
 __global__ void __launch_bounds__(kThreads)
     cg_update_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q,
-                     long long n, double *__restrict__ part, const int *__restrict__ ic, int it) {
+                     long long n, double *__restrict__ part, const int *__restrict__ ic, int it,
+                     const V *__restrict__ dinv = nullptr) {
   if (ic[I_DONE]) return;
-  const double pq = slot_sum(part, P_PQ), rr_old = slot_sum(part, P_RR0 + (it & 1));
+  const double pq = slot_sum(part, P_PQ), rr_old = slot_sum(part, (PRE ? P_RZ0 : P_RR0) + (it & 1));
   const double alpha = pq != 0.0 ? rr_old / pq : 0.0;
   constexpr int W = Vec16<V>::W;
   typedef typename Vec16<V>::type VT;
   const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  double s = 0.0;
+  double s = 0.0, sz = 0.0;
   for (long long i = t0; i < nv; i += stride) {
     VT uv = reinterpret_cast<VT *>(u)[i], rv = reinterpret_cast<VT *>(r)[i];
     const VT pv = reinterpret_cast<const VT *>(p)[i], qv = reinterpret_cast<const VT *>(q)[i];
+    VT dv;
+    if (PRE) dv = reinterpret_cast<const VT *>(dinv)[i];
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       uv[k] = (V)((double)uv[k] + alpha * (double)pv[k]);
       const double ri = (double)rv[k] - alpha * (double)qv[k];
       rv[k] = (V)ri;
       s += ri * ri;
+      if (PRE) sz += (double)rv[k] * ((double)rv[k] * (double)dv[k]);
     }
     reinterpret_cast<VT *>(u)[i] = uv;
     reinterpret_cast<VT *>(r)[i] = rv;
@@ -149,41 +195,56 @@ __global__ void __launch_bounds__(kThreads)
   for (long long i = nv * W + t0; i < n; i += stride) {
     u[i] = (V)((double)u[i] + alpha * (double)p[i]);
     const double ri = (double)r[i] - alpha * (double)q[i];
-    r[i] = (V)ri;
+    const V rn = (V)ri;
+    r[i] = rn;
     s += ri * ri;
+    if (PRE) sz += (double)rn * ((double)rn * (double)dinv[i]);
   }
   s = block_sum(s);
-  if (threadIdx.x == 0) part[(P_RR0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = s;
+  if (PRE) sz = block_sum(sz);
+  if (threadIdx.x == 0) {
+    part[(P_RR0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = s;
+    if (PRE) part[(P_RZ0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = sz;
+  }
 }
 
 // beta = rr' / rr;  p = r + beta p;  one thread: iteration count, convergence flag (rr' <= stop)
-template <typename V>
+// PRE: beta = rz' / rz;  p = dinv r + beta p;  the flag still from rr' (only workgroup 0 adds it up)
+template <typename V, bool PRE = false>
 __global__ void __launch_bounds__(kThreads)
     cg_direction_kernel(V *__restrict__ p, const V *__restrict__ r, long long n, const double *__restrict__ part,
-                        int *__restrict__ ic, int it, double stop) {
+                        int *__restrict__ ic, int it, double stop, const V *__restrict__ dinv = nullptr) {
   if (ic[I_DONE]) return;
-  const double rr = slot_sum(part, P_RR0 + (it & 1)), rrn = slot_sum(part, P_RR0 + ((it + 1) & 1));
+  const int s0 = PRE ? P_RZ0 : P_RR0;
+  const double rr = slot_sum(part, s0 + (it & 1)), rrn = slot_sum(part, s0 + ((it + 1) & 1));
   const double beta = rr != 0.0 ? rrn / rr : 0.0;
+  double res = rrn; // what the stopping rule looks at: r . r
+  if (PRE && blockIdx.x == 0) res = slot_sum(part, P_RR0 + ((it + 1) & 1));
   constexpr int W = Vec16<V>::W;
   typedef typename Vec16<V>::type VT;
   const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
   for (long long i = t0; i < nv; i += stride) {
     VT pv = reinterpret_cast<VT *>(p)[i];
     const VT rv = reinterpret_cast<const VT *>(r)[i];
+    VT dv;
+    if (PRE) dv = reinterpret_cast<const VT *>(dinv)[i];
 #pragma unroll
-    for (int k = 0; k < W; ++k) pv[k] = (V)((double)rv[k] + beta * (double)pv[k]);
+    for (int k = 0; k < W; ++k)
+      pv[k] = (V)((PRE ? (double)rv[k] * (double)dv[k] : (double)rv[k]) + beta * (double)pv[k]);
     reinterpret_cast<VT *>(p)[i] = pv;
   }
-  for (long long i = nv * W + t0; i < n; i += stride) p[i] = (V)((double)r[i] + beta * (double)p[i]);
+  for (long long i = nv * W + t0; i < n; i += stride)
+    p[i] = (V)((PRE ? (double)r[i] * (double)dinv[i] : (double)r[i]) + beta * (double)p[i]);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     ic[I_ITER] += 1; // (counted on the device: a replayed graph passes the same `it` again, only its parity matters)
     // (!(x > y): a NaN residual also ends the iteration)
-    if (!(rrn > stop)) ic[I_DONE] = 1;
+    if (!(res > stop)) ic[I_DONE] = 1;
   }
 }
 
 // u: in = first guess, out = solution.  Returns 0 / an error code; *iterations, *relres as documented in cfs_hip.h
-template <typename V, class Handle>
+// PRE: Jacobi (cfs_hip_sym_pcg); PRE = false is cfs_hip_sym_cg, launch for launch
+template <typename V, bool PRE = false, class Handle>
 int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int check_every, int *iterations,
        double *relres, hipStream_t st) {
   using cfs_rt::DevBuf;
@@ -200,8 +261,10 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
     return cfs_rt::set_err(CFS_HIP_ERR_ARG, "cg: u and b must be 16-byte aligned");
   V *u = (V *)u_dev;
   const V *b = (const V *)b_dev;
-  DevBuf rbuf, pbuf, qbuf, pbuf_part, cnt;
+  DevBuf rbuf, pbuf, qbuf, pbuf_part, cnt, dbuf;
   int rc;
+  if (PRE && (rc = dbuf.alloc((size_t)n * sizeof(V) + 64))) return rc;
+  const V *dinv = (const V *)dbuf.p;
   if ((rc = rbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf.alloc((size_t)n * sizeof(V) + 64)) ||
       (rc = qbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) ||
       (rc = cnt.alloc(I_COUNT * sizeof(int))))
@@ -220,14 +283,25 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
   };
   HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
   HIPCHK(hipMemsetAsync(ic, 0, I_COUNT * sizeof(int), st));
-  // r = b - A u, p = r, rr[0] = r . r, bb = b . b
+  if (PRE) { // dinv from the handle's own diagonal; entries that are not finite and > 0 are counted
+    if ((rc = h->diagonal(dbuf.p, st))) return rc;
+    hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)dbuf.p, n, part);
+  }
+  // r = b - A u, p = r, rr[0] = r . r, bb = b . b  (PRE: p = dinv r, rz[0] = r . p)
   if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
-  hipLaunchKernelGGL((cg_residual_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, r, p, b, (const V *)q, n, part,
-                     (int)P_RR0, 1);
+  hipLaunchKernelGGL((cg_residual_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, r, p, b, (const V *)q, n, part,
+                     (int)P_RR0, 1, dinv);
   HIPCHK(hipGetLastError());
   double rr0 = 0.0, bb = 0.0;
   if ((rc = read_slot(P_RR0, &rr0))) return rc;
   for (int g = 0; g < kGrid; g++) bb += hp[(size_t)P_BB * kGrid + g];
+  if (PRE) { // (read with the first host look: u has not been touched yet)
+    double bad = 0.0;
+    for (int g = 0; g < kGrid; g++) bad += hp[(size_t)P_BAD * kGrid + g];
+    if (bad != 0.0)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg: Jacobi needs a positive diagonal, " + std::to_string((long long)bad) +
+                                                  " of " + std::to_string(n) + " entries are zero, negative or not finite");
+  }
   const double stop = tol * tol * bb;
   bool done = !(rr0 > stop); // the first guess already solves it (or b = 0)
   int host_ic[I_COUNT] = {0, 0};
@@ -237,10 +311,10 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
     if (r2) return r2;
     hipLaunchKernelGGL((cg_pq_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part,
                        (const int *)ic);
-    hipLaunchKernelGGL((cg_update_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n,
-                       part, (const int *)ic, k);
-    hipLaunchKernelGGL((cg_direction_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
-                       (const double *)part, ic, k, stop);
+    hipLaunchKernelGGL((cg_update_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n,
+                       part, (const int *)ic, k, dinv);
+    hipLaunchKernelGGL((cg_direction_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
+                       (const double *)part, ic, k, stop, dinv);
     return 0;
   };
   // CFS_HIP_CG_GRAPH=1: two iterations (both parities) captured once and replayed as one graph launch.
@@ -287,8 +361,8 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
   }
   // the true residual of what is returned
   if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
-  hipLaunchKernelGGL((cg_residual_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b,
-                     (const V *)q, n, part, (int)P_RES, 0);
+  hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b,
+                     (const V *)q, n, part, (int)P_RES, 0, (const V *)nullptr);
   HIPCHK(hipGetLastError());
   double res2 = 0.0;
   if ((rc = read_slot(P_RES, &res2))) return rc;

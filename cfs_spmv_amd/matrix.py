@@ -55,6 +55,7 @@ FLAG_SHARD_EXCHANGE = 64  # include/cfs_hip.h: CFS_HIP_FLAG_SHARD_EXCHANGE
 FLAG_KEEP_VALUE_MAP = 2048  # CFS_HIP_FLAG_KEEP_VALUE_MAP
 FLAG_HOST_PLAN = 4096  # CFS_HIP_FLAG_HOST_PLAN: build the schedule with the host builder
 # CFS_HIP_KERNEL_WORDS: cfs_sym_tile_kernel<V, BLOCK, MODE, NT, OFFB, U, DET, COMB> ("value_bytes" = sizeof(V))
+PRECOND = {"none": _lib.PRECOND_NONE, "jacobi": _lib.PRECOND_JACOBI}  # CFS_HIP_PRECOND_*
 KERNEL_NAMES = ["value_bytes", "block", "mode", "nt", "offb", "u", "det", "comb"]
 DIGEST_WORDS = 28  # CFS_HIP_DIGEST_WORDS
 DIGEST_NAMES = ["tiles", "gfirst", "group_range", "slot_col", "rowinfo", "diag", "slice_meta", "leadlane",
@@ -229,6 +230,35 @@ class SymMatrix:
         it, res = C.c_int(), C.c_double()
         _lib.check(_lib.load().cfs_hip_sym_cg(self._h, _ptr(u), _ptr(b), float(tol), int(maxiter), int(check_every),
                                               C.byref(it), C.byref(res), _stream_ptr(stream)))
+        return it.value, res.value
+
+    def diagonal(self, out=None, stream=None):
+        """the diagonal of the rows this handle owns (cfs_hip_sym_diagonal_async): a device tensor of
+        row_end - row_begin values of the matrix's value type, 0 where the matrix stores no diagonal
+        entry, gathered from the handle's device arrays (so it follows update_values).  `out`: a
+        device tensor to fill instead of a new one."""
+        import torch
+        rows = self.row_end - self.row_begin
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if out is None:
+            out = torch.empty(rows, dtype=tdt, device="cuda")
+        elif out.dtype != tdt or out.numel() < rows or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {tdt} tensor of at least {rows} values")
+        _lib.check(_lib.load().cfs_hip_sym_diagonal_async(self._h, _ptr(out), _stream_ptr(stream)))
+        return out
+
+    def pcg(self, u, b, precond="jacobi", tol=1e-10, maxiter=1000, check_every=8, stream=None):
+        """preconditioned conjugate gradients inside the library (cfs_hip_sym_pcg): like cg(), with
+        precond = "jacobi" (the diagonal of the handle; it must be positive) or "none" (exactly
+        cg()).  Stops on the unpreconditioned residual ||r|| <= tol ||b||.  Returns (iterations,
+        ||b - A u|| / ||b||)."""
+        if isinstance(precond, str):
+            if precond not in PRECOND:
+                raise ValueError(f"unknown preconditioner {precond!r}: one of {sorted(PRECOND)}")
+            precond = PRECOND[precond]
+        it, res = C.c_int(), C.c_double()
+        _lib.check(_lib.load().cfs_hip_sym_pcg(self._h, _ptr(u), _ptr(b), int(precond), float(tol), int(maxiter),
+                                               int(check_every), C.byref(it), C.byref(res), _stream_ptr(stream)))
         return it.value, res.value
 
     # -- sharded operation --

@@ -1,4 +1,5 @@
-"""Solver-style caller of the SpMV path: conjugate gradients on resident vectors.
+"""Solver-style caller of the SpMV path: (Jacobi-preconditioned) conjugate gradients on
+resident vectors.
 
 SURVEY.md 8(f)-4 / 8(e): the reference's only caller is a benchmark loop with a
 fixed x; a solver feeds every product back as the next input, which is what the
@@ -44,6 +45,52 @@ def cg_native(A, b, tol=1e-10, maxiter=1000, x0=None, check_every=8):
     import torch
     u = torch.zeros_like(b) if x0 is None else x0.clone()
     it, res = A.cg(u, b, tol=tol, maxiter=maxiter, check_every=check_every)
+    return u, it, res
+
+
+def pcg(A, b, tol=1e-10, maxiter=1000, x0=None):
+    """Jacobi-preconditioned conjugate gradients, host-driven: the recurrence of cfs_hip_sym_pcg
+    (z = D^-1 r, alpha = r.z / p.q, beta = r'.z' / r.z, stop on the unpreconditioned ||r|| <= tol ||b||)
+    with the diagonal taken from the handle (A.diagonal()), so the caller's CSR is not needed.
+    Returns (u, iterations, relative residual), like cg()."""
+    import torch
+    d = A.diagonal()
+    if not bool(torch.all(torch.isfinite(d) & (d > 0))):
+        raise ValueError("pcg: Jacobi needs a positive diagonal")
+    dinv = (1.0 / d.double()).to(b.dtype)
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    q = torch.empty_like(b)
+    A.dense_vector_multiply(q, u)
+    r = b - q
+    z = r * dinv
+    p = z.clone()
+    rz = float(torch.dot(r, z))
+    rr = float(torch.dot(r, r))
+    bnorm = math.sqrt(float(torch.dot(b, b))) or 1.0
+    it = 0
+    while it < maxiter and math.sqrt(rr) > tol * bnorm:
+        A.dense_vector_multiply(q, p)          # the hot path
+        alpha = rz / float(torch.dot(p, q))
+        u.add_(p, alpha=alpha)
+        r.add_(q, alpha=-alpha)
+        torch.mul(r, dinv, out=z)
+        rz_new = float(torch.dot(r, z))
+        rr = float(torch.dot(r, r))
+        p.mul_(rz_new / rz).add_(z)
+        rz = rz_new
+        it += 1
+    A.dense_vector_multiply(q, u)
+    res = math.sqrt(float(torch.dot(b - q, b - q))) / bnorm
+    return u, it, res
+
+
+def pcg_native(A, b, precond="jacobi", tol=1e-10, maxiter=1000, x0=None, check_every=8):
+    """the same iteration inside the library (cfs_hip_sym_pcg): still five launches per iteration, the
+    diagonal gathered from the handle, z = D^-1 r never stored.  Returns (u, iterations, relative
+    residual), like pcg()."""
+    import torch
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    it, res = A.pcg(u, b, precond=precond, tol=tol, maxiter=maxiter, check_every=check_every)
     return u, it, res
 
 

@@ -259,8 +259,36 @@ int cfs_hip_sym_spmv(cfs_hip_sym_t h, void *y, const void *x);
  * the vector kernels run on its home device, the products on all of them); not a shard.       */
 int cfs_hip_sym_cg(cfs_hip_sym_t h, void *u_dev, const void *b_dev, double tol, int maxiter, int check_every,
                    int *iterations, double *relres, void *stream);
+/* The same iteration with a preconditioner.  CFS_HIP_PRECOND_NONE is cfs_hip_sym_cg: the same code
+ * path, the same bits.  CFS_HIP_PRECOND_JACOBI runs
+ *     r = b - A u;  z = D^-1 r;  p = z;  rz = r.z
+ *     q = A p;  alpha = rz / p.q;  u += alpha p;  r -= alpha q;  z = D^-1 r;  rz' = r.z;  rr' = r.r
+ *     beta = rz' / rz;  p = z + beta p
+ * with D the diagonal of the handle (gathered from its device arrays, as cfs_hip_sym_diagonal_async
+ * does, so it follows cfs_hip_sym_update_values_*).  STILL five launches per iteration and no host
+ * round trip: dinv_i = (V)(1.0 / (double)a_ii) is stored once in the value type; z_i = (double)r_i *
+ * (double)dinv_i (r_i as stored) is formed in fp64 inside the fused update (for r.z) and the direction
+ * kernel and never written to memory.  Stops on the UNPRECONDITIONED residual, r.r <= tol^2 b.b --
+ * the rule of cfs_hip_sym_cg, so iteration counts and tolerances of the two compare directly.
+ * Alignment, placement, check_every, *iterations, *relres, CFS_HIP_CG_GRAPH and the handles
+ * accepted are those of cfs_hip_sym_cg (a shard: CFS_HIP_ERR_UNSUPPORTED).  A diagonal entry that is
+ * zero (or not stored), negative or not finite: CFS_HIP_ERR_ARG, u untouched, *iterations = 0.  An
+ * unknown `precond`: CFS_HIP_ERR_ARG.                                                         */
+#define CFS_HIP_PRECOND_NONE 0
+#define CFS_HIP_PRECOND_JACOBI 1
+int cfs_hip_sym_pcg(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int precond, double tol, int maxiter,
+                    int check_every, int *iterations, double *relres, void *stream);
 int cfs_hip_sym_spmv_async(cfs_hip_sym_t h, void *y_dev, const void *x_dev,
                            void *stream);
+/* d_dev[i - row_begin] = a_ii for the rows the handle owns (n for a whole matrix, the block for a
+ * shard), 0 where the matrix stores none; device pointer of the handle's device and value type;
+ * enqueued on `stream`.  Read from the handle's DEVICE arrays, so it follows
+ * cfs_hip_sym_update_values_* and needs nothing of the caller's CSR (which may have been freed
+ * after tune()).  One launch, every entry written exactly once (no atomics, nothing zeroed first).
+ * A multi-device handle gathers every block on its shard's device and stream and brings it home
+ * the way the y block of an SpMV comes home (cfs_hip_sym_multi_set_xmode).  A null argument, a
+ * host pointer or a pointer on another device: CFS_HIP_ERR_ARG.                              */
+int cfs_hip_sym_diagonal_async(cfs_hip_sym_t h, void *d_dev, void *stream);
 
 /* ---- sharded operation: y_block = local rows; contributions to rows owned
  *      by lower ranks are packed into send_buf (device), exchanged by the

@@ -1,6 +1,9 @@
 """per-iteration time of conjugate gradients on resident vectors: the torch-driven loop of
 cfs_spmv_amd/solver.py (two host-read dot products per iteration) against cfs_hip_sym_cg (the whole
-iteration behind the C ABI, no host round trip).  Fixed number of iterations (tol = 0).
+iteration behind the C ABI, no host round trip), and the same pair with the Jacobi preconditioner
+(solver.pcg against cfs_hip_sym_pcg: dinv read in two kernels, 2 n s bytes more per iteration).
+Fixed number of iterations (tol = 0).  The Jacobi columns are left out when the library loaded
+through CFS_HIP_LIB has no cfs_hip_sym_pcg (an A/B run against an older build).
 usage: python tools/cg_bench.py [matrix[:scale] ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,7 +11,9 @@ import numpy as np
 import torch
 import cfs_spmv_amd as cfs
 from cfs_spmv_amd import synth
-from cfs_spmv_amd.solver import cg, cg_native
+from cfs_spmv_amd.solver import cg, cg_native, pcg, pcg_native
+
+HAVE_PCG = hasattr(cfs.load(), "cfs_hip_sym_pcg")
 
 out = {}
 for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
@@ -37,10 +42,18 @@ for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
             torch.cuda.current_stream().wait_stream(side)
             return out
         return run
-    for label, fn in (("torch_loop", lambda: cg(A, b, tol=0.0, maxiter=K)),
-                      ("native_side_stream", on_side(lambda: cg_native(A, b, tol=0.0, maxiter=K, check_every=16))),
-                      ("native_check8", lambda: cg_native(A, b, tol=0.0, maxiter=K, check_every=8)),
-                      ("native_check16", lambda: cg_native(A, b, tol=0.0, maxiter=K, check_every=16))):
+    runs = [("torch_loop", lambda: cg(A, b, tol=0.0, maxiter=K)),
+            ("native_side_stream", on_side(lambda: cg_native(A, b, tol=0.0, maxiter=K, check_every=16))),
+            ("native_check8", lambda: cg_native(A, b, tol=0.0, maxiter=K, check_every=8)),
+            ("native_check16", lambda: cg_native(A, b, tol=0.0, maxiter=K, check_every=16))]
+    if HAVE_PCG:
+        runs += [("jacobi_torch_loop", lambda: pcg(A, b, tol=0.0, maxiter=K)),
+                 ("jacobi_native_check8", lambda: pcg_native(A, b, tol=0.0, maxiter=K, check_every=8)),
+                 ("jacobi_native_check16", lambda: pcg_native(A, b, tol=0.0, maxiter=K, check_every=16))]
+        # bytes of the plain iteration (B_alg + 11 n s) against the 2 n s more that dinv costs
+        st, s_ = A.stats(), A.dtype.itemsize
+        res["jacobi_extra_bytes_ratio"] = round(2 * n * s_ / (st["bytes_algorithmic"] + 11 * n * s_), 4)
+    for label, fn in runs:
         fn()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
