@@ -138,8 +138,14 @@ typedef struct {
  * does not depend on how the matrix is scaled.  Costs LDS (26 instead of 16 bytes per
  * slot: smaller tiles) and ALU; 512- or 1 024-thread workgroups.  Far entries (HYB) are
  * covered: the x values they gather from outside the window enter the tile's scale.  A
- * contribution keeps 2^-80 of (row 1-norm) x (largest |x| the TILE reads).  A NaN / Inf in x or in the matrix reads
- * NaN in the rows it reaches.  Same tolerance against the oracle as the default.   */
+ * contribution keeps 2^-80 of (row 1-norm) x (largest |x| the TILE reads).
+ * NaN / Inf (they have no fixed-point image) are handled per TILE: every row that the contract at
+ * cfs_hip_sym_spmv calls non-finite reads NaN (never +-Inf, never a finite number), and so does every
+ * other slot of a tile whose window -- or whose far entries -- hold a non-finite x, and of a tile that
+ * holds a non-finite matrix value.  One bad x_j therefore costs at most (1 + rows that hold j) x
+ * max_slots_used rows, one bad a_ij = a_ji at most 2 x max_slots_used; every other row is the same
+ * number as without it, and the NaN pattern is as reproducible as the rest.
+ * Same tolerance against the oracle as the default.                                   */
 #define CFS_HIP_FLAG_DETERMINISTIC 1024
 /* keep, for every stored value of the device format, its position in the caller's CSR
  * value array (4 bytes per stored nonzero of device memory): cfs_hip_sym_update_values_*
@@ -243,7 +249,20 @@ int cfs_hip_sym_update_values_f32(cfs_hip_sym_t h, const float *values, long lon
  *                         so a caller that reads y back always sees it done.
  * cfs_hip_sym_spmv_async: device pointers only, enqueued on `stream`
  *                         (a hipStream_t; NULL = HIP's null stream), returns
- *                         immediately.                                       */
+ *                         immediately.
+ *
+ * NaN and Inf.  The product is y_i = d_i x_i + sum over the stored off-diagonal (i, j) of
+ * a_ij x_j, with d_i = 0 where no diagonal is stored (the reference's SSS kernels with their
+ * dense diagonal, csr_matrix.tpp:2989): row i is non-finite if and only if x_i is, or a stored
+ * (i, j) / (j, i) has a non-finite x_j or a_ij -- a missing diagonal does not shield a row from
+ * its own x_i -- and every other row is the number it would be without the NaN / Inf (no clamped
+ * or padded load is ever multiplied in).  Where x_i is finite the class of a non-finite y_i (NaN,
+ * +Inf, -Inf) is that of the plain IEEE evaluation.  Where x_i itself is non-finite, y_i has
+ * that class or is NaN: a row the schedule splits over several lanes carries its diagonal in
+ * the first lane only and adds 0 * x_i in the others, so x_i = +-Inf may give NaN there where the
+ * reference has +-Inf (which rows are split depends on the tile's other rows and on the order
+ * of the rows).  CFS_HIP_FLAG_DETERMINISTIC handles: per tile, see the flag.
+ * (tests/test_gpu_sym_confinement.py)                                                    */
 int cfs_hip_sym_spmv(cfs_hip_sym_t h, void *y, const void *x);
 /* A solver-style caller of the path, native (no counterpart in the reference: its only callers
  * are a benchmark loop and a self-check with a fixed x, bench/bench_spmv_mmf.cpp:139-173):

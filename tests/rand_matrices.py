@@ -404,3 +404,194 @@ def csr_confinement_case(rng, groups=12, rows=51, length=9):
     rowptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
     return (len(lengths), ncols, rowptr, np.concatenate(cols).astype(np.int32),
             np.asarray(special), np.asarray(owners))
+
+
+# ---- the symmetric tile path (cfs_sym_tile_kernel): a matrix whose every clamped, padded or shared
+# ---- load of the kernel has one designated column that a test may set to NaN / Inf
+SYM_CONFINE_RUN = 2400  # rows of the hub run: longer than a chunk of rows of any launch layout is
+
+
+def sym_confinement_case(rng, dof=None, n_nodes=36000, links=3):
+    """a chain of mesh nodes of 1-4 unknowns (`dof`: the same number for every node), each coupled --
+    dense blocks -- to the `links` nodes before it, with designed sites; pattern only.  Returns
+    (n, rowptr, colind, special, expect): `special` the columns a test poisons, all at once or one by
+    one, `expect[j]` the rows with a stored (i, j) or (j, i), and j itself (sorted).  No two special
+    columns share a row.  The sites, by the key of `expect.sites` (name -> column, or list of columns):
+
+      col0      column 0, the padding column of the far sections
+      band      a column of the plain band: in the packets of some rows, in the len % 4 leftovers of others
+      nodiag    a column whose own row stores no diagonal; a row that references it stores none either
+      sibling   node X of three unknowns coupled to 8 columns (two nodes of four), not to node X - 1;
+                its last row alone also holds the two unknowns of X - 1: three packets where its
+                siblings have two, the first extra column special -- the siblings follow the long row's
+                slots (a sibling chain) and are inactive in the packet that holds it
+      long_col  a row of 160 more lower entries (the 160 columns before it): split into virtual rows
+                in any tile of some rows; the special column lies in its last quarter
+      long_row  such a row, special itself: x_i of a split row
+      hub       the column before a run of SYM_CONFINE_RUN rows that hold exactly the 16 columns up to
+                it and nothing else: a tile inside the run has those 16 halo columns, the special one
+                the last slot of its window (natural order)
+      lonely    every 37th row of that run has no entry but the diagonal: no lower entries, zero packets.
+                Zero-packet rows sort behind all others, so the last virtual row of every tile inside
+                the run is one of them (tests pick out such tiles from the group features: one tile,
+                16 halo slots, no COO leftovers -- and ask for one whose virtual rows are no multiple of 64)
+      far_once  a column of the first quarter that one row of the last quarter references: a halo
+                column its tile uses once (a far entry under Format::hyb; strip and fold without),
+                an off-block column of every shard cut in between
+      far_node  the same, referenced by every row of two later nodes: a halo column owned by a much
+                earlier tile and used several times
+      sender    a ROW of the last quarter that references a column of the first quarter: in exchange
+                form its contribution to that column is packed and sent
+      last      row n - 1
+    The first-quarter / last-quarter sites lie below n // 4 and above 3 n // 4."""
+    assert links == 3 and n_nodes >= 8000
+    nd = rng.integers(1, 5, n_nodes) if dof is None else np.full(n_nodes, int(dof))
+    X, LA, LB, FN, SN = n_nodes // 2, n_nodes // 3, n_nodes // 3 + 800, n_nodes - 3000, n_nodes - 2000
+    nd[X - 3], nd[X - 2], nd[X - 1], nd[X] = 4, 4, 2, 3
+    nd[FN], nd[FN + 1] = 3, 2
+    # the hub run sits between node H - 1 and node H as SYM_CONFINE_RUN nodes of one unknown, uncoupled
+    H = 2 * n_nodes // 3
+    nd = np.concatenate([nd[:H], np.ones(SYM_CONFINE_RUN, np.int64), nd[H:]])
+    shift = lambda k: k if k < H else k + SYM_CONFINE_RUN  # node index after the insertion
+    nn = nd.size
+    first = np.concatenate([[0], np.cumsum(nd)])  # first unknown of every node
+    n = int(first[-1])
+    a = np.repeat(np.arange(nn), links)
+    b = a - np.tile(np.arange(1, links + 1), nn)
+    run = (np.arange(nn) >= H) & (np.arange(nn) < H + SYM_CONFINE_RUN)
+    keep = (b >= 0) & ~run[a] & ~run[np.maximum(b, 0)]
+    keep &= ~((a == X) & (b == X - 1))
+    N = sp.coo_matrix((np.ones(int(keep.sum())), (a[keep], b[keep])), shape=(nn, nn)) + sp.identity(nn)
+    node = np.repeat(np.arange(nn), nd)
+    E = sp.coo_matrix((np.ones(n), (np.arange(n), node)), shape=(n, nn)).tocsr()
+    L = sp.tril(E @ N.tocsr() @ E.T, k=-1).tocoo()
+    rows, cols = [L.row], [L.col]
+    extra = lambda r, c: (rows.append(np.broadcast_to(r, np.shape(c)).ravel()), cols.append(np.ravel(c)))
+    u = lambda k: int(first[shift(k)])  # first unknown of (original) node k
+    site = {"col0": 0, "band": u(n_nodes // 5) + 0, "nodiag": u(n_nodes // 5 + 400)}
+    # sibling: the last row of X also holds the two unknowns of X - 1
+    extra(u(X) + 2, np.array([u(X - 1), u(X - 1) + 1]))
+    site["sibling"] = u(X - 1)
+    # long rows: the 160 columns before the row's node
+    for key, k in (("long_col", LA), ("long_row", LB)):
+        r = u(k)
+        have = L.col[L.row == r]
+        c = np.setdiff1d(np.arange(u(k) - 160, u(k)), have)
+        extra(r, c)
+        site[key] = r - 40 if key == "long_col" else r
+    # hub run: rows hub + 1 .. hub + RUN hold the 16 columns hub - 15 .. hub; two of them nothing
+    hub = int(first[H]) - 1
+    lonely = [int(v) for v in hub + 1 + np.arange(20, SYM_CONFINE_RUN, 37)]
+    rr = np.setdiff1d(np.arange(hub + 1, hub + 1 + SYM_CONFINE_RUN), lonely)
+    extra(np.repeat(rr, 16), np.tile(np.arange(hub - 15, hub + 1), rr.size))
+    site["hub"], site["lonely"] = hub, lonely
+    # long-range couplings: first quarter <- last quarter
+    site["far_once"] = u(n_nodes // 10)
+    extra(u(SN), np.array([site["far_once"]]))
+    site["far_node"] = u(n_nodes // 10 + 300)
+    fr = np.arange(u(FN), u(FN + 2))
+    extra(fr, np.full(fr.size, site["far_node"]))
+    site["sender"] = u(SN + 500)
+    extra(site["sender"], np.array([u(n_nodes // 10 + 600)]))
+    site["last"] = n - 1
+    r, c = np.concatenate(rows), np.concatenate(cols)
+    assert np.all(c < r)
+    Lp = sp.coo_matrix((np.ones(r.size), (r, c)), shape=(n, n)).tocsr()
+    Lp.sum_duplicates()
+    Lp.data[:] = 1
+    d = np.ones(n)
+    d[site["nodiag"]] = 0
+    d[site["nodiag"] + int(nd[shift(n_nodes // 5 + 400)]) + 1] = 0  # a row of the next node: it references the column
+    A = (Lp + Lp.T + sp.diags(d)).tocsr()
+    A.eliminate_zeros()
+    A.sort_indices()
+    rp, ci = A.indptr.astype(np.int32), A.indices.astype(np.int32)
+    special = np.unique(np.concatenate([np.atleast_1d(v) for v in site.values()])).astype(np.int64)
+    S = (A + sp.identity(n)).tocsc()  # (row j itself whether or not it stores a diagonal)
+    expect = {int(j): np.unique(S.indices[S.indptr[j]:S.indptr[j + 1]]).astype(np.int64) for j in special}
+    allrows = np.concatenate(list(expect.values()))
+    assert np.unique(allrows).size == allrows.size, "two special columns share a row"
+    assert max(site["far_once"], site["far_node"], u(n_nodes // 10 + 600)) < n // 4
+    assert min(u(SN), u(FN), site["sender"]) > 3 * n // 4 + 1
+    expect = SymExpect(expect)
+    expect.sites = site
+    return n, rp, ci, special, expect
+
+
+class SymExpect(dict):
+    """expect of sym_confinement_case: {special column: rows}, and .sites = {site name: column(s)}"""
+    sites = None
+
+
+def sym_int_values(rng, n, rowptr, colind, dtype=np.float64):
+    """symmetric integer values for a pattern: off-diagonal +-1 .. +-8 (a_ij = a_ji), diagonal 1 .. 8;
+    and an integer x in -8 .. 8 without zeros.  Every product and every row sum of up to 2^18 entries
+    is an integer below 2^24: exact in fp32 and fp64 in any order.  Returns (values, x)."""
+    rowptr = np.asarray(rowptr, np.int64)
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    col = np.asarray(colind, np.int64)
+    lo, hi = np.minimum(row, col), np.maximum(row, col)
+    key = lo * n + hi
+    uniq, inv = np.unique(key, return_inverse=True)
+    v = rng.integers(1, 9, uniq.size) * rng.choice([-1, 1], uniq.size)
+    va = v[inv].astype(np.float64)
+    va[row == col] = np.abs(va[row == col])
+    x = (rng.integers(1, 9, n) * rng.choice([-1, 1], n)).astype(np.float64)
+    return va.astype(dtype), x.astype(dtype)
+
+
+def sym_reference(n, rowptr, colind, values, x):
+    """the contract of the symmetric path in plain IEEE arithmetic (float64, numpy):
+    y_i = d_i x_i + sum over the stored off-diagonal (i, j) of a_ij x_j, d_i = 0 where no diagonal is
+    stored -- so a missing diagonal does not shield row i from a NaN / Inf x_i (0 * Inf = NaN).
+    Returns y; a row is non-finite exactly where the contract says so, with its class."""
+    rowptr = np.asarray(rowptr, np.int64)
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    col = np.asarray(colind, np.int64)
+    va, x = np.asarray(values, np.float64), np.asarray(x, np.float64)
+    dg = np.zeros(n)
+    on = row == col
+    dg[row[on]] = va[on]
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = dg * x
+        np.add.at(y, row[~on], va[~on] * x[col[~on]])
+    return y
+
+
+def sym_int_product(n, rowptr, colind, values, x):
+    """A x in int64 for integer-valued data (finite entries only)"""
+    rowptr = np.asarray(rowptr, np.int64)
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    y = np.zeros(n, np.int64)
+    np.add.at(y, row, np.asarray(values).astype(np.int64) * np.asarray(x).astype(np.int64)[np.asarray(colind, np.int64)])
+    return y
+
+
+def sym_row_features(n, rowptr, colind, special, expect):
+    """what the CSR alone says about where each special column j sits in the rows that hold it (the
+    schedule stores the strict lower triangle of row i in stored order: the first 4 * (len // 4)
+    entries in packets, the last len % 4 as COO leftovers).  Returns {j: set of tags}: "packet" /
+    "leftover" (j in that part of some row i > j), "late" (beyond the first half of a row of >= 32
+    packets), "no_lower" (row j has no lower entry), "no_diag_self" / "no_diag_ref" (row j / a row
+    that references j stores no diagonal)."""
+    rowptr = np.asarray(rowptr, np.int64)
+    out = {}
+    for j in special:
+        j, tags = int(j), set()
+        for i in expect[j]:
+            c = np.asarray(colind[rowptr[i]:rowptr[i + 1]], np.int64)
+            low = c[c < i]
+            if i not in c:
+                tags.add("no_diag_self" if i == j else "no_diag_ref")
+            if i == j:
+                if low.size == 0:
+                    tags.add("no_lower")
+                continue
+            if i < j:
+                continue
+            at = int(np.flatnonzero(low == j)[0])
+            tags.add("packet" if at < 4 * (low.size // 4) else "leftover")
+            if low.size >= 128 and at >= low.size // 2 and at < 4 * (low.size // 4):
+                tags.add("late")
+        out[j] = tags
+    return out

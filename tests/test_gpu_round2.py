@@ -253,7 +253,12 @@ def test_deterministic_mode_propagates_nan_and_inf(where, bad):
                 va[q] = bad
     y_plain = _spmv(cfs.SymMatrix(n, rp, ci, va, options=cfs.make_options(flags=FLAG_NO_CAL)), x, torch)
     y_det = _spmv(cfs.SymMatrix(n, rp, ci, va, options=cfs.make_options(flags=FLAG_DET | FLAG_NO_CAL)), x, torch)
-    reached = ~np.isfinite(y_plain)  # the rows the bad number reaches in the default mode
+    # the rows the bad number reaches, from the CSR: row i itself and every row with a stored (r, i) for a
+    # bad x_i; rows i and c of a bad a_ic = a_ci -- and the default mode's non-finite rows are exactly those
+    reached = np.zeros(n, bool)
+    reached[i] = True
+    reached[ci[rp[i]:rp[i + 1]] if where == "x" else c] = True
+    assert np.array_equal(np.flatnonzero(~np.isfinite(y_plain)), np.flatnonzero(reached))
     assert reached.any()
     assert not np.isfinite(y_det[reached]).any(), "finite garbage where the default mode has NaN / Inf"
     # ... and rows of tiles it does not reach are still numbers
