@@ -12,6 +12,7 @@ class CfsHipError(RuntimeError):
 
 
 PRECOND_NONE, PRECOND_JACOBI = 0, 1  # include/cfs_hip.h: CFS_HIP_PRECOND_*
+EXCHANGE_REDUCE_SCATTER, EXCHANGE_SPARSE = 0, 1  # CFS_HIP_EXCHANGE_*
 ERR_ARG, ERR_DEVICE, ERR_UNSUPPORTED, ERR_NOMEM, ERR_INTERNAL, ERR_MIRROR = -1, -2, -3, -4, -5, -6
 
 
@@ -53,7 +54,7 @@ SYMBOLS = [
     "cfs_hip_memcpy", "cfs_hip_memset", "cfs_hip_sym_create_f64", "cfs_hip_sym_create_f32",
     "cfs_hip_sym_create_shard_f64", "cfs_hip_sym_create_shard_f32",
     "cfs_hip_sym_create_multi_f64", "cfs_hip_sym_create_multi_f32", "cfs_hip_comm_create", "cfs_hip_comm_info", "cfs_hip_comm_destroy", "cfs_hip_comm_reduce_scatter",
-    "cfs_hip_comm_allgather", "cfs_hip_comm_wait_consumed", "cfs_hip_sym_num_gpus", "cfs_hip_sym_multi_set_xmode", "cfs_hip_sym_multi_devices", "cfs_hip_sym_balanced_splits", "cfs_hip_sym_destroy", "cfs_hip_sym_update_values_f64", "cfs_hip_sym_update_values_f32", "cfs_hip_sym_spmv",
+    "cfs_hip_comm_allgather", "cfs_hip_comm_alltoallv", "cfs_hip_comm_wait_consumed", "cfs_hip_sym_num_gpus", "cfs_hip_sym_multi_set_xmode", "cfs_hip_sym_multi_set_exchange", "cfs_hip_sym_multi_exchange_info", "cfs_hip_sym_multi_devices", "cfs_hip_sym_balanced_splits", "cfs_hip_sym_destroy", "cfs_hip_sym_update_values_f64", "cfs_hip_sym_update_values_f32", "cfs_hip_sym_spmv",
     "cfs_hip_sym_spmv_async", "cfs_hip_sym_cg", "cfs_hip_sym_pcg", "cfs_hip_sym_diagonal_async", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
     "cfs_hip_sym_shard_set_recv", "cfs_hip_sym_spmv_local_async",
     "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_fold_lists", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
@@ -120,6 +121,10 @@ def load():
     if hasattr(lib, "cfs_hip_sym_multi_set_xmode"):
         lib.cfs_hip_sym_multi_set_xmode.argtypes = [vp, C.c_int]
         lib.cfs_hip_sym_multi_devices.argtypes = [vp, vp, C.c_int, ip]
+    if hasattr(lib, "cfs_hip_comm_alltoallv"):  # (absent from older builds loaded through CFS_HIP_LIB)
+        lib.cfs_hip_comm_alltoallv.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+        lib.cfs_hip_sym_multi_set_exchange.argtypes = [vp, C.c_int]
+        lib.cfs_hip_sym_multi_exchange_info.argtypes = [vp, ip, C.POINTER(i64), C.POINTER(i64)]
     lib.cfs_hip_sym_destroy.argtypes = [vp]
     lib.cfs_hip_sym_update_values_f64.argtypes = [vp, vp, C.c_longlong]
     lib.cfs_hip_sym_update_values_f32.argtypes = [vp, vp, C.c_longlong]

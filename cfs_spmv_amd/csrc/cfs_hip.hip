@@ -1977,6 +1977,81 @@ int cfs_hip_comm_allgather(cfs_hip_comm_t c, void *const *send, void *const *rec
   }
   return 0;
 }
+// the packed all-to-all: counts[g * N + r] values go from rank g (its blocks for r = 0..N-1 back
+// to back in send[g]) to rank r (the blocks from g = 0..N-1 back to back in recv[r])
+int cfs_hip_comm_alltoallv(cfs_hip_comm_t c, void *const *send, void *const *recv, const int64_t *counts,
+                           int value_bytes, void *const *streams) {
+  if (!c || !send || !recv || !counts || !streams || (value_bytes != 4 && value_bytes != 8))
+    return set_err(CFS_HIP_ERR_ARG, "bad argument");
+  const int N = (int)c->dev.size();
+  for (int g = 0; g < N; g++) {
+    int64_t out = 0, in = 0;
+    for (int r = 0; r < N; r++) {
+      if (counts[(size_t)g * N + r] < 0) return set_err(CFS_HIP_ERR_ARG, "alltoallv: negative count");
+      out += counts[(size_t)g * N + r];
+      in += counts[(size_t)r * N + g];
+    }
+    if ((out && !send[g]) || (in && !recv[g])) return set_err(CFS_HIP_ERR_ARG, "alltoallv: null buffer of a rank that moves values");
+  }
+  if (c->use_rccl) {
+    cfs_comm::Rccl &R = cfs_comm::rccl();
+    if (!R.p2p_ok)
+      return set_err(CFS_HIP_ERR_UNSUPPORTED, "alltoallv: librccl.so lacks ncclSend / ncclRecv (use the peer transport)");
+    const int dt = value_bytes == 8 ? cfs_comm::kNcclFloat64 : cfs_comm::kNcclFloat32;
+    int r2 = R.GroupStart();
+    for (int g = 0; g < N && r2 == 0; g++) {
+      DeviceGuard dg(c->dev[g]);
+      hipStream_t st = (hipStream_t)streams[g];
+      size_t soff = 0, roff = 0;
+      for (int r = 0; r < N && r2 == 0; r++) {
+        const size_t k = (size_t)counts[(size_t)g * N + r];
+        if (k) r2 = R.Send((const char *)send[g] + soff * value_bytes, k, dt, r, c->comm[g], st);
+        soff += k;
+      }
+      for (int s = 0; s < N && r2 == 0; s++) {
+        const size_t k = (size_t)counts[(size_t)s * N + g];
+        if (k) r2 = R.Recv((char *)recv[g] + roff * value_bytes, k, dt, s, c->comm[g], st);
+        roff += k;
+      }
+    }
+    const int r3 = R.GroupEnd();
+    if (r2 == 0) r2 = r3;
+    if (r2 != 0) return set_err(CFS_HIP_ERR_DEVICE, std::string("ncclSend / ncclRecv: ") + (R.GetErrorString ? R.GetErrorString(r2) : "?"));
+    return 0;
+  }
+  // peer transport: rank r pulls its blocks with one launch (cfs_peer_alltoallv_kernel)
+  for (int g = 0; g < N; g++) {
+    DeviceGuard dg(c->dev[g]);
+    HIPCHK(hipEventRecord(c->ready[g], (hipStream_t)streams[g]));
+  }
+  for (int r = 0; r < N; r++) {
+    DeviceGuard dg(c->dev[r]);
+    hipStream_t st = (hipStream_t)streams[r];
+    cfs_comm::A2aTable t;
+    memset(&t, 0, sizeof t);
+    t.nranks = N;
+    for (int g = 0; g < N; g++) {
+      size_t soff = 0; // where rank g's block for r starts in send[g]
+      for (int q = 0; q < r; q++) soff += (size_t)counts[(size_t)g * N + q];
+      const int64_t k = counts[(size_t)g * N + r];
+      t.src[g] = k ? (const char *)send[g] + soff * value_bytes : nullptr;
+      t.prefix[g + 1] = t.prefix[g] + k;
+      if (k) HIPCHK(hipStreamWaitEvent(st, c->ready[g], 0)); // (only the sources this rank reads)
+    }
+    const int64_t total = t.prefix[N];
+    if (total) {
+      const int grid = (int)std::min<int64_t>((total + 255) / 256, 2048);
+      if (value_bytes == 8)
+        hipLaunchKernelGGL((cfs_comm::cfs_peer_alltoallv_kernel<double>), dim3(grid), dim3(256), 0, st, (double *)recv[r], t);
+      else
+        hipLaunchKernelGGL((cfs_comm::cfs_peer_alltoallv_kernel<float>), dim3(grid), dim3(256), 0, st, (float *)recv[r], t);
+    }
+    HIPCHK(hipEventRecord(c->done[r], st));
+  }
+  c->done_valid = true;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 // ---------------------------------------------------------------------------
 // One host thread, N GPUs (the C++ surface with CFS_NUM_GPUS=N; reference knob:
@@ -2026,35 +2101,132 @@ struct MultiSym : cfs_hip_sym_s {
   // ranks, scatter them into a dense vector of N equal blocks and ONE native reduce-scatter
   // (cfs_hip_comm_*: RCCL over xGMI, or the peer transport) hands every owner its sums --
   // the north-star's form, without Python.  The local fold runs beside the collective.
+  //
+  // Two forms of that exchange on one handle (cfs_hip_sym_multi_set_exchange; the buffers of a
+  // form are allocated at its first use):
+  //   CFS_HIP_EXCHANGE_REDUCE_SCATTER  the dense one above: memset, tiles, pack, scatter, the sum
+  //       kernel (or ncclReduceScatter), local fold, add -- N * rs_rows values per rank;
+  //   CFS_HIP_EXCHANGE_SPARSE  the packed all-to-all (cfs_hip_comm_alltoallv): tiles, pack, the
+  //       pull kernel (or grouped ncclSend / ncclRecv), local fold, fold of what arrived -- one
+  //       value per remote boundary row, no memset, no scatter, no add.
   cfs_hip_comm_s *comm = nullptr;
+  int form = CFS_HIP_EXCHANGE_REDUCE_SCATTER;
   int rs_rows = 0; // block length of the reduce-scatter (longest row block)
-  std::vector<DevBuf> sbuf, pos, dense, rsout;
+  std::vector<DevBuf> sbuf, pos, dense, rsout, rbuf;
   std::vector<int> nsend_;
-  template <typename V> int setup_exchange(int transport) {
+  std::vector<int64_t> a2a_counts_; // N x N, [g * N + r] = values shard g packs for shard r
+  bool dense_ready_ = false, sparse_ready_ = false;
+  template <typename V> int setup_exchange(int transport, int first_form) {
     const int N = (int)shard.size();
     int rc = cfs_hip_comm_create(N, dev.data(), transport, &comm);
     if (rc) return rc;
     rs_rows = 0;
     for (int g = 0; g < N; g++) rs_rows = std::max(rs_rows, splits[g + 1] - splits[g]);
     sbuf = std::vector<DevBuf>(N);
-    pos = std::vector<DevBuf>(N);
-    dense = std::vector<DevBuf>(N);
-    rsout = std::vector<DevBuf>(N);
     nsend_.assign(N, 0);
     for (int g = 0; g < N; g++) {
       DeviceGuard dg(dev[g]);
-      const std::vector<int32_t> &rows = shard[g]->send_rows();
-      nsend_[g] = (int)rows.size();
-      std::vector<int32_t> p(rows.size());
-      for (size_t k = 0; k < rows.size(); k++) {
-        const int owner = (int)(std::upper_bound(splits.begin(), splits.end(), rows[k]) - splits.begin()) - 1;
-        p[k] = owner * rs_rows + (rows[k] - splits[owner]);
-      }
-      if ((rc = pos[g].upload(p.data(), p.size() * 4)) || (rc = sbuf[g].alloc(std::max<size_t>(1, rows.size()) * sizeof(V))) ||
-          (rc = dense[g].alloc((size_t)N * rs_rows * sizeof(V))) || (rc = rsout[g].alloc((size_t)rs_rows * sizeof(V))))
-        return rc;
-      // this shard receives nothing through the sparse route: recv side stays empty
+      nsend_[g] = (int)shard[g]->send_rows().size();
+      if ((rc = sbuf[g].alloc(std::max<size_t>(1, (size_t)nsend_[g]) * sizeof(V)))) return rc;
     }
+    if ((rc = ensure_form<V>(first_form))) return rc;
+    form = first_form;
+    return 0;
+  }
+  template <typename V> int ensure_form(int f) {
+    const int N = (int)shard.size();
+    int rc;
+    if (f == CFS_HIP_EXCHANGE_REDUCE_SCATTER && !dense_ready_) {
+      pos = std::vector<DevBuf>(N);
+      dense = std::vector<DevBuf>(N);
+      rsout = std::vector<DevBuf>(N);
+      for (int g = 0; g < N; g++) {
+        DeviceGuard dg(dev[g]);
+        const std::vector<int32_t> &rows = shard[g]->send_rows();
+        std::vector<int32_t> p(rows.size());
+        for (size_t k = 0; k < rows.size(); k++) {
+          const int owner = (int)(std::upper_bound(splits.begin(), splits.end(), rows[k]) - splits.begin()) - 1;
+          p[k] = owner * rs_rows + (rows[k] - splits[owner]);
+        }
+        if ((rc = pos[g].upload(p.data(), p.size() * 4)) || (rc = dense[g].alloc((size_t)N * rs_rows * sizeof(V))) ||
+            (rc = rsout[g].alloc((size_t)rs_rows * sizeof(V))))
+          return rc;
+        // this shard receives nothing through the sparse route: recv side stays empty
+      }
+      dense_ready_ = true;
+    }
+    if (f == CFS_HIP_EXCHANGE_SPARSE && !sparse_ready_) {
+      // the receive side: for every owner r the rows of each (higher) rank's send_rows() that are
+      // destined for r, concatenated by source rank -- the order cfs_hip_comm_alltoallv delivers
+      a2a_counts_.assign((size_t)N * N, 0);
+      std::vector<size_t> first((size_t)N * N, 0); // [g * N + r]: where g's block for r starts
+      for (int g = 0; g < N; g++) {
+        const std::vector<int32_t> &sc = shard[g]->send_counts();
+        size_t off = 0;
+        for (int r = 0; r < N && r < (int)sc.size(); r++) {
+          a2a_counts_[(size_t)g * N + r] = sc[r];
+          first[(size_t)g * N + r] = off;
+          off += (size_t)sc[r];
+        }
+        if (off != shard[g]->send_rows().size()) return set_err(CFS_HIP_ERR_INTERNAL, "send counts and send rows disagree");
+      }
+      rbuf = std::vector<DevBuf>(N);
+      for (int r = 0; r < N; r++) {
+        DeviceGuard dg(dev[r]);
+        std::vector<int> rows;
+        for (int g = 0; g < N; g++) {
+          const std::vector<int32_t> &sr = shard[g]->send_rows();
+          const size_t b = first[(size_t)g * N + r];
+          rows.insert(rows.end(), sr.begin() + b, sr.begin() + b + (size_t)a2a_counts_[(size_t)g * N + r]);
+        }
+        if ((rc = shard[r]->set_recv((int)rows.size(), rows.data())) ||
+            (rc = rbuf[r].alloc(std::max<size_t>(1, rows.size()) * sizeof(V))))
+          return rc;
+      }
+      sparse_ready_ = true;
+    }
+    return 0;
+  }
+  // sparse form, per shard stream: wait on start_, replicate x where copies(g), wait_consumed,
+  // tiles + pack into sbuf[g], the all-to-all, local fold, fold of rbuf[g], y block home, done_
+  template <typename V> int spmv_sparse(void *y, const void *x, hipStream_t st) {
+    const int N = (int)shard.size();
+    HIPCHK(hipEventRecord(start_, st));
+    void *sp[cfs_rt::kMaxDevices], *rp[cfs_rt::kMaxDevices], *streams[cfs_rt::kMaxDevices], *yg[cfs_rt::kMaxDevices];
+    const void *xg[cfs_rt::kMaxDevices];
+    int rc;
+    for (int g = 0; g < N; g++) {
+      DeviceGuard dg(dev[g]);
+      HIPCHK(hipStreamWaitEvent(st_[g], start_, 0));
+      xg[g] = x;
+      yg[g] = (char *)y + (size_t)splits[g] * value_bytes;
+      if (copies(g)) {
+        if ((rc = ensure_copies(g))) return rc;
+        HIPCHK(hipMemcpyPeerAsync(xrep[g].p, dev[g], x, device, (size_t)n_ * value_bytes, st_[g]));
+        xg[g] = xrep[g].p;
+        yg[g] = yloc[g].p;
+      }
+      if ((rc = cfs_hip_comm_wait_consumed(comm, g, st_[g]))) return rc;
+      if ((rc = shard[g]->spmv_local(yg[g], xg[g], sbuf[g].p, st_[g], CFS_HIP_PHASE_TILES | CFS_HIP_PHASE_PACK))) return rc;
+      sp[g] = sbuf[g].p;
+      rp[g] = rbuf[g].p;
+      streams[g] = (void *)st_[g];
+    }
+    if ((rc = cfs_hip_comm_alltoallv(comm, sp, rp, a2a_counts_.data(), value_bytes, streams))) return rc;
+    for (int g = 0; g < N; g++) {
+      DeviceGuard dg(dev[g]);
+      const int rows_g = splits[g + 1] - splits[g];
+      // (stream order, as in the dense form: the local fold is enqueued behind this rank's part of
+      // the collective; overlapping the two needs a second stream per shard)
+      if ((rc = shard[g]->spmv_local(yg[g], xg[g], sbuf[g].p, st_[g], CFS_HIP_PHASE_FOLD))) return rc;
+      if ((rc = shard[g]->recv_fold(yg[g], rbuf[g].p, st_[g]))) return rc;
+      if (copies(g) && rows_g > 0)
+        HIPCHK(hipMemcpyPeerAsync((char *)y + (size_t)splits[g] * value_bytes, device, yloc[g].p, dev[g],
+                                  (size_t)rows_g * value_bytes, st_[g]));
+      HIPCHK(hipEventRecord(done_[g], st_[g]));
+    }
+    for (int g = 0; g < N; g++) HIPCHK(hipStreamWaitEvent(st, done_[g], 0));
+    HIPCHK(hipGetLastError());
     return 0;
   }
   template <typename V> int spmv_exchange(void *y, const void *x, hipStream_t st) {
@@ -2123,6 +2295,8 @@ struct MultiSym : cfs_hip_sym_s {
     delete comm;
   }
   int spmv_local(void *y, const void *x, void *, hipStream_t st, int phases) override {
+    if (comm && form == CFS_HIP_EXCHANGE_SPARSE)
+      return value_bytes == 8 ? spmv_sparse<double>(y, x, st) : spmv_sparse<float>(y, x, st);
     if (comm) return value_bytes == 8 ? spmv_exchange<double>(y, x, st) : spmv_exchange<float>(y, x, st);
     HIPCHK(hipEventRecord(start_, st));
     for (size_t g = 0; g < shard.size(); g++) {
@@ -2254,9 +2428,14 @@ static int sym_create_multi(int n, const int *rowptr, const int *colind, const V
   if (opt) o2 = *opt;
   // default: mirrored shards, nothing to exchange.  With CFS_HIP_FLAG_SHARD_EXCHANGE (or
   // CFS_MULTI_EXCHANGE=reduce_scatter) the shards take the exchange form and one native
-  // reduce-scatter per SpMV (MultiSym::spmv_exchange)
+  // reduce-scatter per SpMV (MultiSym::spmv_exchange); CFS_MULTI_EXCHANGE=sparse: the same
+  // shards and the packed all-to-all (MultiSym::spmv_sparse)
   bool exchange = (o2.flags & CFS_HIP_FLAG_SHARD_EXCHANGE) != 0;
-  if (const char *e = getenv("CFS_MULTI_EXCHANGE")) exchange = !strcmp(e, "reduce_scatter");
+  int first_form = CFS_HIP_EXCHANGE_REDUCE_SCATTER;
+  if (const char *e = getenv("CFS_MULTI_EXCHANGE")) {
+    exchange = !strcmp(e, "reduce_scatter") || !strcmp(e, "sparse");
+    if (!strcmp(e, "sparse")) first_form = CFS_HIP_EXCHANGE_SPARSE;
+  }
   if (ngpus < 2) exchange = false;
   if (exchange) o2.flags = (o2.flags | CFS_HIP_FLAG_SHARD_EXCHANGE) & ~(CFS_HIP_FLAG_HYB);
   else o2.flags &= ~CFS_HIP_FLAG_SHARD_EXCHANGE;
@@ -2307,7 +2486,7 @@ static int sym_create_multi(int n, const int *rowptr, const int *colind, const V
     int transport = CFS_HIP_TRANSPORT_AUTO;
     if (const char *e = getenv("CFS_MULTI_TRANSPORT"))
       transport = !strcmp(e, "rccl") ? CFS_HIP_TRANSPORT_RCCL : (!strcmp(e, "peer") ? CFS_HIP_TRANSPORT_PEER : CFS_HIP_TRANSPORT_AUTO);
-    if ((rc = m->template setup_exchange<V>(transport))) {
+    if ((rc = m->template setup_exchange<V>(transport, first_form))) {
       std::string e = cfs_rt::last_error();
       delete m;
       return set_err(rc, e);
@@ -2337,6 +2516,37 @@ int cfs_hip_sym_multi_set_xmode(cfs_hip_sym_t h, int xmode) {
     HIPCHK(hipStreamSynchronize(m->st_[g]));
   }
   m->xmode = xmode;
+  return 0;
+}
+int cfs_hip_sym_multi_set_exchange(cfs_hip_sym_t h, int form) {
+  if (!h) return set_err(CFS_HIP_ERR_ARG, "null handle");
+  auto *m = dynamic_cast<MultiSym *>(h);
+  if (!m || !m->comm) return set_err(CFS_HIP_ERR_ARG, "not an exchange-form multi-device handle");
+  if (form != CFS_HIP_EXCHANGE_REDUCE_SCATTER && form != CFS_HIP_EXCHANGE_SPARSE)
+    return set_err(CFS_HIP_ERR_ARG, "unknown exchange form");
+  // pending SpMVs of the other form finish first (the receive side is uploaded below)
+  for (size_t g = 0; g < m->shard.size(); g++) {
+    DeviceGuard dg(m->dev[g]);
+    HIPCHK(hipStreamSynchronize(m->st_[g]));
+  }
+  int rc = m->value_bytes == 8 ? m->ensure_form<double>(form) : m->ensure_form<float>(form);
+  if (rc) return rc;
+  m->form = form;
+  return 0;
+}
+int cfs_hip_sym_multi_exchange_info(cfs_hip_sym_t h, int *form, int64_t *values_moved, int64_t *bytes_moved) {
+  if (!h) return set_err(CFS_HIP_ERR_ARG, "null handle");
+  auto *m = dynamic_cast<MultiSym *>(h);
+  if (!m || !m->comm) return set_err(CFS_HIP_ERR_ARG, "not an exchange-form multi-device handle");
+  const int64_t N = (int64_t)m->shard.size();
+  int64_t v = 0;
+  if (m->form == CFS_HIP_EXCHANGE_SPARSE)
+    for (int k : m->nsend_) v += k;
+  else
+    v = N * N * m->rs_rows;
+  if (form) *form = m->form;
+  if (values_moved) *values_moved = v;
+  if (bytes_moved) *bytes_moved = v * m->value_bytes;
   return 0;
 }
 int cfs_hip_sym_multi_devices(cfs_hip_sym_t h, int *devices, int capacity, int *distinct) {

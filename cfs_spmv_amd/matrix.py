@@ -55,6 +55,8 @@ FLAG_SHARD_EXCHANGE = 64  # include/cfs_hip.h: CFS_HIP_FLAG_SHARD_EXCHANGE
 FLAG_KEEP_VALUE_MAP = 2048  # CFS_HIP_FLAG_KEEP_VALUE_MAP
 FLAG_HOST_PLAN = 4096  # CFS_HIP_FLAG_HOST_PLAN: build the schedule with the host builder
 # CFS_HIP_KERNEL_WORDS: cfs_sym_tile_kernel<V, BLOCK, MODE, NT, OFFB, U, DET, COMB> ("value_bytes" = sizeof(V))
+EXCHANGE_REDUCE_SCATTER, EXCHANGE_SPARSE = _lib.EXCHANGE_REDUCE_SCATTER, _lib.EXCHANGE_SPARSE  # CFS_HIP_EXCHANGE_*
+EXCHANGE = {"reduce_scatter": EXCHANGE_REDUCE_SCATTER, "sparse": EXCHANGE_SPARSE}
 PRECOND = {"none": _lib.PRECOND_NONE, "jacobi": _lib.PRECOND_JACOBI}  # CFS_HIP_PRECOND_*
 KERNEL_NAMES = ["value_bytes", "block", "mode", "nt", "offb", "u", "det", "comb"]
 DIGEST_WORDS = 28  # CFS_HIP_DIGEST_WORDS
@@ -260,6 +262,23 @@ class SymMatrix:
         _lib.check(_lib.load().cfs_hip_sym_pcg(self._h, _ptr(u), _ptr(b), int(precond), float(tol), int(maxiter),
                                                int(check_every), C.byref(it), C.byref(res), _stream_ptr(stream)))
         return it.value, res.value
+
+    # -- the exchange of a one-process multi-device handle (ngpus > 1, FLAG_SHARD_EXCHANGE) --
+    def set_exchange(self, form):
+        """"sparse": one packed all-to-all per SpMV (cfs_hip_comm_alltoallv); "reduce_scatter": the
+        dense reduce-scatter.  Switchable at any time (cfs_hip_sym_multi_set_exchange)."""
+        if isinstance(form, str):
+            if form not in EXCHANGE:
+                raise ValueError(f"unknown exchange form {form!r}: one of {sorted(EXCHANGE)}")
+            form = EXCHANGE[form]
+        _lib.check(_lib.load().cfs_hip_sym_multi_set_exchange(self._h, int(form)))
+
+    def exchange_info(self):
+        """dict(form, values_moved, bytes_moved): the current form and what the ranks hand to the
+        collective per SpMV under it (cfs_hip_sym_multi_exchange_info)"""
+        form, vals, nbytes = C.c_int(), C.c_int64(), C.c_int64()
+        _lib.check(_lib.load().cfs_hip_sym_multi_exchange_info(self._h, C.byref(form), C.byref(vals), C.byref(nbytes)))
+        return {"form": form.value, "values_moved": vals.value, "bytes_moved": nbytes.value}
 
     # -- sharded operation --
     def send_counts(self):

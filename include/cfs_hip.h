@@ -217,6 +217,24 @@ int cfs_hip_sym_num_gpus(cfs_hip_sym_t h, int *ngpus); /* shards of the handle (
 #define CFS_HIP_XMODE_REPLICATE 1
 #define CFS_HIP_XMODE_REPLICATE_ALL 2
 int cfs_hip_sym_multi_set_xmode(cfs_hip_sym_t h, int xmode);
+/* The exchange of a multi-device handle whose shards are in the exchange form
+ * (CFS_HIP_FLAG_SHARD_EXCHANGE at create, or env CFS_MULTI_EXCHANGE=reduce_scatter | sparse), switched
+ * at run time; the buffers of a form are allocated at its first use.
+ * REDUCE_SCATTER (what the flag alone selects): the packed contributions are scattered into a zeroed
+ * vector of ngpus equal blocks and ONE cfs_hip_comm_reduce_scatter hands every owner its sums --
+ * seven launches per shard and SpMV (memset, tiles, pack, scatter, sum, local fold, add).
+ * SPARSE (CFS_MULTI_EXCHANGE=sparse at create): ONE cfs_hip_comm_alltoallv moves the packed values
+ * alone, one per remote boundary row, and the owner folds them in with the receive fold of a shard
+ * (cfs_hip_sym_shard_set_recv, built here at the first switch) -- five launches (tiles, pack, pull,
+ * local fold, receive fold).  A mirrored multi-device handle, a plain handle, a shard, NULL or an
+ * unknown form: CFS_HIP_ERR_ARG.                                                            */
+#define CFS_HIP_EXCHANGE_REDUCE_SCATTER 0
+#define CFS_HIP_EXCHANGE_SPARSE 1
+int cfs_hip_sym_multi_set_exchange(cfs_hip_sym_t h, int form);
+/* *form = the current form; *values_moved = values the ranks hand to the collective per SpMV under
+ * it (SPARSE: the sum of the shards' packed values; REDUCE_SCATTER: ngpus * ngpus * longest block);
+ * *bytes_moved = that times the value size.  Any of the three may be NULL.  Handles: as above. */
+int cfs_hip_sym_multi_exchange_info(cfs_hip_sym_t h, int *form, int64_t *values_moved, int64_t *bytes_moved);
 /* devices[g] = device of shard g (may be NULL); *distinct = number of distinct devices */
 int cfs_hip_sym_multi_devices(cfs_hip_sym_t h, int *devices, int capacity, int *distinct);
 /* nnz_low-balanced row boundaries (multiples of 16, csr_matrix.tpp:418) for
@@ -363,6 +381,17 @@ int cfs_hip_comm_reduce_scatter(cfs_hip_comm_t c, void *const *send, void *const
                                 int value_bytes, void *const *streams);
 /* all-gather: recv[g] (ndev * count values) = the blocks send[0..ndev-1] (count values each) */
 int cfs_hip_comm_allgather(cfs_hip_comm_t c, void *const *send, void *const *recv, size_t count,
+                           int value_bytes, void *const *streams);
+/* packed all-to-all (the sparse form of the reduce-scatter): counts is a HOST array of ndev * ndev
+ * entries, counts[g * ndev + r] = values rank g hands to rank r.  send[g] holds rank g's blocks for
+ * r = 0..ndev-1 back to back (the order of cfs_hip_sym_shard_send_counts / the pack), recv[r] the
+ * blocks from g = 0..ndev-1 back to back (the "concatenated by source rank" order of
+ * cfs_hip_sym_shard_set_recv).  Zero counts and self blocks (g = r) are legal; a rank that sends
+ * (receives) nothing may pass NULL for its send (receive) buffer.  Enqueued on streams[g], returns
+ * at once; counts is read before the call returns.  PEER: one pull kernel per receiving rank; RCCL:
+ * ncclSend / ncclRecv in one group (a librccl.so without them: CFS_HIP_ERR_UNSUPPORTED).  value_bytes
+ * other than 4 or 8, a null argument or a negative count: CFS_HIP_ERR_ARG.                  */
+int cfs_hip_comm_alltoallv(cfs_hip_comm_t c, void *const *send, void *const *recv, const int64_t *counts,
                            int value_bytes, void *const *streams);
 /* before rank `rank` overwrites its send buffer on `stream`: wait until the previous
  * collective has consumed it (PEER transport: other ranks' kernels read it)                */

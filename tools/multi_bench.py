@@ -1,7 +1,8 @@
 """One process, N row blocks (cfs_hip_sym_create_multi_*: what CSRMatrix::tune builds for
 CFS_NUM_GPUS=N): ms per SpMV of the native forms of the one-process multi-device handle --
 mirrored shards with x over peer access / replicated x, and the exchange form with one native
-reduce-scatter per SpMV (cfs_hip_comm_*).  On a one-GPU box the N shards share the device (a
+reduce-scatter per SpMV or, on the SAME handle, one packed all-to-all (cfs_hip_comm_*;
+cfs_hip_sym_multi_set_exchange), with the values and bytes each form hands to its collective.  On a one-GPU box the N shards share the device (a
 REHEARSAL of the code paths: copies are device-local, the collective runs on the peer
 transport); on an N-GPU node the same script times the real thing.
 usage: multi_bench.py [matrix] [scale] [ngpus ...]"""
@@ -54,8 +55,12 @@ for N in counts:
         assert float((y - yref).abs().max()) < 1e-9
     A.close()
     A = cfs.SymMatrix(n, rp, ci, va, ngpus=N, options=cfs.make_options(flags=32 | cfs.FLAG_SHARD_EXCHANGE))
-    res["exchange_reduce_scatter_native"] = timed(A)
-    assert float((y - yref).abs().max()) < 1e-9
+    for form, tag in (("reduce_scatter", "exchange_reduce_scatter_native"), ("sparse", "exchange_sparse_native")):
+        A.set_exchange(form)
+        res[tag] = timed(A)
+        assert float((y - yref).abs().max()) < 1e-9
+        info = A.exchange_info()
+        res[tag + "_values_moved"], res[tag + "_bytes_moved"] = info["values_moved"], info["bytes_moved"]
     A.close()
     res["shards_per_device"] = -(-N // max(1, ndev))
     out["forms"][str(N)] = res
