@@ -83,12 +83,18 @@ inline Rccl &rccl() {
 constexpr int kNcclSum = 0, kNcclFloat32 = 7, kNcclFloat64 = 8; // rccl.h enumerators
 
 // out[i] = sum over ranks g of in[g][off + i]  (the peer transport's reduce-scatter)
+// The table of the ranks' send buffers travels BY VALUE in the kernel-argument segment, like the
+// all-to-all's below: it is read from the caller's array before the call returns, and nothing is
+// copied from host memory behind the event waits of a stream.
+struct SumTable {
+  const void *src[cfs_rt::kMaxDevices];
+  int nranks;
+};
 template <typename V>
-__global__ void __launch_bounds__(256)
-    cfs_peer_sum_kernel(V *__restrict__ out, const V *const *__restrict__ in, int nranks, size_t off, size_t count) {
+__global__ void __launch_bounds__(256) cfs_peer_sum_kernel(V *__restrict__ out, const SumTable t, size_t off, size_t count) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
     V s = V(0);
-    for (int g = 0; g < nranks; ++g) s += in[g][off + i]; // fixed order: bit-reproducible
+    for (int g = 0; g < t.nranks; ++g) s += ((const V *)t.src[g])[off + i]; // fixed order: bit-reproducible
     out[i] = s;
   }
 }
@@ -130,8 +136,8 @@ struct cfs_hip_comm_s {
   std::vector<void *> comm;      // RCCL communicators (transport rccl)
   bool use_rccl = false;
   std::string note;              // why the peer transport is in use
-  std::vector<cfs_rt::DevBuf> ptrs; // per rank: the table of the ranks' send buffers (peer transport)
   std::vector<hipEvent_t> ready, done; // peer transport: send buffer written / block summed
+  std::vector<hipEvent_t> entered;     // peer all-gather: what rank r enqueued before the call is behind it
   bool done_valid = false;
   ~cfs_hip_comm_s() {
     for (size_t g = 0; g < dev.size(); g++) {
@@ -139,6 +145,7 @@ struct cfs_hip_comm_s {
       if (use_rccl && g < comm.size() && comm[g]) (void)cfs_comm::rccl().CommDestroy(comm[g]);
       if (g < ready.size() && ready[g]) (void)hipEventDestroy(ready[g]);
       if (g < done.size() && done[g]) (void)hipEventDestroy(done[g]);
+      if (g < entered.size() && entered[g]) (void)hipEventDestroy(entered[g]);
     }
   }
 };

@@ -1852,9 +1852,9 @@ int cfs_hip_comm_create(int ndev, const int *devices, int transport, cfs_hip_com
       return set_err(CFS_HIP_ERR_DEVICE, "ncclCommInitAll: " + e);
     }
   } else {
-    c->ptrs = std::vector<DevBuf>(ndev);
     c->ready.assign(ndev, nullptr);
     c->done.assign(ndev, nullptr);
+    c->entered.assign(ndev, nullptr);
     for (int g = 0; g < ndev; g++) {
       DeviceGuard dg(c->dev[g]);
       for (int q = 0; q < ndev; q++) // every rank reads every other rank's buffers
@@ -1873,9 +1873,9 @@ int cfs_hip_comm_create(int ndev, const int *devices, int transport, cfs_hip_com
         }
       if (hipEventCreateWithFlags(&c->ready[g], hipEventDisableTiming) != hipSuccess ||
           hipEventCreateWithFlags(&c->done[g], hipEventDisableTiming) != hipSuccess ||
-          c->ptrs[g].alloc((size_t)ndev * sizeof(void *)) != 0) {
+          hipEventCreateWithFlags(&c->entered[g], hipEventDisableTiming) != hipSuccess) {
         delete c;
-        return set_err(CFS_HIP_ERR_DEVICE, "event / table creation failed");
+        return set_err(CFS_HIP_ERR_DEVICE, "event creation failed");
       }
     }
   }
@@ -1924,19 +1924,23 @@ int cfs_hip_comm_reduce_scatter(cfs_hip_comm_t c, void *const *send, void *const
     DeviceGuard dg(c->dev[g]);
     HIPCHK(hipEventRecord(c->ready[g], (hipStream_t)streams[g]));
   }
+  // (the table of send buffers goes to the kernels by value: read here, before the call returns)
+  cfs_comm::SumTable t;
+  memset(&t, 0, sizeof t);
+  t.nranks = N;
+  for (int g = 0; g < N; g++) t.src[g] = send[g];
   for (int r = 0; r < N; r++) {
     DeviceGuard dg(c->dev[r]);
     hipStream_t st = (hipStream_t)streams[r];
     for (int g = 0; g < N; g++) HIPCHK(hipStreamWaitEvent(st, c->ready[g], 0));
-    HIPCHK(hipMemcpyAsync(c->ptrs[r].p, send, (size_t)N * sizeof(void *), hipMemcpyHostToDevice, st));
     const int grid = (int)std::min<size_t>((count + 255) / 256, 2048);
     if (count) {
       if (value_bytes == 8)
-        hipLaunchKernelGGL((cfs_comm::cfs_peer_sum_kernel<double>), dim3(grid), dim3(256), 0, st, (double *)recv[r],
-                           (const double *const *)c->ptrs[r].p, N, (size_t)r * count, count);
+        hipLaunchKernelGGL((cfs_comm::cfs_peer_sum_kernel<double>), dim3(grid), dim3(256), 0, st, (double *)recv[r], t,
+                           (size_t)r * count, count);
       else
-        hipLaunchKernelGGL((cfs_comm::cfs_peer_sum_kernel<float>), dim3(grid), dim3(256), 0, st, (float *)recv[r],
-                           (const float *const *)c->ptrs[r].p, N, (size_t)r * count, count);
+        hipLaunchKernelGGL((cfs_comm::cfs_peer_sum_kernel<float>), dim3(grid), dim3(256), 0, st, (float *)recv[r], t,
+                           (size_t)r * count, count);
     }
     HIPCHK(hipEventRecord(c->done[r], st));
   }
@@ -1962,11 +1966,19 @@ int cfs_hip_comm_allgather(cfs_hip_comm_t c, void *const *send, void *const *rec
     if (r2 != 0) return set_err(CFS_HIP_ERR_DEVICE, std::string("ncclAllGather: ") + (R.GetErrorString ? R.GetErrorString(r2) : "?"));
     return 0;
   }
-  // peer transport: rank g pushes its block into every rank's receive buffer
+  // peer transport: rank g pushes its block into every rank's receive buffer -- behind what rank r
+  // had enqueued on its own stream when the call was made (`entered[r]`): r may still be reading
+  // recv[r] of the round before
   const size_t bytes = count * (size_t)value_bytes;
+  for (int r = 0; r < N; r++) {
+    DeviceGuard dg(c->dev[r]);
+    HIPCHK(hipEventRecord(c->entered[r], (hipStream_t)streams[r]));
+  }
   for (int g = 0; g < N; g++) {
     DeviceGuard dg(c->dev[g]);
     hipStream_t st = (hipStream_t)streams[g];
+    for (int r = 0; r < N && bytes; r++)
+      if (r != g) HIPCHK(hipStreamWaitEvent(st, c->entered[r], 0));
     for (int r = 0; r < N && bytes; r++)
       HIPCHK(hipMemcpyPeerAsync((char *)recv[r] + (size_t)g * bytes, c->dev[r], send[g], c->dev[g], bytes, st));
     HIPCHK(hipEventRecord(c->ready[g], st));

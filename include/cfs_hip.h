@@ -366,7 +366,21 @@ int cfs_hip_sym_spmv_phases_async(cfs_hip_sym_t h, void *y_block_dev,
  *      (plain kernels / copies over peer access: what several ranks on ONE device -- the
  *      test boxes -- use, RCCL refusing two ranks per device; also the fall-back when RCCL
  *      cannot be loaded).  AUTO = RCCL when the devices are distinct and it loads.
- *      NOTE: with more than one rank the RCCL transport has not run on hardware yet.      */
+ *      NOTE: what has run on hardware is the PEER transport with 2 / 3 / 4 / 8 ranks sharing one
+ *      device and the RCCL transport with ONE rank (tests/test_gpu_comm.py, test_gpu_comm_edges.py,
+ *      test_gpu_sparse_exchange.py).  With more than one rank the RCCL transport has not run on
+ *      hardware yet, nor has the PEER transport between two physical devices.
+ *
+ *      Buffers and streams, all three collectives (pinned by tests/test_gpu_comm_edges.py):
+ *      - a call is enqueued on streams[0..ndev-1] and returns at once; the host arrays it is given
+ *        (send, recv, streams, counts) are read before it returns and may be reused or freed then;
+ *      - rank g's part runs behind what is on streams[g] at the call: what g enqueued there before --
+ *        writing its send buffer, reading its receive buffer of an earlier round -- is ordered before
+ *        this call's reads of send[g] AND before its writes to recv[g], whichever rank's stream does
+ *        them; work enqueued on streams[g] after the call sees recv[g] complete;
+ *      - a send buffer is read by OTHER ranks' streams (PEER reduce-scatter and all-to-all): before
+ *        rank g overwrites send[g], cfs_hip_comm_wait_consumed(c, g, streams[g]).  The all-gather
+ *        reads send[g] on streams[g] itself and needs no such call.                            */
 typedef struct cfs_hip_comm_s *cfs_hip_comm_t;
 #define CFS_HIP_TRANSPORT_AUTO 0
 #define CFS_HIP_TRANSPORT_RCCL 1
@@ -376,10 +390,15 @@ int cfs_hip_comm_create(int ndev, const int *devices, int transport, cfs_hip_com
 int cfs_hip_comm_info(cfs_hip_comm_t c, int *ndev, int *transport);
 int cfs_hip_comm_destroy(cfs_hip_comm_t c);
 /* sum-reduce-scatter: rank g contributes send[g] (ndev * count values, on its device) and
- * receives the g-th block of the sum in recv[g] (count values); enqueued on streams[g]     */
+ * receives the g-th block of the sum in recv[g] (count values); enqueued on streams[g], returns at
+ * once; the tables are read before it returns (PEER: they go to the sum kernels by value).  PEER
+ * adds in rank order from 0: the sum is the same bits in every call.  count = 0 moves nothing.  */
 int cfs_hip_comm_reduce_scatter(cfs_hip_comm_t c, void *const *send, void *const *recv, size_t count,
                                 int value_bytes, void *const *streams);
-/* all-gather: recv[g] (ndev * count values) = the blocks send[0..ndev-1] (count values each) */
+/* all-gather: recv[g] (ndev * count values) = the blocks send[0..ndev-1] (count values each);
+ * enqueued on streams[g], returns at once.  PEER: rank g pushes its block into every recv[r] on
+ * streams[g], behind an event recorded on streams[r] at entry -- so a rank that is still reading
+ * recv[r] of the round before, on its own stream, is not overtaken.                          */
 int cfs_hip_comm_allgather(cfs_hip_comm_t c, void *const *send, void *const *recv, size_t count,
                            int value_bytes, void *const *streams);
 /* packed all-to-all (the sparse form of the reduce-scatter): counts is a HOST array of ndev * ndev

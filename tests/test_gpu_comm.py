@@ -5,7 +5,11 @@ the off-block y contributions without Python or torch.distributed.
 On a one-GPU box: the PEER transport with 2-4 ranks sharing cuda:0 (RCCL refuses two ranks
 per device), and the RCCL transport with ONE rank (the N = 1 rehearsal: ncclCommInitAll,
 ncclReduceScatter and ncclAllGather really run).  What crosses a block boundary are the
-reference's direct conflicts, include/matrix/csr_matrix.tpp:1443-1451."""
+reference's direct conflicts, include/matrix/csr_matrix.tpp:1443-1451.
+
+This file holds the collectives at one ordinary size against a tolerance, on idle streams.  Their edges
+(counts of 0, 1 and around a block and a full grid, guard values, bit-exact sums, pointers aligned to the
+value size only) and the event protocol under held streams are in tests/test_gpu_comm_edges.py."""
 import ctypes as C
 
 import numpy as np
