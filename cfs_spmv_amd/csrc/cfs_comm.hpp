@@ -26,6 +26,8 @@
 
 #include <dlfcn.h>
 
+#include <memory>
+
 namespace cfs_comm {
 
 using cfs_rt::DeviceGuard;
@@ -149,3 +151,239 @@ struct cfs_hip_comm_s {
     }
   }
 };
+
+// ---------------------------------------------------------------------------
+// cfs_hip_comm_* (declared extern "C" in cfs_hip.h): RCCL over xGMI, or kernels / copies over
+// peer access
+// ---------------------------------------------------------------------------
+using cfs_rt::DeviceGuard;
+using cfs_rt::set_err;
+
+int cfs_hip_comm_create(int ndev, const int *devices, int transport, cfs_hip_comm_t *out) {
+  if (!out || ndev < 1 || ndev > cfs_rt::kMaxDevices) return set_err(CFS_HIP_ERR_ARG, "bad argument");
+  *out = nullptr;
+  int rc = cfs_rt::ensure_home();
+  if (rc) return rc;
+  int visible = 0, cur = 0;
+  HIPCHK(hipGetDeviceCount(&visible));
+  HIPCHK(hipGetDevice(&cur));
+  std::unique_ptr<cfs_hip_comm_s> c(new cfs_hip_comm_s());
+  bool distinct = true;
+  for (int g = 0; g < ndev; g++) {
+    const int d = devices ? devices[g] : (cur + g) % std::max(1, visible);
+    if (d < 0 || d >= visible) return set_err(CFS_HIP_ERR_ARG, "bad device index");
+    for (int q : c->dev) distinct = distinct && q != d;
+    c->dev.push_back(d);
+  }
+  cfs_comm::Rccl &R = cfs_comm::rccl();
+  if (transport == CFS_HIP_TRANSPORT_RCCL && (!distinct || !R.ok))
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "rccl transport: " + (!distinct ? "RCCL needs one rank per device" : R.why));
+  c->use_rccl = transport != CFS_HIP_TRANSPORT_PEER && distinct && R.ok;
+  if (!c->use_rccl) c->note = transport == CFS_HIP_TRANSPORT_PEER ? "asked for" : (!distinct ? "ranks share a device" : R.why);
+  if (c->use_rccl) {
+    c->comm.assign(ndev, nullptr);
+    const int r2 = R.CommInitAll(c->comm.data(), ndev, c->dev.data());
+    if (r2 != 0) {
+      c->use_rccl = false; // (nothing to destroy)
+      return set_err(CFS_HIP_ERR_DEVICE, std::string("ncclCommInitAll: ") + (R.GetErrorString ? R.GetErrorString(r2) : "?"));
+    }
+  } else {
+    c->ready.assign(ndev, nullptr);
+    c->done.assign(ndev, nullptr);
+    c->entered.assign(ndev, nullptr);
+    for (int g = 0; g < ndev; g++) {
+      DeviceGuard dg(c->dev[g]);
+      for (int q = 0; q < ndev; q++) // every rank reads every other rank's buffers
+        if (c->dev[q] != c->dev[g] && !cfs_rt::enable_peer_access(c->dev[g], c->dev[q]))
+          return set_err(CFS_HIP_ERR_DEVICE, "peer access between the devices of the communicator is not available");
+      if (hipEventCreateWithFlags(&c->ready[g], hipEventDisableTiming) != hipSuccess ||
+          hipEventCreateWithFlags(&c->done[g], hipEventDisableTiming) != hipSuccess ||
+          hipEventCreateWithFlags(&c->entered[g], hipEventDisableTiming) != hipSuccess)
+        return set_err(CFS_HIP_ERR_DEVICE, "event creation failed");
+    }
+  }
+  *out = c.release();
+  return 0;
+}
+int cfs_hip_comm_info(cfs_hip_comm_t c, int *ndev, int *transport) {
+  if (!c) return set_err(CFS_HIP_ERR_ARG, "null communicator");
+  if (ndev) *ndev = (int)c->dev.size();
+  if (transport) *transport = c->use_rccl ? CFS_HIP_TRANSPORT_RCCL : CFS_HIP_TRANSPORT_PEER;
+  return 0;
+}
+int cfs_hip_comm_destroy(cfs_hip_comm_t comm) {
+  delete comm;
+  return 0;
+}
+// make `stream` (of rank `rank`) wait until the previous collective has consumed that rank's
+// send buffer (peer transport: other ranks' kernels read it; RCCL orders on the stream itself)
+int cfs_hip_comm_wait_consumed(cfs_hip_comm_t c, int rank, void *stream) {
+  if (!c || rank < 0 || rank >= (int)c->dev.size()) return set_err(CFS_HIP_ERR_ARG, "bad argument");
+  if (c->use_rccl || !c->done_valid) return 0;
+  DeviceGuard dg(c->dev[rank]);
+  for (size_t r = 0; r < c->dev.size(); r++) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, c->done[r], 0));
+  return 0;
+}
+int cfs_hip_comm_reduce_scatter(cfs_hip_comm_t c, void *const *send, void *const *recv, size_t count,
+                                int value_bytes, void *const *streams) {
+  if (!c || !send || !recv || !streams || (value_bytes != 4 && value_bytes != 8))
+    return set_err(CFS_HIP_ERR_ARG, "bad argument");
+  const int N = (int)c->dev.size();
+  if (c->use_rccl) {
+    cfs_comm::Rccl &R = cfs_comm::rccl();
+    int r2 = R.GroupStart();
+    for (int g = 0; g < N && r2 == 0; g++) {
+      DeviceGuard dg(c->dev[g]);
+      r2 = R.ReduceScatter(send[g], recv[g], count, value_bytes == 8 ? cfs_comm::kNcclFloat64 : cfs_comm::kNcclFloat32,
+                           cfs_comm::kNcclSum, c->comm[g], (hipStream_t)streams[g]);
+    }
+    const int r3 = R.GroupEnd();
+    if (r2 == 0) r2 = r3;
+    if (r2 != 0) return set_err(CFS_HIP_ERR_DEVICE, std::string("ncclReduceScatter: ") + (R.GetErrorString ? R.GetErrorString(r2) : "?"));
+    return 0;
+  }
+  // peer transport: rank r sums the r-th block of every rank's send buffer
+  for (int g = 0; g < N; g++) {
+    DeviceGuard dg(c->dev[g]);
+    HIPCHK(hipEventRecord(c->ready[g], (hipStream_t)streams[g]));
+  }
+  // (the table of send buffers goes to the kernels by value: read here, before the call returns)
+  cfs_comm::SumTable t;
+  memset(&t, 0, sizeof t);
+  t.nranks = N;
+  for (int g = 0; g < N; g++) t.src[g] = send[g];
+  for (int r = 0; r < N; r++) {
+    DeviceGuard dg(c->dev[r]);
+    hipStream_t st = (hipStream_t)streams[r];
+    for (int g = 0; g < N; g++) HIPCHK(hipStreamWaitEvent(st, c->ready[g], 0));
+    const int grid = (int)std::min<size_t>((count + 255) / 256, 2048);
+    if (count) {
+      if (value_bytes == 8)
+        hipLaunchKernelGGL((cfs_comm::cfs_peer_sum_kernel<double>), dim3(grid), dim3(256), 0, st, (double *)recv[r], t,
+                           (size_t)r * count, count);
+      else
+        hipLaunchKernelGGL((cfs_comm::cfs_peer_sum_kernel<float>), dim3(grid), dim3(256), 0, st, (float *)recv[r], t,
+                           (size_t)r * count, count);
+    }
+    HIPCHK(hipEventRecord(c->done[r], st));
+  }
+  c->done_valid = true;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+int cfs_hip_comm_allgather(cfs_hip_comm_t c, void *const *send, void *const *recv, size_t count,
+                           int value_bytes, void *const *streams) {
+  if (!c || !send || !recv || !streams || (value_bytes != 4 && value_bytes != 8))
+    return set_err(CFS_HIP_ERR_ARG, "bad argument");
+  const int N = (int)c->dev.size();
+  if (c->use_rccl) {
+    cfs_comm::Rccl &R = cfs_comm::rccl();
+    int r2 = R.GroupStart();
+    for (int g = 0; g < N && r2 == 0; g++) {
+      DeviceGuard dg(c->dev[g]);
+      r2 = R.AllGather(send[g], recv[g], count, value_bytes == 8 ? cfs_comm::kNcclFloat64 : cfs_comm::kNcclFloat32,
+                       c->comm[g], (hipStream_t)streams[g]);
+    }
+    const int r3 = R.GroupEnd();
+    if (r2 == 0) r2 = r3;
+    if (r2 != 0) return set_err(CFS_HIP_ERR_DEVICE, std::string("ncclAllGather: ") + (R.GetErrorString ? R.GetErrorString(r2) : "?"));
+    return 0;
+  }
+  // peer transport: rank g pushes its block into every rank's receive buffer -- behind what rank r
+  // had enqueued on its own stream when the call was made (`entered[r]`): r may still be reading
+  // recv[r] of the round before
+  const size_t bytes = count * (size_t)value_bytes;
+  for (int r = 0; r < N; r++) {
+    DeviceGuard dg(c->dev[r]);
+    HIPCHK(hipEventRecord(c->entered[r], (hipStream_t)streams[r]));
+  }
+  for (int g = 0; g < N; g++) {
+    DeviceGuard dg(c->dev[g]);
+    hipStream_t st = (hipStream_t)streams[g];
+    for (int r = 0; r < N && bytes; r++)
+      if (r != g) HIPCHK(hipStreamWaitEvent(st, c->entered[r], 0));
+    for (int r = 0; r < N && bytes; r++)
+      HIPCHK(hipMemcpyPeerAsync((char *)recv[r] + (size_t)g * bytes, c->dev[r], send[g], c->dev[g], bytes, st));
+    HIPCHK(hipEventRecord(c->ready[g], st));
+  }
+  for (int r = 0; r < N; r++) {
+    DeviceGuard dg(c->dev[r]);
+    for (int g = 0; g < N; g++) HIPCHK(hipStreamWaitEvent((hipStream_t)streams[r], c->ready[g], 0));
+  }
+  return 0;
+}
+// the packed all-to-all: counts[g * N + r] values go from rank g (its blocks for r = 0..N-1 back
+// to back in send[g]) to rank r (the blocks from g = 0..N-1 back to back in recv[r])
+int cfs_hip_comm_alltoallv(cfs_hip_comm_t c, void *const *send, void *const *recv, const int64_t *counts,
+                           int value_bytes, void *const *streams) {
+  if (!c || !send || !recv || !counts || !streams || (value_bytes != 4 && value_bytes != 8))
+    return set_err(CFS_HIP_ERR_ARG, "bad argument");
+  const int N = (int)c->dev.size();
+  for (int g = 0; g < N; g++) {
+    int64_t out = 0, in = 0;
+    for (int r = 0; r < N; r++) {
+      if (counts[(size_t)g * N + r] < 0) return set_err(CFS_HIP_ERR_ARG, "alltoallv: negative count");
+      out += counts[(size_t)g * N + r];
+      in += counts[(size_t)r * N + g];
+    }
+    if ((out && !send[g]) || (in && !recv[g])) return set_err(CFS_HIP_ERR_ARG, "alltoallv: null buffer of a rank that moves values");
+  }
+  if (c->use_rccl) {
+    cfs_comm::Rccl &R = cfs_comm::rccl();
+    if (!R.p2p_ok)
+      return set_err(CFS_HIP_ERR_UNSUPPORTED, "alltoallv: librccl.so lacks ncclSend / ncclRecv (use the peer transport)");
+    const int dt = value_bytes == 8 ? cfs_comm::kNcclFloat64 : cfs_comm::kNcclFloat32;
+    int r2 = R.GroupStart();
+    for (int g = 0; g < N && r2 == 0; g++) {
+      DeviceGuard dg(c->dev[g]);
+      hipStream_t st = (hipStream_t)streams[g];
+      size_t soff = 0, roff = 0;
+      for (int r = 0; r < N && r2 == 0; r++) {
+        const size_t k = (size_t)counts[(size_t)g * N + r];
+        if (k) r2 = R.Send((const char *)send[g] + soff * value_bytes, k, dt, r, c->comm[g], st);
+        soff += k;
+      }
+      for (int s = 0; s < N && r2 == 0; s++) {
+        const size_t k = (size_t)counts[(size_t)s * N + g];
+        if (k) r2 = R.Recv((char *)recv[g] + roff * value_bytes, k, dt, s, c->comm[g], st);
+        roff += k;
+      }
+    }
+    const int r3 = R.GroupEnd();
+    if (r2 == 0) r2 = r3;
+    if (r2 != 0) return set_err(CFS_HIP_ERR_DEVICE, std::string("ncclSend / ncclRecv: ") + (R.GetErrorString ? R.GetErrorString(r2) : "?"));
+    return 0;
+  }
+  // peer transport: rank r pulls its blocks with one launch (cfs_peer_alltoallv_kernel)
+  for (int g = 0; g < N; g++) {
+    DeviceGuard dg(c->dev[g]);
+    HIPCHK(hipEventRecord(c->ready[g], (hipStream_t)streams[g]));
+  }
+  for (int r = 0; r < N; r++) {
+    DeviceGuard dg(c->dev[r]);
+    hipStream_t st = (hipStream_t)streams[r];
+    cfs_comm::A2aTable t;
+    memset(&t, 0, sizeof t);
+    t.nranks = N;
+    for (int g = 0; g < N; g++) {
+      size_t soff = 0; // where rank g's block for r starts in send[g]
+      for (int q = 0; q < r; q++) soff += (size_t)counts[(size_t)g * N + q];
+      const int64_t k = counts[(size_t)g * N + r];
+      t.src[g] = k ? (const char *)send[g] + soff * value_bytes : nullptr;
+      t.prefix[g + 1] = t.prefix[g] + k;
+      if (k) HIPCHK(hipStreamWaitEvent(st, c->ready[g], 0)); // (only the sources this rank reads)
+    }
+    const int64_t total = t.prefix[N];
+    if (total) {
+      const int grid = (int)std::min<int64_t>((total + 255) / 256, 2048);
+      if (value_bytes == 8)
+        hipLaunchKernelGGL((cfs_comm::cfs_peer_alltoallv_kernel<double>), dim3(grid), dim3(256), 0, st, (double *)recv[r], t);
+      else
+        hipLaunchKernelGGL((cfs_comm::cfs_peer_alltoallv_kernel<float>), dim3(grid), dim3(256), 0, st, (float *)recv[r], t);
+    }
+    HIPCHK(hipEventRecord(c->done[r], st));
+  }
+  c->done_valid = true;
+  HIPCHK(hipGetLastError());
+  return 0;
+}

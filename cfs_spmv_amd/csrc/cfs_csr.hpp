@@ -452,7 +452,7 @@ static int csr_create(int nrows, int ncols, const int *rowptr, const int *colind
   if ((rc = ensure_init())) return rc;
   int cur_dev = 0;
   HIPCHK(hipGetDevice(&cur_dev));
-  auto *m = new cfs_hip_csr_s();
+  std::unique_ptr<cfs_hip_csr_s> m(new cfs_hip_csr_s());
   m->value_bytes = (int)sizeof(V);
   m->device = cur_dev;
   m->nrows = nrows;
@@ -460,10 +460,8 @@ static int csr_create(int nrows, int ncols, const int *rowptr, const int *colind
   m->nnz = rowptr[nrows];
   if ((rc = m->rowptr.upload(rowptr, ((size_t)nrows + 1) * 4)) ||
       (rc = m->colind.upload(colind, (size_t)m->nnz * 4)) ||
-      (rc = m->values.upload(values, (size_t)m->nnz * sizeof(V)))) {
-    delete m;
+      (rc = m->values.upload(values, (size_t)m->nnz * sizeof(V))))
     return rc;
-  }
   { // row blocks of at most kCsrNnz nonzeros (a longer row is a block by itself)
     std::vector<int32_t> blk(1, 0);
     int r = 0;
@@ -475,10 +473,7 @@ static int csr_create(int nrows, int ncols, const int *rowptr, const int *colind
       r = e;
     }
     m->nblocks = (int)blk.size() - 1;
-    if ((rc = m->blk_row.upload(blk.data(), blk.size() * 4))) {
-      delete m;
-      return rc;
-    }
+    if ((rc = m->blk_row.upload(blk.data(), blk.size() * 4))) return rc;
     const char *e16 = getenv("CFS_HIP_CSR_COL16");
     if (m->nblocks > 0 && m->nnz > 0 && !(e16 && atoi(e16) == 0)) {
       DevBuf cnt;
@@ -551,10 +546,8 @@ static int csr_create(int nrows, int ncols, const int *rowptr, const int *colind
     m->nchunks = (int)cd.size();
     m->nlong = (int)lr.size();
     if ((rc = m->chunks.upload(cd.data(), cd.size() * sizeof(int4))) ||
-        (rc = m->longrows.upload(lr.data(), lr.size() * 4))) {
-      delete m;
+        (rc = m->longrows.upload(lr.data(), lr.size() * 4)))
       return rc;
-    }
     // persistent waves: as many workgroups as are co-resident
     int nb = 0;
     const void *k = sizeof(V) == 8 ? (const void *)cfs_csr_wave_kernel<double> : (const void *)cfs_csr_wave_kernel<float>;
@@ -572,7 +565,7 @@ static int csr_create(int nrows, int ncols, const int *rowptr, const int *colind
       m->form_measured = true;
     }
   }
-  *out = m;
+  *out = m.release();
   return 0;
 }
 

@@ -811,21 +811,6 @@ __global__ void __launch_bounds__(256)
   send[i] = s;
 }
 
-// the dense form of the exchange (north-star: reduce-scatter of the off-block contributions):
-// a shard's packed contributions go to their slot of a zeroed vector of nranks equal blocks ...
-template <typename V>
-__global__ void __launch_bounds__(256)
-    cfs_scatter_pos_kernel(V *__restrict__ dense, const int32_t *__restrict__ pos, const V *__restrict__ packed, int m) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < m) dense[pos[i]] = packed[i];
-}
-// ... and the block a rank receives is added to its rows
-template <typename V>
-__global__ void __launch_bounds__(256) cfs_add_rows_kernel(V *__restrict__ y, const V *__restrict__ add, int m) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < m) y[i] += add[i];
-}
-
 // ---------------------------------------------------------------------------
 // host objects
 // ---------------------------------------------------------------------------
@@ -1379,6 +1364,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
 #include "cfs_devplan.hpp" // tune() on the GPU (needs SymMatrix and cfs_value_scatter_kernel)
 #include "cfs_csr.hpp"     // the general CSR path: kernels, handle, create / launch
 #include "cfs_solver.hpp"  // conjugate gradients on resident vectors (a solver-style caller)
+#include "cfs_multi.hpp"   // one host thread, N devices: MultiSym, its create and cfs_hip_sym_multi_*
 
 
 // ---------------------------------------------------------------------------
@@ -1616,14 +1602,11 @@ static int sym_create(int n, const int *rowptr, const int *colind, const V *valu
   if (rc) return rc;
   int cur_dev = 0;
   HIPCHK(hipGetDevice(&cur_dev));
-  auto *m = new SymMatrix<V>();
+  std::unique_ptr<SymMatrix<V>> m(new SymMatrix<V>());
   m->value_bytes = (int)sizeof(V);
   m->device = cur_dev;
   cfs_plan::Options po = to_opts(opt);
-  if ((rc = query_residency<V>(po))) {
-    delete m;
-    return rc;
-  }
+  if ((rc = query_residency<V>(po))) return rc;
   ct.lap("create: runtime + kernel residency");
   // kept until the window-shape step below has had its chance to reuse it
   cfs_plan::ScheduleSpace<V> space;
@@ -1649,12 +1632,9 @@ static int sym_create(int n, const int *rowptr, const int *colind, const V *valu
       return set_err(plan_error_code(h->P.error), h->P.error);
     return h->upload();
   };
-  rc = build_handle(m, po, want_tuning ? &space : nullptr);
+  rc = build_handle(m.get(), po, want_tuning ? &space : nullptr);
   ct.lap("create: schedule (build + upload)");
-  if (rc) {
-    delete m;
-    return rc;
-  }
+  if (rc) return rc;
   // ---- window shape (Tuning::Aggressive; CFS_HIP_FLAG_NO_CALIBRATE skips it) -------
   // Default: 512 threads, 4 992 slots, two workgroups per CU.  A matrix that is
   // scheduled in clustered order (compact 3-D tiles) can be faster with ONE
@@ -1717,15 +1697,15 @@ static int sym_create(int n, const int *rowptr, const int *colind, const V *valu
       int r2 = ensure_xy();
       if (r2) return r2;
     }
-    auto *alt = new SymMatrix<V>();
+    std::unique_ptr<SymMatrix<V>> alt(new SymMatrix<V>());
     alt->value_bytes = (int)sizeof(V);
     alt->device = cur_dev;
     alt->nnz_caller = rowptr[n];
     float t_def = 0, t_alt = 0;
-    bool ok = query_residency<V>(po2) == 0 && build_handle(alt, po2, sp) == 0 && choose_kernel(alt) == 0;
+    bool ok = query_residency<V>(po2) == 0 && build_handle(alt.get(), po2, sp) == 0 && choose_kernel(alt.get()) == 0;
     for (int round = 0; ok && round < 3; round++) {
       float a = 0, b = 0;
-      ok = time_spmv(m, &a) == 0 && time_spmv(alt, &b) == 0;
+      ok = time_spmv(m.get(), &a) == 0 && time_spmv(alt.get(), &b) == 0;
       t_def = round == 0 ? a : std::min(t_def, a);
       t_alt = round == 0 ? b : std::min(t_alt, b);
     }
@@ -1737,18 +1717,12 @@ static int sym_create(int n, const int *rowptr, const int *colind, const V *valu
     const char *force = getenv("CFS_HIP_KEEP_ALT");
     if (force && atoi(force) != 0) forced = 1;
     if (ok && forced != 0 && (t_alt < 0.99f * t_def || forced == 1)) {
-      delete m;
-      m = alt;
+      m = std::move(alt);
       po = po2;
-    } else {
-      delete alt;
     }
     return 0;
   };
-  if (tuning && (rc = choose_kernel(m))) {
-    delete m;
-    return rc;
-  }
+  if (tuning && (rc = choose_kernel(m.get()))) return rc;
   // (natural-order schedules are tried too: a 1/8 row block of the Flan stand-in runs 11 %
   // faster with 256 workgroups of 1 024 threads -- a third less halo, half as many window
   // phases per CU -- while pwtk, ldoor and Queen stay with the default)
@@ -1760,10 +1734,7 @@ static int sym_create(int n, const int *rowptr, const int *colind, const V *valu
     // must run the schedule its bench line ran, whatever the clock says under the profiler)
     int forced = -1;
     if (const char *e = getenv("CFS_HIP_SHAPE")) forced = atoi(e) == 1024 ? 1 : (atoi(e) == 512 ? 0 : -1);
-    if ((rc = try_alternative(po2, &space, "window shape 512 x 2 per CU vs 1024 x 1", forced))) {
-      delete m;
-      return rc;
-    }
+    if ((rc = try_alternative(po2, &space, "window shape 512 x 2 per CU vs 1024 x 1", forced))) return rc;
   }
   // ---- HYB by measurement (Format::sss, Tuning::Aggressive) --------------------------
   // A halo column that its tile uses once costs a slot, a slot-table entry, an x
@@ -1778,14 +1749,11 @@ static int sym_create(int n, const int *rowptr, const int *colind, const V *valu
     int forced = -1; // CFS_HIP_TAKE_HYB=1|0: keep / drop the alternative whatever the clock says (tests)
     if (const char *e = getenv("CFS_HIP_TAKE_HYB")) forced = atoi(e) != 0 ? 1 : 0;
     // (the kept upload / schedule space of the builds above serves this one too)
-    if ((rc = try_alternative(po2, &space, "tile format vs HYB (far entries apart)", forced))) {
-      delete m;
-      return rc;
-    }
+    if ((rc = try_alternative(po2, &space, "tile format vs HYB (far entries apart)", forced))) return rc;
   }
   space.drop(); // release the schedule-space matrix / the kept upload
   m->ablate_mode = opt ? (opt->flags & CFS_HIP_FLAG_ABLATE_MASK) : 0;
-  *out = m;
+  *out = m.release();
   ct.lap("create: measured alternatives");
   return 0;
 }
@@ -1809,774 +1777,6 @@ int cfs_hip_sym_create_shard_f32(int n, const int *rowptr, const int *colind,
                                  const int *row_splits, const cfs_hip_options *opt,
                                  cfs_hip_sym_t *out) {
   return sym_create<float>(n, rowptr, colind, values, nranks, rank, row_splits, opt, out);
-}
-
-
-// ---------------------------------------------------------------------------
-// native exchange (cfs_comm.hpp): RCCL over xGMI, or kernels / copies over peer access
-// ---------------------------------------------------------------------------
-int cfs_hip_comm_create(int ndev, const int *devices, int transport, cfs_hip_comm_t *out) {
-  if (!out || ndev < 1 || ndev > cfs_rt::kMaxDevices) return set_err(CFS_HIP_ERR_ARG, "bad argument");
-  *out = nullptr;
-  int rc = ensure_init();
-  if (rc) return rc;
-  int visible = 0, cur = 0;
-  HIPCHK(hipGetDeviceCount(&visible));
-  HIPCHK(hipGetDevice(&cur));
-  auto *c = new cfs_hip_comm_s();
-  bool distinct = true;
-  for (int g = 0; g < ndev; g++) {
-    const int d = devices ? devices[g] : (cur + g) % std::max(1, visible);
-    if (d < 0 || d >= visible) {
-      delete c;
-      return set_err(CFS_HIP_ERR_ARG, "bad device index");
-    }
-    for (int q : c->dev) distinct = distinct && q != d;
-    c->dev.push_back(d);
-  }
-  cfs_comm::Rccl &R = cfs_comm::rccl();
-  if (transport == CFS_HIP_TRANSPORT_RCCL && (!distinct || !R.ok)) {
-    const std::string why = !distinct ? "RCCL needs one rank per device" : R.why;
-    delete c;
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, "rccl transport: " + why);
-  }
-  c->use_rccl = transport != CFS_HIP_TRANSPORT_PEER && distinct && R.ok;
-  if (!c->use_rccl) c->note = transport == CFS_HIP_TRANSPORT_PEER ? "asked for" : (!distinct ? "ranks share a device" : R.why);
-  if (c->use_rccl) {
-    c->comm.assign(ndev, nullptr);
-    const int r2 = R.CommInitAll(c->comm.data(), ndev, c->dev.data());
-    if (r2 != 0) {
-      const std::string e = R.GetErrorString ? R.GetErrorString(r2) : "?";
-      c->use_rccl = false; // (nothing to destroy)
-      delete c;
-      return set_err(CFS_HIP_ERR_DEVICE, "ncclCommInitAll: " + e);
-    }
-  } else {
-    c->ready.assign(ndev, nullptr);
-    c->done.assign(ndev, nullptr);
-    c->entered.assign(ndev, nullptr);
-    for (int g = 0; g < ndev; g++) {
-      DeviceGuard dg(c->dev[g]);
-      for (int q = 0; q < ndev; q++) // every rank reads every other rank's buffers
-        if (c->dev[q] != c->dev[g]) {
-          int can = 0;
-          (void)hipDeviceCanAccessPeer(&can, c->dev[g], c->dev[q]);
-          hipError_t e = can ? hipDeviceEnablePeerAccess(c->dev[q], 0) : hipErrorPeerAccessUnsupported;
-          if (e == hipErrorPeerAccessAlreadyEnabled) {
-            (void)hipGetLastError();
-            e = hipSuccess;
-          }
-          if (e != hipSuccess) {
-            delete c;
-            return set_err(CFS_HIP_ERR_DEVICE, "peer access between the devices of the communicator is not available");
-          }
-        }
-      if (hipEventCreateWithFlags(&c->ready[g], hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&c->done[g], hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&c->entered[g], hipEventDisableTiming) != hipSuccess) {
-        delete c;
-        return set_err(CFS_HIP_ERR_DEVICE, "event creation failed");
-      }
-    }
-  }
-  *out = c;
-  return 0;
-}
-int cfs_hip_comm_info(cfs_hip_comm_t c, int *ndev, int *transport) {
-  if (!c) return set_err(CFS_HIP_ERR_ARG, "null communicator");
-  if (ndev) *ndev = (int)c->dev.size();
-  if (transport) *transport = c->use_rccl ? CFS_HIP_TRANSPORT_RCCL : CFS_HIP_TRANSPORT_PEER;
-  return 0;
-}
-int cfs_hip_comm_destroy(cfs_hip_comm_t c) {
-  delete c;
-  return 0;
-}
-// make `stream` (of rank `rank`) wait until the previous collective has consumed that rank's
-// send buffer (peer transport: other ranks' kernels read it; RCCL orders on the stream itself)
-int cfs_hip_comm_wait_consumed(cfs_hip_comm_t c, int rank, void *stream) {
-  if (!c || rank < 0 || rank >= (int)c->dev.size()) return set_err(CFS_HIP_ERR_ARG, "bad argument");
-  if (c->use_rccl || !c->done_valid) return 0;
-  DeviceGuard dg(c->dev[rank]);
-  for (size_t r = 0; r < c->dev.size(); r++) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, c->done[r], 0));
-  return 0;
-}
-int cfs_hip_comm_reduce_scatter(cfs_hip_comm_t c, void *const *send, void *const *recv, size_t count,
-                                int value_bytes, void *const *streams) {
-  if (!c || !send || !recv || !streams || (value_bytes != 4 && value_bytes != 8))
-    return set_err(CFS_HIP_ERR_ARG, "bad argument");
-  const int N = (int)c->dev.size();
-  if (c->use_rccl) {
-    cfs_comm::Rccl &R = cfs_comm::rccl();
-    int r2 = R.GroupStart();
-    for (int g = 0; g < N && r2 == 0; g++) {
-      DeviceGuard dg(c->dev[g]);
-      r2 = R.ReduceScatter(send[g], recv[g], count, value_bytes == 8 ? cfs_comm::kNcclFloat64 : cfs_comm::kNcclFloat32,
-                           cfs_comm::kNcclSum, c->comm[g], (hipStream_t)streams[g]);
-    }
-    const int r3 = R.GroupEnd();
-    if (r2 == 0) r2 = r3;
-    if (r2 != 0) return set_err(CFS_HIP_ERR_DEVICE, std::string("ncclReduceScatter: ") + (R.GetErrorString ? R.GetErrorString(r2) : "?"));
-    return 0;
-  }
-  // peer transport: rank r sums the r-th block of every rank's send buffer
-  for (int g = 0; g < N; g++) {
-    DeviceGuard dg(c->dev[g]);
-    HIPCHK(hipEventRecord(c->ready[g], (hipStream_t)streams[g]));
-  }
-  // (the table of send buffers goes to the kernels by value: read here, before the call returns)
-  cfs_comm::SumTable t;
-  memset(&t, 0, sizeof t);
-  t.nranks = N;
-  for (int g = 0; g < N; g++) t.src[g] = send[g];
-  for (int r = 0; r < N; r++) {
-    DeviceGuard dg(c->dev[r]);
-    hipStream_t st = (hipStream_t)streams[r];
-    for (int g = 0; g < N; g++) HIPCHK(hipStreamWaitEvent(st, c->ready[g], 0));
-    const int grid = (int)std::min<size_t>((count + 255) / 256, 2048);
-    if (count) {
-      if (value_bytes == 8)
-        hipLaunchKernelGGL((cfs_comm::cfs_peer_sum_kernel<double>), dim3(grid), dim3(256), 0, st, (double *)recv[r], t,
-                           (size_t)r * count, count);
-      else
-        hipLaunchKernelGGL((cfs_comm::cfs_peer_sum_kernel<float>), dim3(grid), dim3(256), 0, st, (float *)recv[r], t,
-                           (size_t)r * count, count);
-    }
-    HIPCHK(hipEventRecord(c->done[r], st));
-  }
-  c->done_valid = true;
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-int cfs_hip_comm_allgather(cfs_hip_comm_t c, void *const *send, void *const *recv, size_t count,
-                           int value_bytes, void *const *streams) {
-  if (!c || !send || !recv || !streams || (value_bytes != 4 && value_bytes != 8))
-    return set_err(CFS_HIP_ERR_ARG, "bad argument");
-  const int N = (int)c->dev.size();
-  if (c->use_rccl) {
-    cfs_comm::Rccl &R = cfs_comm::rccl();
-    int r2 = R.GroupStart();
-    for (int g = 0; g < N && r2 == 0; g++) {
-      DeviceGuard dg(c->dev[g]);
-      r2 = R.AllGather(send[g], recv[g], count, value_bytes == 8 ? cfs_comm::kNcclFloat64 : cfs_comm::kNcclFloat32,
-                       c->comm[g], (hipStream_t)streams[g]);
-    }
-    const int r3 = R.GroupEnd();
-    if (r2 == 0) r2 = r3;
-    if (r2 != 0) return set_err(CFS_HIP_ERR_DEVICE, std::string("ncclAllGather: ") + (R.GetErrorString ? R.GetErrorString(r2) : "?"));
-    return 0;
-  }
-  // peer transport: rank g pushes its block into every rank's receive buffer -- behind what rank r
-  // had enqueued on its own stream when the call was made (`entered[r]`): r may still be reading
-  // recv[r] of the round before
-  const size_t bytes = count * (size_t)value_bytes;
-  for (int r = 0; r < N; r++) {
-    DeviceGuard dg(c->dev[r]);
-    HIPCHK(hipEventRecord(c->entered[r], (hipStream_t)streams[r]));
-  }
-  for (int g = 0; g < N; g++) {
-    DeviceGuard dg(c->dev[g]);
-    hipStream_t st = (hipStream_t)streams[g];
-    for (int r = 0; r < N && bytes; r++)
-      if (r != g) HIPCHK(hipStreamWaitEvent(st, c->entered[r], 0));
-    for (int r = 0; r < N && bytes; r++)
-      HIPCHK(hipMemcpyPeerAsync((char *)recv[r] + (size_t)g * bytes, c->dev[r], send[g], c->dev[g], bytes, st));
-    HIPCHK(hipEventRecord(c->ready[g], st));
-  }
-  for (int r = 0; r < N; r++) {
-    DeviceGuard dg(c->dev[r]);
-    for (int g = 0; g < N; g++) HIPCHK(hipStreamWaitEvent((hipStream_t)streams[r], c->ready[g], 0));
-  }
-  return 0;
-}
-// the packed all-to-all: counts[g * N + r] values go from rank g (its blocks for r = 0..N-1 back
-// to back in send[g]) to rank r (the blocks from g = 0..N-1 back to back in recv[r])
-int cfs_hip_comm_alltoallv(cfs_hip_comm_t c, void *const *send, void *const *recv, const int64_t *counts,
-                           int value_bytes, void *const *streams) {
-  if (!c || !send || !recv || !counts || !streams || (value_bytes != 4 && value_bytes != 8))
-    return set_err(CFS_HIP_ERR_ARG, "bad argument");
-  const int N = (int)c->dev.size();
-  for (int g = 0; g < N; g++) {
-    int64_t out = 0, in = 0;
-    for (int r = 0; r < N; r++) {
-      if (counts[(size_t)g * N + r] < 0) return set_err(CFS_HIP_ERR_ARG, "alltoallv: negative count");
-      out += counts[(size_t)g * N + r];
-      in += counts[(size_t)r * N + g];
-    }
-    if ((out && !send[g]) || (in && !recv[g])) return set_err(CFS_HIP_ERR_ARG, "alltoallv: null buffer of a rank that moves values");
-  }
-  if (c->use_rccl) {
-    cfs_comm::Rccl &R = cfs_comm::rccl();
-    if (!R.p2p_ok)
-      return set_err(CFS_HIP_ERR_UNSUPPORTED, "alltoallv: librccl.so lacks ncclSend / ncclRecv (use the peer transport)");
-    const int dt = value_bytes == 8 ? cfs_comm::kNcclFloat64 : cfs_comm::kNcclFloat32;
-    int r2 = R.GroupStart();
-    for (int g = 0; g < N && r2 == 0; g++) {
-      DeviceGuard dg(c->dev[g]);
-      hipStream_t st = (hipStream_t)streams[g];
-      size_t soff = 0, roff = 0;
-      for (int r = 0; r < N && r2 == 0; r++) {
-        const size_t k = (size_t)counts[(size_t)g * N + r];
-        if (k) r2 = R.Send((const char *)send[g] + soff * value_bytes, k, dt, r, c->comm[g], st);
-        soff += k;
-      }
-      for (int s = 0; s < N && r2 == 0; s++) {
-        const size_t k = (size_t)counts[(size_t)s * N + g];
-        if (k) r2 = R.Recv((char *)recv[g] + roff * value_bytes, k, dt, s, c->comm[g], st);
-        roff += k;
-      }
-    }
-    const int r3 = R.GroupEnd();
-    if (r2 == 0) r2 = r3;
-    if (r2 != 0) return set_err(CFS_HIP_ERR_DEVICE, std::string("ncclSend / ncclRecv: ") + (R.GetErrorString ? R.GetErrorString(r2) : "?"));
-    return 0;
-  }
-  // peer transport: rank r pulls its blocks with one launch (cfs_peer_alltoallv_kernel)
-  for (int g = 0; g < N; g++) {
-    DeviceGuard dg(c->dev[g]);
-    HIPCHK(hipEventRecord(c->ready[g], (hipStream_t)streams[g]));
-  }
-  for (int r = 0; r < N; r++) {
-    DeviceGuard dg(c->dev[r]);
-    hipStream_t st = (hipStream_t)streams[r];
-    cfs_comm::A2aTable t;
-    memset(&t, 0, sizeof t);
-    t.nranks = N;
-    for (int g = 0; g < N; g++) {
-      size_t soff = 0; // where rank g's block for r starts in send[g]
-      for (int q = 0; q < r; q++) soff += (size_t)counts[(size_t)g * N + q];
-      const int64_t k = counts[(size_t)g * N + r];
-      t.src[g] = k ? (const char *)send[g] + soff * value_bytes : nullptr;
-      t.prefix[g + 1] = t.prefix[g] + k;
-      if (k) HIPCHK(hipStreamWaitEvent(st, c->ready[g], 0)); // (only the sources this rank reads)
-    }
-    const int64_t total = t.prefix[N];
-    if (total) {
-      const int grid = (int)std::min<int64_t>((total + 255) / 256, 2048);
-      if (value_bytes == 8)
-        hipLaunchKernelGGL((cfs_comm::cfs_peer_alltoallv_kernel<double>), dim3(grid), dim3(256), 0, st, (double *)recv[r], t);
-      else
-        hipLaunchKernelGGL((cfs_comm::cfs_peer_alltoallv_kernel<float>), dim3(grid), dim3(256), 0, st, (float *)recv[r], t);
-    }
-    HIPCHK(hipEventRecord(c->done[r], st));
-  }
-  c->done_valid = true;
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// One host thread, N GPUs (the C++ surface with CFS_NUM_GPUS=N; reference knob:
-// CFS_NUM_THREADS, src/runtime.cpp:10-21): N mirrored 1-D row-block shards, one per
-// device, each on a stream of its own.  x and y stay where the caller put them (the
-// handle's HOME device); a shard on another device reads x and writes its rows of y
-// through peer access over xGMI.  An SpMV is ordered like any other work of the
-// caller's stream: the shard streams wait for an event recorded on it, it waits for
-// theirs.  (The performance path for several GPUs is one process per GPU, bench.py;
-// this is the drop-in path of an unmodified single-process caller.)
-// ---------------------------------------------------------------------------
-struct MultiSym : cfs_hip_sym_s {
-  std::vector<cfs_hip_sym_s *> shard;
-  std::vector<int> dev, splits;
-  std::vector<hipStream_t> st_;
-  std::vector<hipEvent_t> done_;
-  hipEvent_t start_ = nullptr;
-  int n_ = 0;
-  std::vector<int32_t> none_;
-  // How a shard on another device than the handle's home reaches x and y:
-  //   CFS_HIP_XMODE_REPLICATE (default)  x is REPLICATED (north-star / SURVEY 8e): one
-  //       hipMemcpyPeerAsync home -> device per shard and SpMV into the shard's own copy,
-  //       the kernels gather x and write their y block in LOCAL HBM, one peer copy brings
-  //       the block home;
-  //   CFS_HIP_XMODE_PEER  the kernels read x and write y in the home device's memory
-  //       through peer access over xGMI (no copies, every gather crosses the fabric).
-  // Shards on the home device itself never copy.  CFS_HIP_XMODE_REPLICATE_ALL copies for
-  // every shard, home or not: the way a one-GPU box exercises the copy path.
-  int xmode = CFS_HIP_XMODE_REPLICATE;
-  std::vector<DevBuf> xrep, yloc; // per shard, on its device (allocated on first use)
-  int ensure_copies(size_t g) {
-    if (xrep.size() != shard.size()) {
-      xrep = std::vector<DevBuf>(shard.size());
-      yloc = std::vector<DevBuf>(shard.size());
-    }
-    if (xrep[g].p) return 0;
-    DeviceGuard dg(dev[g]);
-    int rc;
-    if ((rc = xrep[g].alloc((size_t)n_ * value_bytes))) return rc;
-    return yloc[g].alloc((size_t)(splits[g + 1] - splits[g]) * value_bytes);
-  }
-  bool copies(size_t g) const {
-    return xmode == CFS_HIP_XMODE_REPLICATE_ALL || (xmode == CFS_HIP_XMODE_REPLICATE && dev[g] != device);
-  }
-  // Exchange form (CFS_HIP_FLAG_SHARD_EXCHANGE at create, or CFS_MULTI_EXCHANGE=reduce_scatter):
-  // the shards keep their off-block entries two-sided, pack the contributions to rows of lower
-  // ranks, scatter them into a dense vector of N equal blocks and ONE native reduce-scatter
-  // (cfs_hip_comm_*: RCCL over xGMI, or the peer transport) hands every owner its sums --
-  // the north-star's form, without Python.  The local fold runs beside the collective.
-  //
-  // Two forms of that exchange on one handle (cfs_hip_sym_multi_set_exchange; the buffers of a
-  // form are allocated at its first use):
-  //   CFS_HIP_EXCHANGE_REDUCE_SCATTER  the dense one above: memset, tiles, pack, scatter, the sum
-  //       kernel (or ncclReduceScatter), local fold, add -- N * rs_rows values per rank;
-  //   CFS_HIP_EXCHANGE_SPARSE  the packed all-to-all (cfs_hip_comm_alltoallv): tiles, pack, the
-  //       pull kernel (or grouped ncclSend / ncclRecv), local fold, fold of what arrived -- one
-  //       value per remote boundary row, no memset, no scatter, no add.
-  cfs_hip_comm_s *comm = nullptr;
-  int form = CFS_HIP_EXCHANGE_REDUCE_SCATTER;
-  int rs_rows = 0; // block length of the reduce-scatter (longest row block)
-  std::vector<DevBuf> sbuf, pos, dense, rsout, rbuf;
-  std::vector<int> nsend_;
-  std::vector<int64_t> a2a_counts_; // N x N, [g * N + r] = values shard g packs for shard r
-  bool dense_ready_ = false, sparse_ready_ = false;
-  template <typename V> int setup_exchange(int transport, int first_form) {
-    const int N = (int)shard.size();
-    int rc = cfs_hip_comm_create(N, dev.data(), transport, &comm);
-    if (rc) return rc;
-    rs_rows = 0;
-    for (int g = 0; g < N; g++) rs_rows = std::max(rs_rows, splits[g + 1] - splits[g]);
-    sbuf = std::vector<DevBuf>(N);
-    nsend_.assign(N, 0);
-    for (int g = 0; g < N; g++) {
-      DeviceGuard dg(dev[g]);
-      nsend_[g] = (int)shard[g]->send_rows().size();
-      if ((rc = sbuf[g].alloc(std::max<size_t>(1, (size_t)nsend_[g]) * sizeof(V)))) return rc;
-    }
-    if ((rc = ensure_form<V>(first_form))) return rc;
-    form = first_form;
-    return 0;
-  }
-  template <typename V> int ensure_form(int f) {
-    const int N = (int)shard.size();
-    int rc;
-    if (f == CFS_HIP_EXCHANGE_REDUCE_SCATTER && !dense_ready_) {
-      pos = std::vector<DevBuf>(N);
-      dense = std::vector<DevBuf>(N);
-      rsout = std::vector<DevBuf>(N);
-      for (int g = 0; g < N; g++) {
-        DeviceGuard dg(dev[g]);
-        const std::vector<int32_t> &rows = shard[g]->send_rows();
-        std::vector<int32_t> p(rows.size());
-        for (size_t k = 0; k < rows.size(); k++) {
-          const int owner = (int)(std::upper_bound(splits.begin(), splits.end(), rows[k]) - splits.begin()) - 1;
-          p[k] = owner * rs_rows + (rows[k] - splits[owner]);
-        }
-        if ((rc = pos[g].upload(p.data(), p.size() * 4)) || (rc = dense[g].alloc((size_t)N * rs_rows * sizeof(V))) ||
-            (rc = rsout[g].alloc((size_t)rs_rows * sizeof(V))))
-          return rc;
-        // this shard receives nothing through the sparse route: recv side stays empty
-      }
-      dense_ready_ = true;
-    }
-    if (f == CFS_HIP_EXCHANGE_SPARSE && !sparse_ready_) {
-      // the receive side: for every owner r the rows of each (higher) rank's send_rows() that are
-      // destined for r, concatenated by source rank -- the order cfs_hip_comm_alltoallv delivers
-      a2a_counts_.assign((size_t)N * N, 0);
-      std::vector<size_t> first((size_t)N * N, 0); // [g * N + r]: where g's block for r starts
-      for (int g = 0; g < N; g++) {
-        const std::vector<int32_t> &sc = shard[g]->send_counts();
-        size_t off = 0;
-        for (int r = 0; r < N && r < (int)sc.size(); r++) {
-          a2a_counts_[(size_t)g * N + r] = sc[r];
-          first[(size_t)g * N + r] = off;
-          off += (size_t)sc[r];
-        }
-        if (off != shard[g]->send_rows().size()) return set_err(CFS_HIP_ERR_INTERNAL, "send counts and send rows disagree");
-      }
-      rbuf = std::vector<DevBuf>(N);
-      for (int r = 0; r < N; r++) {
-        DeviceGuard dg(dev[r]);
-        std::vector<int> rows;
-        for (int g = 0; g < N; g++) {
-          const std::vector<int32_t> &sr = shard[g]->send_rows();
-          const size_t b = first[(size_t)g * N + r];
-          rows.insert(rows.end(), sr.begin() + b, sr.begin() + b + (size_t)a2a_counts_[(size_t)g * N + r]);
-        }
-        if ((rc = shard[r]->set_recv((int)rows.size(), rows.data())) ||
-            (rc = rbuf[r].alloc(std::max<size_t>(1, rows.size()) * sizeof(V))))
-          return rc;
-      }
-      sparse_ready_ = true;
-    }
-    return 0;
-  }
-  // sparse form, per shard stream: wait on start_, replicate x where copies(g), wait_consumed,
-  // tiles + pack into sbuf[g], the all-to-all, local fold, fold of rbuf[g], y block home, done_
-  template <typename V> int spmv_sparse(void *y, const void *x, hipStream_t st) {
-    const int N = (int)shard.size();
-    HIPCHK(hipEventRecord(start_, st));
-    void *sp[cfs_rt::kMaxDevices], *rp[cfs_rt::kMaxDevices], *streams[cfs_rt::kMaxDevices], *yg[cfs_rt::kMaxDevices];
-    const void *xg[cfs_rt::kMaxDevices];
-    int rc;
-    for (int g = 0; g < N; g++) {
-      DeviceGuard dg(dev[g]);
-      HIPCHK(hipStreamWaitEvent(st_[g], start_, 0));
-      xg[g] = x;
-      yg[g] = (char *)y + (size_t)splits[g] * value_bytes;
-      if (copies(g)) {
-        if ((rc = ensure_copies(g))) return rc;
-        HIPCHK(hipMemcpyPeerAsync(xrep[g].p, dev[g], x, device, (size_t)n_ * value_bytes, st_[g]));
-        xg[g] = xrep[g].p;
-        yg[g] = yloc[g].p;
-      }
-      if ((rc = cfs_hip_comm_wait_consumed(comm, g, st_[g]))) return rc;
-      if ((rc = shard[g]->spmv_local(yg[g], xg[g], sbuf[g].p, st_[g], CFS_HIP_PHASE_TILES | CFS_HIP_PHASE_PACK))) return rc;
-      sp[g] = sbuf[g].p;
-      rp[g] = rbuf[g].p;
-      streams[g] = (void *)st_[g];
-    }
-    if ((rc = cfs_hip_comm_alltoallv(comm, sp, rp, a2a_counts_.data(), value_bytes, streams))) return rc;
-    for (int g = 0; g < N; g++) {
-      DeviceGuard dg(dev[g]);
-      const int rows_g = splits[g + 1] - splits[g];
-      // (stream order, as in the dense form: the local fold is enqueued behind this rank's part of
-      // the collective; overlapping the two needs a second stream per shard)
-      if ((rc = shard[g]->spmv_local(yg[g], xg[g], sbuf[g].p, st_[g], CFS_HIP_PHASE_FOLD))) return rc;
-      if ((rc = shard[g]->recv_fold(yg[g], rbuf[g].p, st_[g]))) return rc;
-      if (copies(g) && rows_g > 0)
-        HIPCHK(hipMemcpyPeerAsync((char *)y + (size_t)splits[g] * value_bytes, device, yloc[g].p, dev[g],
-                                  (size_t)rows_g * value_bytes, st_[g]));
-      HIPCHK(hipEventRecord(done_[g], st_[g]));
-    }
-    for (int g = 0; g < N; g++) HIPCHK(hipStreamWaitEvent(st, done_[g], 0));
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  template <typename V> int spmv_exchange(void *y, const void *x, hipStream_t st) {
-    const int N = (int)shard.size();
-    HIPCHK(hipEventRecord(start_, st));
-    std::vector<void *> sp(N), rp(N), streams(N);
-    std::vector<const void *> xg(N);
-    std::vector<void *> yg(N);
-    for (int g = 0; g < N; g++) {
-      DeviceGuard dg(dev[g]);
-      HIPCHK(hipStreamWaitEvent(st_[g], start_, 0));
-      int rc;
-      xg[g] = x;
-      yg[g] = (char *)y + (size_t)splits[g] * value_bytes;
-      if (copies(g)) {
-        if ((rc = ensure_copies(g))) return rc;
-        HIPCHK(hipMemcpyPeerAsync(xrep[g].p, dev[g], x, device, (size_t)n_ * value_bytes, st_[g]));
-        xg[g] = xrep[g].p;
-        yg[g] = yloc[g].p;
-      }
-      if ((rc = cfs_hip_comm_wait_consumed(comm, g, st_[g]))) return rc;
-      HIPCHK(hipMemsetAsync(dense[g].p, 0, (size_t)N * rs_rows * sizeof(V), st_[g]));
-      rc = shard[g]->spmv_local(yg[g], xg[g], sbuf[g].p, st_[g], CFS_HIP_PHASE_TILES | CFS_HIP_PHASE_PACK);
-      if (rc) return rc;
-      if (nsend_[g] > 0)
-        hipLaunchKernelGGL((cfs_scatter_pos_kernel<V>), dim3((nsend_[g] + 255) / 256), dim3(256), 0, st_[g],
-                           (V *)dense[g].p, (const int32_t *)pos[g].p, (const V *)sbuf[g].p, nsend_[g]);
-      sp[g] = dense[g].p;
-      rp[g] = rsout[g].p;
-      streams[g] = (void *)st_[g];
-    }
-    int rc = cfs_hip_comm_reduce_scatter(comm, sp.data(), rp.data(), (size_t)rs_rows, value_bytes, streams.data());
-    if (rc) return rc;
-    for (int g = 0; g < N; g++) {
-      DeviceGuard dg(dev[g]);
-      const int rows_g = splits[g + 1] - splits[g];
-      // (stream order: the local fold is enqueued behind the collective of this rank; on the
-      // RCCL transport the two run on the same stream, on the peer transport the sum kernel is
-      // short -- overlapping them needs a second stream per shard and has not been measured)
-      rc = shard[g]->spmv_local(yg[g], xg[g], sbuf[g].p, st_[g], CFS_HIP_PHASE_FOLD);
-      if (rc) return rc;
-      if (rows_g > 0)
-        hipLaunchKernelGGL((cfs_add_rows_kernel<V>), dim3((rows_g + 255) / 256), dim3(256), 0, st_[g], (V *)yg[g],
-                           (const V *)rsout[g].p, rows_g);
-      if (copies(g) && rows_g > 0)
-        HIPCHK(hipMemcpyPeerAsync((char *)y + (size_t)splits[g] * value_bytes, device, yloc[g].p, dev[g],
-                                  (size_t)rows_g * value_bytes, st_[g]));
-      HIPCHK(hipEventRecord(done_[g], st_[g]));
-    }
-    for (int g = 0; g < N; g++) HIPCHK(hipStreamWaitEvent(st, done_[g], 0));
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  ~MultiSym() override {
-    for (size_t g = 0; g < shard.size(); g++) {
-      DeviceGuard dg(dev[g]);
-      if (g < st_.size() && st_[g]) (void)hipStreamSynchronize(st_[g]);
-      delete shard[g];
-      if (g < done_.size() && done_[g]) (void)hipEventDestroy(done_[g]);
-      if (g < st_.size() && st_[g]) (void)hipStreamDestroy(st_[g]);
-    }
-    if (start_) {
-      DeviceGuard dg(device);
-      (void)hipEventDestroy(start_);
-    }
-    delete comm;
-  }
-  int spmv_local(void *y, const void *x, void *, hipStream_t st, int phases) override {
-    if (comm && form == CFS_HIP_EXCHANGE_SPARSE)
-      return value_bytes == 8 ? spmv_sparse<double>(y, x, st) : spmv_sparse<float>(y, x, st);
-    if (comm) return value_bytes == 8 ? spmv_exchange<double>(y, x, st) : spmv_exchange<float>(y, x, st);
-    HIPCHK(hipEventRecord(start_, st));
-    for (size_t g = 0; g < shard.size(); g++) {
-      DeviceGuard dg(dev[g]);
-      HIPCHK(hipStreamWaitEvent(st_[g], start_, 0));
-      char *yg = (char *)y + (size_t)splits[g] * value_bytes;
-      const size_t ybytes = (size_t)(splits[g + 1] - splits[g]) * value_bytes;
-      int rc;
-      if (copies(g)) { // replicated x, local y block
-        if ((rc = ensure_copies(g))) return rc;
-        HIPCHK(hipMemcpyPeerAsync(xrep[g].p, dev[g], x, device, (size_t)n_ * value_bytes, st_[g]));
-        rc = shard[g]->spmv_local(yloc[g].p, xrep[g].p, nullptr, st_[g],
-                                  phases & (CFS_HIP_PHASE_TILES | CFS_HIP_PHASE_FOLD));
-        if (rc) return rc;
-        if (ybytes) HIPCHK(hipMemcpyPeerAsync(yg, device, yloc[g].p, dev[g], ybytes, st_[g]));
-      } else {
-        rc = shard[g]->spmv_local(yg, x, nullptr, st_[g], phases & (CFS_HIP_PHASE_TILES | CFS_HIP_PHASE_FOLD));
-        if (rc) return rc;
-      }
-      HIPCHK(hipEventRecord(done_[g], st_[g]));
-    }
-    for (size_t g = 0; g < shard.size(); g++) HIPCHK(hipStreamWaitEvent(st, done_[g], 0));
-    return 0;
-  }
-  int recv_fold(void *, const void *, hipStream_t) override { return 0; }
-  int set_recv(int, const int *) override { return set_err(CFS_HIP_ERR_ARG, "not a shard"); }
-  void stats(cfs_hip_sym_stats *o) override {
-    memset(o, 0, sizeof *o);
-    for (auto *h : shard) {
-      cfs_hip_sym_stats t;
-      h->stats(&t);
-      o->nnz_low += t.nnz_low;
-      o->nnz_diag += t.nnz_diag;
-      o->nnz_full += t.nnz_full;
-      o->ntiles += t.ntiles;
-      o->nslices += t.nslices;
-      o->halo_slots += t.halo_slots;
-      o->fold_rows += t.fold_rows;
-      o->bytes_algorithmic += t.bytes_algorithmic;
-      o->bytes_streamed += t.bytes_streamed;
-      o->device_bytes += t.device_bytes;
-      o->mirror_entries += t.mirror_entries;
-      o->far_entries += t.far_entries;
-      o->ngroups += t.ngroups;
-      o->max_slots_used = std::max(o->max_slots_used, t.max_slots_used);
-      o->lds_bytes = std::max(o->lds_bytes, t.lds_bytes);
-      o->block_threads = t.block_threads;
-      o->value_bytes = t.value_bytes;
-    }
-    o->n = n_;
-    o->row_begin = 0;
-    o->row_end = n_;
-  }
-  const std::vector<int32_t> &send_counts() override { return none_; }
-  const std::vector<int32_t> &send_rows() override { return none_; }
-  int n() override { return n_; }
-  int rows() override { return n_; }
-  int timeline(void *, const void *, unsigned long long *, int, int *) override {
-    return set_err(CFS_HIP_ERR_ARG, "no timeline for a multi-device handle");
-  }
-  int group_features(long long *, int, int *) override {
-    return set_err(CFS_HIP_ERR_ARG, "no group features for a multi-device handle");
-  }
-  int update_values(const void *values_dev, long long nnz, hipStream_t st) override {
-    // (values_dev lives on the home device; shards on other devices read it over peer access)
-    HIPCHK(hipStreamSynchronize(st));
-    for (size_t g = 0; g < shard.size(); g++) {
-      DeviceGuard dg(dev[g]);
-      int rc = shard[g]->update_values(values_dev, nnz, st_[g]);
-      if (rc) return rc;
-      HIPCHK(hipStreamSynchronize(st_[g]));
-    }
-    return 0;
-  }
-  // every shard gathers its block on its own device and stream; the block comes home the way its
-  // y block does (a peer copy in the replicate modes, written in place otherwise)
-  int diagonal(void *d, hipStream_t st) override {
-    HIPCHK(hipEventRecord(start_, st));
-    for (size_t g = 0; g < shard.size(); g++) {
-      DeviceGuard dg(dev[g]);
-      HIPCHK(hipStreamWaitEvent(st_[g], start_, 0));
-      char *dg_home = (char *)d + (size_t)splits[g] * value_bytes;
-      const size_t bytes = (size_t)(splits[g + 1] - splits[g]) * value_bytes;
-      int rc;
-      if (copies(g)) {
-        if ((rc = ensure_copies(g)) || (rc = shard[g]->diagonal(yloc[g].p, st_[g]))) return rc;
-        if (bytes) HIPCHK(hipMemcpyPeerAsync(dg_home, device, yloc[g].p, dev[g], bytes, st_[g]));
-      } else if ((rc = shard[g]->diagonal(dg_home, st_[g]))) {
-        return rc;
-      }
-      HIPCHK(hipEventRecord(done_[g], st_[g]));
-    }
-    for (size_t g = 0; g < shard.size(); g++) HIPCHK(hipStreamWaitEvent(st, done_[g], 0));
-    return 0;
-  }
-  int ngpus() const { return (int)shard.size(); }
-};
-
-template <typename V>
-static int sym_create_multi(int n, const int *rowptr, const int *colind, const V *values, int ngpus,
-                            const int *devices, const cfs_hip_options *opt, cfs_hip_sym_t *out) {
-  if (!out) return set_err(CFS_HIP_ERR_ARG, "out is NULL");
-  *out = nullptr;
-  if (ngpus < 1 || ngpus > cfs_rt::kMaxDevices) return set_err(CFS_HIP_ERR_ARG, "bad ngpus");
-  if (n < 0 || !rowptr) return set_err(CFS_HIP_ERR_ARG, "null CSR array");
-  int rc = ensure_init();
-  if (rc) return rc;
-  int home = 0, ndev = 0;
-  HIPCHK(hipGetDevice(&home));
-  HIPCHK(hipGetDeviceCount(&ndev));
-  auto *m = new MultiSym();
-  m->value_bytes = (int)sizeof(V);
-  m->device = home;
-  m->n_ = n;
-  m->splits.assign(ngpus + 1, 0);
-  cfs_plan::balanced_splits(n, rowptr, colind, ngpus, m->splits.data());
-  if (const char *e = getenv("CFS_MULTI_X")) // peer | replicate | replicate_all
-    m->xmode = !strcmp(e, "peer") ? CFS_HIP_XMODE_PEER
-               : !strcmp(e, "replicate_all") ? CFS_HIP_XMODE_REPLICATE_ALL : CFS_HIP_XMODE_REPLICATE;
-  {
-    DeviceGuard dg(home);
-    if (hipEventCreateWithFlags(&m->start_, hipEventDisableTiming) != hipSuccess) {
-      delete m;
-      return set_err(CFS_HIP_ERR_DEVICE, "hipEventCreate failed");
-    }
-  }
-  cfs_hip_options o2;
-  memset(&o2, 0, sizeof o2);
-  if (opt) o2 = *opt;
-  // default: mirrored shards, nothing to exchange.  With CFS_HIP_FLAG_SHARD_EXCHANGE (or
-  // CFS_MULTI_EXCHANGE=reduce_scatter) the shards take the exchange form and one native
-  // reduce-scatter per SpMV (MultiSym::spmv_exchange); CFS_MULTI_EXCHANGE=sparse: the same
-  // shards and the packed all-to-all (MultiSym::spmv_sparse)
-  bool exchange = (o2.flags & CFS_HIP_FLAG_SHARD_EXCHANGE) != 0;
-  int first_form = CFS_HIP_EXCHANGE_REDUCE_SCATTER;
-  if (const char *e = getenv("CFS_MULTI_EXCHANGE")) {
-    exchange = !strcmp(e, "reduce_scatter") || !strcmp(e, "sparse");
-    if (!strcmp(e, "sparse")) first_form = CFS_HIP_EXCHANGE_SPARSE;
-  }
-  if (ngpus < 2) exchange = false;
-  if (exchange) o2.flags = (o2.flags | CFS_HIP_FLAG_SHARD_EXCHANGE) & ~(CFS_HIP_FLAG_HYB);
-  else o2.flags &= ~CFS_HIP_FLAG_SHARD_EXCHANGE;
-  for (int g = 0; g < ngpus; g++) {
-    // devices[g] when given, else the visible devices round-robin (several shards may
-    // share a device: that is how a one-GPU box rehearses the path)
-    const int d = devices ? devices[g] : (home + g) % std::max(1, ndev);
-    if (d < 0 || d >= ndev) {
-      delete m;
-      return set_err(CFS_HIP_ERR_ARG, "bad device index");
-    }
-    DeviceGuard dg(d);
-    if (d != home) { // the shard reads x / writes y on the home device
-      int can = 0;
-      (void)hipDeviceCanAccessPeer(&can, d, home);
-      hipError_t e = can ? hipDeviceEnablePeerAccess(home, 0) : hipErrorPeerAccessUnsupported;
-      if (e == hipErrorPeerAccessAlreadyEnabled) {
-        (void)hipGetLastError();
-        e = hipSuccess;
-      }
-      if (e != hipSuccess) {
-        delete m;
-        return set_err(CFS_HIP_ERR_DEVICE, "device " + std::to_string(d) + " cannot access device " +
-                                               std::to_string(home) + " (peer access)");
-      }
-    }
-    hipStream_t st = nullptr;
-    hipEvent_t ev = nullptr;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-      delete m;
-      return set_err(CFS_HIP_ERR_DEVICE, "stream / event creation failed");
-    }
-    cfs_hip_sym_t h = nullptr;
-    rc = sym_create<V>(n, rowptr, colind, values, ngpus, g, m->splits.data(), &o2, &h);
-    m->dev.push_back(d);
-    m->st_.push_back(st);
-    m->done_.push_back(ev);
-    if (rc) {
-      std::string e = cfs_rt::last_error();
-      m->shard.push_back(nullptr);
-      delete m;
-      return set_err(rc, e);
-    }
-    m->shard.push_back(h);
-  }
-  if (exchange) {
-    int transport = CFS_HIP_TRANSPORT_AUTO;
-    if (const char *e = getenv("CFS_MULTI_TRANSPORT"))
-      transport = !strcmp(e, "rccl") ? CFS_HIP_TRANSPORT_RCCL : (!strcmp(e, "peer") ? CFS_HIP_TRANSPORT_PEER : CFS_HIP_TRANSPORT_AUTO);
-    if ((rc = m->template setup_exchange<V>(transport, first_form))) {
-      std::string e = cfs_rt::last_error();
-      delete m;
-      return set_err(rc, e);
-    }
-  }
-  *out = m;
-  return 0;
-}
-int cfs_hip_sym_create_multi_f64(int n, const int *rowptr, const int *colind, const double *values,
-                                 int ngpus, const int *devices, const cfs_hip_options *opt,
-                                 cfs_hip_sym_t *out) {
-  return sym_create_multi<double>(n, rowptr, colind, values, ngpus, devices, opt, out);
-}
-int cfs_hip_sym_create_multi_f32(int n, const int *rowptr, const int *colind, const float *values,
-                                 int ngpus, const int *devices, const cfs_hip_options *opt,
-                                 cfs_hip_sym_t *out) {
-  return sym_create_multi<float>(n, rowptr, colind, values, ngpus, devices, opt, out);
-}
-int cfs_hip_sym_multi_set_xmode(cfs_hip_sym_t h, int xmode) {
-  auto *m = dynamic_cast<MultiSym *>(h);
-  if (!m) return set_err(CFS_HIP_ERR_ARG, "not a multi-device handle");
-  if (xmode != CFS_HIP_XMODE_PEER && xmode != CFS_HIP_XMODE_REPLICATE && xmode != CFS_HIP_XMODE_REPLICATE_ALL)
-    return set_err(CFS_HIP_ERR_ARG, "unknown x mode");
-  // pending SpMVs of the other mode finish first
-  for (size_t g = 0; g < m->shard.size(); g++) {
-    DeviceGuard dg(m->dev[g]);
-    HIPCHK(hipStreamSynchronize(m->st_[g]));
-  }
-  m->xmode = xmode;
-  return 0;
-}
-int cfs_hip_sym_multi_set_exchange(cfs_hip_sym_t h, int form) {
-  if (!h) return set_err(CFS_HIP_ERR_ARG, "null handle");
-  auto *m = dynamic_cast<MultiSym *>(h);
-  if (!m || !m->comm) return set_err(CFS_HIP_ERR_ARG, "not an exchange-form multi-device handle");
-  if (form != CFS_HIP_EXCHANGE_REDUCE_SCATTER && form != CFS_HIP_EXCHANGE_SPARSE)
-    return set_err(CFS_HIP_ERR_ARG, "unknown exchange form");
-  // pending SpMVs of the other form finish first (the receive side is uploaded below)
-  for (size_t g = 0; g < m->shard.size(); g++) {
-    DeviceGuard dg(m->dev[g]);
-    HIPCHK(hipStreamSynchronize(m->st_[g]));
-  }
-  int rc = m->value_bytes == 8 ? m->ensure_form<double>(form) : m->ensure_form<float>(form);
-  if (rc) return rc;
-  m->form = form;
-  return 0;
-}
-int cfs_hip_sym_multi_exchange_info(cfs_hip_sym_t h, int *form, int64_t *values_moved, int64_t *bytes_moved) {
-  if (!h) return set_err(CFS_HIP_ERR_ARG, "null handle");
-  auto *m = dynamic_cast<MultiSym *>(h);
-  if (!m || !m->comm) return set_err(CFS_HIP_ERR_ARG, "not an exchange-form multi-device handle");
-  const int64_t N = (int64_t)m->shard.size();
-  int64_t v = 0;
-  if (m->form == CFS_HIP_EXCHANGE_SPARSE)
-    for (int k : m->nsend_) v += k;
-  else
-    v = N * N * m->rs_rows;
-  if (form) *form = m->form;
-  if (values_moved) *values_moved = v;
-  if (bytes_moved) *bytes_moved = v * m->value_bytes;
-  return 0;
-}
-int cfs_hip_sym_multi_devices(cfs_hip_sym_t h, int *devices, int capacity, int *distinct) {
-  auto *m = dynamic_cast<MultiSym *>(h);
-  if (!m || !distinct) return set_err(CFS_HIP_ERR_ARG, "not a multi-device handle");
-  std::vector<int> seen;
-  for (size_t g = 0; g < m->dev.size(); g++) {
-    if (devices && (int)g < capacity) devices[g] = m->dev[g];
-    if (std::find(seen.begin(), seen.end(), m->dev[g]) == seen.end()) seen.push_back(m->dev[g]);
-  }
-  *distinct = (int)seen.size();
-  return 0;
-}
-int cfs_hip_sym_num_gpus(cfs_hip_sym_t h, int *ngpus) {
-  if (!h || !ngpus) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  auto *m = dynamic_cast<MultiSym *>(h);
-  *ngpus = m ? m->ngpus() : 1;
-  return 0;
 }
 
 int cfs_hip_sym_balanced_splits(int n, const int *rowptr, const int *colind, int nranks,

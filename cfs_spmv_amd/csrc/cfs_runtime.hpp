@@ -76,6 +76,24 @@ struct DeviceGuard {
   }
 };
 
+// let kernels and copies of device `from` reach the memory of device `to` (enabled already: fine)
+inline bool enable_peer_access(int from, int to) {
+  DeviceGuard g(from);
+  int can = 0;
+  (void)hipDeviceCanAccessPeer(&can, from, to);
+  hipError_t e = can ? hipDeviceEnablePeerAccess(to, 0) : hipErrorPeerAccessUnsupported;
+  if (e == hipErrorPeerAccessAlreadyEnabled) {
+    (void)hipGetLastError();
+    e = hipSuccess;
+  }
+  return e == hipSuccess;
+}
+
+// f(double()) or f(float()): the one place where a handle's value_bytes becomes a value type
+template <class F> inline int with_value_type(int value_bytes, F &&f) {
+  return value_bytes == 8 ? f(double()) : f(float());
+}
+
 // context of `device`; its stream is created on first use.  Other devices'
 // contexts are left alone.
 inline int device_ctx(int device, DevCtx **out) {
@@ -246,6 +264,10 @@ struct DevBuf {
   size_t bytes = 0;
   DevBuf() {}
   DevBuf(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) : p(o.p), bytes(o.bytes) {
+    o.p = nullptr;
+    o.bytes = 0;
+  }
   DevBuf &operator=(DevBuf &&o) {
     if (this != &o) {
       if (p) (void)hipFree(p);

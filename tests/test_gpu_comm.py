@@ -1,5 +1,5 @@
 """The native exchange of the C ABI (cfs_hip_comm_*, cfs_comm.hpp) and the exchange form of a
-one-process multi-device handle (MultiSym::spmv_exchange): the north-star's reduce-scatter of
+one-process multi-device handle (MultiSym::spmv_exchange, cfs_multi.hpp): the north-star's reduce-scatter of
 the off-block y contributions without Python or torch.distributed.
 
 On a one-GPU box: the PEER transport with 2-4 ranks sharing cuda:0 (RCCL refuses two ranks
