@@ -13,7 +13,7 @@ class CfsHipError(RuntimeError):
 
 PRECOND_NONE, PRECOND_JACOBI = 0, 1  # include/cfs_hip.h: CFS_HIP_PRECOND_*
 EXCHANGE_REDUCE_SCATTER, EXCHANGE_SPARSE = 0, 1  # CFS_HIP_EXCHANGE_*
-ERR_ARG, ERR_DEVICE, ERR_UNSUPPORTED, ERR_NOMEM, ERR_INTERNAL, ERR_MIRROR = -1, -2, -3, -4, -5, -6
+ERR_ARG, ERR_DEVICE, ERR_UNSUPPORTED, ERR_NOMEM, ERR_INTERNAL, ERR_MIRROR, ERR_FILE = -1, -2, -3, -4, -5, -6, -7
 
 
 class Options(C.Structure):
@@ -47,6 +47,22 @@ class PlanReport(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PlanFileInfo(C.Structure):
+    _fields_ = [("format_version", C.c_int), ("value_bytes", C.c_int), ("n", C.c_int), ("row_begin", C.c_int),
+                ("row_end", C.c_int), ("nranks", C.c_int), ("rank", C.c_int), ("flags", C.c_int),
+                ("ntiles", C.c_int), ("ngroups", C.c_int), ("block_threads", C.c_int), ("lds_slots", C.c_int),
+                ("has_value_map", C.c_int), ("deterministic", C.c_int), ("device_built", C.c_int),
+                ("nsections", C.c_int), ("nnz_low", C.c_int64), ("nslices", C.c_int64), ("halo_slots", C.c_int64),
+                ("stream_len", C.c_int64), ("fold_rows", C.c_int64), ("remote_vals", C.c_int64),
+                ("mirror_entries", C.c_int64), ("far_entries", C.c_int64), ("payload_bytes", C.c_int64),
+                ("file_bytes", C.c_int64), ("tag", C.c_char * 256)]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["tag"] = d["tag"].decode(errors="replace")
+        return d
+
+
 # every symbol include/cfs_hip.h declares (tests check the .so exports them all)
 SYMBOLS = [
     "cfs_hip_abi_version", "cfs_hip_last_error", "cfs_hip_device_count", "cfs_hip_init",
@@ -58,7 +74,8 @@ SYMBOLS = [
     "cfs_hip_sym_spmv_async", "cfs_hip_sym_cg", "cfs_hip_sym_pcg", "cfs_hip_sym_diagonal_async", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
     "cfs_hip_sym_shard_set_recv", "cfs_hip_sym_spmv_local_async",
     "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_fold_lists", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
-    "cfs_hip_sym_plan_check_f32", "cfs_hip_sym_plan_send_info_f64", "cfs_hip_csr_create_f64", "cfs_hip_csr_create_f32",
+    "cfs_hip_sym_plan_check_f32", "cfs_hip_sym_plan_send_info_f64",
+    "cfs_hip_sym_save", "cfs_hip_sym_load", "cfs_hip_plan_file_check", "cfs_hip_debug_checksum", "cfs_hip_sym_plan_save_f64", "cfs_hip_sym_plan_save_f32", "cfs_hip_csr_create_f64", "cfs_hip_csr_create_f32",
     "cfs_hip_csr_spmv", "cfs_hip_csr_spmv_async", "cfs_hip_csr_destroy", "cfs_hip_csr_kernel_form", "cfs_hip_csr_stats",
     "cfs_hip_csr_debug_layout",
     "cfs_hip_event_create", "cfs_hip_event_record", "cfs_hip_event_elapsed_ms",
@@ -125,6 +142,14 @@ def load():
         lib.cfs_hip_comm_alltoallv.argtypes = [vp, vp, vp, vp, C.c_int, vp]
         lib.cfs_hip_sym_multi_set_exchange.argtypes = [vp, C.c_int]
         lib.cfs_hip_sym_multi_exchange_info.argtypes = [vp, ip, C.POINTER(i64), C.POINTER(i64)]
+    if hasattr(lib, "cfs_hip_sym_save"):  # (absent from older builds loaded through CFS_HIP_LIB)
+        lib.cfs_hip_sym_save.argtypes = [vp, C.c_char_p, C.c_char_p]
+        lib.cfs_hip_sym_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
+        lib.cfs_hip_plan_file_check.argtypes = [C.c_char_p, C.POINTER(PlanFileInfo)]
+        lib.cfs_hip_debug_checksum.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(C.c_ulonglong)]
+        for suf in ("f64", "f32"):
+            getattr(lib, "cfs_hip_sym_plan_save_" + suf).argtypes = [
+                C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(Options), C.c_char_p, C.c_char_p]
     lib.cfs_hip_sym_destroy.argtypes = [vp]
     lib.cfs_hip_sym_update_values_f64.argtypes = [vp, vp, C.c_longlong]
     lib.cfs_hip_sym_update_values_f32.argtypes = [vp, vp, C.c_longlong]

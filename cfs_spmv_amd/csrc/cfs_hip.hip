@@ -20,6 +20,7 @@
 
 #include "cfs_hip.h"
 #include "cfs_plan.hpp"
+#include "cfs_planfile.hpp"
 #include "cfs_runtime.hpp"
 #include "cfs_comm.hpp"
 
@@ -836,19 +837,9 @@ static int raise_lds_limit(const void *kernel, int device) {
 static void make_fold_records(const std::vector<int32_t> &dst, const std::vector<int32_t> &ptr,
                               const std::vector<int32_t> &idx, std::vector<int4> &rec,
                               std::vector<int32_t> &rest) {
-  rec.assign(dst.size() + 1, make_int4(0, 0, -1, -1));
-  rest.clear();
-  for (size_t i = 0; i < dst.size(); i++) {
-    const int b = ptr[i], len = ptr[i + 1] - ptr[i];
-    int4 r = make_int4(dst[i], idx[b], len > 1 ? idx[b + 1] : -1, len == 3 ? idx[b + 2] : -1);
-    if (len > 3) {
-      r.w = -((int)rest.size() + 2);
-      rest.push_back(len - 2);
-      rest.insert(rest.end(), idx.begin() + b + 2, idx.begin() + b + len);
-    }
-    rec[i] = r;
-  }
+  cfs_planfile::make_fold_records(dst, ptr, idx, rec, rest, [](int a, int b, int c, int d) { return make_int4(a, b, c, d); });
 }
+static_assert(sizeof(int4) == sizeof(cfs_planfile::FoldRec), "a plan file stores fold records as int4");
 
 // staging of a handle for callers that pass HOST pointers (the reference's API
 // hands raw host pointers every call, include/kernel/sparse_kernel.hpp:22-23):
@@ -964,6 +955,16 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
   int64_t halo_slots = 0, stream_len = 0, slot_len = 0, nslices = 0, coo_len = 0, far_len = 0, far_entries = 0;
 
   bool device_built = false; // the schedule was built by cfs_devplan.hpp (arrays never on the host)
+  int build_flags = 0, num_cus = 0; // what a plan file records: the caller's option flags, the CUs the grid was sized for
+
+  // the size rules of the two kernel choices (finish_setup; tune() may overrule the first by measurement)
+  static bool size_rule_combine(const SymPlan<V> &P) {
+    return P.chained_packets * 10 >= P.lane_packets && P.chained_packets > 0 &&
+           P.stream_len * (int64_t)sizeof(V) + P.slot_len * 2 >= (int64_t)200 * 1000 * 1000;
+  }
+  static bool size_rule_nt(const SymPlan<V> &P) {
+    return (P.stream_len * (int64_t)sizeof(V) + P.slot_len * 2) > (int64_t)240 * 1024 * 1024;
+  }
 
   int upload() {
     int rc;
@@ -1057,7 +1058,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
     // dependency chain per entry to hide (measured: ldoor stand-in, 283 MB per launch,
     // +3 %; 1/8 shards, 89-131 MB, -8 %); tune() times both where it may (sym_create)
     combine_ok = P.chained_packets * 10 >= P.lane_packets && P.chained_packets > 0;
-    combine = combine_ok && P.stream_len * (int64_t)sizeof(V) + P.slot_len * 2 >= (int64_t)200 * 1000 * 1000;
+    combine = size_rule_combine(P);
     combine_forced = false;
     // developer knob CFS_HIP_COMBINE (read only when set; a forced choice skips choose_kernel):
     // 0 = no sibling chains in the plan (to_opts), 2 = the combining kernel whatever the size
@@ -1096,7 +1097,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
     dev.lds_slots = P.lds_slots;
     lds_bytes = (size_t)P.lds_slots * (size_t)cfs_plan::slot_lds_bytes<V>(P.deterministic);
     // the stream is cacheable across SpMVs only if it fits the 256 MiB Infinity Cache
-    nt_stream = (stream_len * (int64_t)sizeof(V) + slot_len * 2) > (int64_t)240 * 1024 * 1024;
+    nt_stream = size_rule_nt(P);
     // developer knob CFS_HIP_NT=0|1 (read only when set): cacheable / non-temporal stream
     // loads whatever the size, so that tests reach both instantiations at small sizes
     if (const char *e = getenv("CFS_HIP_NT")) nt_stream = atoi(e) != 0;
@@ -1753,6 +1754,8 @@ static int sym_create(int n, const int *rowptr, const int *colind, const V *valu
   }
   space.drop(); // release the schedule-space matrix / the kept upload
   m->ablate_mode = opt ? (opt->flags & CFS_HIP_FLAG_ABLATE_MASK) : 0;
+  m->build_flags = opt ? opt->flags : 0;
+  m->num_cus = po.num_cus;
   *out = m.release();
   ct.lap("create: measured alternatives");
   return 0;
@@ -2324,6 +2327,358 @@ int cfs_hip_sym_plan_send_info_f64(int n, const int *rowptr, const int *colind,
     for (size_t i = 0; i < P.send_row.size(); i++) rows[i] = P.send_row[i];
   }
   return 0;
+}
+
+// ---- plan files (cfs_planfile.hpp is the format; cfs_hip.h the contract) -----------------------
+namespace pf = cfs_planfile;
+
+// The file checksum (pf::checksum) of [p, p + bytes) from device memory: a grid-stride loop of
+// 16-byte loads (two words each, p 16-byte aligned), a wave reduction, one partial per workgroup;
+// the tail of fewer than 16 bytes is read byte by byte by one thread, so nothing outside the range
+// is touched.  The sum is an integer sum: any order gives the same bits.
+__device__ __forceinline__ unsigned long long cfs_block_sum_u64(unsigned long long s) {
+  __shared__ unsigned long long ws[4];
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return ws[0] + ws[1] + ws[2] + ws[3]; // (256 threads = 4 waves)
+}
+__global__ __launch_bounds__(256) void cfs_checksum_kernel(const unsigned char *__restrict__ p, unsigned long long bytes,
+                                                           unsigned long long *__restrict__ partial) {
+  const uint4 *q = reinterpret_cast<const uint4 *>(p);
+  const unsigned long long nvec = bytes / 16;
+  unsigned long long s = 0;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (unsigned long long)gridDim.x * 256) {
+    const uint4 v = q[i];
+    s += pf::word_term((unsigned long long)v.x | ((unsigned long long)v.y << 32), 2 * i) +
+         pf::word_term((unsigned long long)v.z | ((unsigned long long)v.w << 32), 2 * i + 1);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (unsigned long long base = nvec * 16; base < bytes; base += 8) {
+      unsigned long long w = 0;
+      for (int k = 0; k < 8 && base + k < bytes; k++) w |= (unsigned long long)p[base + k] << (8 * k);
+      s += pf::word_term(w, base / 8);
+    }
+  s = cfs_block_sum_u64(s);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void cfs_checksum_final_kernel(const unsigned long long *__restrict__ partial, int n,
+                                                                 unsigned long long *__restrict__ out) {
+  unsigned long long s = 0;
+  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
+  s = cfs_block_sum_u64(s);
+  if (threadIdx.x == 0) *out = s;
+}
+constexpr int kChecksumGrid = 1024;
+
+// sums[i] = checksum of the device range (ptr[i], bytes[i]), i < count; enqueued on `st`, complete on return
+static int device_checksums(const void *const *ptr, const uint64_t *bytes, int count, uint64_t *sums, hipStream_t st) {
+  DevBuf scratch; // per range: kChecksumGrid partials; then one result per range
+  int rc = scratch.alloc(((size_t)count * kChecksumGrid + (size_t)count) * 8);
+  if (rc) return rc;
+  unsigned long long *partial = (unsigned long long *)scratch.p, *res = partial + (size_t)count * kChecksumGrid;
+  HIPCHK(hipMemsetAsync(res, 0, (size_t)count * 8, st));
+  for (int i = 0; i < count; i++) {
+    if (bytes[i] == 0) continue;
+    if (!ptr[i] || ((uintptr_t)ptr[i] & 15) != 0)
+      return set_err(CFS_HIP_ERR_INTERNAL, "internal: checksum of a device array that is not 16-byte aligned");
+    const int grid = (int)std::min<uint64_t>((bytes[i] / 16 + 255) / 256 + 1, kChecksumGrid);
+    hipLaunchKernelGGL(cfs_checksum_kernel, dim3(grid), dim3(256), 0, st, (const unsigned char *)ptr[i],
+                       (unsigned long long)bytes[i], partial + (size_t)i * kChecksumGrid);
+    hipLaunchKernelGGL(cfs_checksum_final_kernel, dim3(1), dim3(256), 0, st, partial + (size_t)i * kChecksumGrid, grid, res + i);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(sums, res, (size_t)count * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// two page-locked blocks of the pool, an event each and a stream: a file streams through them in
+// 16 MiB pieces, the disk side of one piece overlapping the bus side of the other
+struct PlanStage {
+  static constexpr size_t kPiece = (size_t)16 << 20;
+  void *pin[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipStream_t st = nullptr;
+  bool used[2] = {false, false};
+  int init() {
+    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    for (int k = 0; k < 2; k++) {
+      int rc = cfs_rt::pinned().alloc(kPiece, &pin[k]);
+      if (rc) return rc;
+      HIPCHK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+    }
+    return 0;
+  }
+  ~PlanStage() {
+    if (st) (void)hipStreamSynchronize(st); // nothing may still use the blocks
+    for (int k = 0; k < 2; k++) {
+      if (ev[k]) (void)hipEventDestroy(ev[k]);
+      if (pin[k]) (void)cfs_rt::pinned().release(pin[k]);
+    }
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+// the device arrays of a handle in section order (pf::S_TILES .. pf::S_SLOT_EXP)
+template <typename V> static void plan_dev_sections(SymMatrix<V> *m, DevBuf **b) {
+  DevBuf *const list[pf::kHostFirst] = {&m->tiles, &m->slot_col, &m->rowinfo, &m->diag, &m->slice_meta, &m->leadlane,
+                                        &m->vals, &m->slots, &m->cvals, &m->crows, &m->ccols, &m->fvals, &m->frows,
+                                        &m->fcols, &m->val_map, &m->cval_map, &m->fval_map, &m->diag_map, &m->fold_rec,
+                                        &m->fold_idx, &m->send_ptr, &m->send_idx, &m->slot_exp};
+  for (uint32_t i = 0; i < pf::kHostFirst; i++) b[i] = list[i];
+}
+
+template <typename V> static int sym_save(SymMatrix<V> *m, const char *path, const char *tag) {
+  DeviceGuard g(m->device);
+  HIPCHK(hipDeviceSynchronize());
+  pf::Extras x;
+  x.flags = m->build_flags, x.num_cus = m->num_cus, x.nnz_caller = m->nnz_caller, x.nslices = m->nslices;
+  x.combine = m->combine, x.nt_stream = m->nt_stream, x.device_built = m->device_built, x.plan_note = m->plan_note;
+  pf::Header h;
+  pf::fill_header(m->P, x, tag, m->has_value_map, h);
+  DevBuf *dv[pf::kHostFirst];
+  plan_dev_sections(m, dv);
+  const void *ptr[pf::kSections];
+  uint64_t bytes[pf::kSections], sums[pf::kSections];
+  uint32_t elem[pf::kSections];
+  for (uint32_t i = 0; i < pf::kHostFirst; i++) ptr[i] = dv[i]->p, bytes[i] = dv[i]->p ? dv[i]->bytes : 0;
+  for (uint32_t i = pf::kHostFirst; i < pf::kSections; i++) pf::host_section(m->P, i, &ptr[i], &bytes[i]);
+  for (uint32_t i = 0; i < pf::kSections; i++) elem[i] = pf::expect(h, i).elem;
+  PlanStage s;
+  int rc = s.init();
+  if (rc) return rc;
+  if ((rc = device_checksums(ptr, bytes, (int)pf::kHostFirst, sums, s.st))) return rc;
+  for (uint32_t i = pf::kHostFirst; i < pf::kSections; i++) sums[i] = pf::checksum(ptr[i], (size_t)bytes[i]);
+  pf::Writer w;
+  if (!w.begin(path, h, elem, bytes)) return set_err(CFS_HIP_ERR_FILE, w.error);
+  for (uint32_t i = 0; i < pf::kHostFirst; i++) {
+    const size_t B = (size_t)bytes[i];
+    size_t off = 0, written = 0, plen[2] = {0, 0};
+    int k = 0;
+    auto issue = [&](int kk) -> int {
+      plen[kk] = std::min(PlanStage::kPiece, B - off);
+      HIPCHK(hipMemcpyAsync(s.pin[kk], (const char *)ptr[i] + off, plen[kk], hipMemcpyDeviceToHost, s.st));
+      HIPCHK(hipEventRecord(s.ev[kk], s.st));
+      off += plen[kk];
+      return 0;
+    };
+    if (B && (rc = issue(0))) return rc;
+    while (written < B) { // the next piece is on the bus while this one goes to the file
+      if (off < B && (rc = issue(k ^ 1))) return rc;
+      HIPCHK(hipEventSynchronize(s.ev[k]));
+      if (!w.put(i, s.pin[k], plen[k])) return set_err(CFS_HIP_ERR_FILE, w.error);
+      written += plen[k];
+      k ^= 1;
+    }
+    if (B == 0 && !w.put(i, nullptr, 0)) return set_err(CFS_HIP_ERR_FILE, w.error);
+  }
+  for (uint32_t i = pf::kHostFirst; i < pf::kSections; i++)
+    if (!w.put(i, ptr[i], (size_t)bytes[i])) return set_err(CFS_HIP_ERR_FILE, w.error);
+  if (!w.finish(sums)) return set_err(CFS_HIP_ERR_FILE, w.error);
+  return 0;
+}
+
+int cfs_hip_sym_save(cfs_hip_sym_t h, const char *path, const char *tag) {
+  if (!h || !path) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (tag && strlen(tag) > (size_t)pf::kTagMax) return set_err(CFS_HIP_ERR_ARG, "tag longer than 255 bytes");
+  if (auto *d = dynamic_cast<SymMatrix<double> *>(h)) return sym_save<double>(d, path, tag);
+  if (auto *f = dynamic_cast<SymMatrix<float> *>(h)) return sym_save<float>(f, path, tag);
+  return set_err(CFS_HIP_ERR_UNSUPPORTED, "a multi-device handle cannot be saved: save its shards");
+}
+
+template <typename V> static int sym_load(FILE *f, const char *path, const pf::Parsed &F, cfs_hip_sym_t *out) {
+  const pf::Header &h = F.h;
+  const pf::Scalars &s = h.s;
+  auto bad_file = [&](const std::string &what) { return set_err(CFS_HIP_ERR_FILE, std::string(path) + ": " + what); };
+  int rc = ensure_init();
+  if (rc) return rc;
+  int cur_dev = 0;
+  HIPCHK(hipGetDevice(&cur_dev));
+  std::unique_ptr<SymMatrix<V>> m(new SymMatrix<V>());
+  m->value_bytes = (int)sizeof(V);
+  m->device = cur_dev;
+  SymPlan<V> &P = m->P;
+  P.n = (int)s.n, P.row_begin = (int)s.row_begin, P.row_end = (int)s.row_end, P.nranks = (int)s.nranks, P.rank = (int)s.rank;
+  P.nnz_low = s.nnz_low, P.nnz_diag = s.nnz_diag, P.nnz_full = s.nnz_full;
+  P.max_slots = (int)s.max_slots, P.block_threads = (int)s.block_threads, P.lds_slots = (int)s.lds_slots;
+  P.wg_per_cu = (int)s.wg_per_cu, P.deterministic = s.deterministic != 0, P.mirrored = s.mirrored != 0;
+  P.ngroups = (int)s.ngroups, P.nvrows = s.nvrows, P.nhalo = s.nhalo, P.onesided_slots = s.onesided_slots;
+  P.stream_len = s.stream_len, P.slot_len = s.slot_len, P.coo_len = s.coo_len, P.coo_entries = s.coo_entries;
+  P.far_len = s.far_len, P.far_entries = s.far_entries, P.far_candidates = s.far_candidates;
+  P.chained_packets = s.chained_packets, P.lane_packets = s.lane_packets, P.mirror_entries = s.mirror_entries;
+  // the stored window must fit this device: the check of query_residency, for the stored shape
+  {
+    const size_t lds = (size_t)P.lds_slots * (size_t)cfs_plan::slot_lds_bytes<V>(P.deterministic);
+    int nb = 0;
+    if (lds > (size_t)160 * 1024 - 64) nb = 0, rc = 0;
+    else if (P.block_threads == 256) rc = residency_one<V, 256>(lds, &nb);
+    else if (P.block_threads == 512) rc = residency_one<V, 512>(lds, &nb, P.deterministic);
+    else rc = residency_one<V, 1024>(lds, &nb, P.deterministic);
+    if (rc) return rc;
+    if (nb < 1)
+      return set_err(CFS_HIP_ERR_UNSUPPORTED, std::string(path) + ": a window of " + std::to_string(P.lds_slots) + " slots (" +
+                                                  std::to_string(lds) + " bytes of LDS, " + std::to_string(P.block_threads) +
+                                                  " threads) does not fit this device");
+  }
+  // the small host arrays (their lengths were checked against the header's counts by pf::parse_file)
+  auto read_host = [&](uint32_t id, auto &vec) -> int {
+    const pf::Row &r = F.rows[id];
+    vec.resize((size_t)(r.bytes / sizeof(vec[0])));
+    if (r.bytes && (fseek(f, (long)r.offset, SEEK_SET) != 0 || fread(vec.data(), 1, (size_t)r.bytes, f) != r.bytes))
+      return bad_file(std::string("cannot read section ") + pf::section_name(id));
+    if (pf::checksum(vec.data(), (size_t)r.bytes) != r.sum)
+      return bad_file(std::string("checksum mismatch in section ") + pf::section_name(id));
+    return 0;
+  };
+  if ((rc = read_host(pf::S_GROUP_FIRST, P.group_first)) || (rc = read_host(pf::S_GROUP_PTR, P.group_ptr)) ||
+      (rc = read_host(pf::S_LAUNCH_ORDER, P.launch_order)) || (rc = read_host(pf::S_FOLD_DST, P.fold_dst)) ||
+      (rc = read_host(pf::S_SEND_ROW, P.send_row)) || (rc = read_host(pf::S_SEND_COUNTS, P.send_counts)) ||
+      (rc = read_host(pf::S_TILE_ROUNDS, P.tile_rounds)) || (rc = read_host(pf::S_ROW_SPLITS, P.row_splits)))
+    return rc;
+  // the device arrays: allocated as DevBuf::upload does (64 zeroed bytes behind the array), the file
+  // streamed through the two page-locked blocks
+  DevBuf *dv[pf::kHostFirst];
+  plan_dev_sections(m.get(), dv);
+  PlanStage st;
+  if ((rc = st.init())) return rc;
+  const void *ptr[pf::kHostFirst];
+  uint64_t bytes[pf::kHostFirst], sums[pf::kHostFirst];
+  int k = 0;
+  for (uint32_t i = 0; i < pf::kHostFirst; i++) {
+    const pf::Row &r = F.rows[i];
+    DevBuf &b = *dv[i];
+    const bool absent = r.bytes == 0 && (i == pf::S_SLOT_EXP || (i >= pf::S_VAL_MAP && i <= pf::S_DIAG_MAP));
+    ptr[i] = nullptr, bytes[i] = r.bytes;
+    if (absent) continue; // (as after create: no value map, no slot exponents)
+    HIPCHK(hipMalloc(&b.p, (size_t)r.bytes + 64));
+    b.bytes = (size_t)r.bytes;
+    HIPCHK(hipMemsetAsync((char *)b.p + b.bytes, 0, 64, st.st));
+    ptr[i] = b.p;
+    if (r.bytes && fseek(f, (long)r.offset, SEEK_SET) != 0) return bad_file(std::string("cannot seek to section ") + pf::section_name(i));
+    for (size_t off = 0; off < b.bytes; off += PlanStage::kPiece, k ^= 1) {
+      const size_t len = std::min(PlanStage::kPiece, b.bytes - off);
+      if (st.used[k]) HIPCHK(hipEventSynchronize(st.ev[k]));
+      if (fread(st.pin[k], 1, len, f) != len) return bad_file(std::string("cannot read section ") + pf::section_name(i));
+      HIPCHK(hipMemcpyAsync((char *)b.p + off, st.pin[k], len, hipMemcpyHostToDevice, st.st));
+      HIPCHK(hipEventRecord(st.ev[k], st.st));
+      st.used[k] = true;
+    }
+  }
+  // every uploaded array against the table, by the device kernel; nothing of the schedule runs before
+  if ((rc = device_checksums(ptr, bytes, (int)pf::kHostFirst, sums, st.st))) return rc;
+  for (uint32_t i = 0; i < pf::kHostFirst; i++)
+    if (sums[i] != F.rows[i].sum) return bad_file(std::string("checksum mismatch in section ") + pf::section_name(i));
+  P.tiles.resize((size_t)s.ntiles);
+  if (s.ntiles) HIPCHK(hipMemcpy(P.tiles.data(), m->tiles.p, P.tiles.size() * sizeof(Tile), hipMemcpyDeviceToHost));
+  if (s.nsend > 0) {
+    P.send_ptr.resize((size_t)s.nsend + 1);
+    HIPCHK(hipMemcpy(P.send_ptr.data(), m->send_ptr.p, P.send_ptr.size() * 4, hipMemcpyDeviceToHost));
+  }
+  m->has_value_map = s.has_value_map != 0;
+  m->nnz_caller = s.nnz_caller;
+  m->device_built = s.device_built != 0;
+  m->plan_note = h.plan_note;
+  m->build_flags = (int)s.flags;
+  m->num_cus = (int)s.num_cus;
+  if (P.deterministic) m->dev_slot_exp = (const short *)m->slot_exp.p;
+  if ((rc = m->finish_setup(s.nslices))) return rc;
+  // the choices the saved handle had kept (finish_setup applied the size rules and the developer knobs)
+  if (!m->combine_forced) m->combine = s.combine != 0 && m->combine_ok;
+  if (!getenv("CFS_HIP_NT")) m->nt_stream = s.nt_stream != 0;
+  *out = m.release();
+  return 0;
+}
+
+int cfs_hip_sym_load(const char *path, const char *expected_tag, cfs_hip_sym_t *out) {
+  if (out) *out = nullptr;
+  if (!path || !out) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  std::string err;
+  uint64_t fsize = 0;
+  FILE *f = pf::open_plan(path, &fsize, err);
+  if (!f) return set_err(CFS_HIP_ERR_FILE, err);
+  struct Closer {
+    FILE *f;
+    ~Closer() { fclose(f); }
+  } closer{f};
+  std::unique_ptr<pf::Parsed> F(new pf::Parsed());
+  if (pf::parse_file(f, fsize, *F, err)) return set_err(CFS_HIP_ERR_FILE, std::string(path) + ": " + err);
+  if (expected_tag && strcmp(expected_tag, F->h.tag) != 0)
+    return set_err(CFS_HIP_ERR_FILE, std::string(path) + ": tag mismatch: the file was saved with \"" + F->h.tag +
+                                         "\", the caller expects \"" + expected_tag + "\"");
+  const int rc = F->h.value_bytes == 8 ? sym_load<double>(f, path, *F, out) : sym_load<float>(f, path, *F, out);
+  if (rc) *out = nullptr;
+  return rc;
+}
+
+int cfs_hip_plan_file_check(const char *path, cfs_hip_plan_file_info *info) {
+  if (!path || !info) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  memset(info, 0, sizeof *info);
+  std::unique_ptr<pf::Parsed> F(new pf::Parsed());
+  std::string err;
+  if (pf::check_file(path, *F, err)) return set_err(CFS_HIP_ERR_FILE, err);
+  const pf::Header &h = F->h;
+  const pf::Scalars &s = h.s;
+  info->format_version = (int)h.version, info->value_bytes = (int)h.value_bytes;
+  info->n = (int)s.n, info->row_begin = (int)s.row_begin, info->row_end = (int)s.row_end;
+  info->nranks = (int)s.nranks, info->rank = (int)s.rank, info->flags = (int)s.flags;
+  info->ntiles = (int)s.ntiles, info->ngroups = (int)s.ngroups, info->block_threads = (int)s.block_threads;
+  info->lds_slots = (int)s.lds_slots, info->has_value_map = (int)s.has_value_map, info->deterministic = (int)s.deterministic;
+  info->device_built = (int)s.device_built, info->nsections = (int)h.nsections;
+  info->nnz_low = s.nnz_low, info->nslices = s.nslices, info->halo_slots = s.nhalo, info->stream_len = s.stream_len;
+  info->fold_rows = s.nfold, info->remote_vals = s.nsend, info->mirror_entries = s.mirror_entries;
+  info->far_entries = s.far_entries, info->payload_bytes = (int64_t)h.payload_bytes, info->file_bytes = (int64_t)h.file_bytes;
+  snprintf(info->tag, sizeof info->tag, "%s", h.tag);
+  return 0;
+}
+
+// developer / test: the file checksum of a byte range, by the device kernel (p a 16-byte aligned device
+// pointer) or by the host function (cfs_hip.h)
+int cfs_hip_debug_checksum(const void *p, size_t bytes, int on_device, unsigned long long *out) {
+  if (!out || (bytes && !p)) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (!on_device) {
+    *out = pf::checksum(p, bytes);
+    return 0;
+  }
+  int rc = ensure_init();
+  if (rc) return rc;
+  const cfs_rt::PtrInfo pi = cfs_rt::classify(p);
+  if (bytes && !pi.device) return set_err(CFS_HIP_ERR_ARG, "not a device pointer");
+  DeviceGuard g(pi.device ? pi.dev : -1);
+  const void *ptr[1] = {p};
+  uint64_t len[1] = {bytes}, sum[1] = {0};
+  if ((rc = device_checksums(ptr, len, 1, sum, (hipStream_t)0))) return rc;
+  *out = sum[0];
+  return 0;
+}
+
+template <typename V>
+static int plan_save(int n, const int *rowptr, const int *colind, const V *values, int nranks, int rank,
+                     const int *row_splits, const cfs_hip_options *opt, const char *path, const char *tag) {
+  if (!path) return set_err(CFS_HIP_ERR_ARG, "path is NULL");
+  if (tag && strlen(tag) > (size_t)pf::kTagMax) return set_err(CFS_HIP_ERR_ARG, "tag longer than 255 bytes");
+  if (n < 0 || !rowptr || (n > 0 && rowptr[n] > 0 && (!colind || !values)))
+    return set_err(CFS_HIP_ERR_ARG, "null CSR array");
+  if (nranks < 1 || rank < 0 || rank >= nranks || (nranks > 1 && !row_splits))
+    return set_err(CFS_HIP_ERR_ARG, "bad rank / nranks / row_splits");
+  SymPlan<V> P;
+  const cfs_plan::Options po = to_opts(opt);
+  if (!cfs_plan::build_plan<V>(n, rowptr, colind, values, nranks, rank, nranks > 1 ? row_splits : nullptr, po, P))
+    return set_err(plan_error_code(P.error), P.error);
+  pf::Extras x;
+  x.flags = opt ? opt->flags : 0, x.num_cus = po.num_cus, x.nnz_caller = rowptr[n];
+  x.combine = SymMatrix<V>::size_rule_combine(P), x.nt_stream = SymMatrix<V>::size_rule_nt(P);
+  std::string err;
+  if (!pf::save_plan(P, x, path, tag, err)) return set_err(CFS_HIP_ERR_FILE, err);
+  return 0;
+}
+int cfs_hip_sym_plan_save_f64(int n, const int *rowptr, const int *colind, const double *values, int nranks, int rank,
+                              const int *row_splits, const cfs_hip_options *opt, const char *path, const char *tag) {
+  return plan_save<double>(n, rowptr, colind, values, nranks, rank, row_splits, opt, path, tag);
+}
+int cfs_hip_sym_plan_save_f32(int n, const int *rowptr, const int *colind, const float *values, int nranks, int rank,
+                              const int *row_splits, const cfs_hip_options *opt, const char *path, const char *tag) {
+  return plan_save<float>(n, rowptr, colind, values, nranks, rank, row_splits, opt, path, tag);
 }
 
 // ---- general CSR ------------------------------------------------------------

@@ -10,6 +10,8 @@ so the parity tests read like test/test_spmv_mmf.cpp.  torch is used only for
 device memory and streams; nothing here computes an SpMV on the host."""
 import ctypes as C
 import enum
+import os
+import struct
 
 import numpy as np
 
@@ -93,6 +95,32 @@ def plan_check(n, rowptr, colind, values, nranks=1, rank=0, row_splits=None, opt
     return rep.asdict()
 
 
+def _cstr(s):
+    return None if s is None else os.fsencode(s)
+
+
+def plan_file_info(path):
+    """host-only: validate a plan file (header, section table, lengths, checksums) and return what
+    its header says (cfs_hip_plan_file_check); raises CfsHipError (code ERR_FILE) with the reason"""
+    info = _lib.PlanFileInfo()
+    _lib.check(_lib.load().cfs_hip_plan_file_check(_cstr(path), C.byref(info)))
+    return info.asdict()
+
+
+def plan_save(path, n, rowptr, colind, values, nranks=1, rank=0, row_splits=None, options=None, tag=None):
+    """host-only: build the schedule with the host builder, as plan_check does, and write it as a
+    plan file that SymMatrix.load reads on a machine with a GPU (cfs_hip_sym_plan_save_*)"""
+    lib = _lib.load()
+    rowptr, colind = _np_i32(rowptr), _np_i32(colind)
+    values = np.ascontiguousarray(values)
+    suf = "f64" if values.dtype == np.float64 else "f32"
+    rs = _np_i32(row_splits) if row_splits is not None else None
+    _lib.check(getattr(lib, "cfs_hip_sym_plan_save_" + suf)(
+        n, rowptr.ctypes.data, colind.ctypes.data, values.ctypes.data, nranks, rank,
+        rs.ctypes.data if rs is not None else None,
+        C.byref(options) if options is not None else None, _cstr(path), _cstr(tag)))
+
+
 def plan_send_info(n, rowptr, colind, values, nranks, rank, row_splits, options=None):
     """host-only (send_counts, send_rows) of one shard in the EXCHANGE form
     (CFS_HIP_FLAG_SHARD_EXCHANGE) -- for the CPU exchange tests"""
@@ -161,6 +189,31 @@ class SymMatrix:
         self._tuned = True
         st = self.stats()
         self.row_begin, self.row_end = st["row_begin"], st["row_end"]
+
+    # -- plan files: the tuned handle on disk (cfs_hip_sym_save / cfs_hip_sym_load) --
+    def save(self, path, tag=None):
+        """write the handle -- the schedule and the kernel choices tune() kept -- to `path`; `tag` (at
+        most 255 bytes) is stored verbatim for load(expected_tag=...)"""
+        _lib.check(_lib.load().cfs_hip_sym_save(self._h, _cstr(path), _cstr(tag)))
+
+    @classmethod
+    def load(cls, path, expected_tag=None):
+        """a handle from a plan file, on the current device, without tune(); raises CfsHipError (code
+        ERR_FILE) when the file is damaged, of another format version or saved with another tag"""
+        lib = _lib.load()
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        _lib.check(lib.cfs_hip_sym_load(_cstr(path), _cstr(expected_tag), C.byref(self._h)))
+        self._tuned = True
+        st = self.stats()
+        self.dtype = np.dtype(np.float64 if st["value_bytes"] == 8 else np.float32)
+        self.n = st["n"]
+        self.row_begin, self.row_end = st["row_begin"], st["row_end"]
+        # (nranks / rank: the 4th and 5th 64-bit scalar behind the 64 fixed bytes of the header,
+        # cfs_planfile.hpp -- read directly, plan_file_info would checksum the whole file again)
+        with open(path, "rb") as f:
+            self.nranks, self.rank = struct.unpack_from("<2q", f.read(104), 88)
+        return self
 
     # -- SparseMatrix surface (sparse_matrix.hpp:25-33) --
     def nrows(self):

@@ -43,6 +43,9 @@ extern "C" {
 /* a shard cannot be built in the mirrored form (off-block structure unsymmetric
  * or duplicated): rebuild it with CFS_HIP_FLAG_SHARD_EXCHANGE                   */
 #define CFS_HIP_ERR_MIRROR (-6)
+/* a plan file (cfs_hip_sym_save / _load): cannot open / truncated / not a plan file / version
+ * or layout mismatch / checksum / tag mismatch; the message says which                        */
+#define CFS_HIP_ERR_FILE (-7)
 
 typedef struct cfs_hip_sym_s *cfs_hip_sym_t; /* symmetric (SSS) matrix handle */
 typedef struct cfs_hip_csr_s *cfs_hip_csr_t; /* general CSR matrix handle     */
@@ -514,6 +517,67 @@ int cfs_hip_sym_plan_check_f32(int n, const int *rowptr, const int *colind,
                                const float *values, int nranks, int rank,
                                const int *row_splits, const cfs_hip_options *opt,
                                cfs_hip_plan_report *report);
+
+/* ---- plan files: a tuned symmetric handle saved to a file and loaded back without tune()
+ *      (cfs_spmv_amd/csrc/cfs_planfile.hpp is the format: little-endian, self-describing, one
+ *      64-bit checksum per section).  One file holds one handle: a plain one or one shard of
+ *      either form; the value type, the struct layouts of this library version and the LDS
+ *      window must fit where it is loaded.  A file whose checksums pass is trusted input:
+ *      the cache is not a security boundary.
+ *
+ * save: waits for the handle's device, has a device kernel compute every section's checksum
+ * from the DEVICE arrays, copies them back through page-locked blocks and writes
+ * path + ".tmp", renamed to `path` once complete.  The handle is unchanged.  `tag`: an opaque
+ * string of at most 255 bytes, stored verbatim (NULL = ""); a caller's key for "is this file
+ * still the schedule of my matrix".  A multi-device handle: CFS_HIP_ERR_UNSUPPORTED.
+ *
+ * load: validates the header and the section table on the host (before anything is allocated
+ * from a size of the file), uploads the arrays to the CURRENT device through two page-locked
+ * blocks, has the checksum kernel verify every uploaded array, and only then sets the handle up.
+ * A non-NULL expected_tag must equal the stored tag.  CFS_HIP_ERR_FILE for anything wrong with
+ * the file, CFS_HIP_ERR_UNSUPPORTED when the stored LDS window does not fit this device; on any
+ * failure *out = NULL and nothing stays allocated.  The loaded handle is a full handle: it
+ * launches the schedule and the kernel choices (window shape, HYB, sibling-combined or plain
+ * kernel, stream-load policy) that the saved one had kept -- the developer knobs CFS_HIP_NT and
+ * CFS_HIP_COMBINE still override, as at create -- and has the same stats, digests and
+ * update_values behaviour; the owner of a shard calls cfs_hip_sym_shard_set_recv again.  The
+ * timing-only ablation mode is not stored.                                                    */
+int cfs_hip_sym_save(cfs_hip_sym_t h, const char *path, const char *tag);
+int cfs_hip_sym_load(const char *path, const char *expected_tag, cfs_hip_sym_t *out);
+
+/* host-only (no GPU): the validator -- magic, version and struct sizes; the file size against
+ * the section table; every section length against the header's counts; the checksums -- and
+ * what the header says.                                                                       */
+typedef struct {
+  int format_version, value_bytes;
+  int n, row_begin, row_end, nranks, rank;
+  int flags; /* cfs_hip_options.flags the schedule was built with (ablation bits cleared) */
+  int ntiles, ngroups, block_threads, lds_slots;
+  int has_value_map, deterministic, device_built;
+  int nsections;
+  int64_t nnz_low, nslices, halo_slots, stream_len, fold_rows, remote_vals, mirror_entries, far_entries;
+  int64_t payload_bytes, file_bytes;
+  char tag[256];
+} cfs_hip_plan_file_info;
+int cfs_hip_plan_file_check(const char *path, cfs_hip_plan_file_info *info);
+/* developer / test: the checksum of cfs_planfile.hpp over [p, p + bytes): on_device = 1, p is a
+ * 16-byte aligned device pointer and the kernel that save and load use computes it (enqueued on
+ * the null stream, complete on return); on_device = 0, p is a host pointer and the host function
+ * does.  The two agree bit for bit for every length.                                           */
+int cfs_hip_debug_checksum(const void *p, size_t bytes, int on_device, unsigned long long *out);
+/* host-only: build the schedule with the host builder exactly as cfs_hip_sym_plan_check_* does
+ * and write it as a plan file (checksums in their host form): a file can be produced and
+ * inspected on a machine without a GPU and loaded on one.  The launch shape is sized for the
+ * default device (256 CUs, estimated residency), so the file need not equal a GPU-made one
+ * byte for byte.                                                                              */
+int cfs_hip_sym_plan_save_f64(int n, const int *rowptr, const int *colind,
+                              const double *values, int nranks, int rank,
+                              const int *row_splits, const cfs_hip_options *opt,
+                              const char *path, const char *tag);
+int cfs_hip_sym_plan_save_f32(int n, const int *rowptr, const int *colind,
+                              const float *values, int nranks, int rank,
+                              const int *row_splits, const cfs_hip_options *opt,
+                              const char *path, const char *tag);
 
 /* host-only: the send side of rank `rank`'s shard (what cfs_hip_sym_shard_send_
  * counts / _rows would return) without touching a device; used by the CPU

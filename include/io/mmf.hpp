@@ -24,6 +24,8 @@ template <typename IndexType, typename ValueType> struct CsrArrays {
   IndexType nrows = 0, ncols = 0;
   long nnz = 0; // expanded count
   bool symmetric = false;
+  // the source file as stat() saw it (the .csrbin rule; also keys the plan cache of tune()): -1 = unknown
+  long long src_size = -1, src_mtime_ns = 0;
   std::vector<IndexType> rowptr, colind;
   std::vector<ValueType> values;
 };

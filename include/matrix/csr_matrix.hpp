@@ -63,6 +63,10 @@ private:
   void *sym_handle_;   // cfs_hip_sym_t
   void *csr_handle_;   // cfs_hip_csr_t
   size_t device_bytes_;
+  // a matrix that came from a file: its name, size and mtime (the plan cache of tune(),
+  // CFS_PLAN_CACHE_DIR); a matrix built from arrays has none
+  std::string source_;
+  long long src_size_ = -1, src_mtime_ns_ = 0;
   void release_host_csr();
 };
 

@@ -45,6 +45,9 @@ CSRMatrix<IndexT, ValueT>::CSRMatrix(const std::string &filename, Platform platf
     exit(1);
   }
   symmetric_ = a.symmetric && symmetric; // csr_matrix.tpp:13-15
+  source_ = filename;
+  src_size_ = a.src_size;
+  src_mtime_ns_ = a.src_mtime_ns;
 #ifdef _LOG_INFO
   if (!symmetric)
     std::cout << "[INFO]: using CSR format to store the sparse matrix..." << std::endl;
@@ -106,6 +109,7 @@ bool CSRMatrix<IndexT, ValueT>::tune(Kernel, Tuning t) {
   static_assert(std::is_same<IndexT, int>::value, "int indices only (src/csr.cpp:10-11)");
   int rc;
   bool use_sss = symmetric_;
+  std::string plan_path, plan_tag; // non-empty: the plan cache applies to this tune()
   if (use_sss) {
 #ifdef _LOG_INFO
     std::cout << "[INFO]: compressing for symmetry: MI355X tile schedule" << std::endl;
@@ -120,6 +124,31 @@ bool CSRMatrix<IndexT, ValueT>::tune(Kernel, Tuning t) {
     // tile uses only once leave the tile format (kept by both tiles, one-sided)
     if (hybrid_) opt.flags |= CFS_HIP_FLAG_HYB;
     const int ngpus = cfs::util::runtime::get_num_gpus();
+    // Plan cache (one GPU, a matrix that came from a file): with CFS_PLAN_CACHE_DIR set to a writable
+    // directory the tuned handle is kept as <dir>/<basename>.<f32|f64>.<none|aggr>[.hyb].plan and
+    // loaded instead of tune() on later runs.  The tag -- the source file's size and mtime (the
+    // .csrbin rule, src/mmf.cpp), the tuning level and the HYB setting -- must match; anything else
+    // is ignored and rewritten.
+    const char *cdir = getenv("CFS_PLAN_CACHE_DIR");
+    if (cdir && *cdir && ngpus == 1 && !source_.empty() && src_size_ >= 0) {
+      const size_t slash = source_.find_last_of('/');
+      plan_path = std::string(cdir) + "/" + (slash == std::string::npos ? source_ : source_.substr(slash + 1)) +
+                  (sizeof(ValueT) == 8 ? ".f64" : ".f32") + (t == Tuning::None ? ".none" : ".aggr") + (hybrid_ ? ".hyb" : "") +
+                  ".plan";
+      plan_tag = "size=" + std::to_string(src_size_) + " mtime_ns=" + std::to_string(src_mtime_ns_) +
+                 " tuning=" + (t == Tuning::None ? "none" : "aggressive") + " hyb=" + (hybrid_ ? "1" : "0");
+      if (cfs_hip_sym_load(plan_path.c_str(), plan_tag.c_str(), &h) == 0) {
+        std::cout << "[INFO]: plan cache hit: " << plan_path << std::endl;
+        sym_handle_ = h;
+        cfs_hip_sym_stats st;
+        cfs_hip_sym_get_stats(h, &st);
+        device_bytes_ = (size_t)st.device_bytes;
+        release_host_csr();
+        tuned_ = true;
+        return true;
+      }
+      std::cout << "[INFO]: plan cache miss (" << cfs_hip_last_error() << "): running tune()" << std::endl;
+    }
     if (ngpus > 1) { // CFS_NUM_GPUS: one shard per GPU, one stream each, this thread drives them
       if (std::is_same<ValueT, double>::value)
         rc = cfs_hip_sym_create_multi_f64(nrows_, rowptr_, colind_, (const double *)values_, ngpus,
@@ -204,6 +233,8 @@ bool CSRMatrix<IndexT, ValueT>::tune(Kernel, Tuning t) {
               << st.far_entries << " far entries, " << st.lds_bytes << " B LDS per workgroup, "
               << cfs::util::runtime::get_num_gpus() << " shard(s)" << std::endl;
 #endif
+    if (!plan_path.empty() && cfs_hip_sym_save((cfs_hip_sym_t)sym_handle_, plan_path.c_str(), plan_tag.c_str()) != 0)
+      std::cout << "[INFO]: plan cache not written: " << cfs_hip_last_error() << std::endl; // best effort
     release_host_csr(); // csr_matrix.tpp:1700-1706
   } else {
     cfs_hip_csr_t h = nullptr;

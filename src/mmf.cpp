@@ -220,8 +220,13 @@ bool LoadMmfCsr(const std::string &filename, CsrArrays<IndexType, ValueType> &ou
   const std::string cpath = cache_path(filename, sizeof(ValueType));
   struct stat st;
   const bool have_stat = stat(filename.c_str(), &st) == 0;
-  if (!cpath.empty() && have_stat && cache_load<IndexType, ValueType>(cpath, st, out)) return true;
-  if (!ParseMmfCsr<IndexType, ValueType>(filename, out, error)) return false;
+  const bool cached = !cpath.empty() && have_stat && cache_load<IndexType, ValueType>(cpath, st, out);
+  if (!cached && !ParseMmfCsr<IndexType, ValueType>(filename, out, error)) return false;
+  if (have_stat) {
+    out.src_size = (long long)st.st_size;
+    out.src_mtime_ns = (long long)st.st_mtim.tv_sec * 1000000000LL + st.st_mtim.tv_nsec;
+  }
+  if (cached) return true;
   if (!cpath.empty() && have_stat) cache_store<IndexType, ValueType>(cpath, st, out);
   return true;
 }
