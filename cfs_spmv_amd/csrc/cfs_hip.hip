@@ -799,6 +799,96 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// the bs x bs diagonal blocks of a whole matrix, out of its schedule (cfs_hip_sym_block_diagonal_async):
+// out[k bs^2 + (i mod bs) bs + (j mod bs)] = a_ij for i, j in block k, both triangles.  `out` is zeroed
+// in front of the launch.  A workgroup per tile, as above.  The diagonal positions take the words of
+// `diag` through the same LDS window as cfs_diag_gather_kernel, so they are its bits.  The off-diagonal
+// positions are found by walking the tile's stored entries the way cfs_plan::decode_plan does on the
+// host: a wave per slice (rowinfo packet counts, lanes per packet by ballot, the leader's rank for the
+// slot block), then the COO section up to ncoo and the far section up to nfar_low -- the mirror images
+// [nfar_low, nfar) repeat entries another tile has already delivered.  Row and column of an entry come
+// back to the caller's numbering through slot_col (far columns are stored in it already); in clustered
+// order the stored orientation follows the schedule, hence (hi, lo) = (max, min).  An entry inside a
+// block is added to both of its positions: atomics, because a matrix may store a position twice (the
+// SpMV sums them too) and because the two triangles of a block may come from different tiles.  Set-up
+// work, one pass over the index stream; every lane reads single words.
+template <typename V>
+__global__ void __launch_bounds__(256)
+    cfs_block_gather_kernel(V *__restrict__ out, const Tile *__restrict__ tiles, int ntiles, SymDev<V> d, int n, int bs,
+                            int window) {
+  extern __shared__ __align__(16) unsigned char cfs_block_smem[];
+  V *w = reinterpret_cast<V *>(cfs_block_smem);
+  typedef typename std::conditional<sizeof(V) == 8, unsigned long long, unsigned>::type Bits;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto val_pos = [](int l, int j, int cnt) { // cfs_plan::packet_val_pos
+    return sizeof(V) == 8 ? (j >> 1) * 2 * cnt + l * 2 + (j & 1) : l * 4 + j;
+  };
+  auto put = [&](int a, int b, V v) {
+    const int hi = max(a, b), lo = min(a, b);
+    if (hi == lo || lo < 0 || hi >= n || hi / bs != lo / bs) return;
+    V *blk = out + (size_t)(hi / bs) * (size_t)(bs * bs);
+    const int i = hi % bs, j = lo % bs;
+    atomicAdd(blk + i * bs + j, v);
+    atomicAdd(blk + j * bs + i, v);
+  };
+  for (int ti = blockIdx.x; ti < ntiles; ti += gridDim.x) {
+    const Tile t = tiles[ti];
+    const int nown = min(t.nown, window), nvr = t.nvrows;
+    const int32_t *sc = d.slot_col + t.slot_off;
+    // the diagonal, as cfs_diag_gather_kernel
+    for (int i = threadIdx.x; i < nown; i += 256) w[i] = V(0);
+    __syncthreads();
+    for (int v = threadIdx.x; v < nvr; v += 256) {
+      const V dg = d.diag[t.vrow_off + v];
+      const int r = (int)(d.rowinfo[t.vrow_off + v] & 0xffffu);
+      Bits bits;
+      __builtin_memcpy(&bits, &dg, sizeof bits);
+      if (bits != 0 && r < nown) w[r] = dg; // (a split row's other chunks hold +0 and do not overwrite)
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nown; i += 256) {
+      const int o = sc[i];
+      if ((unsigned)o < (unsigned)n) out[(size_t)(o / bs) * (size_t)(bs * bs) + (size_t)(o % bs) * (bs + 1)] = w[i];
+    }
+    // packets: wave `wave` walks slices wave, wave + 4, ...
+    const V *tv = d.vals + t.nnz_off;
+    const uint16_t *ts = d.slots + t.sl_off;
+    for (int s = wave; s < t.nslices; s += 4) {
+      const int p0 = s * 64 + lane;
+      const uint32_t info = p0 < nvr ? d.rowinfo[t.vrow_off + p0] : 0u;
+      const int r = (int)(info & 0xffffu), a = (int)(info >> 16);
+      const uint4 sm = d.slice_meta[t.slice_base + s];
+      const unsigned long long leaders = ((unsigned long long)sm.w << 32) | sm.z;
+      long long o = sm.x, os = sm.y & 0x1ffffffu;
+      const int Ld = d.leadlane[(size_t)(t.slice_base + s) * 64 + lane] & 63;
+      const int rank = leader_rank(leaders, Ld);
+      const int row = p0 < nvr ? sc[r] : -1;
+      const int amax = __builtin_amdgcn_readfirstlane(a); // rows are sorted: lane 0 is longest
+      for (int g = 0; g < amax; ++g) {
+        const int cnt = __popcll(__ballot(a > g));
+        if (a > g) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) put(row, sc[ts[os + rank * 4 + j]], tv[o + val_pos(lane, j, cnt)]);
+        }
+        o += 4 * (long long)cnt;
+        os += 4 * (long long)active_leaders(leaders, cnt);
+      }
+    }
+    // COO leftovers and the lower far entries: 256-entry packets, slots at [lane][4]
+    for (int e = threadIdx.x; e < t.ncoo; e += 256) {
+      const size_t pk = (size_t)t.coo_off + (size_t)(e & ~255);
+      put(sc[d.crows[(size_t)t.coo_off + e]], sc[d.ccols[(size_t)t.coo_off + e]],
+          d.cvals[pk + val_pos((e & 255) >> 2, e & 3, 64)]);
+    }
+    for (int e = threadIdx.x; e < t.nfar_low; e += 256) {
+      const size_t pk = (size_t)t.far_off + (size_t)(e & ~255);
+      put(sc[d.frows[(size_t)t.far_off + e]], d.fcols[(size_t)t.far_off + e],
+          d.fvals[pk + val_pos((e & 255) >> 2, e & 3, 64)]);
+    }
+    __syncthreads(); // the next tile zeroes the window
+  }
+}
+
 // pack contributions for rows owned by lower ranks: one value per remote row
 template <typename V>
 __global__ void __launch_bounds__(256)
@@ -923,6 +1013,13 @@ struct cfs_hip_sym_s {
   virtual int update_values(const void *values_dev, long long nnz, hipStream_t st) = 0;
   // d_dev[i - row_begin] = a_ii of the owned rows, from the device arrays (cfs_hip_sym_diagonal_async)
   virtual int diagonal(void *d_dev, hipStream_t st) = 0;
+  // the block_rows x block_rows diagonal blocks of a whole matrix on one device, zeroing included
+  // (cfs_hip_sym_block_diagonal_async); a shard or a multi-device handle has no such thing: a block
+  // straddles the row splits
+  virtual int block_diagonal(void *, int, hipStream_t) {
+    return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "block diagonal: a handle of the whole matrix on one device (blocks "
+                                                    "straddle the row splits of a multi-device handle)");
+  }
   int device = 0; // the device this handle's arrays live on (current device at create)
   std::string plan_note; // why the device builder handed the schedule to the host builder ("" = it did not)
   HostStage stage; // host-pointer callers
@@ -1355,6 +1452,25 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
     hipLaunchKernelGGL((cfs_diag_gather_kernel<V>), dim3(std::min(T, 4096)), dim3(256), (size_t)window * sizeof(V), st,
                        (V *)d_dev, dev.tiles, T, dev.slot_col, dev.rowinfo, dev.diag, (int)P.row_begin,
                        (int)(P.row_end - P.row_begin), window);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  int block_diagonal(void *blocks_dev, int bs, hipStream_t st) override {
+    if (P.nranks != 1 || P.row_begin != 0 || P.row_end != P.n)
+      return set_err(CFS_HIP_ERR_UNSUPPORTED, "block diagonal: a handle of the whole matrix, not a shard (blocks straddle "
+                                              "the row splits)");
+    if (bs == 1) return diagonal(blocks_dev, st); // the diagonal itself: every word written exactly once
+    const long long nb = ((long long)P.n + bs - 1) / bs;
+    HIPCHK(hipMemsetAsync(blocks_dev, 0, (size_t)nb * bs * bs * sizeof(V), st));
+    const int T = (int)P.tiles.size();
+    if (T == 0) return 0;
+    int window = 1; // own rows of the tallest tile
+    for (const Tile &t : P.tiles) window = std::max(window, (int)t.nown);
+    const void *k = (const void *)cfs_block_gather_kernel<V>;
+    int rc = raise_lds_limit(k, device);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cfs_block_gather_kernel<V>), dim3(std::min(T, 4096)), dim3(256), (size_t)window * sizeof(V), st,
+                       (V *)blocks_dev, dev.tiles, T, dev, (int)P.n, bs, window);
     HIPCHK(hipGetLastError());
     return 0;
   }
@@ -1869,6 +1985,80 @@ int cfs_hip_sym_diagonal_async(cfs_hip_sym_t h, void *d_dev, void *stream) {
                                         std::to_string(h->device));
   DeviceGuard g(h->device);
   return h->diagonal(d_dev, (hipStream_t)stream);
+}
+
+static bool block_rows_ok(int bs) { return bs == 1 || bs == 2 || bs == 3 || bs == 4 || bs == 6; }
+// f(V(), std::integral_constant<int, BS>()) for the handle's value type and a block size of 2, 3, 4 or 6
+template <class F> static int with_block(int value_bytes, int bs, F &&f) {
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    switch (bs) {
+    case 2: return f(v, std::integral_constant<int, 2>());
+    case 3: return f(v, std::integral_constant<int, 3>());
+    case 4: return f(v, std::integral_constant<int, 4>());
+    default: return f(v, std::integral_constant<int, 6>());
+    }
+  });
+}
+// the output of the two block entry points: a device pointer on the handle's device
+static int check_block_out(cfs_hip_sym_t h, const void *p, const char *who) {
+  const cfs_rt::PtrInfo di = cfs_rt::classify(p);
+  if (!di.device) return set_err(CFS_HIP_ERR_ARG, std::string(who) + " needs a device pointer");
+  if (di.dev != h->device)
+    return set_err(CFS_HIP_ERR_ARG, "the blocks live on device " + std::to_string(di.dev) + ", the matrix on device " +
+                                        std::to_string(h->device));
+  return 0;
+}
+
+int cfs_hip_sym_block_diagonal_async(cfs_hip_sym_t h, int block_rows, void *blocks_dev, void *stream) {
+  if (!h || !blocks_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (!block_rows_ok(block_rows))
+    return set_err(CFS_HIP_ERR_ARG, "block diagonal: block_rows " + std::to_string(block_rows) + " is not one of 1, 2, 3, 4, 6");
+  int rc = check_block_out(h, blocks_dev, "cfs_hip_sym_block_diagonal_async");
+  if (rc) return rc;
+  DeviceGuard g(h->device);
+  return h->block_diagonal(blocks_dev, block_rows, (hipStream_t)stream);
+}
+
+int cfs_hip_sym_block_inverse_async(cfs_hip_sym_t h, int block_rows, void *minv_dev, void *stream) {
+  if (!h || !minv_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (!block_rows_ok(block_rows))
+    return set_err(CFS_HIP_ERR_ARG, "block inverse: block_rows " + std::to_string(block_rows) + " is not one of 1, 2, 3, 4, 6");
+  int rc = check_block_out(h, minv_dev, "cfs_hip_sym_block_inverse_async");
+  if (rc) return rc;
+  DeviceGuard g(h->device);
+  if (block_rows == 1)
+    return cfs_rt::with_value_type(h->value_bytes, [&](auto v) {
+      return cfs_solver::block_inverse<decltype(v), 1>(h, minv_dev, (hipStream_t)stream);
+    });
+  return with_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::block_inverse<decltype(v), decltype(bs)::value>(h, minv_dev, (hipStream_t)stream);
+  });
+}
+
+int cfs_hip_sym_pcg_block(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int block_rows, double tol, int maxiter,
+                          int check_every, int *iterations, double *relres, void *stream) {
+  if (!h || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (iterations) *iterations = 0;
+  if (relres) *relres = 0.0;
+  if (!block_rows_ok(block_rows))
+    return set_err(CFS_HIP_ERR_ARG, "pcg: block_rows " + std::to_string(block_rows) + " is not one of 1, 2, 3, 4, 6");
+  if (block_rows == 1) // Jacobi: the same code path, the same bits
+    return cfs_hip_sym_pcg(h, u_dev, b_dev, CFS_HIP_PRECOND_JACOBI, tol, maxiter, check_every, iterations, relres, stream);
+  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg: u and b must be different vectors");
+  if (!h->send_rows().empty() || h->rows() != h->n())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg: a handle of the whole matrix, not a shard");
+  int ngpus = 1;
+  if (cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg: block Jacobi needs the whole matrix on one device (blocks straddle the "
+                                            "row splits of a multi-device handle)");
+  int rc = check_placement(h, u_dev, b_dev);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  DeviceGuard g(h->device);
+  return with_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::cg<decltype(v), true, decltype(bs)::value>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres,
+                                                                  (hipStream_t)stream);
+  });
 }
 
 int cfs_hip_sym_spmv(cfs_hip_sym_t h, void *y, const void *x) {

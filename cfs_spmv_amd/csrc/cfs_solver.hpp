@@ -29,6 +29,17 @@
 //                                 unpreconditioned residual, the same rule as without)
 // r . z has two slots alternating with the parity of the iteration, like r . r.  The PRE = false
 // instantiations are the kernels of the plain iteration, operation for operation.
+//
+// Block Jacobi (cfs_hip_sym_pcg_block, BS = 2, 3, 4, 6 below): M = blockdiag(A) on the BS x BS node blocks
+// of a multi-dof mesh matrix, whose couplings inside a node are as strong as the diagonal.  Set-up, once
+// per call: the blocks are gathered from the handle (cfs_block_gather_kernel) and cg_binv_kernel inverts
+// them, one thread per block, in fp64 registers (Cholesky, then the inverse); the inverse is stored rounded
+// to the value type as its packed lower triangle, structure of arrays (word t of block k at minv[t nb + k]:
+// consecutive lanes read consecutive words).  The same five launches per iteration: z_i = sum_j
+// (double)Minv_ij (double)r_j over the block, r_j the rounded value in memory, is formed in fp64 inside
+// cg_update_block_kernel (for r . z) and again in cg_direction_block_kernel, and never stored.  These walk
+// the vectors one node block per thread, grid-stride; the scalars are the same partial-sum slots, so a solve
+// on a deterministic handle stays bit-reproducible.  The kernels above are not touched by it.
 #pragma once
 
 namespace cfs_solver {
@@ -242,9 +253,235 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// ---- block Jacobi --------------------------------------------------------------------------------
+constexpr int tri_words(int bs) { return bs * (bs + 1) / 2; } // packed lower triangle of a block
+
+// minv <- the inverse of every BS x BS block of `blocks` (row-major, as cfs_block_gather_kernel leaves
+// them), rounded to V, packed lower triangle, word t = i (i + 1) / 2 + j of block k at minv[t nb + k].
+// fp64 registers: A = L L^T, then L^-1, then A^-1 = L^-T L^-1.  The positions of a trailing partial block
+// that lie outside the matrix count as identity.  part[P_BAD] <- blocks with a pivot that is not finite
+// and > 0.  BS = 1: (V)(1 / a), the word cg_dinv_kernel stores.
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cg_binv_kernel(const V *__restrict__ blocks, V *__restrict__ minv, long long nb, long long n, double *__restrict__ part) {
+  double bad = 0.0;
+  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+    double a[BS][BS], li[BS][BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j)
+        a[i][j] = k * BS + i < n ? (double)blocks[k * (BS * BS) + i * BS + j] : (i == j ? 1.0 : 0.0);
+    if (BS == 1) {
+      if (!(a[0][0] > 0.0) || a[0][0] * 0.0 != 0.0) bad += 1.0;
+      minv[k] = (V)(1.0 / a[0][0]);
+      continue;
+    }
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) { // Cholesky, column by column: a <- L
+      double dj = a[j][j];
+#pragma unroll
+      for (int c = 0; c < j; ++c) dj -= a[j][c] * a[j][c];
+      // (!(dj > 0): a NaN counts too)
+      if (!(dj > 0.0) || dj * 0.0 != 0.0) ok = false;
+      const double l = sqrt(dj);
+      a[j][j] = l;
+#pragma unroll
+      for (int i = j + 1; i < BS; ++i) {
+        double v = a[i][j];
+#pragma unroll
+        for (int c = 0; c < j; ++c) v -= a[i][c] * a[j][c];
+        a[i][j] = v / l;
+      }
+    }
+    if (!ok) bad += 1.0;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) { // li <- L^-1, column by column
+      li[j][j] = 1.0 / a[j][j];
+#pragma unroll
+      for (int i = j + 1; i < BS; ++i) {
+        double v = 0.0;
+#pragma unroll
+        for (int c = j; c < i; ++c) v += a[i][c] * li[c][j];
+        li[i][j] = -v / a[i][i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        double v = 0.0;
+#pragma unroll
+        for (int c = i; c < BS; ++c) v += li[c][i] * li[c][j];
+        minv[(long long)(i * (i + 1) / 2 + j) * nb + k] = (V)v;
+      }
+  }
+  bad = block_sum(bad);
+  if (threadIdx.x == 0) part[P_BAD * kGrid + blockIdx.x] = bad;
+}
+
+// full <- the packed inverse as nb full row-major blocks, both triangles (cfs_hip_sym_block_inverse_async)
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cg_bunpack_kernel(V *__restrict__ full, const V *__restrict__ minv, long long nb) {
+  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads)
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        const V v = minv[(long long)(i * (i + 1) / 2 + j) * nb + k];
+        full[k * (BS * BS) + i * BS + j] = v;
+        full[k * (BS * BS) + j * BS + i] = v;
+      }
+}
+
+// z = Minv_k r over node block k, in fp64 (r: the block's rounded residual, 0 outside the matrix)
+template <typename V, int BS>
+__device__ __forceinline__ void block_apply(const V *__restrict__ minv, long long nb, long long k, const double (&r)[BS],
+                                            double (&z)[BS]) {
+  double m[BS][BS];
+#pragma unroll
+  for (int i = 0; i < BS; ++i)
+#pragma unroll
+    for (int j = 0; j <= i; ++j) m[i][j] = m[j][i] = (double)minv[(long long)(i * (i + 1) / 2 + j) * nb + k];
+#pragma unroll
+  for (int i = 0; i < BS; ++i) {
+    double v = 0.0;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) v += m[i][j] * r[j];
+    z[i] = v;
+  }
+}
+
+// cg_residual_kernel<V, true> with M = blockdiag(A):  r = b - q;  p = z = Minv r;  part <- r . r, b . b, r . z
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cg_residual_block_kernel(V *__restrict__ r, V *__restrict__ p, const V *__restrict__ b, const V *__restrict__ q,
+                             long long n, double *__restrict__ part, const V *__restrict__ minv, long long nb) {
+  double rr = 0.0, bb = 0.0, rz = 0.0;
+  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+    double rd[BS], z[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      const long long g = k * BS + i;
+      rd[i] = 0.0;
+      if (g < n) {
+        const V bi = b[g], ri = bi - q[g];
+        r[g] = ri;
+        rd[i] = (double)ri;
+        rr += (double)ri * (double)ri;
+        bb += (double)bi * (double)bi;
+      }
+    }
+    block_apply<V, BS>(minv, nb, k, rd, z);
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      const long long g = k * BS + i;
+      if (g < n) {
+        rz += rd[i] * z[i];
+        p[g] = (V)z[i];
+      }
+    }
+  }
+  rr = block_sum(rr);
+  bb = block_sum(bb);
+  rz = block_sum(rz);
+  if (threadIdx.x == 0) {
+    part[P_RR0 * kGrid + blockIdx.x] = rr;
+    part[P_BB * kGrid + blockIdx.x] = bb;
+    part[P_RZ0 * kGrid + blockIdx.x] = rz;
+  }
+}
+
+// cg_update_kernel<V, true> with M = blockdiag(A): z = Minv r of the ROUNDED r
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cg_update_block_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q,
+                           long long n, double *__restrict__ part, const int *__restrict__ ic, int it,
+                           const V *__restrict__ minv, long long nb) {
+  if (ic[I_DONE]) return;
+  const double pq = slot_sum(part, P_PQ), rz_old = slot_sum(part, P_RZ0 + (it & 1));
+  const double alpha = pq != 0.0 ? rz_old / pq : 0.0;
+  double s = 0.0, sz = 0.0;
+  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+    double rd[BS], z[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      const long long g = k * BS + i;
+      rd[i] = 0.0;
+      if (g < n) {
+        u[g] = (V)((double)u[g] + alpha * (double)p[g]);
+        const double ri = (double)r[g] - alpha * (double)q[g];
+        const V rn = (V)ri;
+        r[g] = rn;
+        s += ri * ri;
+        rd[i] = (double)rn;
+      }
+    }
+    block_apply<V, BS>(minv, nb, k, rd, z);
+#pragma unroll
+    for (int i = 0; i < BS; ++i) sz += rd[i] * z[i]; // (rd = 0 outside the matrix)
+  }
+  s = block_sum(s);
+  sz = block_sum(sz);
+  if (threadIdx.x == 0) {
+    part[(P_RR0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = s;
+    part[(P_RZ0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = sz;
+  }
+}
+
+// cg_direction_kernel<V, true> with M = blockdiag(A):  p = Minv r + beta p
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cg_direction_block_kernel(V *__restrict__ p, const V *__restrict__ r, long long n, const double *__restrict__ part,
+                              int *__restrict__ ic, int it, double stop, const V *__restrict__ minv, long long nb) {
+  if (ic[I_DONE]) return;
+  const double rz = slot_sum(part, P_RZ0 + (it & 1)), rzn = slot_sum(part, P_RZ0 + ((it + 1) & 1));
+  const double beta = rz != 0.0 ? rzn / rz : 0.0;
+  double res = rzn;
+  if (blockIdx.x == 0) res = slot_sum(part, P_RR0 + ((it + 1) & 1)); // what the stopping rule looks at: r . r
+  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+    double rd[BS], z[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      const long long g = k * BS + i;
+      rd[i] = g < n ? (double)r[g] : 0.0;
+    }
+    block_apply<V, BS>(minv, nb, k, rd, z);
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      const long long g = k * BS + i;
+      if (g < n) p[g] = (V)(z[i] + beta * (double)p[g]);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ic[I_ITER] += 1;
+    if (!(res > stop)) ic[I_DONE] = 1;
+  }
+}
+
+// the inverse blocks cfs_hip_sym_pcg_block would use now, as nb full row-major blocks
+// (cfs_hip_sym_block_inverse_async): the solver's gather and cg_binv_kernel, then the unpack
+template <typename V, int BS, class Handle> int block_inverse(Handle *h, void *minv_dev, hipStream_t st) {
+  using cfs_rt::DevBuf;
+  const long long n = h->n(), nb = (n + BS - 1) / BS;
+  DevBuf packed, pbuf_part; // (freed on return: hipFree waits for the kernels that use them)
+  int rc;
+  if ((rc = packed.alloc((size_t)nb * tri_words(BS) * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))))
+    return rc;
+  if ((rc = h->block_diagonal(minv_dev, BS, st))) return rc;
+  hipLaunchKernelGGL((cg_binv_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)minv_dev, (V *)packed.p, nb, n,
+                     (double *)pbuf_part.p);
+  hipLaunchKernelGGL((cg_bunpack_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)minv_dev, (const V *)packed.p, nb);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // u: in = first guess, out = solution.  Returns 0 / an error code; *iterations, *relres as documented in cfs_hip.h
 // PRE: Jacobi (cfs_hip_sym_pcg); PRE = false is cfs_hip_sym_cg, launch for launch
-template <typename V, bool PRE = false, class Handle>
+// BS >= 2 (with PRE): block Jacobi on BS x BS blocks (cfs_hip_sym_pcg_block); dbuf then holds the packed inverses
+template <typename V, bool PRE = false, int BS = 0, class Handle>
 int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int check_every, int *iterations,
        double *relres, hipStream_t st) {
   using cfs_rt::DevBuf;
@@ -261,9 +498,14 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
     return cfs_rt::set_err(CFS_HIP_ERR_ARG, "cg: u and b must be 16-byte aligned");
   V *u = (V *)u_dev;
   const V *b = (const V *)b_dev;
-  DevBuf rbuf, pbuf, qbuf, pbuf_part, cnt, dbuf;
+  static_assert(BS == 0 || (PRE && BS >= 2), "block Jacobi is a preconditioner; BS = 1 is Jacobi");
+  constexpr bool BLK = BS >= 2;
+  const long long nb = BLK ? (n + BS - 1) / BS : 0;
+  DevBuf rbuf, pbuf, qbuf, pbuf_part, cnt, dbuf, blkbuf;
   int rc;
-  if (PRE && (rc = dbuf.alloc((size_t)n * sizeof(V) + 64))) return rc;
+  if (BLK && ((rc = dbuf.alloc((size_t)nb * tri_words(BS) * sizeof(V) + 64)) || (rc = blkbuf.alloc((size_t)nb * BS * BS * sizeof(V) + 64))))
+    return rc;
+  if (PRE && !BLK && (rc = dbuf.alloc((size_t)n * sizeof(V) + 64))) return rc;
   const V *dinv = (const V *)dbuf.p;
   if ((rc = rbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf.alloc((size_t)n * sizeof(V) + 64)) ||
       (rc = qbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) ||
@@ -283,14 +525,21 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
   };
   HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
   HIPCHK(hipMemsetAsync(ic, 0, I_COUNT * sizeof(int), st));
-  if (PRE) { // dinv from the handle's own diagonal; entries that are not finite and > 0 are counted
+  if constexpr (BLK) { // the inverse blocks from the handle's own blocks; blocks that are not positive definite are counted
+    if ((rc = h->block_diagonal(blkbuf.p, BS, st))) return rc;
+    hipLaunchKernelGGL((cg_binv_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)blkbuf.p, (V *)dbuf.p, nb, n, part);
+  } else if (PRE) { // dinv from the handle's own diagonal; entries that are not finite and > 0 are counted
     if ((rc = h->diagonal(dbuf.p, st))) return rc;
     hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)dbuf.p, n, part);
   }
   // r = b - A u, p = r, rr[0] = r . r, bb = b . b  (PRE: p = dinv r, rz[0] = r . p)
   if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
-  hipLaunchKernelGGL((cg_residual_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, r, p, b, (const V *)q, n, part,
-                     (int)P_RR0, 1, dinv);
+  if constexpr (BLK)
+    hipLaunchKernelGGL((cg_residual_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, p, b, (const V *)q, n, part,
+                       dinv, nb);
+  else
+    hipLaunchKernelGGL((cg_residual_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, r, p, b, (const V *)q, n, part,
+                       (int)P_RR0, 1, dinv);
   HIPCHK(hipGetLastError());
   double rr0 = 0.0, bb = 0.0;
   if ((rc = read_slot(P_RR0, &rr0))) return rc;
@@ -298,6 +547,10 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
   if (PRE) { // (read with the first host look: u has not been touched yet)
     double bad = 0.0;
     for (int g = 0; g < kGrid; g++) bad += hp[(size_t)P_BAD * kGrid + g];
+    if (BLK && bad != 0.0)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg: block Jacobi needs positive definite diagonal blocks, " +
+                                                  std::to_string((long long)bad) + " of " + std::to_string(nb) + " blocks of " +
+                                                  std::to_string(BS) + " rows have a pivot that is zero, negative or not finite");
     if (bad != 0.0)
       return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg: Jacobi needs a positive diagonal, " + std::to_string((long long)bad) +
                                                   " of " + std::to_string(n) + " entries are zero, negative or not finite");
@@ -311,10 +564,17 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
     if (r2) return r2;
     hipLaunchKernelGGL((cg_pq_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part,
                        (const int *)ic);
-    hipLaunchKernelGGL((cg_update_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n,
-                       part, (const int *)ic, k, dinv);
-    hipLaunchKernelGGL((cg_direction_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
-                       (const double *)part, ic, k, stop, dinv);
+    if constexpr (BLK) {
+      hipLaunchKernelGGL((cg_update_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q,
+                         n, part, (const int *)ic, k, dinv, nb);
+      hipLaunchKernelGGL((cg_direction_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
+                         (const double *)part, ic, k, stop, dinv, nb);
+    } else {
+      hipLaunchKernelGGL((cg_update_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n,
+                         part, (const int *)ic, k, dinv);
+      hipLaunchKernelGGL((cg_direction_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
+                         (const double *)part, ic, k, stop, dinv);
+    }
     return 0;
   };
   // CFS_HIP_CG_GRAPH=1: two iterations (both parities) captured once and replayed as one graph launch.

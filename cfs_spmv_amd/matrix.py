@@ -302,11 +302,43 @@ class SymMatrix:
         _lib.check(_lib.load().cfs_hip_sym_diagonal_async(self._h, _ptr(out), _stream_ptr(stream)))
         return out
 
-    def pcg(self, u, b, precond="jacobi", tol=1e-10, maxiter=1000, check_every=8, stream=None):
+    def _blocks(self, fn, block, out, stream):
+        import torch
+        block = int(block)
+        nb = -(-self.nrows() // block) if block > 0 else 0
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        if out is None:
+            out = torch.empty((nb, max(block, 0), max(block, 0)), dtype=tdt, device="cuda")
+        elif out.dtype != tdt or out.numel() < nb * block * block or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {tdt} tensor of at least {nb * block * block} values")
+        _lib.check(fn(self._h, block, _ptr(out), _stream_ptr(stream)))
+        return out
+
+    def block_diagonal(self, block, out=None, stream=None):
+        """the block x block diagonal blocks of the matrix (cfs_hip_sym_block_diagonal_async): a device
+        tensor (ceil(n / block), block, block) of the value type, both triangles, 0 where the matrix
+        stores nothing and outside the matrix in a trailing partial block; block one of 1, 2, 3, 4, 6.
+        Gathered from the handle's device arrays (so it follows update_values).  A whole-matrix handle
+        on one device.  `out`: a device tensor to fill instead of a new one."""
+        return self._blocks(_lib.load().cfs_hip_sym_block_diagonal_async, block, out, stream)
+
+    def block_inverse(self, block, out=None, stream=None):
+        """the inverse blocks pcg(precond="block_jacobi", block=block) would use now
+        (cfs_hip_sym_block_inverse_async), same shape as block_diagonal(); identity outside the
+        matrix in a trailing partial block.  For developers and tests."""
+        return self._blocks(_lib.load().cfs_hip_sym_block_inverse_async, block, out, stream)
+
+    def pcg(self, u, b, precond="jacobi", tol=1e-10, maxiter=1000, check_every=8, stream=None, block=3):
         """preconditioned conjugate gradients inside the library (cfs_hip_sym_pcg): like cg(), with
-        precond = "jacobi" (the diagonal of the handle; it must be positive) or "none" (exactly
-        cg()).  Stops on the unpreconditioned residual ||r|| <= tol ||b||.  Returns (iterations,
-        ||b - A u|| / ||b||)."""
+        precond = "jacobi" (the diagonal of the handle; it must be positive), "none" (exactly
+        cg()) or "block_jacobi" (cfs_hip_sym_pcg_block: the block x block diagonal blocks, block one
+        of 1, 2, 3, 4, 6; they must be positive definite; block = 1 is "jacobi").  Stops on the
+        unpreconditioned residual ||r|| <= tol ||b||.  Returns (iterations, ||b - A u|| / ||b||)."""
+        if precond == "block_jacobi":
+            it, res = C.c_int(), C.c_double()
+            _lib.check(_lib.load().cfs_hip_sym_pcg_block(self._h, _ptr(u), _ptr(b), int(block), float(tol), int(maxiter),
+                                                         int(check_every), C.byref(it), C.byref(res), _stream_ptr(stream)))
+            return it.value, res.value
         if isinstance(precond, str):
             if precond not in PRECOND:
                 raise ValueError(f"unknown preconditioner {precond!r}: one of {sorted(PRECOND)}")

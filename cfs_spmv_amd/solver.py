@@ -48,21 +48,45 @@ def cg_native(A, b, tol=1e-10, maxiter=1000, x0=None, check_every=8):
     return u, it, res
 
 
-def pcg(A, b, tol=1e-10, maxiter=1000, x0=None):
+def _block_apply(minv, r, z):
+    """z = blockdiag(minv) r: a batched mat-vec over the (nb, bs, bs) inverse blocks, formed in fp64
+    like the library's; the tail of a trailing partial block is padded with zeros"""
+    import torch
+    nb, bs, _ = minv.shape
+    n = r.numel()
+    rp = torch.zeros(nb * bs, dtype=torch.float64, device=r.device)
+    rp[:n] = r
+    zp = torch.bmm(minv.double(), rp.view(nb, bs, 1)).view(-1)
+    z.copy_(zp[:n])
+    return z
+
+
+def pcg(A, b, tol=1e-10, maxiter=1000, x0=None, precond="jacobi", block=3):
     """Jacobi-preconditioned conjugate gradients, host-driven: the recurrence of cfs_hip_sym_pcg
     (z = D^-1 r, alpha = r.z / p.q, beta = r'.z' / r.z, stop on the unpreconditioned ||r|| <= tol ||b||)
     with the diagonal taken from the handle (A.diagonal()), so the caller's CSR is not needed.
+    precond = "block_jacobi": z = M^-1 r with the inverse node blocks of the handle
+    (A.block_inverse(block)), the recurrence of cfs_hip_sym_pcg_block.
     Returns (u, iterations, relative residual), like cg()."""
     import torch
-    d = A.diagonal()
-    if not bool(torch.all(torch.isfinite(d) & (d > 0))):
-        raise ValueError("pcg: Jacobi needs a positive diagonal")
-    dinv = (1.0 / d.double()).to(b.dtype)
+    if precond == "block_jacobi":
+        minv = A.block_inverse(block)
+        if not bool(torch.all(torch.isfinite(minv))):
+            raise ValueError("pcg: block Jacobi needs positive definite diagonal blocks")
+        apply = lambda r, z: _block_apply(minv, r, z)
+    elif precond == "jacobi":
+        d = A.diagonal()
+        if not bool(torch.all(torch.isfinite(d) & (d > 0))):
+            raise ValueError("pcg: Jacobi needs a positive diagonal")
+        dinv = (1.0 / d.double()).to(b.dtype)
+        apply = lambda r, z: torch.mul(r, dinv, out=z)
+    else:
+        raise ValueError(f"unknown preconditioner {precond!r}: 'jacobi' or 'block_jacobi'")
     u = torch.zeros_like(b) if x0 is None else x0.clone()
     q = torch.empty_like(b)
     A.dense_vector_multiply(q, u)
     r = b - q
-    z = r * dinv
+    z = apply(r, torch.empty_like(r))
     p = z.clone()
     rz = float(torch.dot(r, z))
     rr = float(torch.dot(r, r))
@@ -73,7 +97,7 @@ def pcg(A, b, tol=1e-10, maxiter=1000, x0=None):
         alpha = rz / float(torch.dot(p, q))
         u.add_(p, alpha=alpha)
         r.add_(q, alpha=-alpha)
-        torch.mul(r, dinv, out=z)
+        apply(r, z)
         rz_new = float(torch.dot(r, z))
         rr = float(torch.dot(r, r))
         p.mul_(rz_new / rz).add_(z)
@@ -84,13 +108,14 @@ def pcg(A, b, tol=1e-10, maxiter=1000, x0=None):
     return u, it, res
 
 
-def pcg_native(A, b, precond="jacobi", tol=1e-10, maxiter=1000, x0=None, check_every=8):
+def pcg_native(A, b, precond="jacobi", tol=1e-10, maxiter=1000, x0=None, check_every=8, block=3):
     """the same iteration inside the library (cfs_hip_sym_pcg): still five launches per iteration, the
-    diagonal gathered from the handle, z = D^-1 r never stored.  Returns (u, iterations, relative
+    diagonal gathered from the handle, z = D^-1 r never stored.  precond = "block_jacobi":
+    cfs_hip_sym_pcg_block on the block x block node blocks.  Returns (u, iterations, relative
     residual), like pcg()."""
     import torch
     u = torch.zeros_like(b) if x0 is None else x0.clone()
-    it, res = A.pcg(u, b, precond=precond, tol=tol, maxiter=maxiter, check_every=check_every)
+    it, res = A.pcg(u, b, precond=precond, tol=tol, maxiter=maxiter, check_every=check_every, block=block)
     return u, it, res
 
 

@@ -329,6 +329,46 @@ int cfs_hip_sym_spmv_async(cfs_hip_sym_t h, void *y_dev, const void *x_dev,
  * the way the y block of an SpMV comes home (cfs_hip_sym_multi_set_xmode).  A null argument, a
  * host pointer or a pointer on another device: CFS_HIP_ERR_ARG.                              */
 int cfs_hip_sym_diagonal_async(cfs_hip_sym_t h, void *d_dev, void *stream);
+/* The block_rows x block_rows diagonal blocks of the matrix (the node blocks of a multi-dof mesh
+ * matrix), the sibling of cfs_hip_sym_diagonal_async: block k holds rows and columns [k bs, min((k + 1)
+ * bs, n)) of the caller's numbering, nb = ceil(n / bs) blocks, bs = block_rows one of 1, 2, 3, 4, 6
+ * (anything else: CFS_HIP_ERR_ARG).  blocks_dev receives nb bs^2 values of the handle's value type,
+ * row-major per block: blocks_dev[k bs^2 + (i mod bs) bs + (j mod bs)] = a_ij, both triangles, 0 where
+ * the matrix stores no entry and in the positions of a trailing partial block that lie outside the
+ * matrix.  Every word is defined after the call (the zeroing is enqueued on `stream` in front of the
+ * gather) and nothing outside the nb bs^2 words is written.  Read from the handle's DEVICE arrays,
+ * like the diagonal: it follows cfs_hip_sym_update_values_*, needs nothing of the caller's CSR and
+ * works on a handle from cfs_hip_sym_load.  The diagonal positions are bit for bit what
+ * cfs_hip_sym_diagonal_async returns (bs = 1: the output IS that diagonal); an off-diagonal position
+ * holds the stored value, the sum where the matrix stores the position more than once, as the SpMV
+ * gives (+-0 need not keep its sign).  A whole-matrix handle on one device only: blocks straddle the
+ * row splits (multiples of 16, not of bs), so a shard or a multi-device handle gets
+ * CFS_HIP_ERR_UNSUPPORTED -- merging two owners' halves of a block is left for a later change.  A
+ * null argument, a host pointer or a pointer on another device: CFS_HIP_ERR_ARG.             */
+int cfs_hip_sym_block_diagonal_async(cfs_hip_sym_t h, int block_rows, void *blocks_dev, void *stream);
+/* cfs_hip_sym_pcg with M = blockdiag(A) at block size block_rows: z = M^-1 r.  block_rows = 1 is
+ * CFS_HIP_PRECOND_JACOBI, the same code path, the same bits.  For 2, 3, 4, 6: once per call the blocks
+ * are gathered (as cfs_hip_sym_block_diagonal_async does) and inverted, one thread per block in fp64
+ * (the block read as stored; Cholesky, then the inverse; the positions of a trailing partial block
+ * outside the matrix count as identity); the inverse is kept rounded to the value type.  STILL five
+ * launches per iteration and no host round trip: z_i = sum_j (double)Minv_ij (double)r_j over the
+ * block (r_j as stored) is formed in fp64 inside the fused update and the direction kernel and never
+ * written to memory; the same fixed-order partial sums, so a solve on a deterministic handle is
+ * bit-reproducible.  Stopping rule, check_every, *iterations, *relres, alignment, placement and
+ * CFS_HIP_CG_GRAPH are those of cfs_hip_sym_pcg.  A block whose Cholesky pivot is not finite and > 0
+ * ("not positive definite": an indefinite block, a NaN, a missing diagonal entry): CFS_HIP_ERR_ARG, u
+ * untouched, *iterations = 0.  Another block_rows: CFS_HIP_ERR_ARG.  A shard or a multi-device
+ * handle: CFS_HIP_ERR_UNSUPPORTED.                                                            */
+int cfs_hip_sym_pcg_block(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int block_rows, double tol, int maxiter,
+                          int check_every, int *iterations, double *relres, void *stream);
+/* For developers and tests: the inverse blocks cfs_hip_sym_pcg_block would use at this moment, as
+ * nb bs^2 values, full row-major blocks of the value type (both triangles, identity in the positions
+ * of a trailing partial block outside the matrix) -- the solver's two set-up kernels plus an unpack,
+ * so that a test can run the SAME preconditioner in higher precision.  A block that is not positive
+ * definite leaves non-finite or meaningless words; no error is raised for it here.  Arguments and
+ * handles as for cfs_hip_sym_block_diagonal_async; temporary device memory is released before the
+ * call returns, which waits for the kernels.                                                  */
+int cfs_hip_sym_block_inverse_async(cfs_hip_sym_t h, int block_rows, void *minv_dev, void *stream);
 
 /* ---- sharded operation: y_block = local rows; contributions to rows owned
  *      by lower ranks are packed into send_buf (device), exchanged by the

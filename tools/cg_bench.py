@@ -3,7 +3,9 @@ cfs_spmv_amd/solver.py (two host-read dot products per iteration) against cfs_hi
 iteration behind the C ABI, no host round trip), and the same pair with the Jacobi preconditioner
 (solver.pcg against cfs_hip_sym_pcg: dinv read in two kernels, 2 n s bytes more per iteration).
 Fixed number of iterations (tol = 0).  The Jacobi columns are left out when the library loaded
-through CFS_HIP_LIB has no cfs_hip_sym_pcg (an A/B run against an older build).
+through CFS_HIP_LIB has no cfs_hip_sym_pcg (an A/B run against an older build).  Block Jacobi on
+3 x 3 node blocks (cfs_hip_sym_pcg_block) sits beside Jacobi: the native loop's time per iteration,
+taken in the same run with the two interleaved, and for both the iterations down to TOL.
 usage: python tools/cg_bench.py [matrix[:scale] ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,6 +16,8 @@ from cfs_spmv_amd import synth
 from cfs_spmv_amd.solver import cg, cg_native, pcg, pcg_native
 
 HAVE_PCG = hasattr(cfs.load(), "cfs_hip_sym_pcg")
+HAVE_BLOCK = hasattr(cfs.load(), "cfs_hip_sym_pcg_block")
+BLOCK, TOL, MAXITER = 3, 1e-8, 5000
 
 out = {}
 for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
@@ -50,6 +54,9 @@ for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
         runs += [("jacobi_torch_loop", lambda: pcg(A, b, tol=0.0, maxiter=K)),
                  ("jacobi_native_check8", lambda: pcg_native(A, b, tol=0.0, maxiter=K, check_every=8)),
                  ("jacobi_native_check16", lambda: pcg_native(A, b, tol=0.0, maxiter=K, check_every=16))]
+        if HAVE_BLOCK:  # interleaved with the Jacobi runs
+            blk = lambda ce: (lambda: pcg_native(A, b, precond="block_jacobi", block=BLOCK, tol=0.0, maxiter=K, check_every=ce))
+            runs = runs[:-2] + [runs[-2], (f"block{BLOCK}_native_check8", blk(8)), runs[-1], (f"block{BLOCK}_native_check16", blk(16))]
         # bytes of the plain iteration (B_alg + 11 n s) against the 2 n s more that dinv costs
         st, s_ = A.stats(), A.dtype.itemsize
         res["jacobi_extra_bytes_ratio"] = round(2 * n * s_ / (st["bytes_algorithmic"] + 11 * n * s_), 4)
@@ -61,6 +68,13 @@ for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
         torch.cuda.synchronize()
         res[label + "_us_per_iteration"] = round((time.perf_counter() - t0) / max(it, 1) * 1e6, 2)
         res[label + "_iterations"] = it
+    if HAVE_BLOCK:  # what the preconditioners buy: iterations until ||r|| <= TOL ||b||
+        res["tolerance"] = TOL
+        res["jacobi_iterations_to_tolerance"] = pcg_native(A, b, tol=TOL, maxiter=MAXITER, check_every=16)[1]
+        res[f"block{BLOCK}_iterations_to_tolerance"] = pcg_native(A, b, precond="block_jacobi", block=BLOCK, tol=TOL,
+                                                                  maxiter=MAXITER, check_every=16)[1]
+        j16, b16 = res["jacobi_native_check16_us_per_iteration"], res[f"block{BLOCK}_native_check16_us_per_iteration"]
+        res[f"block{BLOCK}_over_jacobi_check16"] = round(b16 / j16 - 1.0, 4)
     out[spec] = res
     A.close()
 print(json.dumps(out))
