@@ -1481,6 +1481,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
 #include "cfs_devplan.hpp" // tune() on the GPU (needs SymMatrix and cfs_value_scatter_kernel)
 #include "cfs_csr.hpp"     // the general CSR path: kernels, handle, create / launch
 #include "cfs_solver.hpp"  // conjugate gradients on resident vectors (a solver-style caller)
+#include "cfs_solver_mixed.hpp" // the same recurrence on an fp32 handle, the solution and true residuals in fp64
 #include "cfs_multi.hpp"   // one host thread, N devices: MultiSym, its create and cfs_hip_sym_multi_*
 
 
@@ -2058,6 +2059,50 @@ int cfs_hip_sym_pcg_block(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int b
   return with_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
     return cfs_solver::cg<decltype(v), true, decltype(bs)::value>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres,
                                                                   (hipStream_t)stream);
+  });
+}
+
+int cfs_hip_sym_pcg_mixed(cfs_hip_sym_t h64, cfs_hip_sym_t h32, void *u_dev, const void *b_dev, int block_rows, double tol,
+                          double delta, int maxiter, int check_every, int *iterations, int *replacements, double *relres,
+                          void *stream) {
+  if (!h64 || !h32 || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (iterations) *iterations = 0;
+  if (replacements) *replacements = 0;
+  if (relres) *relres = 0.0;
+  if (block_rows != 0 && !block_rows_ok(block_rows))
+    return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: block_rows " + std::to_string(block_rows) + " is not one of 0, 1, 2, 3, 4, 6");
+  if (delta == 0.0) delta = 0.1;
+  if (!(delta > 0.0 && delta < 1.0)) return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: delta must lie in (0, 1) (0: the default, 0.1)");
+  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: u and b must be different vectors");
+  if (h64->value_bytes != 8 || h32->value_bytes != 4)
+    return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: the first handle must hold fp64 values and the second fp32 values (got " +
+                                        std::to_string(h64->value_bytes) + " and " + std::to_string(h32->value_bytes) + " bytes)");
+  if (h64->n() != h32->n())
+    return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: the handles hold matrices of " + std::to_string(h64->n()) + " and " +
+                                        std::to_string(h32->n()) + " rows");
+  for (cfs_hip_sym_t h : {h64, h32}) {
+    if (!h->send_rows().empty() || h->rows() != h->n())
+      return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_mixed: handles of the whole matrix, not shards");
+    int ngpus = 1;
+    if (cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
+      return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_mixed: both matrices on one device (the multi-device form is not built)");
+  }
+  if (h64->device != h32->device)
+    return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: the fp64 matrix lives on device " + std::to_string(h64->device) +
+                                        ", the fp32 matrix on device " + std::to_string(h32->device));
+  int rc = check_placement(h64, u_dev, b_dev);
+  if (rc) return rc;
+  // (the iteration's own vectors are library memory on the handles' device)
+  h64->ok_x = h64->ok_y = h32->ok_x = h32->ok_y = nullptr;
+  DeviceGuard g(h64->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (block_rows == 0)
+    return cfs_solver::cg_mixed<false, 0>(h64, h32, u_dev, b_dev, tol, delta, maxiter, check_every, iterations, replacements, relres, st);
+  if (block_rows == 1)
+    return cfs_solver::cg_mixed<true, 0>(h64, h32, u_dev, b_dev, tol, delta, maxiter, check_every, iterations, replacements, relres, st);
+  return with_block(4, block_rows, [&](auto, auto bs) {
+    return cfs_solver::cg_mixed<true, decltype(bs)::value>(h64, h32, u_dev, b_dev, tol, delta, maxiter, check_every, iterations,
+                                                           replacements, relres, st);
   });
 }
 

@@ -421,6 +421,71 @@ class SymMatrix:
             pass
 
 
+class MixedSym:
+    """One symmetric matrix as two handles, fp64 and fp32, for the mixed-precision solver
+    (cfs_hip_sym_pcg_mixed): the iteration's products run on the fp32 handle, the solution and the
+    true residuals are fp64.  Both matrices stay resident: about 5/3 of the fp64 handle's memory.
+
+    Built from one CSR with float64 values; the fp32 handle gets values.astype(float32).
+    `options` go to both handles.  MixedSym.from_handles(A64, A32) wraps two existing SymMatrix
+    objects instead (they stay the caller's: close() leaves them open)."""
+
+    def __init__(self, n, rowptr, colind, values, options=None):
+        values = np.ascontiguousarray(values)
+        if values.dtype != np.float64:
+            raise TypeError("MixedSym takes float64 values (the fp32 handle is built from values.astype(float32))")
+        self.n = int(n)
+        self.A64 = SymMatrix(n, rowptr, colind, values, options=options)
+        try:
+            self.A32 = SymMatrix(n, rowptr, colind, values.astype(np.float32), options=options)
+        except Exception:
+            self.A64.close()
+            raise
+        self._owned = True
+
+    @classmethod
+    def from_handles(cls, A64, A32):
+        if A64.dtype != np.float64 or A32.dtype != np.float32:
+            raise TypeError("from_handles(A64, A32): a float64 and a float32 SymMatrix, in this order")
+        if A64.nrows() != A32.nrows():
+            raise ValueError(f"the two matrices have {A64.nrows()} and {A32.nrows()} rows")
+        self = cls.__new__(cls)
+        self.n, self.A64, self.A32, self._owned = A64.nrows(), A64, A32, False
+        return self
+
+    def nrows(self):
+        return self.n
+
+    def size(self):
+        return self.A64.size() + self.A32.size()
+
+    def pcg(self, u, b, precond="jacobi", block=3, tol=1e-10, delta=0.1, maxiter=1000, check_every=8, stream=None):
+        """mixed-precision PCG inside the library (cfs_hip_sym_pcg_mixed): u (float64 device tensor) holds
+        the first guess and receives the solution of A u = b (float64).  precond "none", "jacobi" or
+        "block_jacobi" (block one of 1, 2, 3, 4, 6), built from the fp32 handle.  delta: the drop of the
+        recurrence's residual that triggers a replacement by the true fp64 residual.  Returns (fp32
+        iterations, replacements, fp64 ||b - A u|| / ||b||)."""
+        if precond == "block_jacobi":
+            block_rows = int(block)
+            if block_rows == 0:
+                raise ValueError("block_jacobi needs block one of 1, 2, 3, 4, 6")
+        elif precond in PRECOND:
+            block_rows = PRECOND[precond]
+        else:
+            raise ValueError(f"unknown preconditioner {precond!r}: one of {sorted(PRECOND) + ['block_jacobi']}")
+        it, rep, res = C.c_int(), C.c_int(), C.c_double()
+        _lib.check(_lib.load().cfs_hip_sym_pcg_mixed(self.A64._h, self.A32._h, _ptr(u), _ptr(b), block_rows, float(tol),
+                                                     float(delta), int(maxiter), int(check_every), C.byref(it), C.byref(rep),
+                                                     C.byref(res), _stream_ptr(stream)))
+        return it.value, rep.value, res.value
+
+    def close(self):
+        if getattr(self, "_owned", False):
+            self.A64.close()
+            self.A32.close()
+        self._owned = False
+
+
 class CsrMatrix:
     """General CSR on the GPU (Format::csr; cpu_mv's role, csr_matrix.tpp:2683-2704)."""
 

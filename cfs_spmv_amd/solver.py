@@ -119,6 +119,86 @@ def pcg_native(A, b, precond="jacobi", tol=1e-10, maxiter=1000, x0=None, check_e
     return u, it, res
 
 
+def pcg_mixed(M, b, tol=1e-10, delta=0.1, maxiter=1000, x0=None, precond="jacobi", block=3, check_every=8):
+    """mixed-precision PCG, host-driven: the recurrence of cfs_hip_sym_pcg_mixed on a MixedSym.  One CG
+    recurrence in float32 (r, p, q and the correction xlo; the products on M.A32; dots and z = M^-1 r in
+    float64); once the recurrence's r.r has fallen below delta^2 times the largest seen at a look (every
+    `check_every` iterations) since the last replacement, or below tol^2 b.b, u += xlo, xlo = 0 and the
+    true float64 residual b - A64 u replaces r -- the search direction is kept.  b, x0: float64
+    device tensors.  Returns (u, iterations, replacements, relative residual in float64)."""
+    import torch
+    f32 = torch.float32
+    A64, A32 = M.A64, M.A32
+    if precond == "block_jacobi":
+        minv = A32.block_inverse(block)
+        if not bool(torch.all(torch.isfinite(minv))):
+            raise ValueError("pcg_mixed: block Jacobi needs positive definite diagonal blocks")
+        apply = lambda r, z: _block_apply(minv, r, z)
+    elif precond == "jacobi":
+        d = A32.diagonal()
+        if not bool(torch.all(torch.isfinite(d) & (d > 0))):
+            raise ValueError("pcg_mixed: Jacobi needs a positive diagonal")
+        dinv = (1.0 / d.double()).to(f32).double()
+        apply = lambda r, z: torch.mul(r.double(), dinv, out=z)
+    elif precond == "none":
+        apply = lambda r, z: z.copy_(r)
+    else:
+        raise ValueError(f"unknown preconditioner {precond!r}: 'none', 'jacobi' or 'block_jacobi'")
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    q64 = torch.empty_like(b)
+    z = torch.empty_like(b)
+    q = torch.empty(b.numel(), dtype=f32, device=b.device)
+    xlo = torch.zeros_like(q)
+
+    def replace():
+        A64.dense_vector_multiply(q64, u)
+        d64 = b - q64
+        r = d64.to(f32)
+        apply(r, z)
+        return r, float(torch.dot(r.double(), z)), float(torch.dot(d64, d64))
+    r, rz, rr = replace()
+    p = z.to(f32)
+    bb = float(torch.dot(b, b))
+    stop, check_every = tol * tol * bb, max(1, min(int(check_every) if check_every >= 1 else 8, 16))
+    it, nrep, rr_ref, folded = 0, 0, rr, True
+    done = not (rr > stop)
+    while not done and it < maxiter:
+        until, flag, thr = min(maxiter, it + check_every), False, max(stop, delta * delta * rr_ref)
+        while it < until and not flag:
+            A32.dense_vector_multiply(q, p)        # the hot path, in float32
+            pq = float(torch.dot(p.double(), q.double()))
+            alpha = rz / pq if pq != 0.0 else 0.0
+            xlo = (xlo.double() + alpha * p.double()).to(f32)
+            rs = r.double() - alpha * q.double()
+            rr = float(torch.dot(rs, rs))
+            r = rs.to(f32)
+            apply(r, z)
+            rz_new = float(torch.dot(r.double(), z))
+            p = (z + (rz_new / rz if rz != 0.0 else 0.0) * p.double()).to(f32)
+            rz, it, folded = rz_new, it + 1, False
+            flag = not (rr > thr)           # (the device flag: the rest of the window does nothing)
+        rr_ref = max(rr_ref, rr)
+        if flag or not (rr >= delta * delta * rr_ref):
+            u.add_(xlo.double())
+            xlo.zero_()
+            r, rz, rr = replace()
+            nrep, folded, rr_ref = nrep + 1, True, rr
+            done = not (rr > stop)
+    if not folded:
+        u.add_(xlo.double())
+        rr = replace()[2]
+    return u, it, nrep, math.sqrt(rr / bb) if bb > 0.0 else math.sqrt(rr)
+
+
+def pcg_mixed_native(M, b, precond="jacobi", tol=1e-10, delta=0.1, maxiter=1000, x0=None, check_every=8, block=3):
+    """the same iteration inside the library (cfs_hip_sym_pcg_mixed): the five float32 launches per iteration
+    and one that raises the replacement flag, no host round trip between two looks.  Returns (u, iterations, replacements, relative residual)."""
+    import torch
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    it, rep, res = M.pcg(u, b, precond=precond, block=block, tol=tol, delta=delta, maxiter=maxiter, check_every=check_every)
+    return u, it, rep, res
+
+
 def cg_sharded(S, row_splits, b_block, tol=1e-10, maxiter=1000):
     """the same iteration over 1-D row blocks (cfs_spmv_amd.dist.ShardedSym): every
     rank keeps its block of u, r, q and a full replica of the search direction p,

@@ -369,6 +369,35 @@ int cfs_hip_sym_pcg_block(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int b
  * handles as for cfs_hip_sym_block_diagonal_async; temporary device memory is released before the
  * call returns, which waits for the kernels.                                                  */
 int cfs_hip_sym_block_inverse_async(cfs_hip_sym_t h, int block_rows, void *minv_dev, void *stream);
+/* Mixed-precision PCG: an fp64 solution from fp32 products.  h64 and h32 are whole-matrix handles of the
+ * SAME matrix on one device, h64 with fp64 values and h32 with fp32 values (the caller builds both; the
+ * memory cost is both matrices resident); u_dev (first guess in, solution out) and b_dev are fp64.
+ * One CG recurrence runs in fp32 on h32 with the launches of cfs_hip_sym_cg / _pcg / _pcg_block,
+ * unchanged and in the same order -- five per iteration, no host round trip -- and accumulates a
+ * correction xlo (fp32) to u.  A REPLACEMENT is made once the recurrence's r.r is no longer above
+ * max(tol^2 b.b, delta^2 rr_ref), rr_ref the largest r.r seen at a host look since the last replacement
+ * (delta in (0, 1); 0 means the default 0.1).  The device evaluates that at every iteration -- a
+ * sixth, single-workgroup launch behind the direction kernel raises the flag that makes the launches
+ * enqueued behind it return at once -- and the host acts on the flag at its next look, every
+ * check_every (at most 16) iterations:
+ *     u += (double)xlo;  xlo = 0;  q64 = A64 u;  r = (float)(b - q64);  r.r from the unrounded fp64
+ *     residual;  r.z from the rounded r and the fp32 preconditioner
+ * The search direction p is kept across a replacement ("CG with residual replacement"), so the Krylov
+ * space is not thrown away as a restart of the iteration would.  The preconditioner is built from h32:
+ * block_rows 0 none, 1 Jacobi, 2 / 3 / 4 / 6 block Jacobi (anything else: CFS_HIP_ERR_ARG); a diagonal
+ * or a block that is not positive is refused as by cfs_hip_sym_pcg / _pcg_block, u untouched.  The solve
+ * ends when a replacement's true residual has r.r <= tol^2 b.b (or is NaN), or after maxiter fp32
+ * iterations, then with a closing fold and true residual.  *iterations: fp32 iterations done;
+ * *replacements: replacements made inside the loop (neither the first residual nor the closing one
+ * counts); *relres: ||b - A64 u|| / ||b|| of the returned u, in fp64 (||b - A64 u|| when b = 0).  The
+ * scalars are fixed-order partial sums: on two CFS_HIP_FLAG_DETERMINISTIC handles the solve is
+ * bit-reproducible.  CFS_HIP_CG_GRAPH is not consulted.
+ * CFS_HIP_ERR_ARG: a null pointer, u == b, u or b not 16-byte aligned, a host pointer or a pointer on
+ * another device, handles on two devices, h64 not fp64 or h32 not fp32, different n, delta outside
+ * (0, 1), tol < 0, maxiter < 0.  A shard or a multi-device handle: CFS_HIP_ERR_UNSUPPORTED.       */
+int cfs_hip_sym_pcg_mixed(cfs_hip_sym_t h64, cfs_hip_sym_t h32, void *u_dev, const void *b_dev, int block_rows, double tol,
+                          double delta, int maxiter, int check_every, int *iterations, int *replacements, double *relres,
+                          void *stream);
 
 /* ---- sharded operation: y_block = local rows; contributions to rows owned
  *      by lower ranks are packed into send_buf (device), exchanged by the

@@ -6,6 +6,9 @@ Fixed number of iterations (tol = 0).  The Jacobi columns are left out when the 
 through CFS_HIP_LIB has no cfs_hip_sym_pcg (an A/B run against an older build).  Block Jacobi on
 3 x 3 node blocks (cfs_hip_sym_pcg_block) sits beside Jacobi: the native loop's time per iteration,
 taken in the same run with the two interleaved, and for both the iterations down to TOL.
+The mixed-precision solver (cfs_hip_sym_pcg_mixed: fp32 products, fp64 solution) sits beside the fp64 native
+Jacobi PCG, on fp64 stand-ins only: time per fp32 iteration over K iterations (replacements included), and
+for both the iterations, the replacements and the wall time down to MIXED_TOL.
 usage: python tools/cg_bench.py [matrix[:scale] ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,11 +16,13 @@ import numpy as np
 import torch
 import cfs_spmv_amd as cfs
 from cfs_spmv_amd import synth
-from cfs_spmv_amd.solver import cg, cg_native, pcg, pcg_native
+from cfs_spmv_amd.solver import cg, cg_native, pcg, pcg_native, pcg_mixed_native
 
 HAVE_PCG = hasattr(cfs.load(), "cfs_hip_sym_pcg")
 HAVE_BLOCK = hasattr(cfs.load(), "cfs_hip_sym_pcg_block")
+HAVE_MIXED = hasattr(cfs.load(), "cfs_hip_sym_pcg_mixed")
 BLOCK, TOL, MAXITER = 3, 1e-8, 5000
+MIXED_TOL, MIXED_MAXITER = 1e-10, 20000
 
 out = {}
 for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
@@ -75,6 +80,33 @@ for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
                                                                   maxiter=MAXITER, check_every=16)[1]
         j16, b16 = res["jacobi_native_check16_us_per_iteration"], res[f"block{BLOCK}_native_check16_us_per_iteration"]
         res[f"block{BLOCK}_over_jacobi_check16"] = round(b16 / j16 - 1.0, 4)
+    if HAVE_MIXED and A.dtype == np.float64:
+        A32 = cfs.SymMatrix(n, rp, ci, va.astype(np.float32))
+        M = cfs.MixedSym.from_handles(A, A32)
+
+        def timed(fn):
+            fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = fn()
+            torch.cuda.synchronize()
+            return r, time.perf_counter() - t0
+        b32 = b.float()  # the floor: the fp32 solver alone, which cannot reach MIXED_TOL
+        (_, it, _), t = timed(lambda: pcg_native(A32, b32, tol=0.0, maxiter=K, check_every=16))
+        res["fp32_jacobi_native_check16_us_per_iteration"] = round(t / max(it, 1) * 1e6, 2)
+        (_, it, nrep, _), t = timed(lambda: pcg_mixed_native(M, b, tol=0.0, maxiter=K, check_every=16))
+        res["mixed_check16_us_per_fp32_iteration"] = round(t / max(it, 1) * 1e6, 2)
+        res["mixed_check16_replacements"] = nrep
+        res["mixed_over_fp64_jacobi_check16"] = round(res["mixed_check16_us_per_fp32_iteration"] /
+                                                      res["jacobi_native_check16_us_per_iteration"], 4)
+        res["mixed_tolerance"] = MIXED_TOL
+        (_, it, nrep, rel), t = timed(lambda: pcg_mixed_native(M, b, tol=MIXED_TOL, maxiter=MIXED_MAXITER, check_every=16))
+        res.update(mixed_iterations_to_tolerance=it, mixed_replacements_to_tolerance=nrep, mixed_relres=rel,
+                   mixed_ms_to_tolerance=round(t * 1e3, 3))
+        (_, it, rel), t = timed(lambda: pcg_native(A, b, tol=MIXED_TOL, maxiter=MIXED_MAXITER, check_every=16))
+        res.update(fp64_jacobi_iterations_to_tolerance=it, fp64_jacobi_relres=rel, fp64_jacobi_ms_to_tolerance=round(t * 1e3, 3))
+        res["mixed_over_fp64_jacobi_time_to_tolerance"] = round(res["mixed_ms_to_tolerance"] / res["fp64_jacobi_ms_to_tolerance"], 4)
+        A32.close()
     out[spec] = res
     A.close()
 print(json.dumps(out))
