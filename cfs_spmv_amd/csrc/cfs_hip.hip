@@ -1482,6 +1482,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
 #include "cfs_csr.hpp"     // the general CSR path: kernels, handle, create / launch
 #include "cfs_solver.hpp"  // conjugate gradients on resident vectors (a solver-style caller)
 #include "cfs_solver_mixed.hpp" // the same recurrence on an fp32 handle, the solution and true residuals in fp64
+#include "cfs_solver_minres.hpp" // MINRES for symmetric indefinite and shifted systems, the same launch layout
 #include "cfs_multi.hpp"   // one host thread, N devices: MultiSym, its create and cfs_hip_sym_multi_*
 
 
@@ -2103,6 +2104,33 @@ int cfs_hip_sym_pcg_mixed(cfs_hip_sym_t h64, cfs_hip_sym_t h32, void *u_dev, con
   return with_block(4, block_rows, [&](auto, auto bs) {
     return cfs_solver::cg_mixed<true, decltype(bs)::value>(h64, h32, u_dev, b_dev, tol, delta, maxiter, check_every, iterations,
                                                            replacements, relres, st);
+  });
+}
+
+int cfs_hip_sym_minres(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int precond, double shift, double tol, int maxiter,
+                       int check_every, int *iterations, double *relres, void *stream) {
+  if (!h || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (iterations) *iterations = 0;
+  if (relres) *relres = 0.0;
+  if (precond != CFS_HIP_PRECOND_NONE && precond != CFS_HIP_PRECOND_JACOBI)
+    return set_err(CFS_HIP_ERR_ARG, "minres: unknown preconditioner " + std::to_string(precond));
+  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "minres: u and b must be different vectors");
+  if ((((uintptr_t)u_dev) | ((uintptr_t)b_dev)) & 15)
+    return set_err(CFS_HIP_ERR_ARG, "minres: u and b must be 16-byte aligned");
+  if (maxiter < 0 || !(tol >= 0.0)) return set_err(CFS_HIP_ERR_ARG, "minres: bad tolerance / iteration limit");
+  if (!std::isfinite(shift)) return set_err(CFS_HIP_ERR_ARG, "minres: the shift must be finite");
+  if (!h->send_rows().empty() || h->rows() != h->n())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "minres: a handle of the whole matrix, not a shard");
+  int rc = check_placement(h, u_dev, b_dev);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  return cfs_rt::with_value_type(h->value_bytes, [&](auto v) {
+    typedef decltype(v) V;
+    if (precond == CFS_HIP_PRECOND_JACOBI)
+      return cfs_solver::minres<V, true>(h, u_dev, b_dev, shift, tol, maxiter, check_every, iterations, relres, st);
+    return cfs_solver::minres<V, false>(h, u_dev, b_dev, shift, tol, maxiter, check_every, iterations, relres, st);
   });
 }
 

@@ -348,6 +348,23 @@ class SymMatrix:
                                                int(check_every), C.byref(it), C.byref(res), _stream_ptr(stream)))
         return it.value, res.value
 
+    def minres(self, u, b, precond="none", shift=0.0, tol=1e-10, maxiter=1000, check_every=8, stream=None):
+        """MINRES inside the library (cfs_hip_sym_minres): u (device tensor) holds the first guess and
+        receives the solution of (A - shift I) u = b, A symmetric and possibly indefinite; five launches per
+        iteration, no host round trip inside the loop.  precond = "none", or "jacobi": M = |diag(A) - shift|
+        (every entry must be nonzero).  Stops when the recurrence's residual, in the M^-1 norm, is at most
+        tol times that norm of b -- with "none", ||r|| <= tol ||b||.  Returns (iterations,
+        ||b - (A - shift I) u|| / ||b||)."""
+        if isinstance(precond, str):
+            if precond not in PRECOND:
+                raise ValueError(f"unknown preconditioner {precond!r}: one of {sorted(PRECOND)}")
+            precond = PRECOND[precond]
+        it, res = C.c_int(), C.c_double()
+        _lib.check(_lib.load().cfs_hip_sym_minres(self._h, _ptr(u), _ptr(b), int(precond), float(shift), float(tol),
+                                                  int(maxiter), int(check_every), C.byref(it), C.byref(res),
+                                                  _stream_ptr(stream)))
+        return it.value, res.value
+
     # -- the exchange of a one-process multi-device handle (ngpus > 1, FLAG_SHARD_EXCHANGE) --
     def set_exchange(self, form):
         """"sparse": one packed all-to-all per SpMV (cfs_hip_comm_alltoallv); "reduce_scatter": the

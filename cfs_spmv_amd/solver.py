@@ -1,5 +1,5 @@
-"""Solver-style caller of the SpMV path: (Jacobi-preconditioned) conjugate gradients on
-resident vectors.
+"""Solver-style caller of the SpMV path: (Jacobi-preconditioned) conjugate gradients, and MINRES for
+symmetric indefinite and shifted systems, on resident vectors.
 
 SURVEY.md 8(f)-4 / 8(e): the reference's only caller is a benchmark loop with a
 fixed x; a solver feeds every product back as the next input, which is what the
@@ -197,6 +197,80 @@ def pcg_mixed_native(M, b, precond="jacobi", tol=1e-10, delta=0.1, maxiter=1000,
     u = torch.zeros_like(b) if x0 is None else x0.clone()
     it, rep, res = M.pcg(u, b, precond=precond, block=block, tol=tol, delta=delta, maxiter=maxiter, check_every=check_every)
     return u, it, rep, res
+
+
+def minres(A, b, precond="none", shift=0.0, tol=1e-10, maxiter=1000, x0=None):
+    """MINRES (Paige & Saunders) for (A - shift I) u = b, host-driven: the recurrence of cfs_hip_sym_minres for a
+    symmetric, possibly indefinite SymMatrix, with the scalars read on the host.  precond = "jacobi":
+    M = |diag(A) - shift| with the diagonal taken from the handle (A.diagonal()).  Stops when the recurrence's
+    phibar is at most tol sqrt(b . M^-1 b).  Returns (u, iterations, relative residual
+    ||b - (A - shift I) u|| / ||b||), the residual recomputed at the end."""
+    import torch
+    f64 = torch.float64
+    if precond == "jacobi":
+        d = (A.diagonal().double() - shift).abs()
+        if not bool(torch.all(torch.isfinite(d) & (d > 0))):
+            raise ValueError("minres: Jacobi needs a nonzero diagonal of A - shift I")
+        dinv = (1.0 / d).to(b.dtype).double()
+    elif precond == "none":
+        dinv = None
+    else:
+        raise ValueError(f"unknown preconditioner {precond!r}: 'none' or 'jacobi'")
+    apply = (lambda r: r.double() * dinv) if dinv is not None else (lambda r: r.double())
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    q = torch.empty_like(b)
+
+    def residual():
+        A.dense_vector_multiply(q, u)
+        return b.double() - (q.double() - shift * u.double())
+    r2 = residual().to(b.dtype)
+    r1 = r2.clone()
+    z = apply(r2)
+    beta1 = math.sqrt(float(torch.dot(r2.double(), z)))
+    bb = float(torch.dot(b.double(), b.double()))
+    stop = tol * math.sqrt(float(torch.dot(b.double(), apply(b))))
+    it = 0
+    if beta1 > stop and beta1 > 0.0 and maxiter > 0:
+        v = (z / beta1).to(b.dtype)
+        w, w2 = torch.zeros_like(b), torch.zeros_like(b)
+        oldb, beta, dbar, epsln, phibar, cs, sn = 0.0, beta1, 0.0, 0.0, beta1, -1.0, 0.0
+        eps = 2.0 ** -52
+        while it < maxiter:
+            A.dense_vector_multiply(q, v)          # the hot path
+            t = q.double() - shift * v.double()
+            if it >= 1:
+                t -= (beta / oldb) * r1.double()
+            t = t.to(b.dtype)
+            alfa = float(torch.dot(v.double(), t.double()))
+            y = (t.double() - (alfa / beta) * r2.double()).to(b.dtype)
+            r1, r2 = r2, y
+            z = apply(y)
+            bn2 = float(torch.dot(y.double(), z))
+            betan = math.sqrt(bn2) if bn2 >= 0.0 else float("nan")
+            oldeps, delta, gbar = epsln, cs * dbar + sn * alfa, sn * dbar - cs * alfa
+            epsln, dbar = sn * betan, -cs * betan
+            gamma = max(math.sqrt(gbar * gbar + betan * betan), eps)
+            cs, sn = gbar / gamma, betan / gamma
+            phi, phibar = cs * phibar, sn * phibar
+            wn = ((v.double() - oldeps * w2.double() - delta * w.double()) / gamma).to(b.dtype)
+            w2, w = w, wn
+            u = (u.double() + phi * wn.double()).to(b.dtype)
+            v = (z / betan).to(b.dtype) if betan > 0.0 else torch.zeros_like(b)
+            oldb, beta, it = beta, betan, it + 1
+            if not (phibar > stop) or not (betan > 0.0):
+                break
+    d = residual()
+    res2 = float(torch.dot(d, d))
+    return u, it, math.sqrt(res2 / bb) if bb > 0.0 else math.sqrt(res2)
+
+
+def minres_native(A, b, precond="none", shift=0.0, tol=1e-10, maxiter=1000, x0=None, check_every=8):
+    """the same iteration inside the library (cfs_hip_sym_minres): five launches per iteration, every scalar in
+    device memory.  Returns (u, iterations, relative residual), like minres()."""
+    import torch
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    it, res = A.minres(u, b, precond=precond, shift=shift, tol=tol, maxiter=maxiter, check_every=check_every)
+    return u, it, res
 
 
 def cg_sharded(S, row_splits, b_block, tol=1e-10, maxiter=1000):

@@ -398,6 +398,33 @@ int cfs_hip_sym_block_inverse_async(cfs_hip_sym_t h, int block_rows, void *minv_
 int cfs_hip_sym_pcg_mixed(cfs_hip_sym_t h64, cfs_hip_sym_t h32, void *u_dev, const void *b_dev, int block_rows, double tol,
                           double delta, int maxiter, int check_every, int *iterations, int *replacements, double *relres,
                           void *stream);
+/* MINRES (Paige & Saunders) for (A - shift I) u = b: A symmetric, possibly INDEFINITE, or singular with a
+ * consistent b -- saddle-point matrices (a zero diagonal block), shifted operators, mixed-sign diagonals, on
+ * which the conjugate gradients above promise nothing (on [[0, K], [K, 0]] with b = [f; 0] their first p.q is
+ * exactly 0 and u stays 0).  One Lanczos recurrence, no breakdown on a nonsingular matrix, and the norm of the
+ * recurrence's residual never increases.  The launch layout is cfs_hip_sym_cg's: five launches per iteration
+ * on `stream` -- the SpMV (two) and three fused vector kernels -- every scalar in device memory as fixed-order
+ * partial sums in fp64, no host round trip inside the loop, so on a CFS_HIP_FLAG_DETERMINISTIC handle the solve
+ * is bit-reproducible whatever check_every.  u_dev, b_dev, alignment, placement, check_every (<= 0: 8; at most
+ * 16), *iterations and the handles accepted are those of cfs_hip_sym_cg (a shard: CFS_HIP_ERR_UNSUPPORTED).
+ * precond: CFS_HIP_PRECOND_NONE, or CFS_HIP_PRECOND_JACOBI, which HERE means M = |diag(A) - shift| (MINRES
+ * needs a positive definite M): dinv_i = (V)(1.0 / fabs((double)a_ii - shift)) is stored once in the value
+ * type, gathered from the handle as for cfs_hip_sym_pcg (it follows cfs_hip_sym_update_values_* and works on a
+ * handle from cfs_hip_sym_load); z = M^-1 r is formed in fp64 where it is needed and never stored.  An entry
+ * whose |a_ii - shift| is zero or not finite (a diagonal that is not stored counts as a_ii = 0):
+ * CFS_HIP_ERR_ARG ("nonzero diagonal"), u untouched, *iterations = 0.  Another `precond`: CFS_HIP_ERR_ARG.
+ * STOPPING RULE: the recurrence's phibar, the M^-1-norm of its residual, against tol sqrt(b . M^-1 b); a NaN
+ * ends the solve.  With CFS_HIP_PRECOND_NONE that is cfs_hip_sym_cg's rule, ||r|| <= tol ||b||.  With Jacobi it
+ * is NOT: MINRES carries no unpreconditioned residual, so the solve stops on sqrt(r . M^-1 r) <= tol sqrt(b .
+ * M^-1 b), and on a badly scaled matrix the two rules differ -- look at *relres.  A vanishing Lanczos beta (the
+ * Krylov space is exhausted, u is exact) is a normal end.  *relres = ||b - (A - shift I) u|| / ||b||, RECOMPUTED
+ * in fp64 from the returned u (the norm alone when b = 0).  CFS_HIP_CG_GRAPH is not consulted.
+ * CFS_HIP_ERR_ARG, before any device work: a null pointer (checked first), an unknown precond, u == b, u or b
+ * not 16-byte aligned, tol < 0, maxiter < 0, a shift that is not finite, a host pointer or a pointer on another
+ * device.                                                                                       */
+int cfs_hip_sym_minres(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int precond, double shift,
+                       double tol, int maxiter, int check_every,
+                       int *iterations, double *relres, void *stream);
 
 /* ---- sharded operation: y_block = local rows; contributions to rows owned
  *      by lower ranks are packed into send_buf (device), exchanged by the

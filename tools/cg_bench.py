@@ -9,6 +9,9 @@ taken in the same run with the two interleaved, and for both the iterations down
 The mixed-precision solver (cfs_hip_sym_pcg_mixed: fp32 products, fp64 solution) sits beside the fp64 native
 Jacobi PCG, on fp64 stand-ins only: time per fp32 iteration over K iterations (replacements included), and
 for both the iterations, the replacements and the wall time down to MIXED_TOL.
+MINRES (cfs_hip_sym_minres) sits beside the Jacobi PCG on the same SPD stand-ins, with M = |diag(A)|: the native loop's
+time per iteration over K iterations against the host-driven loop (solver.minres) and against cfs_hip_sym_pcg, taken in
+the same run with the two native loops interleaved.
 usage: python tools/cg_bench.py [matrix[:scale] ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,11 +19,12 @@ import numpy as np
 import torch
 import cfs_spmv_amd as cfs
 from cfs_spmv_amd import synth
-from cfs_spmv_amd.solver import cg, cg_native, pcg, pcg_native, pcg_mixed_native
+from cfs_spmv_amd.solver import cg, cg_native, minres, minres_native, pcg, pcg_native, pcg_mixed_native
 
 HAVE_PCG = hasattr(cfs.load(), "cfs_hip_sym_pcg")
 HAVE_BLOCK = hasattr(cfs.load(), "cfs_hip_sym_pcg_block")
 HAVE_MIXED = hasattr(cfs.load(), "cfs_hip_sym_pcg_mixed")
+HAVE_MINRES = hasattr(cfs.load(), "cfs_hip_sym_minres")
 BLOCK, TOL, MAXITER = 3, 1e-8, 5000
 MIXED_TOL, MIXED_MAXITER = 1e-10, 20000
 
@@ -107,6 +111,31 @@ for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
         res.update(fp64_jacobi_iterations_to_tolerance=it, fp64_jacobi_relres=rel, fp64_jacobi_ms_to_tolerance=round(t * 1e3, 3))
         res["mixed_over_fp64_jacobi_time_to_tolerance"] = round(res["mixed_ms_to_tolerance"] / res["fp64_jacobi_ms_to_tolerance"], 4)
         A32.close()
+    if HAVE_MINRES and HAVE_PCG:  # the two native loops interleaved, three rounds, the best of each
+        def timed_iteration(fn):
+            fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            it = fn()[1]
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / max(it, 1) * 1e6
+        loops = {"minres_jacobi_native_check16": lambda: minres_native(A, b, precond="jacobi", tol=0.0, maxiter=K, check_every=16),
+                 "minres_none_native_check16": lambda: minres_native(A, b, tol=0.0, maxiter=K, check_every=16),
+                 "pcg_jacobi_native_check16_beside_minres": lambda: pcg_native(A, b, tol=0.0, maxiter=K, check_every=16)}
+        best = {}
+        for _ in range(3):
+            for label, fn in loops.items():
+                best[label] = min(best.get(label, float("inf")), timed_iteration(fn))
+        for label, us in best.items():
+            res[label + "_us_per_iteration"] = round(us, 2)
+        res["minres_jacobi_torch_loop_us_per_iteration"] = round(timed_iteration(
+            lambda: minres(A, b, precond="jacobi", tol=0.0, maxiter=K)), 2)
+        res["minres_over_pcg_jacobi_check16"] = round(best["minres_jacobi_native_check16"] /
+                                                      best["pcg_jacobi_native_check16_beside_minres"], 4)
+        res["minres_native_over_torch_loop"] = round(best["minres_jacobi_native_check16"] /
+                                                     res["minres_jacobi_torch_loop_us_per_iteration"], 4)
+        res["minres_jacobi_iterations_to_tolerance"] = minres_native(A, b, precond="jacobi", tol=TOL, maxiter=MAXITER,
+                                                                     check_every=16)[1]
     out[spec] = res
     A.close()
 print(json.dumps(out))
