@@ -1483,6 +1483,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
 #include "cfs_solver.hpp"  // conjugate gradients on resident vectors (a solver-style caller)
 #include "cfs_solver_mixed.hpp" // the same recurrence on an fp32 handle, the solution and true residuals in fp64
 #include "cfs_solver_minres.hpp" // MINRES for symmetric indefinite and shifted systems, the same launch layout
+#include "cfs_solver_eigs.hpp" // thick-restart Lanczos for extreme eigenpairs: tall-skinny algebra against a resident basis
 #include "cfs_multi.hpp"   // one host thread, N devices: MultiSym, its create and cfs_hip_sym_multi_*
 
 
@@ -2132,6 +2133,84 @@ int cfs_hip_sym_minres(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int prec
       return cfs_solver::minres<V, true>(h, u_dev, b_dev, shift, tol, maxiter, check_every, iterations, relres, st);
     return cfs_solver::minres<V, false>(h, u_dev, b_dev, shift, tol, maxiter, check_every, iterations, relres, st);
   });
+}
+
+// a vector argument of the eigensolver entry points: device memory on the handle's device
+static int check_eigs_ptr(cfs_hip_sym_t h, const void *p, const char *who, const char *what) {
+  const cfs_rt::PtrInfo pi = cfs_rt::classify(p);
+  if (!pi.device) return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": " + what + " must be a device pointer");
+  if (pi.dev != h->device)
+    return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": " + what + " lives on device " + std::to_string(pi.dev) +
+                                        ", the matrix on device " + std::to_string(h->device));
+  return 0;
+}
+
+int cfs_hip_sym_eigs(cfs_hip_sym_t h, int k, int which, int ncv, double tol, int max_restarts, const void *v0_dev,
+                     double *eigenvalues, void *vectors_dev, long long ld, double *residuals, int *nconv, int *restarts,
+                     int *products, void *stream) {
+  if (!h || !eigenvalues) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (nconv) *nconv = 0;
+  if (restarts) *restarts = 0;
+  if (products) *products = 0;
+  if (which != CFS_HIP_EIGS_LARGEST && which != CFS_HIP_EIGS_SMALLEST && which != CFS_HIP_EIGS_MAGNITUDE)
+    return set_err(CFS_HIP_ERR_ARG, "eigs: unknown which " + std::to_string(which));
+  if (k < 1 || ncv < 0 || ncv > CFS_HIP_EIGS_MAX_NCV || (ncv != 0 && k >= ncv) || k >= CFS_HIP_EIGS_MAX_NCV)
+    return set_err(CFS_HIP_ERR_ARG, "eigs: bad k / ncv: 1 <= k < ncv <= min(n, " + std::to_string(CFS_HIP_EIGS_MAX_NCV) +
+                                        ") (ncv = 0: the default), got k = " + std::to_string(k) + ", ncv = " + std::to_string(ncv));
+  if (!(tol >= 0.0) || max_restarts < 0) return set_err(CFS_HIP_ERR_ARG, "eigs: bad tolerance / restart limit");
+  if ((((uintptr_t)v0_dev) | ((uintptr_t)vectors_dev)) & 15)
+    return set_err(CFS_HIP_ERR_ARG, "eigs: v0 and the vectors must be 16-byte aligned");
+  if (!h->send_rows().empty() || h->rows() != h->n())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "eigs: a handle of the whole matrix, not a shard");
+  const long long n = h->n();
+  if (ncv == 0) ncv = (int)std::min<long long>(n, std::max(2 * k + 1, 20));
+  if (ncv > n || k >= ncv)
+    return set_err(CFS_HIP_ERR_ARG, "eigs: bad k / ncv: 1 <= k < ncv <= min(n, " + std::to_string(CFS_HIP_EIGS_MAX_NCV) +
+                                        "), got k = " + std::to_string(k) + ", ncv = " + std::to_string(ncv) + ", n = " + std::to_string(n));
+  if (vectors_dev && (ld < n || (ld * h->value_bytes) % 16 != 0))
+    return set_err(CFS_HIP_ERR_ARG, "eigs: bad ld " + std::to_string(ld) + ": at least n = " + std::to_string(n) +
+                                        " and a multiple of 16 bytes");
+  int rc;
+  if (v0_dev && (rc = check_eigs_ptr(h, v0_dev, "eigs", "v0"))) return rc;
+  if (vectors_dev && (rc = check_eigs_ptr(h, vectors_dev, "eigs", "the vectors"))) return rc;
+  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  return cfs_rt::with_value_type(h->value_bytes, [&](auto v) {
+    return cfs_solver::eigs<decltype(v)>(h, k, which, ncv, tol, max_restarts, v0_dev, eigenvalues, vectors_dev, ld, residuals, nconv,
+                                         restarts, products, st);
+  });
+}
+
+int cfs_hip_sym_debug_lanczos(cfs_hip_sym_t h, const void *v0_dev, int steps, void *basis_dev, long long ld, double *alpha,
+                              double *beta, int *done, void *stream) {
+  if (!h || !basis_dev || !alpha || !beta || !done) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  *done = 0;
+  if (steps < 1 || steps > CFS_HIP_EIGS_MAX_NCV)
+    return set_err(CFS_HIP_ERR_ARG, "lanczos: steps must lie in [1, " + std::to_string(CFS_HIP_EIGS_MAX_NCV) + "]");
+  if ((((uintptr_t)v0_dev) | ((uintptr_t)basis_dev)) & 15)
+    return set_err(CFS_HIP_ERR_ARG, "lanczos: v0 and the basis must be 16-byte aligned");
+  if (!h->send_rows().empty() || h->rows() != h->n())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "lanczos: a handle of the whole matrix, not a shard");
+  if (ld < h->n() || (ld * h->value_bytes) % 16 != 0)
+    return set_err(CFS_HIP_ERR_ARG, "lanczos: bad ld " + std::to_string(ld) + ": at least n and a multiple of 16 bytes");
+  int rc;
+  if (v0_dev && (rc = check_eigs_ptr(h, v0_dev, "lanczos", "v0"))) return rc;
+  if ((rc = check_eigs_ptr(h, basis_dev, "lanczos", "the basis"))) return rc;
+  h->ok_x = h->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  return cfs_rt::with_value_type(h->value_bytes, [&](auto v) {
+    return cfs_solver::debug_lanczos<decltype(v)>(h, v0_dev, steps, basis_dev, ld, alpha, beta, done, st);
+  });
+}
+
+int cfs_hip_debug_symeig(int m, const double *a, double *w, double *s) {
+  if (!a || !w || !s) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (m < 1 || m > CFS_HIP_EIGS_MAX_NCV)
+    return set_err(CFS_HIP_ERR_ARG, "symeig: m must lie in [1, " + std::to_string(CFS_HIP_EIGS_MAX_NCV) + "]");
+  if (cfs_solver::symeig(m, a, w, s) < 0) return set_err(CFS_HIP_ERR_INTERNAL, "symeig: no convergence");
+  return 0;
 }
 
 int cfs_hip_sym_spmv(cfs_hip_sym_t h, void *y, const void *x) {

@@ -60,6 +60,7 @@ FLAG_HOST_PLAN = 4096  # CFS_HIP_FLAG_HOST_PLAN: build the schedule with the hos
 EXCHANGE_REDUCE_SCATTER, EXCHANGE_SPARSE = _lib.EXCHANGE_REDUCE_SCATTER, _lib.EXCHANGE_SPARSE  # CFS_HIP_EXCHANGE_*
 EXCHANGE = {"reduce_scatter": EXCHANGE_REDUCE_SCATTER, "sparse": EXCHANGE_SPARSE}
 PRECOND = {"none": _lib.PRECOND_NONE, "jacobi": _lib.PRECOND_JACOBI}  # CFS_HIP_PRECOND_*
+EIGS_WHICH = {"LA": _lib.EIGS_LARGEST, "SA": _lib.EIGS_SMALLEST, "LM": _lib.EIGS_MAGNITUDE}  # CFS_HIP_EIGS_*
 KERNEL_NAMES = ["value_bytes", "block", "mode", "nt", "offb", "u", "det", "comb"]
 DIGEST_WORDS = 28  # CFS_HIP_DIGEST_WORDS
 DIGEST_NAMES = ["tiles", "gfirst", "group_range", "slot_col", "rowinfo", "diag", "slice_meta", "leadlane",
@@ -364,6 +365,37 @@ class SymMatrix:
                                                   int(maxiter), int(check_every), C.byref(it), C.byref(res),
                                                   _stream_ptr(stream)))
         return it.value, res.value
+
+    def eigs(self, k=6, which="LA", ncv=None, tol=1e-10, max_restarts=100, v0=None, vectors=True, stream=None):
+        """k extreme eigenpairs inside the library (cfs_hip_sym_eigs): thick-restart Lanczos with full
+        re-orthogonalisation on a basis of ncv device vectors (None: min(n, max(2 k + 1, 20))), no host round trip
+        inside a step.  which = "LA" (largest algebraic), "SA" (smallest algebraic) or "LM" (largest magnitude); v0: a
+        device tensor of n values (None: the library's fixed start vector).  Returns (w, X, info): w a numpy float64
+        array (k,) ordered by `which`; X a device tensor (n, k) with strides (1, ld) whose columns are the vectors, or
+        None with vectors=False; info = dict(nconv, restarts, products, residuals) -- residuals recomputed from the
+        returned vectors, the Lanczos estimates without them."""
+        import torch
+        if isinstance(which, str):
+            if which not in EIGS_WHICH:
+                raise ValueError(f"unknown which {which!r}: one of {sorted(EIGS_WHICH)}")
+            which = EIGS_WHICH[which]
+        k = int(k)
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        w, res = np.zeros(max(k, 0), np.float64), np.zeros(max(k, 0), np.float64)
+        X, ld = None, 0
+        if vectors:
+            per = 16 // self.dtype.itemsize
+            ld = -(-self.nrows() // per) * per
+            X = torch.zeros(max(k, 1) * ld, dtype=tdt, device="cuda")
+        dp = C.POINTER(C.c_double)
+        nconv, restarts, products = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(_lib.load().cfs_hip_sym_eigs(
+            self._h, k, int(which), int(ncv or 0), float(tol), int(max_restarts), _ptr(v0) if v0 is not None else None,
+            w.ctypes.data_as(dp), _ptr(X) if X is not None else None, ld, res.ctypes.data_as(dp), C.byref(nconv),
+            C.byref(restarts), C.byref(products), _stream_ptr(stream)))
+        if X is not None:
+            X = torch.as_strided(X, (self.nrows(), k), (1, ld))
+        return w, X, {"nconv": nconv.value, "restarts": restarts.value, "products": products.value, "residuals": res}
 
     # -- the exchange of a one-process multi-device handle (ngpus > 1, FLAG_SHARD_EXCHANGE) --
     def set_exchange(self, form):

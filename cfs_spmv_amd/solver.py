@@ -1,5 +1,5 @@
-"""Solver-style caller of the SpMV path: (Jacobi-preconditioned) conjugate gradients, and MINRES for
-symmetric indefinite and shifted systems, on resident vectors.
+"""Solver-style caller of the SpMV path: (Jacobi-preconditioned) conjugate gradients, MINRES for
+symmetric indefinite and shifted systems, and thick-restart Lanczos for extreme eigenpairs, on resident vectors.
 
 SURVEY.md 8(f)-4 / 8(e): the reference's only caller is a benchmark loop with a
 fixed x; a solver feeds every product back as the next input, which is what the
@@ -271,6 +271,101 @@ def minres_native(A, b, precond="none", shift=0.0, tol=1e-10, maxiter=1000, x0=N
     u = torch.zeros_like(b) if x0 is None else x0.clone()
     it, res = A.minres(u, b, precond=precond, shift=shift, tol=tol, maxiter=maxiter, check_every=check_every)
     return u, it, res
+
+
+def _order(w, which):
+    """indices of the Ritz values w (ascending) in the order of `which`"""
+    import numpy as np
+    if which == "SA":
+        return np.arange(len(w))
+    if which == "LA":
+        return np.arange(len(w))[::-1]
+    if which == "LM":
+        d = np.arange(len(w))[::-1]
+        return d[np.argsort(-np.abs(w[d]), kind="stable")]
+    raise ValueError(f"unknown which {which!r}: 'LA', 'SA' or 'LM'")
+
+
+def eigs(A, k, which="LA", ncv=None, tol=1e-10, max_restarts=100, v0=None):
+    """k extreme eigenpairs by thick-restart Lanczos, host-driven: the recurrence, restart rule and kept count of
+    cfs_hip_sym_eigs (full re-orthogonalisation in two passes, alpha_j = c_j + c'_j, breakdown when beta_j is not above
+    16 u sqrt(q.q), l = k + (ncv - k) / 2 Ritz vectors kept) with torch operations on A's product and every coefficient
+    read on the host -- the model and the baseline of the native loop.  Returns (w, X, info) like SymMatrix.eigs; X is
+    an (n, k) device tensor, info["residuals"] the norms ||A x - theta x|| / ||x|| recomputed at the end."""
+    import numpy as np
+    import torch
+    n = A.nrows()
+    tdt = torch.float64 if A.dtype == np.float64 else torch.float32
+    unit = 2.0 ** -53 if A.dtype == np.float64 else 2.0 ** -24
+    if ncv is None:
+        ncv = min(n, max(2 * k + 1, 20))
+    if not 1 <= k < ncv <= n:
+        raise ValueError("eigs: 1 <= k < ncv <= n")
+    if v0 is None:
+        raise ValueError("eigs: the host-driven loop needs a start vector")
+    f64 = torch.float64
+    V = torch.zeros((ncv + 1, n), dtype=tdt, device=v0.device)  # row j = v_{j+1}
+    q = torch.empty(n, dtype=tdt, device=v0.device)
+    V[0] = (v0.double() / float(torch.linalg.vector_norm(v0.double()))).to(tdt)
+    lkeep = k + (ncv - k) // 2
+    alpha, beta, arrow = np.zeros(ncv), np.zeros(ncv), np.zeros(ncv)
+    l, restarts, products, broke = 0, 0, 0, False
+    while True:
+        m = ncv
+        for j in range(l, ncv):
+            A.dense_vector_multiply(q, V[j])          # the hot path
+            products += 1
+            Vj = V[:j + 1].double()
+            c = Vj @ q.double()
+            qq = float(torch.dot(q.double(), q.double()))
+            q1 = (q.double() - c @ Vj).to(tdt)
+            c2 = Vj @ q1.double()
+            q2 = (q1.double() - c2 @ Vj).to(tdt)
+            alpha[j] = float(c[j]) + float(c2[j])
+            beta[j] = math.sqrt(float(torch.dot(q2.double(), q2.double())))
+            if not beta[j] > 16.0 * unit * math.sqrt(qq):
+                V[j + 1].zero_()
+                m, broke = j + 1, True
+                break
+            V[j + 1] = (q2.double() / beta[j]).to(tdt)
+        T = np.diag(alpha[:m])
+        T[:l, l] = T[l, :l] = arrow[:l]
+        for i in range(l, m - 1):
+            T[i, i + 1] = T[i + 1, i] = beta[i]
+        w, S = np.linalg.eigh(T)
+        order = _order(w, which)
+        bm = 0.0 if broke else beta[m - 1]
+        est = np.abs(bm * S[m - 1, order])
+        kk = min(k, m)
+        nconv = 0
+        while nconv < kk and est[nconv] <= tol * np.max(np.abs(w)):
+            nconv += 1
+        if broke:
+            nconv = kk
+        if broke or nconv == k or restarts >= max_restarts:
+            break
+        Sk = torch.from_numpy(np.ascontiguousarray(S[:, order[:lkeep]])).to(V.device)
+        V[:lkeep] = (Sk.T @ V[:m].double()).to(tdt)
+        V[lkeep] = V[m]
+        alpha[:lkeep], arrow[:lkeep] = w[order[:lkeep]], bm * S[m - 1, order[:lkeep]]
+        l, restarts = lkeep, restarts + 1
+    Sk = torch.from_numpy(np.ascontiguousarray(S[:, order[:kk]])).to(V.device)
+    X = torch.zeros((k, n), dtype=tdt, device=V.device)
+    X[:kk] = (Sk.T @ V[:m].double()).to(tdt)
+    wk, res = np.zeros(k), np.zeros(k)
+    wk[:kk] = w[order[:kk]]
+    for i in range(kk):
+        A.dense_vector_multiply(q, X[i])
+        products += 1
+        d = q.double() - wk[i] * X[i].double()
+        res[i] = float(torch.linalg.vector_norm(d)) / float(torch.linalg.vector_norm(X[i].double()))
+    return wk, X.T, {"nconv": nconv, "restarts": restarts, "products": products, "residuals": res}
+
+
+def eigs_native(A, k, which="LA", ncv=None, tol=1e-10, max_restarts=100, v0=None, vectors=True):
+    """the same iteration inside the library (cfs_hip_sym_eigs): nine launches per step, alpha, beta and the breakdown
+    flag in device memory, the host looks only when the basis is full.  Returns (w, X, info), like eigs()."""
+    return A.eigs(k=k, which=which, ncv=ncv, tol=tol, max_restarts=max_restarts, v0=v0, vectors=vectors)
 
 
 def cg_sharded(S, row_splits, b_block, tol=1e-10, maxiter=1000):

@@ -425,6 +425,64 @@ int cfs_hip_sym_pcg_mixed(cfs_hip_sym_t h64, cfs_hip_sym_t h32, void *u_dev, con
 int cfs_hip_sym_minres(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int precond, double shift,
                        double tol, int maxiter, int check_every,
                        int *iterations, double *relres, void *stream);
+/* k eigenpairs of A at one end of the spectrum -- which = CFS_HIP_EIGS_LARGEST (largest algebraic), _SMALLEST
+ * (smallest algebraic) or _MAGNITUDE (largest |lambda|) -- by thick-restart Lanczos (Wu & Simon) with full
+ * re-orthogonalisation on a basis of ncv vectors resident on the device: lambda_max and lambda_min for condition
+ * numbers, smoother step sizes and the shift of cfs_hip_sym_minres, without a host synchronisation per dot product.
+ * Handles accepted are those of cfs_hip_sym_cg, one device or multi-device (the basis lives on the home device; a
+ * shard: CFS_HIP_ERR_UNSUPPORTED); both value types; the basis is stored in the value type V, EVERY dot product
+ * and scalar is fp64.  Step j of the recurrence, no contracted multiply-adds:
+ *     v_1 = (V)(v0 / ||v0||)
+ *     q = A v_j;  c = V_j^T q;  qq = q.q;  q1 = (V)(q - sum_k c_k v_k)  (fp64, k ascending, rounded once when stored)
+ *     c' = V_j^T q1;  q2 = (V)(q1 - sum_k c'_k v_k);  alpha_j = c_j + c'_j;  beta_j = sqrt(q2.q2)
+ *     breakdown iff !(beta_j > 16 u_V sqrt(qq))  (u_V = 2^-53 / 2^-24);  v_{j+1} = (V)(q2 / beta_j), or 0
+ * Nine launches per step on `stream` (the SpMV's two and seven vector kernels), alpha, beta and the breakdown flag in
+ * device memory, no host round trip inside a step or between steps: the host looks when the basis is full.  It then
+ * solves the projected matrix (cyclic Jacobi in fp64, no LAPACK), and unless the k wanted pairs have converged --
+ * estimate |beta_m s_{m,i}| <= tol max|theta| over the Ritz values of the current projected matrix -- keeps
+ * l = k + (ncv - k) / 2 Ritz vectors, V[:, 0..l) <- V_m S on the device, and continues at step l + 1.  All sums are
+ * fixed-order partial sums: on a CFS_HIP_FLAG_DETERMINISTIC handle the solve is bit-reproducible.  Device memory
+ * held during the call: (ncv + 2) n values.
+ * ncv = 0 means min(n, max(2 k + 1, 20)); otherwise 1 <= k < ncv <= min(n, CFS_HIP_EIGS_MAX_NCV).
+ * v0_dev: the start vector, n values of the value type, 16-byte aligned, not modified.  NULL selects the fixed
+ * vector v0_i = (double)(z_i >> 11) 2^-53 - 0.5 with z_i the splitmix64 finaliser of (i + 1) 0x9E3779B97F4A7C15
+ * (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31; 64-bit wrap-around),
+ * a pure function of the row index i: the same bits in every call.
+ * eigenvalues: host array of k doubles, ordered by `which` (descending, ascending, descending magnitude).
+ * vectors_dev: column i at vectors_dev + i ld values; ld >= n, the pointer and ld sizeof(V) multiples of 16; nothing
+ * outside rows [0, n) of the k columns is written; NULL for values only.  The columns have unit norm up to rounding.
+ * residuals: nullable host array of k doubles, ||A x_i - theta_i x_i||_2 / ||x_i||_2 RECOMPUTED in fp64 from the
+ * returned, stored x_i with k extra products (as *relres is elsewhere); with vectors_dev == NULL the Lanczos
+ * estimates |beta_m s_{m,i}|.  *nconv: the number of leading pairs whose estimate met the tolerance; the call
+ * returns 0 also when nconv < k after max_restarts restarts, all k pairs written, the unconverged ones as the
+ * best available.  *restarts, *products: restarts made and SpMVs issued; any of the three counters may be NULL.
+ * A breakdown at step j means "v0 lies in an invariant subspace of dimension j": the Ritz pairs of T_j are exact
+ * there, the solve ends and returns min(k, j) pairs as converged (in *nconv), return code 0, the remaining
+ * eigenvalues, residuals and columns zero-filled.
+ * SCOPE: plain Lanczos finds the well-separated end of a spectrum quickly and the clustered low end of a stiffness
+ * matrix slowly; shift-invert (an inner cfs_hip_sym_minres or _pcg solve per step) is left for a later change.
+ * CFS_HIP_ERR_ARG, before any device work, in this order: a null h or eigenvalues ("null"); an unknown which; bad
+ * k / ncv (the part against n once the handle is read); tol < 0 or NaN, max_restarts < 0; v0_dev or vectors_dev
+ * not 16-byte aligned, or a bad ld; a host pointer or a pointer on another device.  A start vector whose norm is
+ * zero or not finite: CFS_HIP_ERR_ARG ("start vector"), nothing written.                          */
+#define CFS_HIP_EIGS_LARGEST   0  /* largest algebraic  */
+#define CFS_HIP_EIGS_SMALLEST  1  /* smallest algebraic */
+#define CFS_HIP_EIGS_MAGNITUDE 2  /* largest |lambda|   */
+#define CFS_HIP_EIGS_MAX_NCV 128
+int cfs_hip_sym_eigs(cfs_hip_sym_t h, int k, int which, int ncv, double tol, int max_restarts,
+                     const void *v0_dev, double *eigenvalues, void *vectors_dev, long long ld,
+                     double *residuals, int *nconv, int *restarts, int *products, void *stream);
+/* For developers and tests: `steps` plain steps (no restart) of the recurrence above with the solver's own kernels.
+ * basis_dev receives v_1 .. v_{done+1} (column i at basis_dev + i ld values; ld, alignment and placement as for
+ * vectors_dev; steps + 1 columns of room), alpha[steps] and beta[steps] on the host (0 behind a breakdown),
+ * *done = steps made up to and with a breakdown (column `done` is then 0).  1 <= steps <= CFS_HIP_EIGS_MAX_NCV.
+ * v0_dev as above.  The call waits for the kernels.                                                */
+int cfs_hip_sym_debug_lanczos(cfs_hip_sym_t h, const void *v0_dev, int steps, void *basis_dev, long long ld,
+                              double *alpha, double *beta, int *done, void *stream);
+/* host-only, no GPU: the small dense symmetric eigensolver the restart uses (cyclic Jacobi, fp64).  a: m x m
+ * symmetric, row-major (the upper triangle is read), 1 <= m <= CFS_HIP_EIGS_MAX_NCV (else CFS_HIP_ERR_ARG);
+ * w: the m eigenvalues ascending; s: m x m row-major, eigenvector i in column i.                   */
+int cfs_hip_debug_symeig(int m, const double *a, double *w, double *s);
 
 /* ---- sharded operation: y_block = local rows; contributions to rows owned
  *      by lower ranks are packed into send_buf (device), exchanged by the
