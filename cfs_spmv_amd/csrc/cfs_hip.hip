@@ -1484,6 +1484,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
 #include "cfs_solver_mixed.hpp" // the same recurrence on an fp32 handle, the solution and true residuals in fp64
 #include "cfs_solver_minres.hpp" // MINRES for symmetric indefinite and shifted systems, the same launch layout
 #include "cfs_solver_eigs.hpp" // thick-restart Lanczos for extreme eigenpairs: tall-skinny algebra against a resident basis
+#include "cfs_solver_lobpcg.hpp" // LOBPCG for the smallest eigenpairs with the PCG preconditioners: a small SYRK per iteration
 #include "cfs_multi.hpp"   // one host thread, N devices: MultiSym, its create and cfs_hip_sym_multi_*
 
 
@@ -2211,6 +2212,127 @@ int cfs_hip_debug_symeig(int m, const double *a, double *w, double *s) {
     return set_err(CFS_HIP_ERR_ARG, "symeig: m must lie in [1, " + std::to_string(CFS_HIP_EIGS_MAX_NCV) + "]");
   if (cfs_solver::symeig(m, a, w, s) < 0) return set_err(CFS_HIP_ERR_INTERNAL, "symeig: no convergence");
   return 0;
+}
+
+// ---- LOBPCG ----
+// f(V(), std::integral_constant<int, BS>()) for the handle's value type and block_rows 0, 1, 2, 3, 4 or 6
+template <class F> static int with_lobpcg_block(int value_bytes, int bs, F &&f) {
+  if (bs >= 2) return with_block(value_bytes, bs, f);
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    if (bs == 1) return f(v, std::integral_constant<int, 1>());
+    return f(v, std::integral_constant<int, 0>());
+  });
+}
+// the checks that cfs_hip_sym_lobpcg and cfs_hip_sym_debug_lobpcg share, from "bad k" on, in the documented order
+static int check_lobpcg(cfs_hip_sym_t h, int k, int block_rows, bool tol_ok, const void *x0_dev, long long ld0, const void *vectors_dev,
+                        long long ld) {
+  if (k < 1 || k > CFS_HIP_LOBPCG_MAX_K)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg: bad k: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + " and 3 k <= n, got k = " + std::to_string(k));
+  if (block_rows != 0 && !block_rows_ok(block_rows))
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg: block_rows " + std::to_string(block_rows) + " is not one of 0, 1, 2, 3, 4, 6");
+  if (!tol_ok) return set_err(CFS_HIP_ERR_ARG, "lobpcg: bad tolerance / scale / iteration limit");
+  if ((((uintptr_t)x0_dev) | ((uintptr_t)vectors_dev)) & 15)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg: x0 and the vectors must be 16-byte aligned");
+  if (!h->send_rows().empty() || h->rows() != h->n())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "lobpcg: a handle of the whole matrix, not a shard");
+  const long long n = h->n();
+  if (3LL * k > n)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg: bad k: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + " and 3 k <= n, got k = " + std::to_string(k) +
+                                        ", n = " + std::to_string(n));
+  if (ld < n || (ld * h->value_bytes) % 16 != 0 || (x0_dev && (ld0 < n || (ld0 * h->value_bytes) % 16 != 0)))
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg: bad ld " + std::to_string(ld) + " / ld0 " + std::to_string(ld0) + ": at least n = " +
+                                        std::to_string(n) + " and a multiple of 16 bytes");
+  if (block_rows >= 2) {
+    int ngpus = 1;
+    if (cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
+      return set_err(CFS_HIP_ERR_UNSUPPORTED, "lobpcg: block Jacobi needs the whole matrix on one device (blocks straddle the "
+                                              "row splits of a multi-device handle)");
+  }
+  int rc;
+  if (x0_dev && (rc = check_eigs_ptr(h, x0_dev, "lobpcg", "x0"))) return rc;
+  return check_eigs_ptr(h, vectors_dev, "lobpcg", "the vectors");
+}
+
+int cfs_hip_sym_lobpcg(cfs_hip_sym_t h, int k, int block_rows, double tol, double scale, int maxiter, const void *x0_dev,
+                       long long ld0, double *eigenvalues, void *vectors_dev, long long ld, double *residuals, int *nconv,
+                       int *iterations, int *products, void *stream) {
+  if (!h || !eigenvalues || !vectors_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (nconv) *nconv = 0;
+  if (iterations) *iterations = 0;
+  if (products) *products = 0;
+  const bool tol_ok = tol >= 0.0 && scale > 0.0 && std::isfinite(scale) && maxiter >= 0;
+  int rc = check_lobpcg(h, k, block_rows, tol_ok, x0_dev, ld0, vectors_dev, ld);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  return with_lobpcg_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::lobpcg<decltype(v), decltype(bs)::value>(h, k, tol, scale, maxiter, -1, x0_dev, ld0, eigenvalues, vectors_dev, ld,
+                                                                residuals, nconv, iterations, products, st);
+  });
+}
+
+int cfs_hip_sym_debug_lobpcg(cfs_hip_sym_t h, int k, int block_rows, const void *x0_dev, long long ld0, int iters, double *theta,
+                             void *vectors_dev, long long ld, double *resnorms, void *stream) {
+  if (!h || !theta || !vectors_dev || !resnorms) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  int rc = check_lobpcg(h, k, block_rows, iters >= 0, x0_dev, ld0, vectors_dev, ld);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  return with_lobpcg_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::lobpcg<decltype(v), decltype(bs)::value>(h, k, 0.0, 1.0, 0, iters, x0_dev, ld0, theta, vectors_dev, ld, resnorms,
+                                                                nullptr, nullptr, nullptr, st);
+  });
+}
+
+int cfs_hip_debug_lobpcg_rr(int m, const double *g, const double *hh, int k, double drop, double *theta, double *c, int *rank) {
+  if (!g || !hh || !theta || !c || !rank) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (m < 1 || m > 3 * CFS_HIP_LOBPCG_MAX_K || k < 1 || k > CFS_HIP_LOBPCG_MAX_K || k > m)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg_rr: 1 <= m <= " + std::to_string(3 * CFS_HIP_LOBPCG_MAX_K) + " and 1 <= k <= min(m, " +
+                                        std::to_string(CFS_HIP_LOBPCG_MAX_K) + ")");
+  if (!(drop >= 0.0) || !(drop < 1.0)) return set_err(CFS_HIP_ERR_ARG, "lobpcg_rr: the drop threshold must lie in [0, 1)");
+  if (cfs_solver::lobpcg_rr(m, g, hh, k, drop, theta, c, rank) < 0)
+    return set_err(CFS_HIP_ERR_INTERNAL, "lobpcg_rr: entries that are not finite, or no convergence");
+  return 0;
+}
+
+// the device blocks of the two kernel-level developer entry points: 16-byte aligned device memory, one device
+static int check_lobpcg_block(const void *p, long long ld, long long n, int value_bytes, const char *who, int *dev) {
+  if (value_bytes != 4 && value_bytes != 8) return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": value_bytes must be 4 or 8");
+  if (n < 1 || ld < n || (ld * value_bytes) % 16 != 0 || ((uintptr_t)p & 15))
+    return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": n >= 1, ld >= n, the pointers and ld multiples of 16 bytes");
+  const cfs_rt::PtrInfo pi = cfs_rt::classify(p);
+  if (!pi.device) return set_err(CFS_HIP_ERR_ARG, std::string(who) + " needs device pointers");
+  if (*dev >= 0 && pi.dev != *dev) return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": the blocks live on different devices");
+  *dev = pi.dev;
+  return 0;
+}
+
+int cfs_hip_debug_gram(const void *s_dev, const void *t_dev, long long ld, long long n, int m, int value_bytes, double *g, double *hh,
+                       void *stream) {
+  if (!s_dev || !t_dev || !g || !hh) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (m < 1 || m > 3 * CFS_HIP_LOBPCG_MAX_K)
+    return set_err(CFS_HIP_ERR_ARG, "gram: m must lie in [1, " + std::to_string(3 * CFS_HIP_LOBPCG_MAX_K) + "]");
+  int dev = -1, rc;
+  if ((rc = check_lobpcg_block(s_dev, ld, n, value_bytes, "gram", &dev)) || (rc = check_lobpcg_block(t_dev, ld, n, value_bytes, "gram", &dev)))
+    return rc;
+  DeviceGuard dg(dev);
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    return cfs_solver::debug_gram<decltype(v)>(s_dev, t_dev, ld, n, m, g, hh, (hipStream_t)stream);
+  });
+}
+
+int cfs_hip_debug_lobpcg_update(void *s_dev, long long ld, long long n, int k, int m, const double *c, int value_bytes, void *stream) {
+  if (!s_dev || !c) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (k < 1 || k > CFS_HIP_LOBPCG_MAX_K || m < 1 || m > 3 * k)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg_update: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + " and 1 <= m <= 3 k");
+  int dev = -1, rc;
+  if ((rc = check_lobpcg_block(s_dev, ld, n, value_bytes, "lobpcg_update", &dev))) return rc;
+  DeviceGuard dg(dev);
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    return cfs_solver::debug_update<decltype(v)>(s_dev, ld, n, k, m, c, (hipStream_t)stream);
+  });
 }
 
 int cfs_hip_sym_spmv(cfs_hip_sym_t h, void *y, const void *x) {

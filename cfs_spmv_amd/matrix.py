@@ -60,6 +60,7 @@ FLAG_HOST_PLAN = 4096  # CFS_HIP_FLAG_HOST_PLAN: build the schedule with the hos
 EXCHANGE_REDUCE_SCATTER, EXCHANGE_SPARSE = _lib.EXCHANGE_REDUCE_SCATTER, _lib.EXCHANGE_SPARSE  # CFS_HIP_EXCHANGE_*
 EXCHANGE = {"reduce_scatter": EXCHANGE_REDUCE_SCATTER, "sparse": EXCHANGE_SPARSE}
 PRECOND = {"none": _lib.PRECOND_NONE, "jacobi": _lib.PRECOND_JACOBI}  # CFS_HIP_PRECOND_*
+LOBPCG_PRECOND = {"none": 0, "jacobi": 1, "block_jacobi": 3}  # block_rows of cfs_hip_sym_lobpcg (block_jacobi: `block`)
 EIGS_WHICH = {"LA": _lib.EIGS_LARGEST, "SA": _lib.EIGS_SMALLEST, "LM": _lib.EIGS_MAGNITUDE}  # CFS_HIP_EIGS_*
 KERNEL_NAMES = ["value_bytes", "block", "mode", "nt", "offb", "u", "det", "comb"]
 DIGEST_WORDS = 28  # CFS_HIP_DIGEST_WORDS
@@ -396,6 +397,66 @@ class SymMatrix:
         if X is not None:
             X = torch.as_strided(X, (self.nrows(), k), (1, ld))
         return w, X, {"nconv": nconv.value, "restarts": restarts.value, "products": products.value, "residuals": res}
+
+    def lobpcg(self, k=6, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, stream=None):
+        """the k smallest (algebraic) eigenpairs inside the library (cfs_hip_sym_lobpcg): LOBPCG on blocks of 3 k
+        device columns with the preconditioners of pcg() -- precond = "none", "jacobi" or "block_jacobi" (block one
+        of 1, 2, 3, 4, 6) -- k products per iteration, two host looks per iteration.  Pair i has converged when
+        ||A x_i - theta_i x_i|| / ||x_i|| <= tol scale; scale: an estimate of ||A||_2 (None: |theta| of
+        self.eigs(k=1, which="LM", tol=1e-3), whose products are not counted).  x0: a device tensor (n, k) whose
+        columns are the start block (any strides; None: the library's fixed start block).  Returns (w, X, info): w a
+        numpy float64 array (k,), ascending; X a device tensor (n, k) with strides (1, ld); info = dict(nconv,
+        iterations, products, residuals) -- residuals recomputed from the returned vectors."""
+        import torch
+        if isinstance(precond, str):
+            if precond not in LOBPCG_PRECOND:
+                raise ValueError(f"unknown preconditioner {precond!r}: one of {sorted(LOBPCG_PRECOND)}")
+            block_rows = int(block) if precond == "block_jacobi" else LOBPCG_PRECOND[precond]
+        else:
+            block_rows = int(precond)
+        k = int(k)
+        if scale is None:
+            scale = abs(float(self.eigs(k=1, which="LM", tol=1e-3, vectors=False, stream=stream)[0][0]))
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        n = self.nrows()
+        per = 16 // self.dtype.itemsize
+        ld = -(-n // per) * per
+        w, res = np.zeros(max(k, 0), np.float64), np.zeros(max(k, 0), np.float64)
+        X = torch.zeros(max(k, 1) * ld, dtype=tdt, device="cuda")
+        x0buf = None
+        if x0 is not None:
+            if x0.dtype != tdt or tuple(x0.shape) != (n, k):
+                raise ValueError(f"x0 must be a {tdt} tensor of shape ({n}, {k})")
+            x0buf = torch.zeros(k * ld, dtype=tdt, device="cuda")
+            torch.as_strided(x0buf, (n, k), (1, ld)).copy_(x0)
+        dp = C.POINTER(C.c_double)
+        nconv, iterations, products = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(_lib.load().cfs_hip_sym_lobpcg(
+            self._h, k, block_rows, float(tol), float(scale), int(maxiter), _ptr(x0buf) if x0buf is not None else None, ld,
+            w.ctypes.data_as(dp), _ptr(X), ld, res.ctypes.data_as(dp), C.byref(nconv), C.byref(iterations),
+            C.byref(products), _stream_ptr(stream)))
+        X = torch.as_strided(X, (n, k), (1, ld))
+        return w, X, {"nconv": nconv.value, "iterations": iterations.value, "products": products.value, "residuals": res}
+
+    def debug_lobpcg(self, k, block_rows, iters, x0=None, stream=None):
+        """developer / test: iteration 0 and `iters` more of the solver's own kernels, every pair active
+        (cfs_hip_sym_debug_lobpcg).  Returns (theta, X, resnorms)."""
+        import torch
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        n = self.nrows()
+        per = 16 // self.dtype.itemsize
+        ld = -(-n // per) * per
+        theta, res = np.zeros(k), np.zeros(k)
+        X = torch.zeros(k * ld, dtype=tdt, device="cuda")
+        x0buf = None
+        if x0 is not None:
+            x0buf = torch.zeros(k * ld, dtype=tdt, device="cuda")
+            torch.as_strided(x0buf, (n, k), (1, ld)).copy_(x0)
+        dp = C.POINTER(C.c_double)
+        _lib.check(_lib.load().cfs_hip_sym_debug_lobpcg(
+            self._h, int(k), int(block_rows), _ptr(x0buf) if x0buf is not None else None, ld, int(iters),
+            theta.ctypes.data_as(dp), _ptr(X), ld, res.ctypes.data_as(dp), _stream_ptr(stream)))
+        return theta, torch.as_strided(X, (n, k), (1, ld)), res
 
     # -- the exchange of a one-process multi-device handle (ngpus > 1, FLAG_SHARD_EXCHANGE) --
     def set_exchange(self, form):

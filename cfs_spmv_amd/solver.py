@@ -1,5 +1,6 @@
 """Solver-style caller of the SpMV path: (Jacobi-preconditioned) conjugate gradients, MINRES for
-symmetric indefinite and shifted systems, and thick-restart Lanczos for extreme eigenpairs, on resident vectors.
+symmetric indefinite and shifted systems, thick-restart Lanczos for extreme eigenpairs and LOBPCG for the smallest
+ones, on resident vectors.
 
 SURVEY.md 8(f)-4 / 8(e): the reference's only caller is a benchmark loop with a
 fixed x; a solver feeds every product back as the next input, which is what the
@@ -366,6 +367,182 @@ def eigs_native(A, k, which="LA", ncv=None, tol=1e-10, max_restarts=100, v0=None
     """the same iteration inside the library (cfs_hip_sym_eigs): nine launches per step, alpha, beta and the breakdown
     flag in device memory, the host looks only when the basis is full.  Returns (w, X, info), like eigs()."""
     return A.eigs(k=k, which=which, ncv=ncv, tol=tol, max_restarts=max_restarts, v0=v0, vectors=vectors)
+
+
+def lobpcg_rr(G, H, k, drop):
+    """step 2 of cfs_hip_sym_lobpcg in numpy (the upper triangles of G and H are read): d_j = G_jj^-1/2, columns whose
+    G_jj is not finite and > 0 dropped; the eigenvectors of D G D with w > drop w_max kept, Q = D U w^-1/2; T = Q^T H Q
+    symmetrised; C = Q Z[:, :k].  Returns (theta, C, rank), C (m, k) with zero rows for dropped columns."""
+    import numpy as np
+    m = G.shape[0]
+    G = np.triu(G) + np.triu(G, 1).T
+    H = np.triu(H) + np.triu(H, 1).T
+    g = np.diag(G)
+    with np.errstate(all="ignore"):
+        keep = np.flatnonzero(np.isfinite(g) & (g > 0))
+        d = 1.0 / np.sqrt(g[keep])
+    theta, C = np.zeros(k, G.dtype), np.zeros((m, k), G.dtype)
+    if keep.size == 0:
+        return theta, C, 0
+    w, U = np.linalg.eigh((d[:, None] * G[np.ix_(keep, keep)] * d[None, :]).astype(np.float64))
+    sel = w > drop * w[-1]
+    r = int(np.count_nonzero(sel))
+    if r == 0:
+        return theta, C, 0
+    Q = (d[:, None] * U[:, sel].astype(G.dtype)) / np.sqrt(w[sel].astype(G.dtype))[None, :]
+    T = Q.T @ H[np.ix_(keep, keep)] @ Q
+    T = 0.5 * (T + T.T)
+    tw, Z = np.linalg.eigh(T.astype(np.float64))
+    kk = min(k, r)
+    theta[:kk] = tw[:kk]
+    C[keep, :kk] = Q @ Z[:, :kk].astype(G.dtype)
+    return theta, C, r
+
+
+def default_x0(n, k, dtype):
+    """the start block of a NULL x0_dev (include/cfs_hip.h): x0[i, c] = v0(i + c n) of the splitmix64 sequence, as a
+    numpy array (n, k) of `dtype`"""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        z = (np.arange(n * k, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    v = (z >> np.uint64(11)).astype(np.float64) * 2.0 ** -53 - 0.5
+    return np.ascontiguousarray(v.reshape(k, n).T.astype(dtype))
+
+
+def _lobpcg_minv(A, precond, block):
+    """apply(R) -> M^-1 R in fp64 for an (n, j) block, with the stored inverse diagonal / inverse blocks of the handle"""
+    import torch
+    if precond == "none":
+        return lambda R: R
+    if precond == "jacobi":
+        d = A.diagonal()
+        if not bool(torch.all(torch.isfinite(d) & (d > 0))):
+            raise ValueError("lobpcg: Jacobi needs a positive diagonal")
+        dinv = (1.0 / d.double()).to(d.dtype).double()
+        return lambda R: R * dinv[:, None]
+    if precond == "block_jacobi":
+        minv = A.block_inverse(block)
+        if not bool(torch.all(torch.isfinite(minv))):
+            raise ValueError("lobpcg: block Jacobi needs positive definite diagonal blocks")
+        nb, bs, _ = minv.shape
+        m64 = minv.double()
+
+        def apply(R):
+            n, j = R.shape
+            Rp = torch.zeros((nb * bs, j), dtype=torch.float64, device=R.device)
+            Rp[:n] = R
+            return torch.bmm(m64, Rp.view(nb, bs, j)).reshape(nb * bs, j)[:n]
+        return apply
+    raise ValueError(f"unknown preconditioner {precond!r}: 'none', 'jacobi' or 'block_jacobi'")
+
+
+def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, iters=None):
+    """the k smallest eigenpairs by LOBPCG, host-driven: the recurrence of cfs_hip_sym_lobpcg (Gram matrices of
+    S = [X | W | P_act] in fp64, the Rayleigh-Ritz step with its drop rule, X, P, AX, AP updated implicitly and rounded
+    to the value type when stored, W = M^-1 R in fp64, soft locking, the confirm step) with torch operations on A's
+    product and numpy on the host -- the model and the baseline of the native loop.  iters: like
+    cfs_hip_sym_debug_lobpcg, iteration 0 and `iters` more with every pair active, no convergence test.  Returns
+    (w, X, info) like SymMatrix.lobpcg; with iters, info["residuals"] are those of the implicit AX."""
+    import numpy as np
+    import torch
+    n = A.nrows()
+    tdt = torch.float64 if A.dtype == np.float64 else torch.float32
+    unit = 2.0 ** -53 if A.dtype == np.float64 else 2.0 ** -24
+    if not (1 <= k <= 16 and 3 * k <= n):
+        raise ValueError("lobpcg: 1 <= k <= 16 and 3 k <= n")
+    debug = iters is not None
+    if scale is None and not debug:
+        scale = abs(float(A.eigs(k=1, which="LM", tol=1e-3, vectors=False)[0][0]))
+    thr = 0.0 if debug else tol * scale
+    apply = _lobpcg_minv(A, precond, block)
+    dev = "cuda" if x0 is None else x0.device
+    S = torch.zeros((3 * k, n), dtype=tdt, device=dev)   # row c = physical column c: X | W | P
+    AS = torch.zeros((3 * k, n), dtype=tdt, device=dev)
+    S[:k] = (torch.from_numpy(default_x0(n, k, A.dtype)).to(dev) if x0 is None else x0.to(tdt)).T
+    products = 0
+
+    def product(c):
+        nonlocal products
+        A.dense_vector_multiply(AS[c], S[c])          # the hot path
+        products += 1
+
+    for c in range(k):
+        product(c)
+    theta = np.zeros(k)
+
+    def rayleigh_ritz(cols):
+        nonlocal theta
+        idx = torch.tensor(cols, device=dev)
+        Sa, ASa = S[idx].double(), AS[idx].double()
+        G, H = (Sa @ Sa.T).cpu().numpy(), (Sa @ ASa.T).cpu().numpy()
+        theta, C, rank = lobpcg_rr(G, H, k, 64.0 * unit)
+        Ct = torch.from_numpy(C).to(dev)
+        Cp = Ct.clone()
+        Cp[:k] = 0.0
+        X, AX = (Ct.T @ Sa).to(tdt), (Ct.T @ ASa).to(tdt)
+        if len(cols) > k:
+            S[2 * k:], AS[2 * k:] = (Cp.T @ Sa).to(tdt), (Cp.T @ ASa).to(tdt)
+        S[:k], AS[:k] = X, AX
+        return rank
+
+    res = np.zeros(k)
+
+    def norms():
+        X, AX = S[:k].double(), AS[:k].double()
+        R = AX - torch.from_numpy(theta).to(dev)[:, None] * X
+        S[k:2 * k] = apply(R.T).T.to(tdt)
+        res[:] = (torch.linalg.vector_norm(R, dim=1) / torch.linalg.vector_norm(X, dim=1)).cpu().numpy()
+
+    for attempt in range(3):
+        rank = rayleigh_ritz(list(range(k)))
+        if rank == k:
+            break
+        if attempt == 2:
+            raise ValueError("lobpcg: the start block does not have rank k")
+        fill = default_x0(n, k * (attempt + 2), A.dtype)
+        for c in range(rank, k):
+            S[c] = torch.from_numpy(fill[:, k * (attempt + 1) + c]).to(dev)
+            product(c)
+    norms()
+    it, fresh, have_p = 0, False, False
+    while True:
+        act = [i for i in range(k) if debug or not res[i] <= thr]
+        if not debug and not act:
+            if fresh:
+                break
+            for c in range(k):
+                product(c)
+            norms()
+            fresh = True
+            continue
+        if it >= (iters if debug else maxiter):
+            break
+        for i in act:
+            product(k + i)
+        cols = list(range(k)) + [k + i for i in act] + ([2 * k + i for i in act] if have_p else [])
+        if rayleigh_ritz(cols) < k:
+            raise RuntimeError("lobpcg: the basis lost rank")
+        have_p, fresh = True, False
+        norms()
+        it += 1
+    if not debug and not fresh:
+        for c in range(k):
+            product(c)
+        norms()
+    nconv = 0
+    while nconv < k and res[nconv] <= thr:
+        nconv += 1
+    return theta.copy(), S[:k].T.clone(), {"nconv": nconv, "iterations": it, "products": products, "residuals": res.copy()}
+
+
+def lobpcg_native(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None):
+    """the same iteration inside the library (cfs_hip_sym_lobpcg): the Gram matrices by one small-SYRK kernel, the
+    update in place, residual and preconditioner in one kernel; two host looks per iteration.  Returns (w, X, info),
+    like lobpcg()."""
+    return A.lobpcg(k=k, precond=precond, block=block, tol=tol, scale=scale, maxiter=maxiter, x0=x0)
 
 
 def cg_sharded(S, row_splits, b_block, tol=1e-10, maxiter=1000):

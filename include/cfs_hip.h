@@ -461,6 +461,7 @@ int cfs_hip_sym_minres(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int prec
  * eigenvalues, residuals and columns zero-filled.
  * SCOPE: plain Lanczos finds the well-separated end of a spectrum quickly and the clustered low end of a stiffness
  * matrix slowly; shift-invert (an inner cfs_hip_sym_minres or _pcg solve per step) is left for a later change.
+ * cfs_hip_sym_lobpcg below, which uses the preconditioners directly, is the route to the low end.
  * CFS_HIP_ERR_ARG, before any device work, in this order: a null h or eigenvalues ("null"); an unknown which; bad
  * k / ncv (the part against n once the handle is read); tol < 0 or NaN, max_restarts < 0; v0_dev or vectors_dev
  * not 16-byte aligned, or a bad ld; a host pointer or a pointer on another device.  A start vector whose norm is
@@ -483,6 +484,78 @@ int cfs_hip_sym_debug_lanczos(cfs_hip_sym_t h, const void *v0_dev, int steps, vo
  * symmetric, row-major (the upper triangle is read), 1 <= m <= CFS_HIP_EIGS_MAX_NCV (else CFS_HIP_ERR_ARG);
  * w: the m eigenvalues ascending; s: m x m row-major, eigenvector i in column i.                   */
 int cfs_hip_debug_symeig(int m, const double *a, double *w, double *s);
+/* The k SMALLEST (algebraic) eigenpairs of A by LOBPCG (Knyazev's locally optimal block preconditioned CG) with the
+ * preconditioners of the PCG solvers: the first vibration or buckling modes of a stiffness matrix, the clustered low
+ * end that cfs_hip_sym_eigs finds slowly.  k products per iteration, no factorisation.  Handles accepted are those
+ * of cfs_hip_sym_cg, one device or multi-device (the blocks live on the home device; a shard:
+ * CFS_HIP_ERR_UNSUPPORTED); both value types; the blocks are stored in the value type V, EVERY dot product and
+ * scalar is fp64, no contracted multiply-adds.  1 <= k <= CFS_HIP_LOBPCG_MAX_K and 3 k <= n.
+ * block_rows: 0 no preconditioner, 1 Jacobi, 2, 3, 4, 6 block Jacobi on the node blocks; M is built exactly as
+ * cfs_hip_sym_pcg / cfs_hip_sym_pcg_block build theirs, and a diagonal entry or block that is not positive
+ * (definite) is refused the same way (CFS_HIP_ERR_ARG, nothing written).  Block sizes above 1 on a multi-device
+ * handle: CFS_HIP_ERR_UNSUPPORTED.
+ * An iteration works on S = [X | W | P_act], m <= 3 k columns, and AS, the same columns of A S:
+ *   1. G = S^T S and H = S^T AS, upper triangles, in ONE pass over S and AS: fixed-order partial sums per workgroup,
+ *      added up by a second kernel; the host reads both matrices (first look).
+ *   2. Rayleigh-Ritz on the host, fp64: d_j = G_jj^-1/2, a column whose G_jj is not finite and > 0 is dropped; the
+ *      eigenvectors of D G D with w > 64 u_V w_max are kept (u_V = 2^-53 / 2^-24), Q = D U w^-1/2; T = Q^T H Q,
+ *      symmetrised; C = Q Z[:, :k], theta = the k smallest eigenvalues of T.  (The drop makes a W or P column that
+ *      is nearly dependent on the others harmless.)
+ *   3. X <- (V)(S C), AX <- (V)(AS C), P <- (V)(S C'), AP <- (V)(AS C'), C' = C with its first k rows zeroed: in
+ *      place, fp64 accumulation with the columns ascending, rounded once when stored.
+ *   4. R_i = AX_i - theta_i X_i; the norms ||R_i||, ||X_i||; W_i = (V)(M^-1 R_i) in fp64 from the stored inverse
+ *      diagonal or inverse blocks.  The host reads the norms (second look).  Soft locking: only the pairs with
+ *      r_i = ||R_i|| / ||X_i|| > tol scale contribute their W and P columns to the next S; X always stays whole.
+ *   5. When all k residuals pass, AX = A X is recomputed with k products and step 4 repeated; the solve ends only if
+ *      they still pass, else it goes on with the fresh AX (the drift of the implicitly updated AX does not reach
+ *      the caller).
+ *   6. AW_i = A W_i, one product per active pair.
+ * Iteration 0 is steps 1 - 4 on S = X0, AS by k products.  TWO host looks per iteration are inherent in this
+ * design: C depends on G and H, the active set on the norms.  All sums are fixed-order partial sums: on a
+ * CFS_HIP_FLAG_DETERMINISTIC handle the solve is bit-reproducible.  Device memory held during the call: (6 k + 1) n
+ * values (S, AS and the inverse diagonal; the packed inverse blocks take (block_rows + 1) / 2 n instead of n) plus
+ * the scalars (the partial sums of G and H: 2 (3 k)^2 x 512 doubles).
+ * scale: finite and > 0, the caller's estimate of ||A||_2: pair i has converged when ||A x_i - theta_i x_i||_2 /
+ * ||x_i||_2 <= tol scale -- the criterion of cfs_hip_sym_eigs with lambda_max made explicit, because LOBPCG never
+ * sees the top of the spectrum.
+ * x0_dev: k start columns, column c at x0_dev + c ld0 values, not modified; NULL selects x0[i, c] = v0_{i + c n} of
+ * the fixed sequence documented at cfs_hip_sym_eigs: the same bits in every call.  A start block short of rank k has
+ * its dependent columns replaced from that sequence.
+ * vectors_dev (required): column i at vectors_dev + i ld values; ld, ld0 >= n, the pointers, ld sizeof(V) and
+ * ld0 sizeof(V) multiples of 16; device memory on the handle's device; nothing outside rows [0, n) of the k columns is
+ * written.  The columns have unit norm up to rounding.
+ * eigenvalues: host array of k doubles, ascending.  residuals: nullable host array of k doubles, ||A x_i - theta_i
+ * x_i||_2 / ||x_i||_2 in fp64 from the returned, stored x_i and a fresh product A x_i.  *nconv: the number of
+ * leading pairs whose residual meets the tolerance; the call returns 0 also when nconv < k after maxiter
+ * iterations, the best pairs written.  *iterations (iteration 0 not counted), *products (every SpMV issued): any of
+ * the three counters may be NULL.
+ * CFS_HIP_ERR_ARG, before any device work, in this order: a null h, eigenvalues or vectors_dev ("null"); bad k (the
+ * part against n once the handle is read); an unknown block_rows; tol < 0 or NaN, scale not finite and > 0,
+ * maxiter < 0 ("tolerance"); x0_dev or vectors_dev not 16-byte aligned, or a bad ld / ld0; a host pointer or a
+ * pointer on another device.  On a refusal the counters are zeroed and nothing else is written.            */
+#define CFS_HIP_LOBPCG_MAX_K 16
+int cfs_hip_sym_lobpcg(cfs_hip_sym_t h, int k, int block_rows, double tol, double scale, int maxiter,
+                       const void *x0_dev, long long ld0, double *eigenvalues, void *vectors_dev, long long ld,
+                       double *residuals, int *nconv, int *iterations, int *products, void *stream);
+/* For developers and tests.  host-only: step 2.  g, hh: m x m row-major, upper triangles read
+ * (1 <= m <= 3 CFS_HIP_LOBPCG_MAX_K, 1 <= k <= min(m, CFS_HIP_LOBPCG_MAX_K)); drop: the threshold on w / w_max,
+ * in [0, 1); out: theta[k], c[m x k] row-major, *rank = columns kept (with rank < k the trailing theta and columns
+ * of c are 0).                                                                                            */
+int cfs_hip_debug_lobpcg_rr(int m, const double *g, const double *hh, int k, double drop, double *theta, double *c, int *rank);
+/* G = S^T S, H = S^T T of two n x m device blocks (value_bytes 4 / 8; column c at + c ld values; pointers and
+ * ld value_bytes multiples of 16), full m x m row-major on the host, with the solver's Gram and reduce kernels
+ * (every entry of H is summed; the lower triangle of G mirrors the upper).  The call waits for the kernels.   */
+int cfs_hip_debug_gram(const void *s_dev, const void *t_dev, long long ld, long long n, int m, int value_bytes,
+                       double *g, double *hh, void *stream);
+/* iteration 0 and `iters` more iterations with the solver's own kernels, every pair active, no convergence test,
+ * no confirm step: X, theta and the residual norms ||AX_i - theta_i X_i|| / ||X_i|| of the implicitly updated AX
+ * after the last one (the sibling of cfs_hip_sym_debug_lanczos).  Arguments as for cfs_hip_sym_lobpcg.       */
+int cfs_hip_sym_debug_lobpcg(cfs_hip_sym_t h, int k, int block_rows, const void *x0_dev, long long ld0, int iters,
+                             double *theta, void *vectors_dev, long long ld, double *resnorms, void *stream);
+/* step 3 alone, on one n x 3 k device block (X | W | P): with S its first m columns (1 <= m <= 3 k) and c m x 2 k
+ * row-major on the host, X <- (V)(S c[:, :k]) and P <- (V)(S c[:, k:]), in place.  The call waits for the kernel. */
+int cfs_hip_debug_lobpcg_update(void *s_dev, long long ld, long long n, int k, int m, const double *c, int value_bytes,
+                                void *stream);
 
 /* ---- sharded operation: y_block = local rows; contributions to rows owned
  *      by lower ranks are packed into send_buf (device), exchanged by the

@@ -16,7 +16,7 @@ def cycle(k):
         A = cfs.SymMatrix(n, rp, ci, va, options=cfs.make_options(flags=flags | (32 if k % 2 else 0)))
         A.dense_vector_multiply(y, x); A.close()
     G = cfs.CsrMatrix(n, n, rp, ci, va); G.dense_vector_multiply(y, x); G.close()
-    A = cfs.SymMatrix(n, rp, ci, va); u = torch.zeros_like(x); A.cg(u, x, maxiter=5); A.close()
+    A = cfs.SymMatrix(n, rp, ci, va); u = torch.zeros_like(x); A.cg(u, x, maxiter=5); A.lobpcg(k=2, scale=1.0, maxiter=3); A.close()
     M = cfs.SymMatrix(n, rp, ci, va, ngpus=2); M.dense_vector_multiply(y, x); M.close()
 cycle(0); cycle(1)
 base = used()

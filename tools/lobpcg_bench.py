@@ -1,0 +1,155 @@
+"""time per iteration of LOBPCG: cfs_hip_sym_lobpcg (the Gram, update and residual kernels, two host looks per iteration)
+against the host-driven loop of cfs_spmv_amd/solver.py (solver.lobpcg: the same recurrence with torch operations on the
+same handle).  pwtk, ldoor and Flan_1565 stand-ins, k = 4 and 16, Jacobi and block Jacobi on 3 x 3 blocks, tol = 0 (no
+pair converges: every iteration carries 3 k columns and k products).  The time per iteration is the wall time of a call
+with 2 M iterations minus that of a call with M, over M -- set-up, iteration 0 and the closing products cancel -- the best
+of three runs each (M = 20 native, 5 host-driven, one run).  Beside it the SpMV time of the same handle and the host's
+Rayleigh-Ritz step alone (cfs_hip_debug_lobpcg_rr on a pencil of 3 k columns).
+
+The share of an iteration spent in each kernel comes from a run of its own: this script starts itself as a child
+process under `rocprofv3 --kernel-trace --stats` (no counters), one call of 30 iterations with block Jacobi, and reads
+the per-kernel averages: gram (lobpcg_gram_kernel + its reduce), update, residual (+ its reduce), products (k x tile
+kernel + fold), each over the native time per iteration measured with the profiler off; what is left is the two host
+looks: synchronisation, the copies, the host's Rayleigh-Ritz step and launch gaps.
+
+Last, products and wall time to nconv = 4 at tol 1e-8 on Flan_1565 at scale 0.05 with block Jacobi, beside
+eigs(which="SA") given at least the same number of products.  Prints one JSON line and writes it to
+profiles/lobpcg_bench.json.
+usage: python tools/lobpcg_bench.py [matrix[:scale] ...]"""
+import csv, ctypes as C, glob, json, os, shutil, subprocess, sys, tempfile, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+import cfs_spmv_amd as cfs
+from cfs_spmv_amd import _lib, synth
+from cfs_spmv_amd.solver import lobpcg, lobpcg_native
+
+TRACE_ITERS = 30
+PRECOND = {"jacobi": dict(precond="jacobi"), "block3": dict(precond="block_jacobi", block=3)}
+
+
+def best(fn, rounds=3):
+    fn()
+    t = float("inf")
+    for _ in range(rounds):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        t = min(t, time.perf_counter() - t0)
+    return t
+
+
+def handle(spec):
+    name, _, sc = spec.partition(":")
+    n, rp, ci, va, _ = synth.generate(name, float(sc or 1.0))
+    return n, cfs.SymMatrix(n, rp, ci, va)
+
+
+def child(spec, k):
+    """the traced run: one call of TRACE_ITERS iterations (and a short one before it, to load the code objects)"""
+    n, A = handle(spec)
+    for maxiter in (2, TRACE_ITERS):
+        A.lobpcg(k=k, tol=0.0, scale=1.0, maxiter=maxiter, **PRECOND["block3"])
+    torch.cuda.synchronize()
+    A.close()
+
+
+def traced(spec, k, native_us):
+    """per-kernel microseconds per iteration from the child's kernel statistics, and their shares of native_us"""
+    out = tempfile.mkdtemp(prefix=f"lobpcg_trace_{spec.replace(':', '_')}_k{k}_")
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "--", sys.executable,
+           os.path.abspath(__file__), "--child", spec, str(k)]
+    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+    with open(glob.glob(os.path.join(out, "*", "*_kernel_stats.csv"))[0]) as f:
+        rows = list(csv.DictReader(f))
+    shutil.rmtree(out, ignore_errors=True)
+
+    def avg(word, least_calls=TRACE_ITERS):  # the instantiation the traced iterations launched
+        hit = [r for r in rows if word in r["Name"] and int(r["Calls"]) >= least_calls]
+        return sum(float(r["TotalDurationNs"]) for r in hit) / max(1, sum(int(r["Calls"]) for r in hit)) / 1e3
+    us = {"gram": avg("lobpcg_gram_kernel") + avg("lobpcg_gram_reduce_kernel"), "update": avg("lobpcg_update_kernel"),
+          "residual": avg("lobpcg_residual_kernel") + avg("lobpcg_reduce_kernel"),
+          "products": k * (avg("cfs_sym_tile_kernel", k * TRACE_ITERS) + avg("cfs_fold_kernel", k * TRACE_ITERS))}
+    us["host_looks_and_gaps"] = native_us - sum(us.values())
+    return {"kernel_us_per_iteration": {a: round(b, 2) for a, b in us.items()},
+            "share": {a: round(b / native_us, 4) for a, b in us.items()}}
+
+
+def rr_host_us(m, k):
+    rng = np.random.default_rng(m)
+    S = rng.standard_normal((400, m))
+    Aop = np.diag(np.linspace(1.0, 50.0, 400))
+    g, hh = np.ascontiguousarray(S.T @ S), np.ascontiguousarray(S.T @ Aop @ S)
+    theta, c, rank = np.zeros(k), np.zeros((m, k)), C.c_int()
+    dp = C.POINTER(C.c_double)
+    lib = cfs.load()
+    call = lambda: _lib.check(lib.cfs_hip_debug_lobpcg_rr(m, g.ctypes.data_as(dp), hh.ctypes.data_as(dp), k, 64 * 2.0 ** -53,
+                                                          theta.ctypes.data_as(dp), c.ctypes.data_as(dp), C.byref(rank)))
+    call()
+    t0 = time.perf_counter()
+    for _ in range(20):
+        call()
+    return (time.perf_counter() - t0) / 20 * 1e6
+
+
+def main(specs):
+    out = {}
+    for spec in specs:
+        n, A = handle(spec)
+        x = torch.from_numpy(synth.make_x(n, 11)).cuda()
+        y = torch.empty_like(x)
+        for _ in range(50):
+            A.dense_vector_multiply(y, x)
+        spmv_us = best(lambda: [A.dense_vector_multiply(y, x) for _ in range(200)]) / 200 * 1e6
+        res = {"n": n, "spmv_us": round(spmv_us, 2)}
+        for k in (4, 16):
+            for pname, pkw in PRECOND.items():
+                kw = dict(tol=0.0, scale=1.0, **pkw)
+                M = 20
+                t1 = best(lambda: lobpcg_native(A, k, maxiter=M, **kw))
+                t2 = best(lambda: lobpcg_native(A, k, maxiter=2 * M, **kw))
+                native = (t2 - t1) / M * 1e6
+                h1 = best(lambda: lobpcg(A, k, maxiter=5, **kw), rounds=1)
+                h2 = best(lambda: lobpcg(A, k, maxiter=10, **kw), rounds=1)
+                host = (h2 - h1) / 5 * 1e6
+                res[f"k{k}_{pname}"] = {"native_us_per_iteration": round(native, 2), "host_driven_us_per_iteration": round(host, 2),
+                                        "native_over_host_driven": round(native / host, 4),
+                                        "iteration_over_k_spmv": round(native / (k * spmv_us), 2)}
+            res[f"k{k}_rr_host_us"] = round(rr_host_us(3 * k, k), 2)
+        A.close()
+        for k in (4, 16):  # (the handle is closed: the child builds its own)
+            res[f"k{k}_block3"].update(traced(spec, k, res[f"k{k}_block3"]["native_us_per_iteration"]))
+        out[spec] = res
+    # to convergence: the low end of the Flan stand-in, LOBPCG with block Jacobi against Lanczos with as many products
+    n, A = handle("Flan_1565:0.05")
+    scale = abs(float(A.eigs(k=1, which="LM", tol=1e-3, vectors=False)[0][0]))
+    run = lambda: A.lobpcg(k=4, tol=1e-8, scale=scale, maxiter=2000, **PRECOND["block3"])
+    w, X, info = run()
+    t = best(run, rounds=1)
+    ncv = 20
+    l = 4 + (ncv - 4) // 2
+    restarts = max(0, -(-(info["products"] - ncv - 4) // (ncv - l)))
+    erun = lambda: A.eigs(k=4, which="SA", ncv=ncv, tol=1e-8, max_restarts=restarts)
+    we, Xe, ie = erun()
+    te = best(erun, rounds=1)
+    A.close()
+    out["to_convergence"] = {
+        "matrix": "Flan_1565:0.05", "n": n, "k": 4, "tol": 1e-8, "scale": scale,
+        "lobpcg_block3": {"nconv": info["nconv"], "iterations": info["iterations"], "products": info["products"],
+                          "wall_ms": round(t * 1e3, 2), "theta": [float(v) for v in w],
+                          "max_residual_over_scale": float(np.max(info["residuals"]) / scale)},
+        "eigs_SA": {"nconv": ie["nconv"], "restarts": ie["restarts"], "products": ie["products"], "wall_ms": round(te * 1e3, 2),
+                    "theta": [float(v) for v in we], "max_residual_over_scale": float(np.max(ie["residuals"]) / scale)}}
+    line = json.dumps(out)
+    print(line)
+    with open(os.path.join(ROOT, "profiles", "lobpcg_bench.json"), "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    if sys.argv[1:2] == ["--child"]:
+        child(sys.argv[2], int(sys.argv[3]))
+    else:
+        main(sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"])
