@@ -74,7 +74,7 @@ SYMBOLS = [
     "cfs_hip_sym_create_multi_f64", "cfs_hip_sym_create_multi_f32", "cfs_hip_comm_create", "cfs_hip_comm_info", "cfs_hip_comm_destroy", "cfs_hip_comm_reduce_scatter",
     "cfs_hip_comm_allgather", "cfs_hip_comm_alltoallv", "cfs_hip_comm_wait_consumed", "cfs_hip_sym_num_gpus", "cfs_hip_sym_multi_set_xmode", "cfs_hip_sym_multi_set_exchange", "cfs_hip_sym_multi_exchange_info", "cfs_hip_sym_multi_devices", "cfs_hip_sym_balanced_splits", "cfs_hip_sym_destroy", "cfs_hip_sym_update_values_f64", "cfs_hip_sym_update_values_f32", "cfs_hip_sym_spmv",
     "cfs_hip_sym_spmv_async", "cfs_hip_sym_cg", "cfs_hip_sym_pcg", "cfs_hip_sym_diagonal_async", "cfs_hip_sym_block_diagonal_async",
-    "cfs_hip_sym_pcg_block", "cfs_hip_sym_block_inverse_async", "cfs_hip_sym_pcg_mixed", "cfs_hip_sym_minres", "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
+    "cfs_hip_sym_pcg_block", "cfs_hip_sym_block_inverse_async", "cfs_hip_sym_pcg_mixed", "cfs_hip_sym_minres", "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
     "cfs_hip_sym_shard_set_recv", "cfs_hip_sym_spmv_local_async",
     "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_fold_lists", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
     "cfs_hip_sym_plan_check_f32", "cfs_hip_sym_plan_send_info_f64",
@@ -200,6 +200,9 @@ def load():
                                          ip, ip, ip, vp]
         lib.cfs_hip_sym_debug_lanczos.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, dp, dp, ip, vp]
         lib.cfs_hip_debug_symeig.argtypes = [C.c_int, dp, dp, dp]
+    if hasattr(lib, "cfs_hip_debug_eigs_combine"):  # (absent from older builds loaded through CFS_HIP_LIB)
+        lib.cfs_hip_debug_eigs_combine.argtypes = [vp, C.c_longlong, vp, C.c_longlong, C.c_longlong, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_double), C.c_int, vp]
     if hasattr(lib, "cfs_hip_sym_lobpcg"):  # (absent from older builds loaded through CFS_HIP_LIB)
         dp = C.POINTER(C.c_double)
         lib.cfs_hip_sym_lobpcg.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_longlong, dp, vp,

@@ -2214,6 +2214,36 @@ int cfs_hip_debug_symeig(int m, const double *a, double *w, double *s) {
   return 0;
 }
 
+int cfs_hip_debug_eigs_combine(void *out_dev, long long ldo, const void *basis_dev, long long ld, long long n, int m, int nout,
+                               const double *s, int value_bytes, void *stream) {
+  if (!out_dev || !basis_dev || !s) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (m < 1 || m > CFS_HIP_EIGS_MAX_NCV || nout < 1 || nout > m)
+    return set_err(CFS_HIP_ERR_ARG, "eigs_combine: bad m / nout: 1 <= nout <= m <= " + std::to_string(CFS_HIP_EIGS_MAX_NCV) + ", got m = " +
+                                        std::to_string(m) + ", nout = " + std::to_string(nout));
+  if (value_bytes != 4 && value_bytes != 8) return set_err(CFS_HIP_ERR_ARG, "eigs_combine: value_bytes must be 4 or 8");
+  if ((((uintptr_t)out_dev) | ((uintptr_t)basis_dev)) & 15)
+    return set_err(CFS_HIP_ERR_ARG, "eigs_combine: out and the basis must be 16-byte aligned");
+  // (the upper limit keeps the byte spans below within 63 bits)
+  const long long ldmax = (1LL << 62) / (8LL * CFS_HIP_EIGS_MAX_NCV);
+  if (n < 1 || ld < n || ldo < n || ld > ldmax || ldo > ldmax || (ld * value_bytes) % 16 != 0 || (ldo * value_bytes) % 16 != 0)
+    return set_err(CFS_HIP_ERR_ARG, "eigs_combine: bad ld " + std::to_string(ld) + " / ldo " + std::to_string(ldo) + ": at least n = " +
+                                        std::to_string(n) + " >= 1 and a multiple of 16 bytes");
+  // the two blocks, first byte to the last row of the last column: the same block (the in-place restart), or disjoint
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(((long long)(nout - 1) * ldo + n) * value_bytes);
+  const uintptr_t b0 = (uintptr_t)basis_dev, b1 = b0 + (uintptr_t)(((long long)(m - 1) * ld + n) * value_bytes);
+  if (!(o0 == b0 && ldo == ld) && o0 < b1 && b0 < o1)
+    return set_err(CFS_HIP_ERR_ARG, "eigs_combine: out and the basis overlap: the same block with ldo == ld (in place), or disjoint");
+  int cur = -1;
+  HIPCHK(hipGetDevice(&cur));
+  for (const void *p : {(const void *)out_dev, basis_dev}) {
+    const cfs_rt::PtrInfo pi = cfs_rt::classify(p);
+    if (!pi.device || pi.dev != cur) return set_err(CFS_HIP_ERR_ARG, "eigs_combine: out and the basis must be device memory of the current device");
+  }
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    return cfs_solver::debug_eigs_combine<decltype(v)>(out_dev, ldo, basis_dev, ld, n, m, nout, s, (hipStream_t)stream);
+  });
+}
+
 // ---- LOBPCG ----
 // f(V(), std::integral_constant<int, BS>()) for the handle's value type and block_rows 0, 1, 2, 3, 4 or 6
 template <class F> static int with_lobpcg_block(int value_bytes, int bs, F &&f) {

@@ -456,18 +456,33 @@ template <typename V, class Handle> struct Lanczos {
     }
     return 0;
   }
-  // out[:, 0 .. nout) = V_m S (s: m x nout row-major on the host); out == basis is the in-place restart
-  int combine(V *out, long long ldo, int m, const double *s, int nout, cfs_rt::DevBuf &sdev) {
-    HIPCHK(hipMemcpyAsync(sdev.p, s, (size_t)m * nout * sizeof(double), hipMemcpyHostToDevice, st));
-    constexpr int R = 256 / (int)sizeof(V);
-    const long long ntiles = (n + R - 1) / R;
-    hipLaunchKernelGGL((eigs_combine_kernel<V>), dim3((unsigned)std::min<long long>(ntiles, 4 * kGrid)), dim3(kThreads),
-                       (size_t)m * R * sizeof(V), st, out, ldo, (const V *)basis, ld, m, (const double *)sdev.p, nout, n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st)); // (s is the host's to change again)
-    return 0;
-  }
 };
+
+// out[:, 0 .. nout) = V_m S on rows [0, n) (s: m x nout row-major on the host, uploaded to s_dev, m nout doubles of room);
+// out == basis with ldo == ld is the in-place restart.  THE launch of eigs_combine_kernel: the solver's restart, its
+// returned X and cfs_hip_debug_eigs_combine all come through here.  Synchronises the stream.
+template <typename V>
+int eigs_combine(V *out, long long ldo, const V *basis, long long ld, long long n, int m, const double *s, int nout, double *s_dev,
+                 hipStream_t st) {
+  HIPCHK(hipMemcpyAsync(s_dev, s, (size_t)m * nout * sizeof(double), hipMemcpyHostToDevice, st));
+  constexpr int R = 256 / (int)sizeof(V);
+  const long long ntiles = (n + R - 1) / R;
+  hipLaunchKernelGGL((eigs_combine_kernel<V>), dim3((unsigned)std::min<long long>(ntiles, 4 * kGrid)), dim3(kThreads),
+                     (size_t)m * R * sizeof(V), st, out, ldo, basis, ld, m, (const double *)s_dev, nout, n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st)); // (s is the host's to change again)
+  return 0;
+}
+
+// cfs_hip_debug_eigs_combine (arguments checked by the caller)
+template <typename V>
+int debug_eigs_combine(void *out_dev, long long ldo, const void *basis_dev, long long ld, long long n, int m, int nout, const double *s,
+                       hipStream_t st) {
+  cfs_rt::DevBuf sdev;
+  int rc;
+  if ((rc = sdev.alloc((size_t)m * nout * sizeof(double)))) return rc;
+  return eigs_combine<V>((V *)out_dev, ldo, (const V *)basis_dev, ld, n, m, s, nout, (double *)sdev.p, st);
+}
 
 // cfs_hip_sym_debug_lanczos
 template <typename V, class Handle>
@@ -549,7 +564,7 @@ int eigs(Handle *h, int k, int which, int ncv, double tol, int max_restarts, con
     pack.resize((size_t)m * lkeep);
     for (int r = 0; r < m; ++r)
       for (int c = 0; c < lkeep; ++c) pack[(size_t)r * lkeep + c] = S[(size_t)r * m + order[c]];
-    if ((rc = L.combine(L.basis, ld, m, pack.data(), lkeep, sdev))) return rc;
+    if ((rc = eigs_combine<V>(L.basis, ld, L.basis, ld, n, m, pack.data(), lkeep, (double *)sdev.p, st))) return rc;
     HIPCHK(hipMemcpyAsync(L.col(lkeep), L.col(m), (size_t)n * sizeof(V), hipMemcpyDeviceToDevice, st));
     for (int c = 0; c < lkeep; ++c) {
       alpha[c] = w[order[c]];
@@ -568,7 +583,7 @@ int eigs(Handle *h, int k, int which, int ncv, double tol, int max_restarts, con
     pack.resize((size_t)m * kk);
     for (int r = 0; r < m; ++r)
       for (int c = 0; c < kk; ++c) pack[(size_t)r * kk + c] = S[(size_t)r * m + order[c]];
-    if ((rc = L.combine(X, ldx, m, pack.data(), kk, sdev))) return rc;
+    if ((rc = eigs_combine<V>(X, ldx, L.basis, ld, n, m, pack.data(), kk, (double *)sdev.p, st))) return rc;
     for (int i = kk; i < k; ++i) HIPCHK(hipMemsetAsync(X + (long long)i * ldx, 0, (size_t)n * sizeof(V), st));
     // the residuals of what is returned, from the stored vectors: kk more products, one look
     for (int i = 0; i < kk; ++i) {

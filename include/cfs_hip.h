@@ -484,6 +484,18 @@ int cfs_hip_sym_debug_lanczos(cfs_hip_sym_t h, const void *v0_dev, int steps, vo
  * symmetric, row-major (the upper triangle is read), 1 <= m <= CFS_HIP_EIGS_MAX_NCV (else CFS_HIP_ERR_ARG);
  * w: the m eigenvalues ascending; s: m x m row-major, eigenvector i in column i.                   */
 int cfs_hip_debug_symeig(int m, const double *a, double *w, double *s);
+/* For developers and tests: the restart's V S alone, with the solver's own launch.  out[:, c] = (V)(sum_{k < m} basis[:, k]
+ * s[k nout + c]) for c < nout, rows [0, n); fp64 accumulation, k ascending, rounded once when stored.  basis_dev: n x m
+ * values of value_bytes 4 / 8, column k at basis_dev + k ld values; out_dev: column c at out_dev + c ldo values; s:
+ * m x nout row-major on the host.  1 <= nout <= m <= CFS_HIP_EIGS_MAX_NCV, n >= 1, ld, ldo >= n; the pointers,
+ * ld value_bytes and ldo value_bytes multiples of 16; device memory of the current device.  out_dev == basis_dev with
+ * ldo == ld is the in-place restart; any other overlap of the two blocks (first byte to row n - 1 of the last column)
+ * is refused.  WRITTEN: rows [0, n) of columns [0, nout) of out and nothing else -- not the rows [n, ldo), not a column
+ * from nout on; in place, columns [nout, m) of the basis are read and left as they were.  The call waits for the
+ * kernel.  CFS_HIP_ERR_ARG, before any device work, in this order: a null pointer ("null"); bad m / nout; value_bytes;
+ * a pointer not 16-byte aligned; a bad n / ld / ldo; an overlap; memory that is not the current device's.           */
+int cfs_hip_debug_eigs_combine(void *out_dev, long long ldo, const void *basis_dev, long long ld, long long n,
+                               int m, int nout, const double *s, int value_bytes, void *stream);
 /* The k SMALLEST (algebraic) eigenpairs of A by LOBPCG (Knyazev's locally optimal block preconditioned CG) with the
  * preconditioners of the PCG solvers: the first vibration or buckling modes of a stiffness matrix, the clustered low
  * end that cfs_hip_sym_eigs finds slowly.  k products per iteration, no factorisation.  Handles accepted are those

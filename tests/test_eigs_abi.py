@@ -1,4 +1,4 @@
-"""cfs_hip_sym_eigs, cfs_hip_sym_debug_lanczos and cfs_hip_debug_symeig without a GPU: the header declares them with the
+"""cfs_hip_sym_eigs, cfs_hip_sym_debug_lanczos, cfs_hip_debug_symeig and cfs_hip_debug_eigs_combine without a GPU: the header declares them with the
 documented signatures, the library exports them, the ctypes bindings' argument types match the declarations, the
 Python mirror is there, the argument checks that need no device answer before anything touches one -- and the small
 dense eigensolver of the restart, which runs on the host, against numpy.linalg.eigh.
@@ -30,6 +30,8 @@ SIGNATURES = {
     "cfs_hip_sym_debug_lanczos": ["cfs_hip_sym_t h", "const void *v0_dev", "int steps", "void *basis_dev", "long long ld",
                                   "double *alpha", "double *beta", "int *done", "void *stream"],
     "cfs_hip_debug_symeig": ["int m", "const double *a", "double *w", "double *s"],
+    "cfs_hip_debug_eigs_combine": ["void *out_dev", "long long ldo", "const void *basis_dev", "long long ld", "long long n", "int m",
+                                   "int nout", "const double *s", "int value_bytes", "void *stream"],
 }
 
 
@@ -100,6 +102,11 @@ def test_null_arguments_are_refused_first():
                  (h, None, 3, h, 16, None, b, C.byref(d)), (h, None, 3, h, 16, a, None, C.byref(d)), (h, None, 3, h, 16, a, b, None)):
         assert lib.cfs_hip_sym_debug_lanczos(*args, None) == _lib.ERR_ARG and b"null" in lib.cfs_hip_last_error()
     assert d.value == 7
+    # cfs_hip_debug_eigs_combine: the null check comes before every other one (m, nout, value_bytes, ld are bad too)
+    s = (C.c_double * 4)()
+    for out, basis, sp in ((None, h, s), (h, None, s), (h, h, None), (None, None, None)):
+        assert lib.cfs_hip_debug_eigs_combine(out, 3, basis, 3, 16, 0, 5, sp, 3, None) == _lib.ERR_ARG
+        assert b"null" in lib.cfs_hip_last_error()
     assert lib.cfs_hip_runtime_bound() == bound  # nothing above initialised the runtime
 
 
@@ -133,6 +140,48 @@ def test_checks_that_need_no_device_answer_before_the_handle_is_looked_at():
         assert b"steps" in lib.cfs_hip_last_error() and d.value == 0
     assert lib.cfs_hip_sym_debug_lanczos(h, None, 3, C.c_void_p(0x4008), 16, a, b, C.byref(d), None) == _lib.ERR_ARG
     assert b"16-byte aligned" in lib.cfs_hip_last_error()
+    assert lib.cfs_hip_runtime_bound() == bound  # nothing above initialised the runtime
+
+
+def test_the_restart_kernel_entry_point_refuses_before_any_device_work():
+    """cfs_hip_debug_eigs_combine with pointers that are never dereferenced, in the documented order: every later argument
+    is bad as well"""
+    lib = cfs.load()
+    bound = lib.cfs_hip_runtime_bound()
+    s = (C.c_double * (128 * 128))()
+    good = dict(out=0x100000, ldo=64, basis=0x100000, ld=64, n=60, m=20, nout=12, vb=8)
+
+    def refused(word, **kw):
+        a = dict(good, **kw)
+        rc = lib.cfs_hip_debug_eigs_combine(C.c_void_p(a["out"]), a["ldo"], C.c_void_p(a["basis"]), a["ld"], a["n"], a["m"], a["nout"],
+                                            s, a["vb"], None)
+        msg = lib.cfs_hip_last_error()
+        assert rc == _lib.ERR_ARG and word in msg, (kw, rc, msg)
+    later = dict(vb=3, out=0x100008, ld=59)
+    for m, nout in ((0, 0), (0, 1), (-1, 1), (129, 1), (129, 129), (20, 0), (20, -1), (20, 21), (128, 129), (1, 2)):
+        refused(b"m / nout", m=m, nout=nout, **later)
+    del later["vb"]
+    for vb in (0, 1, 2, 3, 5, 16, -8):
+        refused(b"value_bytes", vb=vb, **later)
+    del later["out"]
+    for kw in (dict(out=0x200008), dict(basis=0x100004), dict(out=0x200001, basis=0x100001), dict(out=0x100008, basis=0x100008)):
+        refused(b"16-byte aligned", **kw, **later)
+    del later["ld"]
+    for kw in (dict(ld=59), dict(ldo=59), dict(out=0x200000, ldo=59), dict(ld=61), dict(ldo=63), dict(n=0), dict(n=-1), dict(n=65),
+               dict(vb=4, ld=62), dict(vb=4, ldo=66), dict(ld=1 << 60, ldo=1 << 60), dict(ld=0, ldo=0, n=0)):
+        refused(b"bad ld", **kw)
+    # the in-place restart is out == basis AND ldo == ld; every other overlap of [first byte, row n - 1 of the last column]
+    vb, ld, n, m, nout = 8, 64, 60, 20, 12
+    base, span_b, span_o = 0x100000, ((m - 1) * ld + n) * vb, ((nout - 1) * ld + n) * vb
+    for kw in (dict(ldo=66),                                     # the same start, another stride
+               dict(out=base + ld * vb),                         # shifted by a column
+               dict(out=base + 16), dict(out=base - 16),         # shifted by two rows
+               dict(out=base + span_b - 16),                     # out begins on the basis's last two rows
+               dict(out=base - span_o + 16),                     # out ends on the basis's first two rows
+               dict(out=base - 0x80000, ldo=0x8000),             # out's wide columns straddle the whole basis
+               dict(out=base + (m - 1) * ld * vb)):              # out begins at the basis's last column
+        refused(b"overlap", **kw)
+    assert span_b % 16 == 0 and span_o % 16 == 0
     assert lib.cfs_hip_runtime_bound() == bound  # nothing above initialised the runtime
 
 

@@ -1,5 +1,5 @@
 """cfs_hip_sym_eigs, the whole solver: thick-restart Lanczos on the GPU against a reference spectrum -- dense
-numpy.linalg.eigvalsh for n <= 1026, scipy.sparse.linalg.eigsh(A64, k, which, tol=0) above (each of its eigenvalues
+numpy.linalg.eigh for n <= 1026, scipy.sparse.linalg.eigsh(A64, k, which, tol=0) above (in both, each eigenvalue
 re-evaluated as the long-double Rayleigh quotient of its own vector, see _case) -- of the matrix as the library
 holds it (the values rounded to the value type).  fp64 runs with tol 1e-10, fp32 with tol 1e-4; k = 4 and ncv = 20
 unless a case says otherwise; the start vector is default_rng(n).uniform(-1, 1, n).
@@ -20,6 +20,11 @@ that returns an interior eigenvalue; the test first asserts from the reference s
 eigenvalues exceed 4 tol lmax.  The library's own `residuals` must agree with r_i within 4 u lmax + 1e-3 r_i (the
 product it recomputes them from is rounded to the value type), and products = ncv + restarts (ncv - l) + k with
 l = k + (ncv - k) / 2.
+
+Wide bases (test_wide_bases_and_many_pairs): ncv up to CFS_HIP_EIGS_MAX_NCV = 128 and k up to 100 on the plain rand1023 and
+rand257, where l = 84, 53, 96 and 114 columns are kept per restart; on the CPU model the cases take 2 / 2, 10 / 8, 3 / 2 and
+9 / 8 restarts (fp64 / fp32), and the smallest wanted gap over 4 tol lmax is 4.3e6 / 4.3, 4.3e6 / 4.3, 1.16e6 / 1.16 and
+1.11e6 / 1.11 -- narrow in fp32 but above 1, from the reference spectrum alone.
 
 Measured on the MI355X (value type, case: restarts, products, nconv, r = max r_i / (tol lmax), dtheta = max |theta_i -
 lambda_i| / lmax, and how far the library's residuals are from r_i):
@@ -52,6 +57,18 @@ lambda_i| / lmax, and how far the library's residuals are from r_i):
   f32 band600001 LA n=600001 k=2 ncv=8 LA: restarts 2, products 16, nconv 2, r 0.040, dtheta 1.61e-08, residuals off by 3.09e-08 lmax
   f64 band20001 plain (two shards) n=20001 k=4 ncv=20 LA: restarts 19, products 176, nconv 4, r 0.431, dtheta 1.91e-16, residuals off by 5.23e-18 lmax
   f32 band20001 plain (two shards) n=20001 k=4 ncv=20 LA: restarts 11, products 112, nconv 4, r 0.178, dtheta 5.43e-09, residuals off by 3.10e-08 lmax
+  f64 rand1023 plain n=1023 k=40 ncv=128 LA: restarts 2, products 256, nconv 40, r 0.000, dtheta 5.89e-16, residuals off by 3.28e-17 lmax
+  f32 rand1023 plain n=1023 k=40 ncv=128 LA: restarts 2, products 256, nconv 40, r 0.001, dtheta 2.35e-08, residuals off by 4.41e-08 lmax
+  f64 rand1023 plain n=1023 k=40 ncv=67 LA: restarts 10, products 247, nconv 40, r 0.224, dtheta 5.89e-16, residuals off by 7.13e-17 lmax
+  f32 rand1023 plain n=1023 k=40 ncv=67 LA: restarts 8, products 219, nconv 40, r 0.222, dtheta 2.36e-08, residuals off by 4.19e-08 lmax
+  f64 rand257 plain n=257 k=64 ncv=128 LA: restarts 3, products 288, nconv 64, r 0.000, dtheta 4.73e-16, residuals off by 6.02e-17 lmax
+  f32 rand257 plain n=257 k=64 ncv=128 LA: restarts 2, products 256, nconv 64, r 0.364, dtheta 1.41e-08, residuals off by 4.11e-08 lmax
+  f64 rand257 plain n=257 k=100 ncv=128 LA: restarts 9, products 354, nconv 100, r 0.003, dtheta 7.43e-16, residuals off by 6.02e-17 lmax
+  f32 rand257 plain n=257 k=100 ncv=128 LA: restarts 8, products 340, nconv 100, r 0.001, dtheta 1.41e-08, residuals off by 4.11e-08 lmax
+
+(against numpy.linalg.eigvalsh's own values, the reference before the wide cases, the fp64 dtheta of these four were 6.59e-15,
+6.95e-15, 2.70e-15 and 2.70e-15 -- above the 16 u = 1.78e-15 of the check, with the SAME theta bits from runs of different
+ncv: the error was eigvalsh's, see _case)
 
 and, from the other tests:
 
@@ -120,9 +137,19 @@ def _case(name, kind, dtype, k=4, which=None):
     va = np.asarray(va).astype(dtype)
     A64 = sp.csr_matrix((va.astype(np.float64), ci, rp), shape=(n, n))
     if n <= 1026:
-        lam = np.linalg.eigvalsh(A64.toarray())
+        # eigvalsh's own eigenvalues are off by up to 57 u lmax inside the spectrum of rand1023 (24 u lmax on rand257) and
+        # differ between machines, more than the 16 u lmax of the check; the top four, all that was compared before the
+        # wide cases, are not.  As below: each is replaced by the Rayleigh quotient of eigh's vector in long double
+        # (eigh's residuals are below 1e-13: within r^2 / gap of the eigenvalue, far below u lmax)
+        from oracle import oracle
+        lam, Q = np.linalg.eigh(A64.toarray())
         lmax = float(np.max(np.abs(lam)))
-        lam = _sorted(lam, which)[:k]
+        pick = {"SA": np.argsort(lam, kind="stable"), "LA": np.argsort(lam, kind="stable")[::-1],
+                "LM": np.argsort(-np.abs(lam), kind="stable")}[which][:k]
+        lam = lam[pick]
+        for i, j in enumerate(pick):
+            x = Q[:, j].astype(np.longdouble)
+            lam[i] = float(np.dot(x, oracle.csr_spmv_ldx(n, rp, ci, va, x)) / np.dot(x, x))
     else:
         # eigsh's own eigenvalues are off by up to 2.4e-14 (13 ulp) on band20001 and differ between machines, more than
         # the 16 u lmax of the check: each is replaced by the Rayleigh quotient of eigsh's vector in long double, which
@@ -198,6 +225,79 @@ def test_extreme_pairs(name, kind, dtype):
     A = cfs.SymMatrix(*case[:4])
     _check(f"{name} {kind}", case, dtype, A, which="LA" if kind == "plain" else kind, plain=kind == "plain")
     A.close()
+
+
+# (name, k, ncv): l = k + (ncv - k) / 2 kept columns = 84; 53 (m = 67 odd); 96; 114 (residual slots up to 199)
+WIDE = [("rand1023", 40, 128), ("rand1023", 40, 67), ("rand257", 64, 128), ("rand257", 100, 128)]
+
+
+@DTYPES
+@pytest.mark.parametrize("name,k,ncv", WIDE)
+def test_wide_bases_and_many_pairs(name, k, ncv, dtype):
+    """the restart at deep bases: V S with more than 64 / 32 kept columns (the second chunk of eigs_combine_kernel's column
+    loop), the arrow of the projected matrix in row l up to 114, k up to 100 returned columns and closing residuals.  Every
+    case restarts at least once (`plain`); the checks are _check's own"""
+    import cfs_spmv_amd as cfs
+    case = _case(name, "plain", dtype, k=k)
+    A = cfs.SymMatrix(*case[:4])
+    _check(f"{name} plain", case, dtype, A, k=k, ncv=ncv, plain=True)
+    A.close()
+
+
+def _pair_invariants(n, rp, ci, va, w, X, lmax):
+    """(max |X^T X - I|, max_i |theta_i - x_i^T A x_i / x_i^T x_i| / lmax) in long double from the returned pairs"""
+    from oracle import oracle
+    Xl = X.astype(np.longdouble)
+    orth = float(np.max(np.abs(Xl.T @ Xl - np.eye(X.shape[1], dtype=np.longdouble))))
+    rq = 0.0
+    for i in range(X.shape[1]):
+        x = Xl[:, i]
+        rq = max(rq, abs(float(np.longdouble(w[i]) - np.dot(x, oracle.csr_spmv_ldx(n, rp, ci, va, x)) / np.dot(x, x))))
+    return orth, rq / lmax
+
+
+@DTYPES
+def test_the_end_of_the_range(dtype):
+    """rand257, k = 127 = CFS_HIP_EIGS_MAX_NCV - 1, ncv = 128, tol = 0, max_restarts = 2: l = 127, every restart keeps 127 of
+    128 columns and adds one product.  No convergence is claimed (127 of 257 eigenvalues do not converge in two restarts,
+    and nothing is compared with the spectrum): return code 0, the counters, finite outputs in descending order, the
+    library's residuals against the long-double recomputation for all 127 pairs (the closing residual slots up to 253),
+    and two invariants of the returned pairs in long double,
+
+        o = max |X^T X - I|        q = max_i |theta_i - x_i^T A x_i / x_i^T x_i| / lmax
+
+    each allowed 4 x the same quantity of solver.eigs, the host-driven model, run here on the same handle with the same
+    arguments, + 16 u.  Measured on the MI355X (native / model):
+
+      f64: nconv 0, o = 5.100e-15 / 3.288e-15, q = 4.626e-16 / 6.113e-16, residuals off by 6.02e-17 lmax
+      f32: nconv 0, o = 8.649e-08 / 8.649e-08, q = 1.406e-08 / 1.406e-08, residuals off by 4.11e-08 lmax
+    """
+    import torch
+    import cfs_spmv_amd as cfs
+    from cfs_spmv_amd import solver
+    k, ncv = 127, 128
+    n, rp, ci, va, v0, lam, lmax = _case("rand257", "plain", dtype, k=k)
+    u = UNIT[dtype]
+    A = cfs.SymMatrix(n, rp, ci, va)
+    w, X, info = _solve(A, v0, k=k, which="LA", ncv=ncv, tol=0.0, max_restarts=2)  # (a return code other than 0 raises)
+    wm, Xm, im = solver.eigs(A, k, which="LA", ncv=ncv, tol=0.0, max_restarts=2, v0=torch.from_numpy(np.array(v0)).cuda())
+    torch.cuda.synchronize()
+    Xm = np.ascontiguousarray(Xm.cpu().numpy())
+    A.close()
+    assert info["restarts"] == 2 and info["products"] == 128 + 2 + 127
+    assert im["restarts"] == 2 and im["products"] == info["products"], "the model ran the same iteration"
+    assert w.shape == (k,) and X.shape == (n, k)
+    assert np.all(np.isfinite(w)) and np.all(np.isfinite(X)) and np.all(np.isfinite(info["residuals"]))
+    assert np.all(np.diff(w) <= 0), "descending"
+    r = _residuals(n, rp, ci, va, w, X)
+    off = np.abs(info["residuals"] - r)
+    assert np.all(off <= 4 * u * lmax + 1e-3 * r), f"residuals off by up to {np.max(off) / lmax:.2e} lmax, at pair {int(np.argmax(off))}"
+    o, q = _pair_invariants(n, rp, ci, va, w, X, lmax)
+    om, qm = _pair_invariants(n, rp, ci, va, wm, Xm, lmax)
+    print(f"eigs {np.dtype(dtype).name} rand257 k=127 ncv=128 two restarts: nconv {info['nconv']} (model {im['nconv']}), "
+          f"|X^T X - I| {o:.3e} / {om:.3e}, |theta - rq| / lmax {q:.3e} / {qm:.3e}, residuals off by {np.max(off) / lmax:.2e} lmax")
+    assert o <= 4 * om + 16 * u, f"|X^T X - I| = {o:.3e}, allowed 4 x {om:.3e} + 16 u"
+    assert q <= 4 * qm + 16 * u, f"|theta - rq| / lmax = {q:.3e}, allowed 4 x {qm:.3e} + 16 u"
 
 
 @DTYPES

@@ -23,6 +23,12 @@ Two invariants are checked instead, computed here in long double from the return
 
 The GPU is allowed 4 x the working-precision model's value + 16 u.
 
+Deep bases: cfs_hip_sym_debug_lanczos admits 128 steps (CFS_HIP_EIGS_MAX_NCV), and the cases above stop at 20.  rand257,
+rand1023 and band20001 are run for 128 steps as well -- the project kernel walks 16 chunks of 8 accumulators, the reduce
+kernel launches 129 workgroups, the subtract kernel's coefficient array is full and the last flag word sits next to the
+first coefficient word -- with the same rule and omega_j, rho_j at j in {20, 40, 64, 65, 100, 127, 128} in addition.  None
+of the three breaks down in 128 steps in either precision on the CPU (the smallest beta is 1.06 to 2.1).
+
 Measured on the MI355X (value type, matrix: the largest over the compared quantities of d / the GPU's deviation; then
 the largest over j of the model's omega / the GPU's omega and of the model's rho / the GPU's rho):
 
@@ -56,6 +62,12 @@ the largest over j of the model's omega / the GPU's omega and of the model's rho
   f32 band20001 (two shards) n=20001 steps=20: d=3.4e-07/gpu=1.6e-07  omega 8.8e-09/7.5e-09  rho 1.5e-08/8.1e-09
   f64 Flan_1565@0.01 (deterministic) n=15647 steps=20: d=1.9e-15/gpu=7.6e-16  omega 2.9e-16/2.3e-16  rho 1.5e-17/6.6e-18
   f32 Flan_1565@0.01 (deterministic) n=15647 steps=20: d=1.0e-06/gpu=3.9e-07  omega 5.3e-09/4.5e-09  rho 1.2e-08/4.3e-09
+  f64 rand257 (deep) n=257 steps=128: d=3.2e-16/gpu=2.9e-16  omega 3.4e-16/2.8e-16  rho 6.2e-17/7.1e-17
+  f32 rand257 (deep) n=257 steps=128: d=2.8e-07/gpu=1.5e-07  omega 3.1e-08/1.7e-08  rho 3.2e-08/1.4e-08
+  f64 rand1023 (deep) n=1023 steps=128: d=4.0e-16/gpu=3.3e-16  omega 6.8e-16/3.5e-16  rho 6.8e-17/5.7e-17
+  f32 rand1023 (deep) n=1023 steps=128: d=2.1e-07/gpu=1.8e-07  omega 3.4e-08/2.1e-08  rho 4.2e-08/2.6e-08
+  f64 band20001 (deep) n=20001 steps=128: d=6.1e-16/gpu=7.6e-16  omega 3.4e-16/2.7e-16  rho 5.0e-17/4.1e-17
+  f32 band20001 (deep) n=20001 steps=128: d=3.4e-07/gpu=1.6e-07  omega 9.0e-09/9.5e-09  rho 1.5e-08/9.5e-09
 """
 import ctypes as C
 import functools
@@ -69,6 +81,9 @@ from test_gpu_kernel_variants import PLAN_KNOBS
 pytestmark = pytest.mark.gpu
 
 JS = (1, 2, 3, 5, 10, 20)
+DEEP = 128  # = CFS_HIP_EIGS_MAX_NCV: the project kernel's 16 chunks, 129 reduce workgroups, cs[] full, the last flag word
+DEEP_JS = JS + (40, 64, 65, 100, 127, 128)
+DEEP_MATRICES = ["rand257", "rand1023", "band20001"]
 STEP_MATRICES = [f"rand{n}" for n in (2, 3, 5, 63, 64, 65, 255, 257, 1023, 1026)] + ["band20001", "band600001", "pwtk@0.05"]
 
 
@@ -118,7 +133,7 @@ def lanczos_reference(n, rp, ci, va, v0, steps, dtype=None, unit=None):
     alpha, beta, done = np.zeros(steps, S), np.zeros(steps, S), steps
     for j in range(steps):
         q = mv(V[j])
-        Vj = V[:j + 1].astype(S)
+        Vj = V[:j + 1].astype(S, copy=False)
         c = Vj @ q.astype(S)
         qq = np.dot(q.astype(S), q.astype(S))
         q1 = project_out(q, c, Vj)
@@ -157,13 +172,13 @@ def _norm_inf(n, rp, va):
     return float(np.max(np.bincount(rows, np.abs(va.astype(np.float64)), n)))
 
 
-def invariants(n, rp, ci, va, V, alpha, beta, done):
-    """{j: (omega_j, rho_j)} in long double for the j of JS not above `done`"""
+def invariants(n, rp, ci, va, V, alpha, beta, done, at=JS):
+    """{j: (omega_j, rho_j)} in long double for the j of `at` not above `done`"""
     from oracle import oracle
     norm = np.longdouble(_norm_inf(n, rp, va))
     Vl = V[:done + 1, :n].astype(np.longdouble)
     a, b = alpha.astype(np.longdouble), beta.astype(np.longdouble)
-    js = [j for j in JS if j <= done]
+    js = [j for j in at if j <= done]
     G = np.abs(Vl @ Vl.T - np.eye(done + 1, dtype=np.longdouble))
     out, rho = {}, 0.0
     for i in range(1, max(js, default=0) + 1):  # column i (1-based) of A V = V T
@@ -177,23 +192,25 @@ def invariants(n, rp, ci, va, V, alpha, beta, done):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(name, dtype):
-    """the matrix in the value type, v0, and the two CPU runs with their invariants: computed once, shared, unchanged"""
+def _case(name, dtype, steps=None):
+    """the matrix in the value type, v0, and the two CPU runs with their invariants: computed once, shared, unchanged.
+    steps None: _steps(name, n), the invariants at JS; DEEP: at DEEP_JS"""
     n, rp, ci, va = _matrix(name)
     va = va.astype(dtype)
     v0 = _v0(n, dtype)
-    steps = _steps(name, n)
+    at = JS if steps is None else DEEP_JS
+    steps = _steps(name, n) if steps is None else steps
     ref = lanczos_reference(n, rp, ci, va, v0, steps, unit=UNIT[dtype])
     work = lanczos_reference(n, rp, ci, va, v0, steps, dtype, unit=UNIT[dtype])
     assert ref[3] == work[3] == steps, f"{name}: a breakdown on the CPU: badly chosen case"
-    inv = invariants(n, rp, ci, va, work[0], work[1], work[2], steps)
+    inv = invariants(n, rp, ci, va, work[0], work[1], work[2], steps, at)
     for x in (rp, ci, va, v0) + ref[:3] + work[:3]:
         x.setflags(write=False)
     return n, rp, ci, va, v0, steps, ref, work, inv
 
 
-def _check(name, dtype, A, label=""):
-    n, rp, ci, va, v0, steps, ref, work, inv = _case(name, dtype)
+def _check(name, dtype, A, label="", deep=None):
+    n, rp, ci, va, v0, steps, ref, work, inv = _case(name, dtype, deep)
     u, norm = UNIT[dtype], _norm_inf(n, rp, va)
     V, alpha, beta, done = lanczos_gpu(A, v0, steps, dtype)
     errors = []
@@ -213,7 +230,7 @@ def _check(name, dtype, A, label=""):
     worst = max(worst, (dev, d))
     if not dev <= 4 * d + 16 * u:
         errors.append(f"v_2: deviation {dev:.3e}, allowed {4 * d + 16 * u:.3e} (d = {d:.3e})")
-    got = invariants(n, rp, ci, va, V, alpha, beta, min(done, steps))
+    got = invariants(n, rp, ci, va, V, alpha, beta, min(done, steps), tuple(inv))
     wo = max(((got[j][0], inv[j][0]) for j in got), default=(0.0, 0.0))
     wr = max(((got[j][1], inv[j][1]) for j in got), default=(0.0, 0.0))
     print(f"lanczos-steps {np.dtype(dtype).name} {name}{label} n={n} steps={steps}: d={worst[1]:.1e}/gpu={worst[0]:.1e}  "
@@ -234,6 +251,18 @@ def test_steps_against_the_long_double_recurrence(name, dtype):
     A = cfs.SymMatrix(n, rp, ci, va)
     assert A.stats()["n"] == n and A.row_end - A.row_begin == n
     _check(name, dtype, A)
+    A.close()
+
+
+@DTYPES
+@pytest.mark.parametrize("name", DEEP_MATRICES)
+def test_deep_bases_against_the_long_double_recurrence(name, dtype):
+    """DEEP = 128 steps, a basis of 129 columns: alpha, beta and v_2 for j <= 3 as above, omega_j and rho_j at DEEP_JS"""
+    import cfs_spmv_amd as cfs
+    n, rp, ci, va, v0, steps, ref, work, inv = _case(name, dtype, DEEP)
+    assert steps == DEEP and sorted(inv) == sorted(DEEP_JS)
+    A = cfs.SymMatrix(n, rp, ci, va)
+    _check(name, dtype, A, label=" (deep)", deep=DEEP)
     A.close()
 
 
@@ -286,6 +315,31 @@ def test_padding_and_a_spare_column_stay_intact(dtype):
     # (the same steps as with the tight layout; the product of a plain handle adds in an order of its own in every
     # run, so alpha_1 -- a sum of n terms of size ||A|| / n -- agrees to rounding, not bitwise)
     assert abs(alpha[0] - at[0]) <= 16 * UNIT[dtype] * _norm_inf(n, rp, va)
+
+
+@DTYPES
+def test_padding_and_a_spare_column_stay_intact_at_a_deep_basis(dtype):
+    """the same at DEEP = 128 steps -- 129 columns with ld = n + 5 and a spare one behind them -- on a deterministic handle,
+    whose products add in a fixed order: the basis, alpha and beta are the same BITS as with the tight layout"""
+    import cfs_spmv_amd as cfs
+    name = "rand1023"
+    n, rp, ci, va, v0 = _case(name, dtype, DEEP)[:5]
+    ld = n + 5
+    assert ld * np.dtype(dtype).itemsize % 16 == 0
+    pattern = np.array([0x7ff8dead0000beef], np.uint64).view(np.float64)[0] if dtype == np.float64 else \
+        np.array([0x7fc0beef], np.uint32).view(np.float32)[0]
+    D = cfs.SymMatrix(n, rp, ci, va, options=cfs.make_options(flags=DET))
+    assert D.kernel_variant()["det"] == 1
+    V, alpha, beta, done = lanczos_gpu(D, v0, DEEP, dtype, ld=ld, spare=1, fill=pattern)
+    Vt, at, bt, dt = lanczos_gpu(D, v0, DEEP, dtype)
+    D.close()
+    assert done == dt == DEEP
+    bits = np.uint64 if dtype == np.float64 else np.uint32
+    assert np.all(V[:, n:].view(bits) == np.array([pattern]).view(bits)[0])
+    assert np.all(V[DEEP + 1].view(bits) == np.array([pattern]).view(bits)[0])
+    assert not np.isnan(V[:DEEP + 1, :n]).any()
+    assert np.array_equal(np.ascontiguousarray(V[:DEEP + 1, :n]).view(bits), np.ascontiguousarray(Vt[:, :n]).view(bits))
+    assert np.array_equal(alpha.view(np.uint64), at.view(np.uint64)) and np.array_equal(beta.view(np.uint64), bt.view(np.uint64))
 
 
 def default_v0(n):
