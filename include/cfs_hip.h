@@ -252,7 +252,17 @@ int cfs_hip_sym_destroy(cfs_hip_sym_t h);
  * pointer.  A device kernel pours it into the existing schedule (the value half of
  * tune()'s packing, on the GPU); tiles, slots, fold index stay.  The handle must have
  * been created with CFS_HIP_FLAG_KEEP_VALUE_MAP; returns after the new values are in
- * place.  Not for CFS_HIP_FLAG_DETERMINISTIC handles (their scale depends on the values). */
+ * place.  Not for CFS_HIP_FLAG_DETERMINISTIC handles (their scale depends on the values).
+ * Ordering: the pour runs on the library's own stream of the handle's device (on the home device
+ * the one cfs_hip_default_stream returns), a BLOCKING stream -- it orders behind work on the null
+ * stream -- and the call waits for it (a multi-device handle: then for every shard's pour), so an
+ * SpMV enqueued afterwards on any stream multiplies with the new values.  What the library cannot
+ * see is the caller's to order BEFORE the call: SpMVs of this handle still in flight on a
+ * non-blocking stream of the caller's, and a device `values` array still being produced on such a
+ * stream.  A matrix without stored entries (nnz = 0) has nothing to pour: the call with nnz = 0 and
+ * a non-null `values` succeeds and changes nothing.  A refused call (CFS_HIP_ERR_ARG: a null
+ * argument, the other value type's entry, another nnz, a handle without the map;
+ * CFS_HIP_ERR_UNSUPPORTED: a deterministic handle) leaves the handle as it was.                    */
 int cfs_hip_sym_update_values_f64(cfs_hip_sym_t h, const double *values, long long nnz);
 int cfs_hip_sym_update_values_f32(cfs_hip_sym_t h, const float *values, long long nnz);
 

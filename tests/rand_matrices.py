@@ -595,3 +595,61 @@ def sym_row_features(n, rowptr, colind, special, expect):
                 tags.add("late")
         out[j] = tags
     return out
+
+
+# ---- exact inputs for the update_values tests: integer values that depend on the POSITION in the caller's
+# ---- array (not on the pair (min, max)), NaN wherever the library has no business reading
+EXACT_RANGE = 1021  # |a_ij| in 1 .. 1021; with |x_j| <= 8 a row of up to 2 048 entries stays below 2^24
+
+
+def exact_values(n, rowptr, colind, seed, dtype=np.float64):
+    """a full-CSR value array: position j with colind[j] <= row holds the integer +-(1 + h % 1021), h = (j + 7919
+    seed) * 2654435761 mod 2^32, the sign from bit 16 of h -- a function of j alone, so the upper image of an entry
+    would not hold the same number even if it were finite; every position with colind[j] > row holds NaN"""
+    rowptr = np.asarray(rowptr, np.int64)
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    j = np.arange(int(rowptr[-1]), dtype=np.uint64)
+    h = ((j + np.uint64(7919 * seed)) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)
+    v = (1 + (h % np.uint64(EXACT_RANGE)).astype(np.int64)) * np.where((h >> np.uint64(16)) & np.uint64(1), -1, 1)
+    out = v.astype(dtype)
+    out[np.asarray(colind, np.int64) > row] = np.nan
+    return out
+
+
+def exact_x(n, seed, dtype=np.float64):
+    """integers in [-8, 8]"""
+    return np.random.default_rng(seed).integers(-8, 9, n).astype(dtype)
+
+
+def exact_matrix(n, rowptr, colind, values):
+    """the int64 matrix the symmetric path has to see: the stored diagonal and strict lower triangle of `values`,
+    the strict lower entries mirrored -- nothing of the upper positions of the caller's array"""
+    rowptr = np.asarray(rowptr, np.int64)
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    col = np.asarray(colind, np.int64)
+    low = col <= row
+    v = np.asarray(values)[low]
+    assert np.all(np.isfinite(v)) and np.array_equal(v, np.rint(v))
+    L = sp.coo_matrix((v.astype(np.int64), (row[low], col[low])), shape=(n, n)).tocsr()
+    return (L + sp.tril(L, k=-1).T).tocsr()
+
+
+def exact_product(n, rowptr, colind, values, x):
+    """y_ref = A_int x_int in int64 (exact_matrix), after asserting from the reference alone that max_i sum_j
+    |a_ij| |x_j| < 2^24: every partial sum of every row is then exact in fp32 and fp64 in any order"""
+    A = exact_matrix(n, rowptr, colind, values)
+    xi = np.asarray(x).astype(np.int64)
+    assert np.array_equal(xi, np.asarray(x))
+    bound = int((abs(A) @ np.abs(xi)).max()) if n and A.nnz else 0
+    assert bound < 2 ** 24, bound
+    return np.asarray(A @ xi, np.int64).reshape(-1)
+
+
+def without_diagonal(n, rowptr, colind, drop):
+    """the pattern (rowptr, colind) without the diagonal entry of the rows where drop[i]"""
+    rowptr = np.asarray(rowptr, np.int64)
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    col = np.asarray(colind, np.int64)
+    keep = ~((row == col) & np.asarray(drop, bool)[row])
+    rp = np.concatenate([[0], np.cumsum(np.bincount(row[keep], minlength=n))]).astype(np.int32)
+    return rp, col[keep].astype(np.int32)
