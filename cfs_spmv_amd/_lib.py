@@ -74,7 +74,7 @@ SYMBOLS = [
     "cfs_hip_sym_create_multi_f64", "cfs_hip_sym_create_multi_f32", "cfs_hip_comm_create", "cfs_hip_comm_info", "cfs_hip_comm_destroy", "cfs_hip_comm_reduce_scatter",
     "cfs_hip_comm_allgather", "cfs_hip_comm_alltoallv", "cfs_hip_comm_wait_consumed", "cfs_hip_sym_num_gpus", "cfs_hip_sym_multi_set_xmode", "cfs_hip_sym_multi_set_exchange", "cfs_hip_sym_multi_exchange_info", "cfs_hip_sym_multi_devices", "cfs_hip_sym_balanced_splits", "cfs_hip_sym_destroy", "cfs_hip_sym_update_values_f64", "cfs_hip_sym_update_values_f32", "cfs_hip_sym_spmv",
     "cfs_hip_sym_spmv_async", "cfs_hip_sym_cg", "cfs_hip_sym_pcg", "cfs_hip_sym_diagonal_async", "cfs_hip_sym_block_diagonal_async",
-    "cfs_hip_sym_pcg_block", "cfs_hip_sym_block_inverse_async", "cfs_hip_sym_pcg_mixed", "cfs_hip_sym_minres", "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
+    "cfs_hip_sym_pcg_block", "cfs_hip_sym_block_inverse_async", "cfs_hip_sym_pcg_mixed", "cfs_hip_sym_minres", "cfs_hip_sym_pcg_cheb", "cfs_hip_sym_cheb_apply", "cfs_hip_sym_precond_lmax", "cfs_hip_debug_cheb_coeffs", "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
     "cfs_hip_sym_shard_set_recv", "cfs_hip_sym_spmv_local_async",
     "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_fold_lists", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
     "cfs_hip_sym_plan_check_f32", "cfs_hip_sym_plan_send_info_f64",
@@ -194,6 +194,13 @@ def load():
     if hasattr(lib, "cfs_hip_sym_minres"):  # (absent from older builds loaded through CFS_HIP_LIB)
         lib.cfs_hip_sym_minres.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, ip,
                                            C.POINTER(C.c_double), vp]
+    if hasattr(lib, "cfs_hip_sym_pcg_cheb"):  # (absent from older builds loaded through CFS_HIP_LIB)
+        dp = C.POINTER(C.c_double)
+        lib.cfs_hip_sym_pcg_cheb.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                             ip, dp, dp, vp]
+        lib.cfs_hip_sym_cheb_apply.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]
+        lib.cfs_hip_sym_precond_lmax.argtypes = [vp, C.c_int, C.c_int, vp, dp, vp]
+        lib.cfs_hip_debug_cheb_coeffs.argtypes = [C.c_int, C.c_double, C.c_double, dp, dp, dp]
     if hasattr(lib, "cfs_hip_sym_eigs"):  # (absent from older builds loaded through CFS_HIP_LIB)
         dp = C.POINTER(C.c_double)
         lib.cfs_hip_sym_eigs.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, dp, vp, C.c_longlong, dp,

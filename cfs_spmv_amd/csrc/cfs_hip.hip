@@ -1485,6 +1485,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
 #include "cfs_solver_minres.hpp" // MINRES for symmetric indefinite and shifted systems, the same launch layout
 #include "cfs_solver_eigs.hpp" // thick-restart Lanczos for extreme eigenpairs: tall-skinny algebra against a resident basis
 #include "cfs_solver_lobpcg.hpp" // LOBPCG for the smallest eigenpairs with the PCG preconditioners: a small SYRK per iteration
+#include "cfs_solver_cheb.hpp" // a Chebyshev polynomial in M^-1 A as the PCG preconditioner, and the power method for its bound
 #include "cfs_multi.hpp"   // one host thread, N devices: MultiSym, its create and cfs_hip_sym_multi_*
 
 
@@ -2134,6 +2135,100 @@ int cfs_hip_sym_minres(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int prec
       return cfs_solver::minres<V, true>(h, u_dev, b_dev, shift, tol, maxiter, check_every, iterations, relres, st);
     return cfs_solver::minres<V, false>(h, u_dev, b_dev, shift, tol, maxiter, check_every, iterations, relres, st);
   });
+}
+
+// f(V(), std::integral_constant<int, BS>()) for the handle's value type and a base of 0 (none), 1 (Jacobi), 2, 3, 4 or 6
+template <class F> static int with_cheb_base(int value_bytes, int bs, F &&f) {
+  if (bs >= 2) return with_block(value_bytes, bs, f);
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    if (bs == 1) return f(v, std::integral_constant<int, 1>());
+    return f(v, std::integral_constant<int, 0>());
+  });
+}
+// the handles a Chebyshev entry point accepts: those of cfs_hip_sym_pcg (base 0, 1) or of cfs_hip_sym_pcg_block
+static int check_cheb_handle(cfs_hip_sym_t h, int block_rows, const char *who) {
+  if (!h->send_rows().empty() || h->rows() != h->n())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, std::string(who) + ": a handle of the whole matrix, not a shard");
+  int ngpus = 1;
+  if (block_rows >= 2 && cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, std::string(who) + ": block Jacobi needs the whole matrix on one device (blocks straddle "
+                                                               "the row splits of a multi-device handle)");
+  return 0;
+}
+// degree and the bounds of the Chebyshev entry points; need_both: both bounds must be given (> 0)
+static int check_cheb_args(const char *who, int block_rows, int degree, double lmin, double lmax, bool need_both) {
+  if (block_rows != 0 && !block_rows_ok(block_rows))
+    return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": block_rows " + std::to_string(block_rows) + " is not one of 0, 1, 2, 3, 4, 6");
+  if (degree < 1 || degree > cfs_solver::kChebMaxDegree)
+    return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": the degree must lie in [1, " + std::to_string(cfs_solver::kChebMaxDegree) +
+                                        "], got " + std::to_string(degree));
+  if (!std::isfinite(lmin) || !std::isfinite(lmax)) return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": the bounds must be finite");
+  if (need_both && !(lmin > 0.0 && lmax > 0.0)) return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": both bounds must be given (> 0)");
+  if (lmin > 0.0 && lmax > 0.0 && !(lmin < lmax))
+    return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": lmin " + std::to_string(lmin) + " is not below lmax " + std::to_string(lmax));
+  return 0;
+}
+
+int cfs_hip_sym_pcg_cheb(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int block_rows, int degree, double lmin, double lmax,
+                         double tol, int maxiter, int check_every, int *iterations, double *relres, double *bounds_used,
+                         void *stream) {
+  if (!h || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (iterations) *iterations = 0;
+  if (relres) *relres = 0.0;
+  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg_cheb: u and b must be different vectors");
+  if ((((uintptr_t)u_dev) | ((uintptr_t)b_dev)) & 15) return set_err(CFS_HIP_ERR_ARG, "pcg_cheb: u and b must be 16-byte aligned");
+  if (maxiter < 0 || !(tol >= 0.0)) return set_err(CFS_HIP_ERR_ARG, "pcg_cheb: bad tolerance / iteration limit");
+  int rc = check_cheb_args("pcg_cheb", block_rows, degree, lmin, lmax, false);
+  if (rc || (rc = check_cheb_handle(h, block_rows, "pcg_cheb")) || (rc = check_placement(h, u_dev, b_dev))) return rc;
+  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  DeviceGuard g(h->device);
+  return with_cheb_base(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::cg_cheb<decltype(v), decltype(bs)::value>(h, u_dev, b_dev, degree, lmin, lmax, tol, maxiter, check_every,
+                                                                 iterations, relres, bounds_used, (hipStream_t)stream);
+  });
+}
+
+int cfs_hip_sym_cheb_apply(cfs_hip_sym_t h, int block_rows, int degree, double lmin, double lmax, void *z_dev, const void *r_dev,
+                           void *stream) {
+  if (!h || !z_dev || !r_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (z_dev == r_dev) return set_err(CFS_HIP_ERR_ARG, "cheb_apply: z and r must be different vectors");
+  if ((((uintptr_t)z_dev) | ((uintptr_t)r_dev)) & 15) return set_err(CFS_HIP_ERR_ARG, "cheb_apply: z and r must be 16-byte aligned");
+  int rc = check_cheb_args("cheb_apply", block_rows, degree, lmin, lmax, true);
+  if (rc || (rc = check_cheb_handle(h, block_rows, "cheb_apply")) || (rc = check_placement(h, z_dev, r_dev))) return rc;
+  h->ok_x = h->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  return with_cheb_base(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::cheb_apply<decltype(v), decltype(bs)::value>(h, degree, lmin, lmax, z_dev, r_dev, (hipStream_t)stream);
+  });
+}
+
+int cfs_hip_sym_precond_lmax(cfs_hip_sym_t h, int block_rows, int steps, const void *v0_dev, double *estimate, void *stream) {
+  if (!h || !estimate) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  *estimate = 0.0;
+  if (block_rows != 0 && !block_rows_ok(block_rows))
+    return set_err(CFS_HIP_ERR_ARG, "precond_lmax: block_rows " + std::to_string(block_rows) + " is not one of 0, 1, 2, 3, 4, 6");
+  int rc = check_cheb_handle(h, block_rows, "precond_lmax");
+  if (rc) return rc;
+  if (v0_dev) {
+    const cfs_rt::PtrInfo pi = cfs_rt::classify(v0_dev);
+    if (!pi.device) return set_err(CFS_HIP_ERR_ARG, "precond_lmax: v0 must be a device pointer");
+    if (pi.dev != h->device)
+      return set_err(CFS_HIP_ERR_ARG, "precond_lmax: v0 lives on device " + std::to_string(pi.dev) + ", the matrix on device " +
+                                          std::to_string(h->device));
+  }
+  h->ok_x = h->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  return with_cheb_base(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::cheb_lmax<decltype(v), decltype(bs)::value>(h, steps, v0_dev, estimate, (hipStream_t)stream);
+  });
+}
+
+int cfs_hip_debug_cheb_coeffs(int degree, double lmin, double lmax, double *theta, double *c1, double *c2) {
+  if (!theta || (degree > 1 && (!c1 || !c2))) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  int rc = check_cheb_args("cheb_coeffs", 0, degree, lmin, lmax, true);
+  if (rc) return rc;
+  cfs_solver::cheb_coeffs(degree, lmin, lmax, theta, c1, c2);
+  return 0;
 }
 
 // a vector argument of the eigensolver entry points: device memory on the handle's device

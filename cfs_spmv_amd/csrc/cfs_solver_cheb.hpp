@@ -1,0 +1,599 @@
+// cfs_solver_cheb.hpp -- a Chebyshev polynomial in M^-1 A as the preconditioner of the native PCG
+// (cfs_hip_sym_pcg_cheb), the polynomial alone (cfs_hip_sym_cheb_apply) and the power method that bounds
+// its interval (cfs_hip_sym_precond_lmax).  M is what the library already builds: nothing (BS = 0), the
+// diagonal (BS = 1, cg_dinv_kernel) or the node blocks (BS = 2, 3, 4, 6: cg_binv_kernel, block_apply).
+//
+// With theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma1 = theta / delta, rho_0 = 1 / sigma1,
+// z = P_m r is the Chebyshev iteration for A z = r from z = 0 in the residual-free form,
+//     z_1 = d_1 = (1 / theta) M^-1 r
+//     j = 1 .. m - 1:  t = A z_j;  rho_j = 1 / (2 sigma1 - rho_{j-1})
+//                      d_{j+1} = rho_j rho_{j-1} d_j + (2 rho_j / delta) M^-1 (r - t);  z_{j+1} = z_j + d_{j+1}
+// m - 1 products for degree m, no vector for the inner residual.  For fixed bounds P_m is a fixed linear
+// operator, a polynomial in M^-1 A times M^-1, hence symmetric, and plain PCG is valid with it.  Its residual
+// polynomial is 1 - lambda p(lambda) = T_m((theta - lambda) / delta) / T_m(sigma1), of modulus below 1 exactly
+// for lambda in (0, lmin + lmax): P_m is positive definite as long as every eigenvalue of M^-1 A lies in that
+// open interval.  That margin -- lmin above the largest eigenvalue the bound missed -- is why an lmax that is a
+// little low only costs iterations, while bounds with lmin + lmax below the true lambda_max (with the default
+// lmin = lmax / 30: lmax below lambda_max / 1.033; whatever lmin: lmax below lambda_max / 2) make P_m
+// indefinite and PCG meaningless; the solver then still reports the true residual of what it returns.
+//
+// The pairs (rho_j rho_{j-1}, 2 rho_j / delta) are computed on the host in fp64 (cheb_coeffs) and passed as
+// kernel arguments: an inner step has no dot product and reads no device scalar.  An outer iteration:
+//   tile kernel + fold            q = A p
+//   cg_pq_kernel                  pq = p . q                                      (cfs_solver.hpp, unchanged)
+//   cheb_update_kernel            u += (rz/pq) p;  r -= (rz/pq) q;  rr' = r . r;  z = d = (1/theta) M^-1 r
+//                                 (degree 1: also rz' = r . z)
+//   m - 1 times:  tile kernel + fold   t = A z        (t lives in the q buffer: q = A p has been consumed)
+//                 cheb_step_kernel     one pass over r, t, d, z and M^-1: d, z written; the last one: rz' = r . z
+//   cheb_direction_kernel         p = z + (rz'/rz) p;  iteration count;  converged?  (rr' <= tol^2 b.b: the
+//                                 unpreconditioned residual, the rule of cfs_hip_sym_pcg)
+// 5 + 3 (m - 1) launches; an inner step moves 7 n words (r, t, d, z read, d, z written, M^-1 read) against
+// the 13 n of a CG iteration's vector kernels.  Memory held during a solve: r, p, q, z, d and the stored M^-1.
+//
+// Rounding: z, d and t are stored in the value type; each update is computed in fp64 from the stored operands
+// and rounded once; M^-1 (r - t) is formed in fp64 from (double)r_i - (double)t_i; r . z sums (double)r_i
+// (double)z_i of the stored r and the stored final z in the fixed-order partial-sum slots of cfs_solver.hpp;
+// r . r comes from the unrounded update as in cg_update_kernel.  Every kernel returns at once when
+// ic[I_DONE] is set.
+#pragma once
+
+namespace cfs_solver {
+
+constexpr int kChebMaxDegree = 16;
+enum ChebLmaxSlot { L_WT = 0, L_VT, L_WW, L_COUNT }; // part[slot][kGrid] of the power method
+
+// theta and the degree - 1 pairs c1[j-1] = rho_j rho_{j-1}, c2[j-1] = 2 rho_j / delta (host, fp64)
+inline void cheb_coeffs(int degree, double lmin, double lmax, double *theta, double *c1, double *c2) {
+  const double th = 0.5 * (lmax + lmin), de = 0.5 * (lmax - lmin), s1 = th / de;
+  double rho = 1.0 / s1;
+  *theta = th;
+  for (int j = 1; j < degree; ++j) {
+    const double rn = 1.0 / (2.0 * s1 - rho);
+    c1[j - 1] = rn * rho;
+    c2[j - 1] = 2.0 * rn / de;
+    rho = rn;
+  }
+}
+
+// One element of the diagonal forms (BS = 0: M = I, BS = 1: the stored dinv), in fp64
+template <typename V, int BS> __device__ __forceinline__ double cheb_minv1(double x, V dinv) {
+  return BS == 1 ? x * (double)dinv : x;
+}
+
+// z = d = (V)((1 / theta) M^-1 r);  rz_slot >= 0: part[rz_slot] <- r . z of the stored values
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cheb_start_kernel(V *__restrict__ z, V *__restrict__ d, const V *__restrict__ r, long long n, double inv_theta, int rz_slot,
+                      double *__restrict__ part, const V *__restrict__ minv, long long nb) {
+  double sz = 0.0;
+  if constexpr (BS >= 2) {
+    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+      double rd[BS], zz[BS];
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        rd[i] = g < n ? (double)r[g] : 0.0;
+      }
+      block_apply<V, BS>(minv, nb, k, rd, zz);
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        if (g < n) {
+          const V zi = (V)(inv_theta * zz[i]);
+          z[g] = zi;
+          d[g] = zi;
+          sz += rd[i] * (double)zi;
+        }
+      }
+    }
+  } else {
+    constexpr int W = Vec16<V>::W;
+    typedef typename Vec16<V>::type VT;
+    const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+    for (long long i = t0; i < nv; i += stride) {
+      const VT rv = reinterpret_cast<const VT *>(r)[i];
+      VT mv, zv;
+      if (BS == 1) mv = reinterpret_cast<const VT *>(minv)[i];
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        zv[k] = (V)(inv_theta * cheb_minv1<V, BS>((double)rv[k], BS == 1 ? mv[k] : (V)1));
+        sz += (double)rv[k] * (double)zv[k];
+      }
+      reinterpret_cast<VT *>(z)[i] = zv;
+      reinterpret_cast<VT *>(d)[i] = zv;
+    }
+    for (long long i = nv * W + t0; i < n; i += stride) {
+      const V ri = r[i];
+      const V zi = (V)(inv_theta * cheb_minv1<V, BS>((double)ri, BS == 1 ? minv[i] : (V)1));
+      z[i] = zi;
+      d[i] = zi;
+      sz += (double)ri * (double)zi;
+    }
+  }
+  if (rz_slot >= 0) { // (uniform over the grid)
+    sz = block_sum(sz);
+    if (threadIdx.x == 0) part[rz_slot * kGrid + blockIdx.x] = sz;
+  }
+}
+
+// cg_update_kernel<V, true> with z stored:  alpha = rz / pq;  u += alpha p;  r -= alpha q;  part[rr'] <- r . r;
+// z = d = (V)((1 / theta) M^-1 r) of the ROUNDED r;  with_rz (degree 1): part[rz'] <- r . z
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cheb_update_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q, V *__restrict__ z,
+                       V *__restrict__ d, long long n, double *__restrict__ part, const int *__restrict__ ic, int it,
+                       double inv_theta, int with_rz, const V *__restrict__ minv, long long nb) {
+  if (ic[I_DONE]) return;
+  const double pq = slot_sum(part, P_PQ), rz_old = slot_sum(part, P_RZ0 + (it & 1));
+  const double alpha = pq != 0.0 ? rz_old / pq : 0.0;
+  double s = 0.0, sz = 0.0;
+  if constexpr (BS >= 2) {
+    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+      double rd[BS], zz[BS];
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        rd[i] = 0.0;
+        if (g < n) {
+          u[g] = (V)((double)u[g] + alpha * (double)p[g]);
+          const double ri = (double)r[g] - alpha * (double)q[g];
+          const V rn = (V)ri;
+          r[g] = rn;
+          s += ri * ri;
+          rd[i] = (double)rn;
+        }
+      }
+      block_apply<V, BS>(minv, nb, k, rd, zz);
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        if (g < n) {
+          const V zi = (V)(inv_theta * zz[i]);
+          z[g] = zi;
+          d[g] = zi;
+          sz += rd[i] * (double)zi;
+        }
+      }
+    }
+  } else {
+    constexpr int W = Vec16<V>::W;
+    typedef typename Vec16<V>::type VT;
+    const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+    for (long long i = t0; i < nv; i += stride) {
+      VT uv = reinterpret_cast<VT *>(u)[i], rv = reinterpret_cast<VT *>(r)[i];
+      const VT pv = reinterpret_cast<const VT *>(p)[i], qv = reinterpret_cast<const VT *>(q)[i];
+      VT mv, zv;
+      if (BS == 1) mv = reinterpret_cast<const VT *>(minv)[i];
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        uv[k] = (V)((double)uv[k] + alpha * (double)pv[k]);
+        const double ri = (double)rv[k] - alpha * (double)qv[k];
+        rv[k] = (V)ri;
+        s += ri * ri;
+        zv[k] = (V)(inv_theta * cheb_minv1<V, BS>((double)rv[k], BS == 1 ? mv[k] : (V)1));
+        sz += (double)rv[k] * (double)zv[k];
+      }
+      reinterpret_cast<VT *>(u)[i] = uv;
+      reinterpret_cast<VT *>(r)[i] = rv;
+      reinterpret_cast<VT *>(z)[i] = zv;
+      reinterpret_cast<VT *>(d)[i] = zv;
+    }
+    for (long long i = nv * W + t0; i < n; i += stride) {
+      u[i] = (V)((double)u[i] + alpha * (double)p[i]);
+      const double ri = (double)r[i] - alpha * (double)q[i];
+      const V rn = (V)ri;
+      r[i] = rn;
+      s += ri * ri;
+      const V zi = (V)(inv_theta * cheb_minv1<V, BS>((double)rn, BS == 1 ? minv[i] : (V)1));
+      z[i] = zi;
+      d[i] = zi;
+      sz += (double)rn * (double)zi;
+    }
+  }
+  s = block_sum(s);
+  if (with_rz) sz = block_sum(sz);
+  if (threadIdx.x == 0) {
+    part[(P_RR0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = s;
+    if (with_rz) part[(P_RZ0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = sz;
+  }
+}
+
+// One inner step:  d = (V)(c1 d + c2 M^-1 (r - t));  z = (V)(z + d);  rz_slot >= 0 (the last step): part[rz_slot] <- r . z
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cheb_step_kernel(const V *__restrict__ r, const V *__restrict__ t, V *__restrict__ d, V *__restrict__ z, long long n, double c1,
+                     double c2, int rz_slot, double *__restrict__ part, const int *__restrict__ ic, const V *__restrict__ minv,
+                     long long nb) {
+  if (ic[I_DONE]) return;
+  double sz = 0.0;
+  if constexpr (BS >= 2) {
+    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+      double rd[BS], w[BS], zz[BS];
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        rd[i] = g < n ? (double)r[g] : 0.0;
+        w[i] = g < n ? rd[i] - (double)t[g] : 0.0;
+      }
+      block_apply<V, BS>(minv, nb, k, w, zz);
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        if (g < n) {
+          const V di = (V)(c1 * (double)d[g] + c2 * zz[i]);
+          const V zi = (V)((double)z[g] + (double)di);
+          d[g] = di;
+          z[g] = zi;
+          sz += rd[i] * (double)zi;
+        }
+      }
+    }
+  } else {
+    constexpr int W = Vec16<V>::W;
+    typedef typename Vec16<V>::type VT;
+    const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+    for (long long i = t0; i < nv; i += stride) {
+      const VT rv = reinterpret_cast<const VT *>(r)[i], tv = reinterpret_cast<const VT *>(t)[i];
+      VT dv = reinterpret_cast<VT *>(d)[i], zv = reinterpret_cast<VT *>(z)[i];
+      VT mv;
+      if (BS == 1) mv = reinterpret_cast<const VT *>(minv)[i];
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        dv[k] = (V)(c1 * (double)dv[k] + c2 * cheb_minv1<V, BS>((double)rv[k] - (double)tv[k], BS == 1 ? mv[k] : (V)1));
+        zv[k] = (V)((double)zv[k] + (double)dv[k]);
+        sz += (double)rv[k] * (double)zv[k];
+      }
+      reinterpret_cast<VT *>(d)[i] = dv;
+      reinterpret_cast<VT *>(z)[i] = zv;
+    }
+    for (long long i = nv * W + t0; i < n; i += stride) {
+      const V ri = r[i];
+      const V di = (V)(c1 * (double)d[i] + c2 * cheb_minv1<V, BS>((double)ri - (double)t[i], BS == 1 ? minv[i] : (V)1));
+      const V zi = (V)((double)z[i] + (double)di);
+      d[i] = di;
+      z[i] = zi;
+      sz += (double)ri * (double)zi;
+    }
+  }
+  if (rz_slot >= 0) { // (uniform over the grid)
+    sz = block_sum(sz);
+    if (threadIdx.x == 0) part[rz_slot * kGrid + blockIdx.x] = sz;
+  }
+}
+
+// cg_direction_kernel<V, true> with z stored:  beta = rz' / rz;  p = z + beta p;  one thread: iteration count,
+// convergence flag from rr' (only workgroup 0 adds it up)
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    cheb_direction_kernel(V *__restrict__ p, const V *__restrict__ z, long long n, const double *__restrict__ part,
+                          int *__restrict__ ic, int it, double stop) {
+  if (ic[I_DONE]) return;
+  const double rz = slot_sum(part, P_RZ0 + (it & 1)), rzn = slot_sum(part, P_RZ0 + ((it + 1) & 1));
+  const double beta = rz != 0.0 ? rzn / rz : 0.0;
+  double res = rzn;
+  if (blockIdx.x == 0) res = slot_sum(part, P_RR0 + ((it + 1) & 1)); // what the stopping rule looks at: r . r
+  constexpr int W = Vec16<V>::W;
+  typedef typename Vec16<V>::type VT;
+  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+  for (long long i = t0; i < nv; i += stride) {
+    VT pv = reinterpret_cast<VT *>(p)[i];
+    const VT zv = reinterpret_cast<const VT *>(z)[i];
+#pragma unroll
+    for (int k = 0; k < W; ++k) pv[k] = (V)((double)zv[k] + beta * (double)pv[k]);
+    reinterpret_cast<VT *>(p)[i] = pv;
+  }
+  for (long long i = nv * W + t0; i < n; i += stride) p[i] = (V)((double)z[i] + beta * (double)p[i]);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ic[I_ITER] += 1;
+    // (!(x > y): a NaN residual also ends the iteration)
+    if (!(res > stop)) ic[I_DONE] = 1;
+  }
+}
+
+// ---- the power method on M^-1 A ------------------------------------------------------------------
+// v <- v0 (the caller's, or the start vector of cfs_hip_sym_eigs), as values of V
+template <typename V>
+__global__ void __launch_bounds__(kThreads) cheb_lmax_start_kernel(V *__restrict__ v, const V *__restrict__ v0, long long n) {
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads)
+    v[i] = v0 ? v0[i] : (V)eigs_default_v0(i);
+}
+
+// w = (V)(M^-1 t);  part <- w . t, v . t, w . w of the stored values
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cheb_lmax_apply_kernel(V *__restrict__ w, const V *__restrict__ t, const V *__restrict__ v, long long n,
+                           double *__restrict__ part, const V *__restrict__ minv, long long nb) {
+  double wt = 0.0, vt = 0.0, ww = 0.0;
+  if constexpr (BS >= 2) {
+    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+      double td[BS], zz[BS];
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        td[i] = g < n ? (double)t[g] : 0.0;
+      }
+      block_apply<V, BS>(minv, nb, k, td, zz);
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        if (g < n) {
+          const V wi = (V)zz[i];
+          w[g] = wi;
+          wt += (double)wi * td[i];
+          vt += (double)v[g] * td[i];
+          ww += (double)wi * (double)wi;
+        }
+      }
+    }
+  } else {
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+      const double ti = (double)t[i];
+      const V wi = (V)cheb_minv1<V, BS>(ti, BS == 1 ? minv[i] : (V)1);
+      w[i] = wi;
+      wt += (double)wi * ti;
+      vt += (double)v[i] * ti;
+      ww += (double)wi * (double)wi;
+    }
+  }
+  wt = block_sum(wt);
+  vt = block_sum(vt);
+  ww = block_sum(ww);
+  if (threadIdx.x == 0) {
+    part[L_WT * kGrid + blockIdx.x] = wt;
+    part[L_VT * kGrid + blockIdx.x] = vt;
+    part[L_WW * kGrid + blockIdx.x] = ww;
+  }
+}
+
+// v = (V)(w / sqrt(w . w)), the scalar read on the device (w . w not finite and > 0: v = w)
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    cheb_lmax_normalise_kernel(V *__restrict__ v, const V *__restrict__ w, long long n, const double *__restrict__ part) {
+  const double ww = slot_sum(part, L_WW);
+  const double nrm = (ww > 0.0 && ww * 0.0 == 0.0) ? sqrt(ww) : 1.0;
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads)
+    v[i] = (V)((double)w[i] / nrm);
+}
+
+// ---- host ----------------------------------------------------------------------------------------
+// the stored M^-1 of one call: nothing (BS = 0), dinv (1) or the packed inverse blocks (>= 2); entries or
+// blocks that are not positive are counted into part[P_BAD] (which the caller has zeroed)
+template <typename V, int BS> struct ChebBase {
+  cfs_rt::DevBuf dbuf, blkbuf;
+  long long nb = 0;
+  const V *minv() const { return (const V *)dbuf.p; }
+  template <class Handle> int setup(Handle *h, double *part, hipStream_t st) {
+    const long long n = h->n();
+    int rc;
+    if constexpr (BS >= 2) {
+      nb = (n + BS - 1) / BS;
+      if ((rc = dbuf.alloc((size_t)nb * tri_words(BS) * sizeof(V) + 64)) || (rc = blkbuf.alloc((size_t)nb * BS * BS * sizeof(V) + 64)) ||
+          (rc = h->block_diagonal(blkbuf.p, BS, st)))
+        return rc;
+      hipLaunchKernelGGL((cg_binv_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)blkbuf.p, (V *)dbuf.p, nb, n, part);
+    } else if constexpr (BS == 1) {
+      if ((rc = dbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = h->diagonal(dbuf.p, st))) return rc;
+      hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)dbuf.p, n, part);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  static int refuse(const char *who, double bad, long long n, long long nb) {
+    if (BS >= 2)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, std::string(who) + ": block Jacobi needs positive definite diagonal blocks, " +
+                                                  std::to_string((long long)bad) + " of " + std::to_string(nb) + " blocks of " +
+                                                  std::to_string(BS) + " rows have a pivot that is zero, negative or not finite");
+    return cfs_rt::set_err(CFS_HIP_ERR_ARG, std::string(who) + ": Jacobi needs a positive diagonal, " + std::to_string((long long)bad) +
+                                                " of " + std::to_string(n) + " entries are zero, negative or not finite");
+  }
+};
+
+// the m - 1 inner steps behind a z = d = z_1 that is already enqueued; t: n values of scratch
+template <typename V, int BS, class Handle>
+int cheb_chain(Handle *h, V *z, V *d, V *t, const V *r, long long n, int degree, const double *c1, const double *c2, int rz_slot,
+               double *part, const int *ic, const V *minv, long long nb, hipStream_t st) {
+  for (int j = 1; j < degree; ++j) {
+    int rc = h->spmv_local(t, z, nullptr, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cheb_step_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, (const V *)t, d, z, n, c1[j - 1], c2[j - 1],
+                       j == degree - 1 ? rz_slot : -1, part, ic, minv, nb);
+  }
+  return 0;
+}
+
+// `steps` power steps on M^-1 A from v (already stored); v, t, w: n values each.  No host look before the last step.
+template <typename V, int BS, class Handle>
+int cheb_power(Handle *h, V *v, V *t, V *w, long long n, int steps, double *lpart, const V *minv, long long nb, double *estimate,
+               hipStream_t st) {
+  for (int s = 0; s < steps; ++s) {
+    int rc = h->spmv_local(t, v, nullptr, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cheb_lmax_apply_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, w, (const V *)t, (const V *)v, n, lpart,
+                       minv, nb);
+    if (s + 1 < steps)
+      hipLaunchKernelGGL((cheb_lmax_normalise_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, v, (const V *)w, n, (const double *)lpart);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<double> hp((size_t)L_COUNT * kGrid);
+  HIPCHK(hipMemcpyAsync(hp.data(), lpart, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  double wt = 0.0, vt = 0.0;
+  for (int g = 0; g < kGrid; g++) wt += hp[(size_t)L_WT * kGrid + g], vt += hp[(size_t)L_VT * kGrid + g];
+  *estimate = wt / vt;
+  return 0;
+}
+
+// cfs_hip_sym_precond_lmax
+template <typename V, int BS, class Handle>
+int cheb_lmax(Handle *h, int steps, const void *v0_dev, double *estimate, hipStream_t st) {
+  using cfs_rt::DevBuf;
+  const long long n = h->n();
+  if (h->rows() != h->n()) return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "precond_lmax: the handle holds a row block, not the whole matrix");
+  if (steps <= 0) steps = 16;
+  DevBuf vbuf, tbuf, wbuf, pbuf_part, lbuf;
+  ChebBase<V, BS> base;
+  int rc;
+  if ((rc = vbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = tbuf.alloc((size_t)n * sizeof(V) + 64)) ||
+      (rc = wbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) ||
+      (rc = lbuf.alloc((size_t)L_COUNT * kGrid * sizeof(double))))
+    return rc;
+  double *part = (double *)pbuf_part.p;
+  HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
+  HIPCHK(hipMemsetAsync(lbuf.p, 0, (size_t)L_COUNT * kGrid * sizeof(double), st));
+  if ((rc = base.setup(h, part, st))) return rc;
+  hipLaunchKernelGGL((cheb_lmax_start_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)vbuf.p, (const V *)v0_dev, n);
+  if ((rc = cheb_power<V, BS>(h, (V *)vbuf.p, (V *)tbuf.p, (V *)wbuf.p, n, steps, (double *)lbuf.p, base.minv(), base.nb, estimate, st)))
+    return rc;
+  std::vector<double> hb(kGrid);
+  HIPCHK(hipMemcpy(hb.data(), part + (size_t)P_BAD * kGrid, kGrid * sizeof(double), hipMemcpyDeviceToHost));
+  double bad = 0.0;
+  for (int g = 0; g < kGrid; g++) bad += hb[g];
+  if (bad != 0.0) return ChebBase<V, BS>::refuse("precond_lmax", bad, n, base.nb);
+  return 0;
+}
+
+// cfs_hip_sym_cheb_apply: z = P_m r
+template <typename V, int BS, class Handle>
+int cheb_apply(Handle *h, int degree, double lmin, double lmax, void *z_dev, const void *r_dev, hipStream_t st) {
+  using cfs_rt::DevBuf;
+  const long long n = h->n();
+  if (h->rows() != h->n()) return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "cheb_apply: the handle holds a row block, not the whole matrix");
+  DevBuf dvec, tvec, pbuf_part, cnt;
+  ChebBase<V, BS> base;
+  int rc;
+  if ((rc = dvec.alloc((size_t)n * sizeof(V) + 64)) || (rc = tvec.alloc((size_t)n * sizeof(V) + 64)) ||
+      (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) || (rc = cnt.alloc(I_COUNT * sizeof(int))))
+    return rc;
+  double *part = (double *)pbuf_part.p;
+  HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
+  HIPCHK(hipMemsetAsync(cnt.p, 0, I_COUNT * sizeof(int), st));
+  if ((rc = base.setup(h, part, st))) return rc;
+  double theta, c1[kChebMaxDegree], c2[kChebMaxDegree];
+  cheb_coeffs(degree, lmin, lmax, &theta, c1, c2);
+  hipLaunchKernelGGL((cheb_start_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)z_dev, (V *)dvec.p, (const V *)r_dev, n,
+                     1.0 / theta, -1, part, base.minv(), base.nb);
+  if ((rc = cheb_chain<V, BS>(h, (V *)z_dev, (V *)dvec.p, (V *)tvec.p, (const V *)r_dev, n, degree, c1, c2, -1, part,
+                              (const int *)cnt.p, base.minv(), base.nb, st)))
+    return rc;
+  HIPCHK(hipGetLastError());
+  std::vector<double> hb(kGrid);
+  HIPCHK(hipMemcpyAsync(hb.data(), part + (size_t)P_BAD * kGrid, kGrid * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  double bad = 0.0;
+  for (int g = 0; g < kGrid; g++) bad += hb[g];
+  if (bad != 0.0) return ChebBase<V, BS>::refuse("cheb_apply", bad, n, base.nb);
+  return 0;
+}
+
+// cfs_hip_sym_pcg_cheb.  u: in = first guess, out = solution; lmin / lmax <= 0: the defaults (cfs_hip.h)
+template <typename V, int BS, class Handle>
+int cg_cheb(Handle *h, void *u_dev, const void *b_dev, int degree, double lmin, double lmax, double tol, int maxiter, int check_every,
+            int *iterations, double *relres, double *bounds_used, hipStream_t st) {
+  using cfs_rt::DevBuf;
+  const long long n = h->n();
+  if (h->rows() != h->n()) return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_cheb: the handle holds a row block, not the whole matrix");
+  if (check_every < 1) check_every = 8;
+  // (the cap of cg(): about 100 enqueued launches stall the runtime; an iteration here is 5 + 3 (m - 1) of them)
+  check_every = std::min(std::min(check_every, 16), std::max(1, 80 / (5 + 3 * (degree - 1))));
+  V *u = (V *)u_dev;
+  const V *b = (const V *)b_dev;
+  DevBuf rbuf, pbuf, qbuf, zbuf, dvec, pbuf_part, cnt, lbuf;
+  ChebBase<V, BS> base;
+  int rc;
+  if ((rc = rbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf.alloc((size_t)n * sizeof(V) + 64)) ||
+      (rc = qbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = zbuf.alloc((size_t)n * sizeof(V) + 64)) ||
+      (rc = dvec.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) ||
+      (rc = cnt.alloc(I_COUNT * sizeof(int))))
+    return rc;
+  V *r = (V *)rbuf.p, *p = (V *)pbuf.p, *q = (V *)qbuf.p, *z = (V *)zbuf.p, *d = (V *)dvec.p;
+  double *part = (double *)pbuf_part.p;
+  int *ic = (int *)cnt.p;
+  std::vector<double> hp((size_t)P_COUNT * kGrid);
+  auto read_slot = [&](int slot, double *out) -> int { // (synchronises the stream)
+    HIPCHK(hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    double s = 0.0;
+    for (int g = 0; g < kGrid; g++) s += hp[(size_t)slot * kGrid + g];
+    *out = s;
+    return 0;
+  };
+  HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
+  HIPCHK(hipMemsetAsync(ic, 0, I_COUNT * sizeof(int), st));
+  if ((rc = base.setup(h, part, st))) return rc;
+  const V *minv = base.minv();
+  const long long nb = base.nb;
+  // r = b - A u, rr[0] = r . r, bb = b . b: the residual kernel of the plain iteration, the same bits
+  if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
+  hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, n, part,
+                     (int)P_RR0, 1, (const V *)nullptr);
+  HIPCHK(hipGetLastError());
+  double rr0 = 0.0, bb = 0.0, bad = 0.0;
+  if ((rc = read_slot(P_RR0, &rr0))) return rc;
+  for (int g = 0; g < kGrid; g++) bb += hp[(size_t)P_BB * kGrid + g], bad += hp[(size_t)P_BAD * kGrid + g];
+  if (bad != 0.0) return ChebBase<V, BS>::refuse("pcg_cheb", bad, n, nb); // (u has not been touched yet)
+  if (!(lmax > 0.0)) { // the power method, in the buffers the iteration does not use yet
+    if ((rc = lbuf.alloc((size_t)L_COUNT * kGrid * sizeof(double)))) return rc;
+    HIPCHK(hipMemsetAsync(lbuf.p, 0, (size_t)L_COUNT * kGrid * sizeof(double), st));
+    hipLaunchKernelGGL((cheb_lmax_start_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)nullptr, n);
+    double est = 0.0;
+    if ((rc = cheb_power<V, BS>(h, p, q, z, n, 16, (double *)lbuf.p, minv, nb, &est, st))) return rc;
+    if (!(est > 0.0) || est * 0.0 != 0.0)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg_cheb: the power method gave no positive estimate of lambda_max(M^-1 A) (" +
+                                                  std::to_string(est) + "): pass lmax");
+    lmax = 1.1 * est;
+  }
+  if (!(lmin > 0.0)) lmin = lmax / 30.0;
+  if (!(lmin < lmax))
+    return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg_cheb: lmin " + std::to_string(lmin) + " is not below the estimated lmax " +
+                                                std::to_string(lmax));
+  if (bounds_used) bounds_used[0] = lmin, bounds_used[1] = lmax;
+  double theta, c1[kChebMaxDegree], c2[kChebMaxDegree];
+  cheb_coeffs(degree, lmin, lmax, &theta, c1, c2);
+  const double inv_theta = 1.0 / theta;
+  const double stop = tol * tol * bb;
+  bool done = !(rr0 > stop); // the first guess already solves it (or b = 0)
+  int host_ic[I_COUNT] = {0, 0};
+  int it = 0;
+  if (!done && maxiter > 0) { // z = P_m r, rz[0] = r . z, p = z
+    hipLaunchKernelGGL((cheb_start_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, z, d, (const V *)r, n, inv_theta,
+                       degree == 1 ? (int)P_RZ0 : -1, part, minv, nb);
+    if ((rc = cheb_chain<V, BS>(h, z, d, q, (const V *)r, n, degree, c1, c2, (int)P_RZ0, part, (const int *)ic, minv, nb, st)))
+      return rc;
+    HIPCHK(hipMemcpyAsync(p, z, (size_t)n * sizeof(V), hipMemcpyDeviceToDevice, st));
+  }
+  auto iteration = [&](int k) -> int {
+    int r2 = h->spmv_local(q, p, nullptr, st);
+    if (r2) return r2;
+    hipLaunchKernelGGL((cg_pq_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part, (const int *)ic);
+    hipLaunchKernelGGL((cheb_update_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, z, d, n, part,
+                       (const int *)ic, k, inv_theta, degree == 1 ? 1 : 0, minv, nb);
+    if ((r2 = cheb_chain<V, BS>(h, z, d, q, (const V *)r, n, degree, c1, c2, (int)P_RZ0 + ((k + 1) & 1), part, (const int *)ic, minv,
+                                nb, st)))
+      return r2;
+    hipLaunchKernelGGL((cheb_direction_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, n, (const double *)part, ic, k,
+                       stop);
+    return 0;
+  };
+  while (!done && it < maxiter) {
+    const int until = std::min(maxiter, it + check_every);
+    for (; it < until; ++it)
+      if ((rc = iteration(it))) return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    done = host_ic[I_DONE] != 0;
+  }
+  // the true residual of what is returned
+  if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
+  hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b, (const V *)q, n,
+                     part, (int)P_RES, 0, (const V *)nullptr);
+  HIPCHK(hipGetLastError());
+  double res2 = 0.0;
+  if ((rc = read_slot(P_RES, &res2))) return rc;
+  HIPCHK(hipMemcpy(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost));
+  if (iterations) *iterations = host_ic[I_ITER];
+  if (relres) *relres = bb > 0.0 ? std::sqrt(res2 / bb) : std::sqrt(res2);
+  return 0;
+}
+
+} // namespace cfs_solver

@@ -350,6 +350,46 @@ class SymMatrix:
                                                int(check_every), C.byref(it), C.byref(res), _stream_ptr(stream)))
         return it.value, res.value
 
+    @staticmethod
+    def _cheb_base(base, block):
+        """block_rows of the Chebyshev entry points: 0 none, 1 Jacobi, `block` block Jacobi"""
+        if isinstance(base, str):
+            if base not in LOBPCG_PRECOND:
+                raise ValueError(f"unknown base preconditioner {base!r}: one of {sorted(LOBPCG_PRECOND)}")
+            return int(block) if base == "block_jacobi" else LOBPCG_PRECOND[base]
+        return int(base)
+
+    def pcg_cheb(self, u, b, base="jacobi", block=3, degree=4, lmin=None, lmax=None, tol=1e-10, maxiter=1000,
+                 check_every=8, stream=None):
+        """PCG with a Chebyshev polynomial of `degree` (1 .. 16) in M^-1 A as the preconditioner
+        (cfs_hip_sym_pcg_cheb): M from base = "none", "jacobi" or "block_jacobi" (block one of 1, 2, 3, 4, 6).
+        degree - 1 products per application and no dot product inside it; 5 + 3 (degree - 1) launches per outer
+        iteration.  lmax None: 1.1 x the power-method estimate of lambda_max(M^-1 A) (precond_lmax()); lmin None:
+        lmax / 30.  The polynomial is positive definite as long as the spectrum of M^-1 A lies in (0, lmin + lmax).
+        Stops on the unpreconditioned residual ||r|| <= tol ||b||.  Returns (iterations, ||b - A u|| / ||b||,
+        (lmin, lmax) actually used -- pass them to the next solve with the same matrix)."""
+        it, res, used = C.c_int(), C.c_double(), (C.c_double * 2)()
+        _lib.check(_lib.load().cfs_hip_sym_pcg_cheb(
+            self._h, _ptr(u), _ptr(b), self._cheb_base(base, block), int(degree), float(lmin or 0.0), float(lmax or 0.0),
+            float(tol), int(maxiter), int(check_every), C.byref(it), C.byref(res), used, _stream_ptr(stream)))
+        return it.value, res.value, (used[0], used[1])
+
+    def cheb_apply(self, z, r, lmin, lmax, base="jacobi", block=3, degree=4, stream=None):
+        """z <- P_m r, the polynomial of pcg_cheb() alone (cfs_hip_sym_cheb_apply): device tensors of nrows()
+        values, both bounds required.  Returns z."""
+        _lib.check(_lib.load().cfs_hip_sym_cheb_apply(self._h, self._cheb_base(base, block), int(degree), float(lmin),
+                                                      float(lmax), _ptr(z), _ptr(r), _stream_ptr(stream)))
+        return z
+
+    def precond_lmax(self, base="jacobi", block=3, steps=16, v0=None, stream=None):
+        """a lower estimate of lambda_max(M^-1 A) by `steps` power steps (cfs_hip_sym_precond_lmax), M as for
+        pcg_cheb(); v0: a device tensor of nrows() values (None: the library's fixed start vector)."""
+        est = C.c_double()
+        _lib.check(_lib.load().cfs_hip_sym_precond_lmax(self._h, self._cheb_base(base, block), int(steps),
+                                                        _ptr(v0) if v0 is not None else None, C.byref(est),
+                                                        _stream_ptr(stream)))
+        return est.value
+
     def minres(self, u, b, precond="none", shift=0.0, tol=1e-10, maxiter=1000, check_every=8, stream=None):
         """MINRES inside the library (cfs_hip_sym_minres): u (device tensor) holds the first guess and
         receives the solution of (A - shift I) u = b, A symmetric and possibly indefinite; five launches per

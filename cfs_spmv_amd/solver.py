@@ -120,6 +120,102 @@ def pcg_native(A, b, precond="jacobi", tol=1e-10, maxiter=1000, x0=None, check_e
     return u, it, res
 
 
+def cheb_coeffs(degree, lmin, lmax):
+    """theta and the degree - 1 pairs (rho_j rho_{j-1}, 2 rho_j / delta) of the Chebyshev iteration on
+    [lmin, lmax], in fp64 as cfs_hip_debug_cheb_coeffs computes them"""
+    theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
+    sigma1 = theta / delta
+    rho, pairs = 1.0 / sigma1, []
+    for _ in range(1, degree):
+        rn = 1.0 / (2.0 * sigma1 - rho)
+        pairs.append((rn * rho, 2.0 * rn / delta))
+        rho = rn
+    return theta, pairs
+
+
+def pcg_cheb(A, b, base="jacobi", block=3, degree=4, lmin=None, lmax=None, tol=1e-10, maxiter=1000, x0=None):
+    """PCG with the Chebyshev polynomial preconditioner, host-driven: the recurrence and the rounding rules
+    of cfs_hip_sym_pcg_cheb with torch operations -- z, d and t stored in the value type, every update computed
+    in fp64 from the stored operands and rounded once, M^-1 from A.diagonal() / A.block_inverse(block).  The
+    default bounds are the library's (1.1 x A.precond_lmax(), lmax / 30).  The model of the native loop and its
+    baseline.  Returns (u, iterations, relative residual, (lmin, lmax))."""
+    import torch
+    f64 = torch.float64
+    if base == "block_jacobi":
+        minv = A.block_inverse(block)
+        if not bool(torch.all(torch.isfinite(minv))):
+            raise ValueError("pcg_cheb: block Jacobi needs positive definite diagonal blocks")
+        apply = lambda x: _block_apply(minv, x, torch.empty_like(x))
+    elif base == "jacobi":
+        dg = A.diagonal()
+        if not bool(torch.all(torch.isfinite(dg) & (dg > 0))):
+            raise ValueError("pcg_cheb: Jacobi needs a positive diagonal")
+        dinv = (1.0 / dg.double()).to(b.dtype).double()
+        apply = lambda x: x * dinv
+    elif base == "none":
+        apply = lambda x: x
+    else:
+        raise ValueError(f"unknown base preconditioner {base!r}: 'none', 'jacobi' or 'block_jacobi'")
+    if not lmax or lmax <= 0:
+        lmax = 1.1 * A.precond_lmax(base=base, block=block)
+    if not lmin or lmin <= 0:
+        lmin = lmax / 30.0
+    theta, pairs = cheb_coeffs(degree, lmin, lmax)
+    t = torch.empty_like(b)
+
+    def poly(r):
+        """z = P_m r of the stored r"""
+        rd = r.double()
+        d = ((1.0 / theta) * apply(rd)).to(b.dtype)
+        z = d.clone()
+        for c1, c2 in pairs:
+            A.dense_vector_multiply(t, z)
+            d = (c1 * d.double() + c2 * apply(rd - t.double())).to(b.dtype)
+            z = (z.double() + d.double()).to(b.dtype)
+        return z
+
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    q = torch.empty_like(b)
+    A.dense_vector_multiply(q, u)
+    r = b - q
+    rr = float(torch.dot(r.double(), r.double()))
+    bb = float(torch.dot(b.double(), b.double()))
+    bnorm = math.sqrt(bb) or 1.0
+    it = 0
+    if maxiter > 0 and rr > tol * tol * bb:
+        z = poly(r)
+        p = z.clone()
+        rz = float(torch.dot(r.double(), z.double()))
+    while it < maxiter and rr > tol * tol * bb:
+        A.dense_vector_multiply(q, p)          # the hot path
+        pq = float(torch.dot(p.double(), q.double()))
+        alpha = rz / pq if pq != 0.0 else 0.0
+        u = (u.double() + alpha * p.double()).to(b.dtype)
+        rs = r.double() - alpha * q.double()
+        rr = float(torch.dot(rs, rs))
+        r = rs.to(b.dtype)
+        z = poly(r)
+        rz_new = float(torch.dot(r.double(), z.double()))
+        p = (z.double() + (rz_new / rz if rz != 0.0 else 0.0) * p.double()).to(b.dtype)
+        rz = rz_new
+        it += 1
+    A.dense_vector_multiply(q, u)
+    res = math.sqrt(float(torch.dot((b - q).double(), (b - q).double()))) / bnorm
+    return u, it, res, (lmin, lmax)
+
+
+def pcg_cheb_native(A, b, base="jacobi", block=3, degree=4, lmin=None, lmax=None, tol=1e-10, maxiter=1000, x0=None,
+                    check_every=8):
+    """the same iteration inside the library (cfs_hip_sym_pcg_cheb): 5 + 3 (degree - 1) launches per outer
+    iteration, no dot product and no device scalar inside the polynomial.  Returns (u, iterations, relative
+    residual, (lmin, lmax)), like pcg_cheb()."""
+    import torch
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    it, res, used = A.pcg_cheb(u, b, base=base, block=block, degree=degree, lmin=lmin, lmax=lmax, tol=tol, maxiter=maxiter,
+                               check_every=check_every)
+    return u, it, res, used
+
+
 def pcg_mixed(M, b, tol=1e-10, delta=0.1, maxiter=1000, x0=None, precond="jacobi", block=3, check_every=8):
     """mixed-precision PCG, host-driven: the recurrence of cfs_hip_sym_pcg_mixed on a MixedSym.  One CG
     recurrence in float32 (r, p, q and the correction xlo; the products on M.A32; dots and z = M^-1 r in

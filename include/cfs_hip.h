@@ -408,6 +408,69 @@ int cfs_hip_sym_block_inverse_async(cfs_hip_sym_t h, int block_rows, void *minv_
 int cfs_hip_sym_pcg_mixed(cfs_hip_sym_t h64, cfs_hip_sym_t h32, void *u_dev, const void *b_dev, int block_rows, double tol,
                           double delta, int maxiter, int check_every, int *iterations, int *replacements, double *relres,
                           void *stream);
+/* cfs_hip_sym_pcg with a Chebyshev polynomial in M^-1 A as the preconditioner, z = P_m r.  M is the base:
+ * block_rows 0 means M = I, 1 the diagonal of cfs_hip_sym_pcg, 2 / 3 / 4 / 6 the node blocks of
+ * cfs_hip_sym_pcg_block (anything else: CFS_HIP_ERR_ARG); dinv and the inverse blocks are built and stored exactly
+ * as there.  With theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma1 = theta / delta, rho_0 = 1 / sigma1,
+ *     z_1 = d_1 = (1 / theta) M^-1 r
+ *     j = 1 .. m - 1:  t = A z_j;  rho_j = 1 / (2 sigma1 - rho_{j-1})
+ *                      d_{j+1} = rho_j rho_{j-1} d_j + (2 rho_j / delta) M^-1 (r - t);  z_{j+1} = z_j + d_{j+1}
+ * the Chebyshev iteration for A z = r from z = 0: degree m = `degree` (1 .. 16) costs m - 1 products; degree 1
+ * is the base preconditioner scaled by 1 / theta and makes none.  For fixed bounds P_m is a fixed symmetric linear
+ * operator, so plain PCG is valid with it.  THE MARGIN: 1 - lambda p(lambda) = T_m((theta - lambda) / delta) /
+ * T_m(sigma1) has modulus below 1 exactly for lambda in (0, lmin + lmax), so P_m is positive definite as long as
+ * every eigenvalue of M^-1 A lies in that open interval.  An lmax that is a little low is therefore survivable
+ * (lmin covers it); one that is badly low makes P_m indefinite, PCG then promises nothing, and *relres says so.
+ * BOUNDS: lmax <= 0 means 1.1 x the estimate of cfs_hip_sym_precond_lmax (16 steps from its default start vector,
+ * made inside this call); lmin <= 0 means lmax / 30.  The 1.1 and the 30 are the conventions of PETSc's and
+ * Ifpack2's Chebyshev smoothers, not numbers measured here.  bounds_used (2 doubles, or NULL) receives the pair
+ * actually used, lmin then lmax, so a caller who solves many systems pays for the estimate once.
+ * LAUNCHES: 5 + 3 (m - 1) per outer iteration -- the product and p.q, a fused update (u, r, r.r and z_1 in one
+ * pass), per inner step the product and one fused kernel (r, t, d, z and M^-1 read, d and z written: 7 n words
+ * against the 13 n of a CG iteration), the direction kernel.  The coefficient pairs are computed on the host in
+ * fp64 and passed as kernel arguments: an inner step has no dot product and reads no device scalar.  The host looks
+ * at the convergence flag every min(check_every, 16, max(1, 80 / (5 + 3 (m - 1)))) iterations (check_every <= 0:
+ * 8).  Memory held during the call: five vectors (r, p, q, z, d; t lives in q) and the stored M^-1.
+ * ROUNDING: z, d and t are stored in the value type; every update is computed in fp64 from the stored operands and
+ * rounded once; M^-1 (r - t) is formed in fp64 from (double)r_i - (double)t_i; r.z sums (double)r_i (double)z_i of
+ * the stored r and the stored final z; r.r as in cfs_hip_sym_pcg; all in the same fixed-order partial sums, so a
+ * solve on a CFS_HIP_FLAG_DETERMINISTIC handle is bit-reproducible.  Stops on the UNPRECONDITIONED residual,
+ * r.r <= tol^2 b.b, the rule of cfs_hip_sym_pcg; a NaN ends the solve; *iterations = outer iterations done,
+ * *relres = ||b - A u|| / ||b|| RECOMPUTED from the returned u.  CFS_HIP_CG_GRAPH is not consulted.
+ * Handles: block_rows 0 or 1, those of cfs_hip_sym_pcg (a multi-device handle is accepted, a shard gets
+ * CFS_HIP_ERR_UNSUPPORTED); block_rows >= 2, those of cfs_hip_sym_pcg_block.  A diagonal entry or a block that is
+ * not positive is refused exactly as there: CFS_HIP_ERR_ARG, u untouched, *iterations = 0.
+ * CFS_HIP_ERR_ARG, before any device work: a null pointer (checked first), u == b, u or b not 16-byte aligned,
+ * tol < 0, maxiter < 0, another block_rows, a degree outside 1 .. 16, a bound that is not finite, lmin >= lmax when
+ * both are given; then a host pointer or a pointer on another device.  Also CFS_HIP_ERR_ARG, u untouched: no
+ * positive estimate (A or M indefinite, or A = 0), or a given lmin that is not below the estimated lmax.     */
+int cfs_hip_sym_pcg_cheb(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int block_rows, int degree, double lmin,
+                         double lmax, double tol, int maxiter, int check_every, int *iterations, double *relres,
+                         double *bounds_used, void *stream);
+/* z = P_m r alone: the polynomial of cfs_hip_sym_pcg_cheb, by the same kernels and with the same rounding, for a
+ * caller who wants it as a smoother and for tests that pin the chain by itself.  Both bounds are required
+ * (0 < lmin < lmax, finite).  z_dev (fully overwritten) and r_dev: different device vectors of n values of the
+ * handle's value type on its device, 16-byte aligned.  block_rows, degree and the handles accepted as for
+ * cfs_hip_sym_pcg_cheb.  m - 1 products and 1 + 3 (m - 1) launches; two vectors of temporary device memory and the
+ * stored M^-1, released before the call returns, which waits for the kernels.  A diagonal entry or a block that
+ * is not positive: CFS_HIP_ERR_ARG once the kernels have run, z then holds nothing meaningful.              */
+int cfs_hip_sym_cheb_apply(cfs_hip_sym_t h, int block_rows, int degree, double lmin, double lmax, void *z_dev,
+                           const void *r_dev, void *stream);
+/* An estimate of lambda_max(M^-1 A) by `steps` power steps (<= 0: 16), M as for cfs_hip_sym_pcg_cheb:
+ *     t = A v;  w = M^-1 t;  est = (w.t) / (v.t);  v = w / sqrt(w.w)
+ * from v = v0_dev (n device values of the value type; NULL: the start vector of cfs_hip_sym_eigs).  w and v are
+ * stored in the value type, all dots are fixed-order fp64 partial sums of the stored values, and the normalising
+ * scalar is read on the device: there is no host look until the last step.  *estimate is the last est.  For
+ * positive definite A and M, est = y^T B^2 y / y^T B y with B = M^-1/2 A M^-1/2 and y = M^1/2 v, so it never
+ * exceeds lambda_max(M^-1 A) (up to rounding): it is a LOWER estimate, which is why cfs_hip_sym_pcg_cheb multiplies
+ * it by 1.1 and keeps the margin described there.  Per step: the product and two launches (the last step: one).
+ * A diagonal entry or a block that is not positive: CFS_HIP_ERR_ARG.  Handles as for cfs_hip_sym_pcg_cheb.     */
+int cfs_hip_sym_precond_lmax(cfs_hip_sym_t h, int block_rows, int steps, const void *v0_dev, double *estimate,
+                             void *stream);
+/* Host only, no device work: *theta and the degree - 1 coefficient pairs cfs_hip_sym_pcg_cheb would pass to its
+ * inner steps for these bounds, c1[j-1] = rho_j rho_{j-1} and c2[j-1] = 2 rho_j / delta for j = 1 .. degree - 1
+ * (c1, c2: degree - 1 doubles each; may be NULL at degree 1).  Both bounds required, 0 < lmin < lmax.          */
+int cfs_hip_debug_cheb_coeffs(int degree, double lmin, double lmax, double *theta, double *c1, double *c2);
 /* MINRES (Paige & Saunders) for (A - shift I) u = b: A symmetric, possibly INDEFINITE, or singular with a
  * consistent b -- saddle-point matrices (a zero diagonal block), shifted operators, mixed-sign diagonals, on
  * which the conjugate gradients above promise nothing (on [[0, K], [K, 0]] with b = [f; 0] their first p.q is

@@ -12,7 +12,12 @@ for both the iterations, the replacements and the wall time down to MIXED_TOL.
 MINRES (cfs_hip_sym_minres) sits beside the Jacobi PCG on the same SPD stand-ins, with M = |diag(A)|: the native loop's
 time per iteration over K iterations against the host-driven loop (solver.minres) and against cfs_hip_sym_pcg, taken in
 the same run with the two native loops interleaved.
-usage: python tools/cg_bench.py [matrix[:scale] ...]"""
+The Chebyshev-preconditioned PCG (cfs_hip_sym_pcg_cheb) sits beside the native Jacobi PCG (and, with 3 x 3 node blocks as
+the base, beside the block-Jacobi PCG): solves down to TOL at degrees 2 and 4, interleaved with the plain solver, CHEB_ROUNDS
+rounds, the best wall time of each; outer iterations, products (the estimate's 16 and the two residuals included) and the
+time per outer iteration.  The default bounds are estimated inside the timed call; "_bounds_given" passes the bounds of
+an earlier call, as a caller with many right-hand sides would.
+usage: python tools/cg_bench.py [--only-cheb] [matrix[:scale] | lap2dNXxNY ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -20,18 +25,70 @@ import torch
 import cfs_spmv_amd as cfs
 from cfs_spmv_amd import synth
 from cfs_spmv_amd.solver import cg, cg_native, minres, minres_native, pcg, pcg_native, pcg_mixed_native
+from cfs_spmv_amd.solver import pcg_cheb_native
 
 HAVE_PCG = hasattr(cfs.load(), "cfs_hip_sym_pcg")
 HAVE_BLOCK = hasattr(cfs.load(), "cfs_hip_sym_pcg_block")
 HAVE_MIXED = hasattr(cfs.load(), "cfs_hip_sym_pcg_mixed")
 HAVE_MINRES = hasattr(cfs.load(), "cfs_hip_sym_minres")
+HAVE_CHEB = hasattr(cfs.load(), "cfs_hip_sym_pcg_cheb")
+ONLY_CHEB = "--only-cheb" in sys.argv
+CHEB_DEGREES, CHEB_ROUNDS = (2, 4), 3
 BLOCK, TOL, MAXITER = 3, 1e-8, 5000
 MIXED_TOL, MIXED_MAXITER = 1e-10, 20000
 
+
+def cheb_section(A, b, res):
+    """solves down to TOL: Jacobi PCG and the Chebyshev polynomial on it at CHEB_DEGREES, the same on 3 x 3 node blocks"""
+    bases = [("jacobi", "jacobi")] + ([(f"block{BLOCK}", "block_jacobi")] if HAVE_BLOCK else [])
+    loops = {}
+    for tag, base in bases:
+        loops[f"pcg_{tag}"] = (lambda base=base: pcg_native(A, b, precond=base, block=BLOCK, tol=TOL, maxiter=MAXITER, check_every=16)[1:3],
+                               lambda it: it + 2)
+        for m in CHEB_DEGREES:
+            used = pcg_cheb_native(A, b, base=base, block=BLOCK, degree=m, tol=TOL, maxiter=1)[3]
+            res[f"cheb_{tag}_bounds"] = list(used)
+            loops[f"cheb{m}_{tag}"] = (lambda base=base, m=m: pcg_cheb_native(A, b, base=base, block=BLOCK, degree=m, tol=TOL,
+                                                                              maxiter=MAXITER, check_every=16)[1:3],
+                                       lambda it, m=m: 16 + 2 + (m - 1) + it * m)
+            loops[f"cheb{m}_{tag}_bounds_given"] = (lambda base=base, m=m, used=used: pcg_cheb_native(
+                A, b, base=base, block=BLOCK, degree=m, lmin=used[0], lmax=used[1], tol=TOL, maxiter=MAXITER, check_every=16)[1:3],
+                lambda it, m=m: 2 + (m - 1) + it * m)
+    best = {}
+    for _ in range(CHEB_ROUNDS):
+        for label, (fn, _) in loops.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            it, rel = fn()
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            if t < best.get(label, (float("inf"),))[0]:
+                best[label] = (t, it, rel)
+    res["cheb_tolerance"], res["cheb_rounds"] = TOL, CHEB_ROUNDS
+    for label, (t, it, rel) in best.items():
+        res[label + "_ms_to_tolerance"] = round(t * 1e3, 3)
+        res[label + "_iterations"] = it
+        res[label + "_products"] = loops[label][1](it)
+        res[label + "_relres"] = rel
+        res[label + "_us_per_outer_iteration"] = round(t / max(it, 1) * 1e6, 2)
+    for tag, _ in bases:
+        for m in CHEB_DEGREES:
+            for suffix in ("", "_bounds_given"):
+                res[f"cheb{m}_{tag}{suffix}_over_pcg_{tag}_time"] = round(best[f"cheb{m}_{tag}{suffix}"][0] / best[f"pcg_{tag}"][0], 4)
+
+
 out = {}
-for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
+for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ldoor", "Flan_1565"]):
     name, _, sc = spec.partition(":")
-    n, rp, ci, va, _ = synth.generate(name, float(sc or 1.0))
+    if name.startswith("lap2d"):  # lap2dNXxNY: the anisotropic 5-point Laplacian of the tests, a matrix that needs many iterations
+        import scipy.sparse as sp
+        nx, ny = (int(v) for v in name[5:].split("x"))
+        T = lambda k: sp.diags([-np.ones(k - 1), 2 * np.ones(k), -np.ones(k - 1)], [-1, 0, 1])
+        L = (sp.kron(sp.identity(ny), T(nx)) + 0.37 * sp.kron(T(ny), sp.identity(nx))).tocsr()
+        L.sort_indices()
+        n, rp, ci, va = L.shape[0], L.indptr.astype(np.int32), L.indices.astype(np.int32), L.data
+    else:
+        n, rp, ci, va, _ = synth.generate(name, float(sc or 1.0))
     A = cfs.SymMatrix(n, rp, ci, va)
     b = torch.from_numpy(synth.make_x(n, 11)).cuda()
     y = torch.empty_like(b)
@@ -45,6 +102,11 @@ for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
     spmv_us = (time.perf_counter() - t0) / 200 * 1e6
     K = 200
     res = {"n": n, "spmv_us": round(spmv_us, 2)}
+    if ONLY_CHEB:
+        cheb_section(A, b, res)
+        out[spec] = res
+        A.close()
+        continue
     side = torch.cuda.Stream()  # (a stream capture needs a stream of its own: CFS_HIP_CG_GRAPH=1)
 
     def on_side(f):
@@ -136,6 +198,8 @@ for spec in (sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"]):
                                                      res["minres_jacobi_torch_loop_us_per_iteration"], 4)
         res["minres_jacobi_iterations_to_tolerance"] = minres_native(A, b, precond="jacobi", tol=TOL, maxiter=MAXITER,
                                                                      check_every=16)[1]
+    if HAVE_CHEB:
+        cheb_section(A, b, res)
     out[spec] = res
     A.close()
 print(json.dumps(out))
