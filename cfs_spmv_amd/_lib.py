@@ -74,7 +74,7 @@ SYMBOLS = [
     "cfs_hip_sym_create_multi_f64", "cfs_hip_sym_create_multi_f32", "cfs_hip_comm_create", "cfs_hip_comm_info", "cfs_hip_comm_destroy", "cfs_hip_comm_reduce_scatter",
     "cfs_hip_comm_allgather", "cfs_hip_comm_alltoallv", "cfs_hip_comm_wait_consumed", "cfs_hip_sym_num_gpus", "cfs_hip_sym_multi_set_xmode", "cfs_hip_sym_multi_set_exchange", "cfs_hip_sym_multi_exchange_info", "cfs_hip_sym_multi_devices", "cfs_hip_sym_balanced_splits", "cfs_hip_sym_destroy", "cfs_hip_sym_update_values_f64", "cfs_hip_sym_update_values_f32", "cfs_hip_sym_spmv",
     "cfs_hip_sym_spmv_async", "cfs_hip_sym_cg", "cfs_hip_sym_pcg", "cfs_hip_sym_diagonal_async", "cfs_hip_sym_block_diagonal_async",
-    "cfs_hip_sym_pcg_block", "cfs_hip_sym_block_inverse_async", "cfs_hip_sym_pcg_mixed", "cfs_hip_sym_minres", "cfs_hip_sym_pcg_cheb", "cfs_hip_sym_cheb_apply", "cfs_hip_sym_precond_lmax", "cfs_hip_debug_cheb_coeffs", "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
+    "cfs_hip_sym_pcg_block", "cfs_hip_sym_block_inverse_async", "cfs_hip_sym_pcg_mixed", "cfs_hip_sym_minres", "cfs_hip_sym_pcg_cheb", "cfs_hip_sym_cheb_apply", "cfs_hip_sym_precond_lmax", "cfs_hip_debug_cheb_coeffs", "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_debug_gram_cols", "cfs_hip_debug_lobpcg_update_cols", "cfs_hip_sym_debug_lobpcg_residual", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
     "cfs_hip_sym_shard_set_recv", "cfs_hip_sym_spmv_local_async",
     "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_fold_lists", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
     "cfs_hip_sym_plan_check_f32", "cfs_hip_sym_plan_send_info_f64",
@@ -218,6 +218,12 @@ def load():
         lib.cfs_hip_debug_gram.argtypes = [vp, vp, C.c_longlong, C.c_longlong, C.c_int, C.c_int, dp, dp, vp]
         lib.cfs_hip_sym_debug_lobpcg.argtypes = [vp, C.c_int, C.c_int, vp, C.c_longlong, C.c_int, dp, vp, C.c_longlong, dp, vp]
         lib.cfs_hip_debug_lobpcg_update.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_int, C.c_int, dp, C.c_int, vp]
+    if hasattr(lib, "cfs_hip_debug_gram_cols"):  # (absent from older builds loaded through CFS_HIP_LIB)
+        dp = C.POINTER(C.c_double)
+        lib.cfs_hip_debug_gram_cols.argtypes = [vp, vp, C.c_longlong, C.c_longlong, C.c_int, ip, C.c_int, C.c_int, dp, dp, vp]
+        lib.cfs_hip_debug_lobpcg_update_cols.argtypes = [vp, vp, C.c_longlong, C.c_longlong, C.c_int, C.c_int, ip, C.c_int, dp,
+                                                         C.c_int, vp]
+        lib.cfs_hip_sym_debug_lobpcg_residual.argtypes = [vp, C.c_int, vp, vp, vp, C.c_longlong, C.c_int, dp, C.c_uint, dp, vp]
     if hasattr(lib, "cfs_hip_csr_stats"):
         lib.cfs_hip_csr_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(lib, "cfs_hip_csr_debug_layout"):

@@ -2422,11 +2422,16 @@ int cfs_hip_debug_lobpcg_rr(int m, const double *g, const double *hh, int k, dou
   return 0;
 }
 
-// the device blocks of the two kernel-level developer entry points: 16-byte aligned device memory, one device
-static int check_lobpcg_block(const void *p, long long ld, long long n, int value_bytes, const char *who, int *dev) {
+// the device blocks of the kernel-level developer entry points: 16-byte aligned (checked for every block first) device
+// memory, one device
+static int check_lobpcg_geom(const void *p, long long ld, long long n, int value_bytes, const char *who) {
   if (value_bytes != 4 && value_bytes != 8) return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": value_bytes must be 4 or 8");
-  if (n < 1 || ld < n || (ld * value_bytes) % 16 != 0 || ((uintptr_t)p & 15))
+  // (the upper limit keeps the byte span of a block within 63 bits)
+  if (n < 1 || ld < n || ld > (1LL << 62) / (8LL * 3 * CFS_HIP_LOBPCG_MAX_K) || (ld * value_bytes) % 16 != 0 || ((uintptr_t)p & 15))
     return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": n >= 1, ld >= n, the pointers and ld multiples of 16 bytes");
+  return 0;
+}
+static int check_lobpcg_dev(const void *p, const char *who, int *dev) {
   const cfs_rt::PtrInfo pi = cfs_rt::classify(p);
   if (!pi.device) return set_err(CFS_HIP_ERR_ARG, std::string(who) + " needs device pointers");
   if (*dev >= 0 && pi.dev != *dev) return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": the blocks live on different devices");
@@ -2434,29 +2439,105 @@ static int check_lobpcg_block(const void *p, long long ld, long long n, int valu
   return 0;
 }
 
-int cfs_hip_debug_gram(const void *s_dev, const void *t_dev, long long ld, long long n, int m, int value_bytes, double *g, double *hh,
-                       void *stream) {
-  if (!s_dev || !t_dev || !g || !hh) return set_err(CFS_HIP_ERR_ARG, "null argument");
+// a column list of the kernel-level entry points: idx[j] in [0, ncols)
+static int check_lobpcg_idx(const int *idx, int m, int ncols, const char *who) {
+  for (int j = 0; j < m; ++j)
+    if (idx[j] < 0 || idx[j] >= ncols)
+      return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": idx[" + std::to_string(j) + "] = " + std::to_string(idx[j]) +
+                                          " is not a column in [0, " + std::to_string(ncols) + ")");
+  return 0;
+}
+
+int cfs_hip_debug_gram_cols(const void *s_dev, const void *t_dev, long long ld, long long n, int m, const int *idx, int full_h,
+                            int value_bytes, double *g, double *hh, void *stream) {
+  if (!s_dev || !t_dev || !idx || !g || !hh) return set_err(CFS_HIP_ERR_ARG, "null argument");
   if (m < 1 || m > 3 * CFS_HIP_LOBPCG_MAX_K)
     return set_err(CFS_HIP_ERR_ARG, "gram: m must lie in [1, " + std::to_string(3 * CFS_HIP_LOBPCG_MAX_K) + "]");
   int dev = -1, rc;
-  if ((rc = check_lobpcg_block(s_dev, ld, n, value_bytes, "gram", &dev)) || (rc = check_lobpcg_block(t_dev, ld, n, value_bytes, "gram", &dev)))
+  if ((rc = check_lobpcg_idx(idx, m, 3 * CFS_HIP_LOBPCG_MAX_K, "gram"))) return rc;
+  if (full_h != 0 && full_h != 1) return set_err(CFS_HIP_ERR_ARG, "gram: full_h must be 0 or 1");
+  if ((rc = check_lobpcg_geom(s_dev, ld, n, value_bytes, "gram")) || (rc = check_lobpcg_geom(t_dev, ld, n, value_bytes, "gram")) ||
+      (rc = check_lobpcg_dev(s_dev, "gram", &dev)) || (rc = check_lobpcg_dev(t_dev, "gram", &dev)))
     return rc;
   DeviceGuard dg(dev);
   return cfs_rt::with_value_type(value_bytes, [&](auto v) {
-    return cfs_solver::debug_gram<decltype(v)>(s_dev, t_dev, ld, n, m, g, hh, (hipStream_t)stream);
+    return cfs_solver::debug_gram<decltype(v)>(s_dev, t_dev, ld, n, m, idx, full_h, g, hh, (hipStream_t)stream);
+  });
+}
+
+int cfs_hip_debug_gram(const void *s_dev, const void *t_dev, long long ld, long long n, int m, int value_bytes, double *g, double *hh,
+                       void *stream) {
+  int idx[3 * CFS_HIP_LOBPCG_MAX_K];
+  for (int j = 0; j < 3 * CFS_HIP_LOBPCG_MAX_K; ++j) idx[j] = j;
+  return cfs_hip_debug_gram_cols(s_dev, t_dev, ld, n, m, idx, 1, value_bytes, g, hh, stream);
+}
+
+int cfs_hip_debug_lobpcg_update_cols(void *s_dev, void *as_dev, long long ld, long long n, int k, int m, const int *idx, int with_p,
+                                     const double *c, int value_bytes, void *stream) {
+  if (!s_dev || !idx || !c) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (k < 1 || k > CFS_HIP_LOBPCG_MAX_K || m < 1 || m > 3 * k)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg_update: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + " and 1 <= m <= 3 k");
+  int dev = -1, rc;
+  if ((rc = check_lobpcg_idx(idx, m, 3 * k, "lobpcg_update"))) return rc;
+  if (with_p != 0 && with_p != 1) return set_err(CFS_HIP_ERR_ARG, "lobpcg_update: with_p must be 0 or 1");
+  if ((rc = check_lobpcg_geom(s_dev, ld, n, value_bytes, "lobpcg_update")) ||
+      (as_dev && (rc = check_lobpcg_geom(as_dev, ld, n, value_bytes, "lobpcg_update"))))
+    return rc;
+  if (as_dev) {
+    // the two blocks, first byte to the last row of the last column, must not overlap
+    const uintptr_t span = (uintptr_t)(((long long)(3 * k - 1) * ld + n) * value_bytes), s0 = (uintptr_t)s_dev, a0 = (uintptr_t)as_dev;
+    if (s0 < a0 + span && a0 < s0 + span) return set_err(CFS_HIP_ERR_ARG, "lobpcg_update: the two blocks overlap");
+  }
+  if ((rc = check_lobpcg_dev(s_dev, "lobpcg_update", &dev)) || (as_dev && (rc = check_lobpcg_dev(as_dev, "lobpcg_update", &dev)))) return rc;
+  DeviceGuard dg(dev);
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    return cfs_solver::debug_update<decltype(v)>(s_dev, as_dev, ld, n, k, m, idx, with_p, c, (hipStream_t)stream);
   });
 }
 
 int cfs_hip_debug_lobpcg_update(void *s_dev, long long ld, long long n, int k, int m, const double *c, int value_bytes, void *stream) {
-  if (!s_dev || !c) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  if (k < 1 || k > CFS_HIP_LOBPCG_MAX_K || m < 1 || m > 3 * k)
-    return set_err(CFS_HIP_ERR_ARG, "lobpcg_update: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + " and 1 <= m <= 3 k");
-  int dev = -1, rc;
-  if ((rc = check_lobpcg_block(s_dev, ld, n, value_bytes, "lobpcg_update", &dev))) return rc;
-  DeviceGuard dg(dev);
-  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
-    return cfs_solver::debug_update<decltype(v)>(s_dev, ld, n, k, m, c, (hipStream_t)stream);
+  int idx[3 * CFS_HIP_LOBPCG_MAX_K];
+  for (int j = 0; j < 3 * CFS_HIP_LOBPCG_MAX_K; ++j) idx[j] = j;
+  return cfs_hip_debug_lobpcg_update_cols(s_dev, nullptr, ld, n, k, m, idx, 1, c, value_bytes, stream);
+}
+
+int cfs_hip_sym_debug_lobpcg_residual(cfs_hip_sym_t h, int block_rows, const void *x_dev, const void *ax_dev, void *w_dev, long long ld,
+                                      int k, const double *theta, unsigned active, double *sums, void *stream) {
+  if (!h || !x_dev || !ax_dev || !w_dev || !theta || !sums) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (k < 1 || k > CFS_HIP_LOBPCG_MAX_K)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: bad k: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + ", got k = " + std::to_string(k));
+  if (block_rows != 0 && !block_rows_ok(block_rows))
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: block_rows " + std::to_string(block_rows) + " is not one of 0, 1, 2, 3, 4, 6");
+  if (active >> k) return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: active names a pair that is not in [0, k)");
+  if ((((uintptr_t)x_dev) | ((uintptr_t)ax_dev) | ((uintptr_t)w_dev)) & 15)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: X, AX and W must be 16-byte aligned");
+  if (!h->send_rows().empty() || h->rows() != h->n())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "lobpcg_residual: a handle of the whole matrix, not a shard");
+  const long long n = h->n();
+  // (the upper limit keeps the byte spans of k columns within 63 bits)
+  if (ld < n || ld > (1LL << 62) / (8LL * CFS_HIP_LOBPCG_MAX_K) || (ld * h->value_bytes) % 16 != 0)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: bad ld " + std::to_string(ld) + ": at least n = " + std::to_string(n) +
+                                        " and a multiple of 16 bytes");
+  // W is written while X and AX are read: the k columns of W may not overlap those of X or AX
+  const uintptr_t span = (uintptr_t)(((long long)(k - 1) * ld + n) * h->value_bytes), w0 = (uintptr_t)w_dev;
+  for (const void *p : {x_dev, ax_dev})
+    if ((uintptr_t)p < w0 + span && w0 < (uintptr_t)p + span)
+      return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: W overlaps X or AX");
+  if (block_rows >= 2) {
+    int ngpus = 1;
+    if (cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
+      return set_err(CFS_HIP_ERR_UNSUPPORTED, "lobpcg_residual: block Jacobi needs the whole matrix on one device (blocks straddle the "
+                                              "row splits of a multi-device handle)");
+  }
+  int rc;
+  if ((rc = check_eigs_ptr(h, x_dev, "lobpcg_residual", "X")) || (rc = check_eigs_ptr(h, ax_dev, "lobpcg_residual", "AX")) ||
+      (rc = check_eigs_ptr(h, w_dev, "lobpcg_residual", "W")))
+    return rc;
+  h->ok_x = h->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  return with_lobpcg_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::debug_residual<decltype(v), decltype(bs)::value>(h, x_dev, ax_dev, w_dev, ld, k, theta, active, sums, st);
   });
 }
 

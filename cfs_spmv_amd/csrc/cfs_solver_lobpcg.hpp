@@ -387,59 +387,16 @@ int lobpcg_update(V *sbuf, V *asbuf, long long ld, long long n, const LobpcgCols
   return 0;
 }
 
-// cfs_hip_debug_gram
-template <typename V>
-int debug_gram(const void *s_dev, const void *t_dev, long long ld, long long n, int m, double *g, double *hh, hipStream_t st) {
-  cfs_rt::DevBuf pbuf, obuf;
-  int rc;
-  if ((rc = pbuf.alloc(lobpcg_gram_part_bytes(m))) || (rc = obuf.alloc((size_t)2 * m * m * sizeof(double)))) return rc;
-  LobpcgCols cols;
-  cols.m = m;
-  for (int j = 0; j < kLobM; ++j) cols.idx[j] = j;
-  return lobpcg_gram<V>((const V *)s_dev, (const V *)t_dev, ld, n, cols, 1, (double *)pbuf.p, (double *)obuf.p, g, hh, st);
-}
-
-// cfs_hip_debug_lobpcg_update
-template <typename V> int debug_update(void *s_dev, long long ld, long long n, int k, int m, const double *c, hipStream_t st) {
-  cfs_rt::DevBuf cbuf;
-  int rc;
-  if ((rc = cbuf.alloc((size_t)m * 2 * k * sizeof(double)))) return rc;
-  LobpcgCols cols;
-  cols.m = m;
-  for (int j = 0; j < kLobM; ++j) cols.idx[j] = j;
-  if ((rc = lobpcg_update<V>((V *)s_dev, (V *)nullptr, ld, n, cols, k, 1, c, (double *)cbuf.p, st))) return rc;
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-
-// cfs_hip_sym_lobpcg, and with debug_iters >= 0 cfs_hip_sym_debug_lobpcg: iteration 0 and debug_iters more, every
-// pair active, no convergence test, no confirm step (arguments checked by the caller)
-template <typename V, int BS, class Handle>
-int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0,
-           double *eigenvalues, void *vectors_dev, long long ldx, double *residuals, int *nconv_out, int *iterations_out,
-           int *products_out, hipStream_t st) {
-  using cfs_rt::DevBuf;
-  const bool debug = debug_iters >= 0;
-  const long long n = h->n();
-  const long long ld = (n + Vec16<V>::W - 1) / Vec16<V>::W * Vec16<V>::W; // columns 16-byte aligned
-  constexpr int B = BS < 1 ? 1 : BS;
-  const long long nb = (n + B - 1) / B;
-  const int mmax = 3 * k;
-  const double unit = sizeof(V) == 8 ? 0x1p-53 : 0x1p-24, drop = 64.0 * unit;
-  DevBuf sb, asb, dbuf, pbuf, gpart, gout, cdev, nout;
-  int rc;
-  if ((rc = sb.alloc((size_t)mmax * ld * sizeof(V) + 64)) || (rc = asb.alloc((size_t)mmax * ld * sizeof(V) + 64)) ||
-      (rc = pbuf.alloc((size_t)std::max<int>(P_COUNT, 2 * kLobK) * kGrid * sizeof(double))) || (rc = gpart.alloc(lobpcg_gram_part_bytes(mmax))) ||
-      (rc = gout.alloc((size_t)2 * mmax * mmax * sizeof(double))) || (rc = cdev.alloc((size_t)mmax * 2 * k * sizeof(double))) ||
-      (rc = nout.alloc((size_t)2 * kLobK * sizeof(double))))
-    return rc;
-  V *S = (V *)sb.p, *AS = (V *)asb.p;
-  double *part = (double *)pbuf.p;
-  auto col = [&](V *base, int c) { return base + (long long)c * ld; };
-  HIPCHK(hipMemsetAsync(part, 0, pbuf.bytes, st));
-  // the preconditioner, exactly as cfs_hip_sym_pcg / _pcg_block build theirs; refused before anything else happens
+// The preconditioner of the iteration, exactly as cfs_hip_sym_pcg / _pcg_block build theirs: dbuf <- the inverse
+// diagonal (BS = 1, cg_dinv_kernel) or the packed inverse node blocks (BS >= 2, cg_binv_kernel); a diagonal entry or a
+// block that is not positive (definite) is refused.  BS = 0: nothing.  part: P_COUNT x kGrid doubles, zeroed, on `st`.
+template <typename V, int BS, class Handle> int lobpcg_precond(Handle *h, cfs_rt::DevBuf &dbuf, double *part, hipStream_t st) {
   if constexpr (BS >= 1) {
-    DevBuf blkbuf;
+    const long long n = h->n();
+    constexpr int B = BS;
+    const long long nb = (n + B - 1) / B;
+    cfs_rt::DevBuf blkbuf;
+    int rc;
     if ((rc = dbuf.alloc((size_t)nb * tri_words(B) * sizeof(V) + 64))) return rc;
     if constexpr (BS >= 2) {
       if ((rc = blkbuf.alloc((size_t)nb * BS * BS * sizeof(V) + 64)) || (rc = h->block_diagonal(blkbuf.p, BS, st))) return rc;
@@ -462,6 +419,99 @@ int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_it
       return cfs_rt::set_err(CFS_HIP_ERR_ARG, "lobpcg: Jacobi needs a positive diagonal, " + std::to_string((long long)bad) + " of " +
                                                   std::to_string(n) + " entries are zero, negative or not finite");
   }
+  return 0;
+}
+inline size_t lobpcg_part_bytes() { return (size_t)std::max<int>(P_COUNT, 2 * kLobK) * kGrid * sizeof(double); }
+
+// step 4 and the host's look: sums[2 i] = R_i . R_i, sums[2 i + 1] = X_i . X_i (host, 2 k doubles); W_i written for the
+// bits set in `active`.  x, ax, w: column 0 of X, AX and W;  out_dev: 2 k doubles.  Waits for the stream.
+template <typename V, int BS>
+int lobpcg_residual(const V *x, const V *ax, V *w, long long ld, long long n, int k, const double *theta, unsigned active,
+                    const V *minv, double *part, double *out_dev, double *sums, hipStream_t st) {
+  constexpr int B = BS < 1 ? 1 : BS;
+  const long long nb = (n + B - 1) / B;
+  LobpcgTheta th;
+  for (int i = 0; i < kLobK; ++i) th.theta[i] = i < k ? theta[i] : 0.0;
+  th.active = active;
+  hipLaunchKernelGGL((lobpcg_residual_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, x, ax, w, ld, n, k, th, minv, nb, part);
+  hipLaunchKernelGGL(lobpcg_reduce_kernel, dim3(2 * k), dim3(kThreads), 0, st, (const double *)part, out_dev);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(sums, out_dev, (size_t)2 * k * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+
+// cfs_hip_debug_gram_cols (cfs_hip_debug_gram: the identity list and full_h = 1)
+template <typename V>
+int debug_gram(const void *s_dev, const void *t_dev, long long ld, long long n, int m, const int *idx, int full_h, double *g,
+               double *hh, hipStream_t st) {
+  cfs_rt::DevBuf pbuf, obuf;
+  int rc;
+  if ((rc = pbuf.alloc(lobpcg_gram_part_bytes(m))) || (rc = obuf.alloc((size_t)2 * m * m * sizeof(double)))) return rc;
+  LobpcgCols cols;
+  cols.m = m;
+  for (int j = 0; j < kLobM; ++j) cols.idx[j] = j < m ? idx[j] : 0;
+  return lobpcg_gram<V>((const V *)s_dev, (const V *)t_dev, ld, n, cols, full_h, (double *)pbuf.p, (double *)obuf.p, g, hh, st);
+}
+
+// cfs_hip_debug_lobpcg_update_cols (cfs_hip_debug_lobpcg_update: the identity list, with_p = 1, no second block)
+template <typename V>
+int debug_update(void *s_dev, void *as_dev, long long ld, long long n, int k, int m, const int *idx, int with_p, const double *c,
+                 hipStream_t st) {
+  cfs_rt::DevBuf cbuf;
+  int rc;
+  if ((rc = cbuf.alloc((size_t)m * 2 * k * sizeof(double)))) return rc;
+  LobpcgCols cols;
+  cols.m = m;
+  for (int j = 0; j < kLobM; ++j) cols.idx[j] = j < m ? idx[j] : 0;
+  if ((rc = lobpcg_update<V>((V *)s_dev, (V *)as_dev, ld, n, cols, k, with_p, c, (double *)cbuf.p, st))) return rc;
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// cfs_hip_sym_debug_lobpcg_residual: the solver's preconditioner set-up, then step 4 alone
+template <typename V, int BS, class Handle>
+int debug_residual(Handle *h, const void *x_dev, const void *ax_dev, void *w_dev, long long ld, int k, const double *theta,
+                   unsigned active, double *sums, hipStream_t st) {
+  cfs_rt::DevBuf dbuf, pbuf, nout;
+  int rc;
+  if ((rc = pbuf.alloc(lobpcg_part_bytes())) || (rc = nout.alloc((size_t)2 * kLobK * sizeof(double)))) return rc;
+  HIPCHK(hipMemsetAsync(pbuf.p, 0, pbuf.bytes, st));
+  if ((rc = lobpcg_precond<V, BS>(h, dbuf, (double *)pbuf.p, st))) return rc;
+  std::vector<double> hn(2 * kLobK);
+  if ((rc = lobpcg_residual<V, BS>((const V *)x_dev, (const V *)ax_dev, (V *)w_dev, ld, h->n(), k, theta, active, (const V *)dbuf.p,
+                                   (double *)pbuf.p, (double *)nout.p, hn.data(), st)))
+    return rc;
+  std::copy(hn.begin(), hn.begin() + 2 * k, sums);
+  return 0;
+}
+
+// cfs_hip_sym_lobpcg, and with debug_iters >= 0 cfs_hip_sym_debug_lobpcg: iteration 0 and debug_iters more, every
+// pair active, no convergence test, no confirm step (arguments checked by the caller)
+template <typename V, int BS, class Handle>
+int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0,
+           double *eigenvalues, void *vectors_dev, long long ldx, double *residuals, int *nconv_out, int *iterations_out,
+           int *products_out, hipStream_t st) {
+  using cfs_rt::DevBuf;
+  const bool debug = debug_iters >= 0;
+  const long long n = h->n();
+  const long long ld = (n + Vec16<V>::W - 1) / Vec16<V>::W * Vec16<V>::W; // columns 16-byte aligned
+  const int mmax = 3 * k;
+  const double unit = sizeof(V) == 8 ? 0x1p-53 : 0x1p-24, drop = 64.0 * unit;
+  DevBuf sb, asb, dbuf, pbuf, gpart, gout, cdev, nout;
+  int rc;
+  if ((rc = sb.alloc((size_t)mmax * ld * sizeof(V) + 64)) || (rc = asb.alloc((size_t)mmax * ld * sizeof(V) + 64)) ||
+      (rc = pbuf.alloc(lobpcg_part_bytes())) || (rc = gpart.alloc(lobpcg_gram_part_bytes(mmax))) ||
+      (rc = gout.alloc((size_t)2 * mmax * mmax * sizeof(double))) || (rc = cdev.alloc((size_t)mmax * 2 * k * sizeof(double))) ||
+      (rc = nout.alloc((size_t)2 * kLobK * sizeof(double))))
+    return rc;
+  V *S = (V *)sb.p, *AS = (V *)asb.p;
+  double *part = (double *)pbuf.p;
+  auto col = [&](V *base, int c) { return base + (long long)c * ld; };
+  HIPCHK(hipMemsetAsync(part, 0, pbuf.bytes, st));
+  // the preconditioner; refused before anything else happens
+  if ((rc = lobpcg_precond<V, BS>(h, dbuf, part, st))) return rc;
   const V *minv = (const V *)dbuf.p;
   int products = 0, it = 0;
   auto product = [&](int c) -> int { // AS[:, c] = A S[:, c]
@@ -497,15 +547,9 @@ int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_it
   };
   // step 4 and the host's look at the norms: res[i] = ||R_i|| / ||X_i||
   auto norms = [&](unsigned wmask) -> int {
-    LobpcgTheta th;
-    for (int i = 0; i < kLobK; ++i) th.theta[i] = i < k ? theta[i] : 0.0;
-    th.active = wmask;
-    hipLaunchKernelGGL((lobpcg_residual_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)S, (const V *)AS, col(S, k), ld, n, k,
-                       th, minv, nb, part);
-    hipLaunchKernelGGL(lobpcg_reduce_kernel, dim3(2 * k), dim3(kThreads), 0, st, (const double *)part, (double *)nout.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hn.data(), nout.p, (size_t)2 * k * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    int r2 = lobpcg_residual<V, BS>((const V *)S, (const V *)AS, col(S, k), ld, n, k, theta.data(), wmask, minv, part, (double *)nout.p,
+                                    hn.data(), st);
+    if (r2) return r2;
     for (int i = 0; i < k; ++i) res[i] = std::sqrt(hn[2 * i]) / std::sqrt(hn[2 * i + 1]);
     return 0;
   };

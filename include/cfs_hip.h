@@ -641,6 +641,41 @@ int cfs_hip_sym_debug_lobpcg(cfs_hip_sym_t h, int k, int block_rows, const void 
  * row-major on the host, X <- (V)(S c[:, :k]) and P <- (V)(S c[:, k:]), in place.  The call waits for the kernel. */
 int cfs_hip_debug_lobpcg_update(void *s_dev, long long ld, long long n, int k, int m, const double *c, int value_bytes,
                                 void *stream);
+/* The three kernels in the forms the solver launches them in, through the solver's own launch functions.  The blocks
+ * are device memory of one device, column c at + c ld values; the pointers and ld value_bytes are multiples of 16.
+ * Each call waits for its kernels.  CFS_HIP_ERR_ARG, before any device work, in this order: a null pointer ("null");
+ * the sizes (k, m, then an idx[j] out of range, then full_h / with_p / block_rows / active); value_bytes; a pointer
+ * not 16-byte aligned or a bad n / ld; an overlap; memory that is not device memory of one device.
+ *
+ * cfs_hip_debug_gram_cols: step 1 on the m listed columns (1 <= m <= 48): column j of S and of T is the physical
+ * column idx[j], 0 <= idx[j] < 48, in any order; the columns that are not listed are not read.  g, hh: m x m row-major
+ * on the host.  full_h = 0 is the solver's form: only the upper triangles of G and H are summed and the lower ones are
+ * their mirror images, bit for bit; full_h = 1 sums every entry of H.  The order of summation depends on (n, m,
+ * full_h) alone, not on idx.  cfs_hip_debug_gram is this call with idx[j] = j and full_h = 1.
+ *
+ * cfs_hip_debug_lobpcg_update_cols: step 3 on blocks of 3 k columns (X | W | P).  S = the m listed columns
+ * (1 <= m <= 3 k, 0 <= idx[j] < 3 k) of s_dev; c: m x nout row-major on the host, nout = 2 k with with_p = 1 and k
+ * with with_p = 0.  Column o < k <- (V)(S c[:, o]) and, with_p = 1, column 2 k + o <- (V)(S c[:, k + o]): for every
+ * row acc = 0, then acc = acc + s_j c_jo for j = 0 .. m - 1 in fp64 with a separate multiply and add, rounded once.
+ * In place: a listed column may be an output.  WRITTEN: rows [0, n) of the k columns of X and, with_p = 1, of ALL k
+ * columns of P, listed or not; nothing else -- not W, not P with with_p = 0, not the rows [n, ld).  as_dev: NULL, or a
+ * second block of the same shape that does not overlap the first; it gets the same c and idx in the same launch.
+ * cfs_hip_debug_lobpcg_update is this call with idx[j] = j, with_p = 1 and as_dev = NULL.
+ *
+ * cfs_hip_sym_debug_lobpcg_residual: step 4 alone, after the solver's own preconditioner set-up for block_rows (0, 1,
+ * 2, 3, 4, 6; a diagonal entry or a block that is not positive (definite) is refused with the words of
+ * cfs_hip_sym_lobpcg, nothing written).  x_dev, ax_dev, w_dev: k columns each (1 <= k <= CFS_HIP_LOBPCG_MAX_K) of the
+ * handle's value type on the handle's device, ld >= n; the columns of W overlap neither X nor AX.  theta: k host
+ * doubles.  active: bit i set: W_i <- (V)(M^-1 (AX_i - theta_i X_i)), rows [0, n); a W_i whose bit is clear is not
+ * touched; a bit from k on is refused.  sums: 2 k host doubles, sums[2 i] = R_i . R_i and sums[2 i + 1] = X_i . X_i
+ * for EVERY pair, whatever the mask.  A shard, or block_rows >= 2 on a multi-device handle: CFS_HIP_ERR_UNSUPPORTED. */
+int cfs_hip_debug_gram_cols(const void *s_dev, const void *t_dev, long long ld, long long n, int m, const int *idx,
+                            int full_h, int value_bytes, double *g, double *hh, void *stream);
+int cfs_hip_debug_lobpcg_update_cols(void *s_dev, void *as_dev, long long ld, long long n, int k, int m, const int *idx,
+                                     int with_p, const double *c, int value_bytes, void *stream);
+int cfs_hip_sym_debug_lobpcg_residual(cfs_hip_sym_t h, int block_rows, const void *x_dev, const void *ax_dev, void *w_dev,
+                                      long long ld, int k, const double *theta, unsigned active, double *sums,
+                                      void *stream);
 
 /* ---- sharded operation: y_block = local rows; contributions to rows owned
  *      by lower ranks are packed into send_buf (device), exchanged by the

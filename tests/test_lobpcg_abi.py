@@ -37,6 +37,13 @@ SIGNATURES = {
                                  "double *theta", "void *vectors_dev", "long long ld", "double *resnorms", "void *stream"],
     "cfs_hip_debug_lobpcg_update": ["void *s_dev", "long long ld", "long long n", "int k", "int m", "const double *c",
                                     "int value_bytes", "void *stream"],
+    "cfs_hip_debug_gram_cols": ["const void *s_dev", "const void *t_dev", "long long ld", "long long n", "int m", "const int *idx",
+                                "int full_h", "int value_bytes", "double *g", "double *hh", "void *stream"],
+    "cfs_hip_debug_lobpcg_update_cols": ["void *s_dev", "void *as_dev", "long long ld", "long long n", "int k", "int m",
+                                         "const int *idx", "int with_p", "const double *c", "int value_bytes", "void *stream"],
+    "cfs_hip_sym_debug_lobpcg_residual": ["cfs_hip_sym_t h", "int block_rows", "const void *x_dev", "const void *ax_dev", "void *w_dev",
+                                          "long long ld", "int k", "const double *theta", "unsigned active", "double *sums",
+                                          "void *stream"],
 }
 
 
@@ -61,7 +68,7 @@ def test_the_symbols_are_declared_exported_and_bound(name):
     assert lib.cfs_hip_abi_version() == 4
     vp, ip, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)
     ctype = {"cfs_hip_sym_t": vp, "void *": vp, "const void *": vp, "int": C.c_int, "double": C.c_double, "int *": ip,
-             "double *": dp, "const double *": dp, "long long": C.c_longlong}
+             "double *": dp, "const double *": dp, "long long": C.c_longlong, "const int *": ip, "unsigned": C.c_uint}
     declared = [ctype[re.sub(r"\w+$", "", p).strip()] for p in params]
     assert getattr(lib, name).argtypes == declared
 
@@ -153,6 +160,67 @@ def test_checks_that_need_no_device_answer_before_the_handle_is_looked_at():
         assert lib.cfs_hip_debug_lobpcg_update(s, ld, n, 1, 2, g, vb, None) == _lib.ERR_ARG
     for k, m in ((0, 1), (17, 3), (2, 7), (2, 0)):
         assert lib.cfs_hip_debug_lobpcg_update(p, 16, 16, k, m, g, 8, None) == _lib.ERR_ARG and b"3 k" in lib.cfs_hip_last_error()
+    assert lib.cfs_hip_runtime_bound() == bound  # nothing above initialised the runtime
+
+
+def test_the_kernel_forms_refuse_in_the_documented_order():
+    """cfs_hip_debug_gram_cols, cfs_hip_debug_lobpcg_update_cols, cfs_hip_sym_debug_lobpcg_residual: a null pointer, the
+    sizes (an index out of range among them), value_bytes, alignment and ld, each with every later argument bad as well,
+    before a pointer is classified or the handle is looked at; nothing is written"""
+    lib = cfs.load()
+    bound = lib.cfs_hip_runtime_bound()
+    g, hh = (C.c_double * 9)(*([7.0] * 9)), (C.c_double * 9)(*([7.0] * 9))
+    p, odd = C.c_void_p(0x4000), C.c_void_p(0x4008)
+    ints = lambda *v: (C.c_int * len(v))(*v)
+    ok = ints(0, 2, 5)
+
+    def refused(f, word, *args):
+        assert f(*args, None) == _lib.ERR_ARG, (f.__name__, args)
+        assert word in lib.cfs_hip_last_error(), (f.__name__, args, lib.cfs_hip_last_error())
+    gram = lib.cfs_hip_debug_gram_cols
+    for s, t, idx, a, b in ((None, p, ok, g, hh), (p, None, ok, g, hh), (p, p, None, g, hh), (p, p, ok, None, hh), (p, p, ok, g, None)):
+        refused(gram, b"null", s, t, 15, 16, 49, idx, 2, 3, a, b)
+    for m in (0, -1, 49):
+        refused(gram, b"m must lie", odd, p, 15, 16, m, ints(48, 0, 0), 2, 3, g, hh)
+    for idx in (ints(0, 48, 1), ints(0, 1, -1), ints(1 << 20, 0, 0)):
+        refused(gram, b"is not a column", odd, p, 15, 16, 3, idx, 2, 3, g, hh)
+    for full_h in (2, -1):
+        refused(gram, b"full_h", odd, p, 15, 16, 3, ok, full_h, 3, g, hh)
+    refused(gram, b"value_bytes", odd, p, 15, 16, 3, ok, 0, 3, g, hh)
+    for s, t, ld, n in ((odd, p, 16, 16), (p, odd, 16, 16), (p, p, 15, 16), (p, p, 17, 17), (p, p, 16, 0), (p, p, 1 << 60, 16)):
+        refused(gram, b"multiples of 16 bytes", s, t, ld, n, 3, ok, 0, 8, g, hh)
+    assert list(g) == [7.0] * 9 and list(hh) == [7.0] * 9
+
+    upd = lib.cfs_hip_debug_lobpcg_update_cols
+    for s, idx, c in ((None, ok, g), (p, None, g), (p, ok, None)):
+        refused(upd, b"null", s, odd, 15, 16, 0, 3, idx, 2, c, 3)
+    for k, m in ((0, 1), (17, 3), (2, 7), (2, 0)):
+        refused(upd, b"3 k", odd, odd, 15, 16, k, m, ints(48, 0, 0), 2, g, 3)
+    for k, idx in ((1, ints(0, 3, 1)), (2, ints(0, 6, 1)), (16, ints(48, 0, 0)), (2, ints(0, 1, -1))):
+        refused(upd, b"is not a column", odd, odd, 15, 16, k, 3, idx, 2, g, 3)
+    for with_p in (2, -1):
+        refused(upd, b"with_p", odd, odd, 15, 16, 2, 3, ok, with_p, g, 3)
+    refused(upd, b"value_bytes", odd, odd, 15, 16, 2, 3, ok, 1, g, 3)
+    for s, a, ld, n in ((odd, None, 16, 16), (p, odd, 16, 16), (p, None, 15, 16), (p, None, 17, 17), (p, None, 16, 0), (p, p, 1 << 60, 16)):
+        refused(upd, b"multiples of 16 bytes", s, a, ld, n, 2, 3, ok, 1, g, 8)
+    for a in (0x4000, 0x4000 + 8 * (5 * 16 + 14), 0x4000 - 8 * (5 * 16 + 14)):  # (a block: 5 ld + n = 96 values of 8 bytes)
+        refused(upd, b"overlap", p, C.c_void_p(a), 16, 16, 2, 3, ok, 1, g, 8)
+
+    res = lib.cfs_hip_sym_debug_lobpcg_residual
+    h = C.c_void_p(0x1000)  # (never dereferenced: the checks of the other arguments come first)
+    th, sums = (C.c_double * 16)(*([0.5] * 16)), (C.c_double * 32)(*([7.0] * 32))
+    for hh_, x, ax, w, t, s in ((None, p, p, p, th, sums), (h, None, p, p, th, sums), (h, p, None, p, th, sums), (h, p, p, None, th, sums),
+                                (h, p, p, p, None, sums), (h, p, p, p, th, None)):
+        refused(res, b"null", hh_, 5, x, ax, w, 1, 0, t, 1, s)
+    for k in (0, -1, 17):
+        refused(res, b"bad k", h, 5, odd, p, p, 1, k, th, 1 << 20, sums)
+    for block_rows in (5, 7, 8, -1, 12):
+        refused(res, b"block_rows", h, block_rows, odd, p, p, 1, 4, th, 1 << 4, sums)
+    for k, active in ((4, 1 << 4), (4, 0xffffffff), (1, 2), (15, 1 << 15), (16, 1 << 16)):
+        refused(res, b"active", h, 1, odd, p, p, 1, k, th, active, sums)
+    for x, ax, w in ((odd, p, p), (p, odd, p), (p, p, odd)):
+        refused(res, b"16-byte aligned", h, 1, x, ax, w, 1, 4, th, 0xf, sums)
+    assert list(sums) == [7.0] * 32
     assert lib.cfs_hip_runtime_bound() == bound  # nothing above initialised the runtime
 
 
