@@ -128,8 +128,8 @@ def _block_distance(x, ref):
     return float(np.max(np.max(np.abs(x - ref), axis=(1, 2)) / np.max(np.abs(ref), axis=(1, 2))))
 
 
-def block_pcg_reference(n, rp, ci, va, b, minv, ks=(), dtype=None, tol=0.0, maxiter=None):
-    """test_gpu_pcg_steps.pcg_reference with z = Minv r over the node blocks: minv (nb, bs, bs) is converted
+def block_pcg_reference(n, rp, ci, va, b, minv, ks=(), dtype=None, tol=0.0, maxiter=None, x0=None):
+    """test_gpu_pcg_steps.pcg_reference (from u = x0, or 0) with z = Minv r over the node blocks: minv (nb, bs, bs) is converted
     exactly to long double (dtype None) / to fp64 (the working precision: z formed in fp64 from the rounded r
     and never rounded)"""
     import scipy.sparse as sp
@@ -155,7 +155,7 @@ def block_pcg_reference(n, rp, ci, va, b, minv, ks=(), dtype=None, tol=0.0, maxi
         for j in range(bs):  # (ascending j, as the kernels)
             z += M[:, :, j] * rb[:, j:j + 1]
         return z.reshape(-1)[:n]
-    u = np.zeros(n, W)
+    u = np.zeros(n, W) if x0 is None else x0.astype(W)
     r = (b.astype(S) - mv(u).astype(S)).astype(W)
     z = apply(r.astype(S))
     p = z.astype(W)

@@ -18,11 +18,14 @@ long-double run; the GPU is allowed 4 d_k + 16 * 2^-24; d_k > D_LIMIT[float32] =
 Measured on the MI355X (matrix, then for k = 1, 2, 3, 5, 10: d_k / the GPU's deviation):
 
   rand1       1.0e-08/1.0e-08  1.0e-08/1.0e-08  0.0e+00/0.0e+00  0.0e+00/0.0e+00  0.0e+00/0.0e+00
+  rand2       3.3e-08/3.3e-08  7.2e-08/7.2e-08  7.2e-08/7.2e-08  7.2e-08/7.2e-08  7.2e-08/7.2e-08
   rand3       5.8e-08/5.8e-08  7.4e-08/7.4e-08  9.0e-08/9.0e-08  9.0e-08/9.0e-08  9.0e-08/9.0e-08
   rand63      3.7e-08/3.7e-08  5.3e-08/4.1e-08  2.8e-08/4.0e-08  7.7e-08/7.7e-08  7.0e-08/7.0e-08
+  rand64      1.5e-08/1.5e-08  3.4e-08/3.4e-08  4.5e-08/4.5e-08  5.7e-08/5.7e-08  7.2e-08/7.2e-08
   rand65      2.9e-08/4.1e-08  1.0e-07/1.0e-07  1.4e-07/1.4e-07  1.5e-07/1.5e-07  1.6e-07/1.6e-07
   rand257     7.2e-08/7.2e-08  6.2e-08/9.4e-08  8.9e-08/9.4e-08  1.2e-07/1.2e-07  1.5e-07/1.5e-07
   rand1023    3.8e-08/4.4e-08  4.7e-08/4.7e-08  5.9e-08/5.9e-08  6.6e-08/6.6e-08  9.5e-08/9.5e-08
+  rand1026    4.9e-08/4.9e-08  9.7e-08/9.7e-08  9.4e-08/9.4e-08  8.9e-08/8.9e-08  1.5e-07/1.5e-07
   band20001   9.6e-08/9.6e-08  1.5e-07/8.5e-08  1.6e-07/1.2e-07  1.8e-07/1.4e-07  2.3e-07/2.3e-07
   pwtk@0.05   8.2e-08/8.2e-08  2.0e-07/8.8e-08  1.4e-07/8.9e-08  1.8e-07/1.1e-07  1.7e-07/1.3e-07
 
@@ -61,7 +64,7 @@ pytestmark = pytest.mark.gpu
 F32, F64 = np.float32, np.float64
 UNIT32 = 2.0 ** -24
 NO_REPLACEMENT = 1e-150  # delta: r.r would have to fall 300 decades below its reference
-CASES = ["rand1", "rand3", "rand63", "rand65", "rand257", "rand1023", "band20001", "pwtk@0.05"]
+CASES = ["rand1", "rand2", "rand3", "rand63", "rand64", "rand65", "rand257", "rand1023", "rand1026", "band20001", "pwtk@0.05"]
 
 
 @pytest.fixture(autouse=True)
@@ -84,10 +87,10 @@ def jacobi_apply(n, rp, ci, va32):
     return lambda r: r * dinv
 
 
-def block_apply(n, rp, ci, va32, bs):
+def block_apply(n, rp, ci, va32, bs, minv=None):
     """z = Minv r over the node blocks in fp64, Minv the fp64 Cholesky inverse of the fp32 blocks rounded to fp32
-    (ascending j, as the kernels)"""
-    M = cholesky_inverse(node_blocks(n, rp, ci, va32, bs), F64).astype(F32).astype(F64)
+    (ascending j, as the kernels); minv: (nb, bs, bs) fp32 inverse blocks to use instead, converted exactly"""
+    M = (cholesky_inverse(node_blocks(n, rp, ci, va32, bs), F64) if minv is None else minv).astype(F32).astype(F64)
     nb = M.shape[0]
 
     def apply(r):
@@ -100,8 +103,11 @@ def block_apply(n, rp, ci, va32, bs):
     return apply
 
 
-def mixed_reference(n, rp, ci, va64, b, apply, tol, delta, maxiter, check_every, x0=None):
-    """(u, iterations, replacements, fp64 relative residual) of the solver's recurrence, see the module docstring"""
+def mixed_reference(n, rp, ci, va64, b, apply, tol, delta, maxiter, check_every, x0=None, plain=False, margins=None):
+    """(u, iterations, replacements, fp64 relative residual) of the solver's recurrence, see the module docstring.
+    plain: no preconditioner, by the rule of the plain kernels -- p = r, and alpha and beta from r.r of the UNROUNDED
+    residual (apply is not called).  margins: a list that receives |x - y| / max(|x|, |y|) of every comparison
+    r.r > thr (one per iteration) and r.r >= delta^2 rr_ref (one per look) that steers the recurrence"""
     import scipy.sparse as sp
     A64 = sp.csr_matrix((va64, ci, rp), shape=(n, n))
     A32 = sp.csr_matrix((va64.astype(F32), ci, rp), shape=(n, n))
@@ -112,8 +118,12 @@ def mixed_reference(n, rp, ci, va64, b, apply, tol, delta, maxiter, check_every,
     def replace():
         d = b - A64 @ u
         r = d.astype(F32)
-        z = apply(r.astype(F64))
-        return r, z, np.dot(r.astype(F64), z), np.dot(d, d)
+        z = r.astype(F64) if plain else apply(r.astype(F64))
+        return r, z, np.dot(d, d) if plain else np.dot(r.astype(F64), z), np.dot(d, d)
+
+    def apart(x, y):
+        if margins is not None:
+            margins.append(abs(x - y) / max(abs(x), abs(y)) if max(abs(x), abs(y)) > 0 else 0.0)
     r, z, rz, rr = replace()
     p = z.astype(F32)
     bb = np.dot(b, b)
@@ -129,11 +139,13 @@ def mixed_reference(n, rp, ci, va64, b, apply, tol, delta, maxiter, check_every,
             rs = r.astype(F64) - alpha * q.astype(F64)
             rr = np.dot(rs, rs)
             r = rs.astype(F32)
-            z = apply(r.astype(F64))
-            rzn = np.dot(r.astype(F64), z)
+            z = r.astype(F64) if plain else apply(r.astype(F64))
+            rzn = rr if plain else np.dot(r.astype(F64), z)
             p = (z + (rzn / rz if rz != 0 else 0.0) * p.astype(F64)).astype(F32)
             rz, it, folded, flag = rzn, it + 1, False, not (rr > thr)
+            apart(rr, thr)
         rr_ref = max(rr_ref, rr)
+        apart(rr, drop * rr_ref)
         if flag or not (rr >= drop * rr_ref):
             u, xlo = u + xlo.astype(F64), np.zeros(n, F32)
             r, z, rz, rr = replace()

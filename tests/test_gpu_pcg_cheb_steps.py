@@ -74,7 +74,7 @@ def _torch_first(monkeypatch):
 # ---- the CPU side -------------------------------------------------------------------------------------
 class Problem:
     """a matrix in the value type, its product and its base preconditioner M^-1 in long double (dtype None) and in
-    the working precision; minv: the (nb, 3, 3) inverse blocks for base "block_jacobi" """
+    the working precision; minv: the (nb, bs, bs) inverse blocks for base "block_jacobi" """
 
     def __init__(self, n, rp, ci, va, base, minv=None):
         import scipy.sparse as sp
@@ -152,11 +152,11 @@ def poly_reference(P, r, degree, lmin, lmax, dtype=None):
     return z
 
 
-def pcg_cheb_reference(P, b, degree, lmin, lmax, ks=(), dtype=None, tol=0.0, maxiter=None):
-    """{k: (u_k, iterations done)} from u = 0 with the kernels' guards (alpha = 0 when p.q = 0, beta = 0 when r.z = 0,
+def pcg_cheb_reference(P, b, degree, lmin, lmax, ks=(), dtype=None, tol=0.0, maxiter=None, x0=None):
+    """{k: (u_k, iterations done)} from u = x0 (0) with the kernels' guards (alpha = 0 when p.q = 0, beta = 0 when r.z = 0,
     nothing more once r.r is not > tol^2 b.b); out["count"] = iterations until then"""
     W, S = P.prec(dtype)
-    u = np.zeros(P.n, W)
+    u = np.zeros(P.n, W) if x0 is None else x0.astype(W)
     r = (b.astype(S) - P.mv(u, dtype).astype(S)).astype(W)
     rr = np.dot(r.astype(S), r.astype(S))
     stop = S(tol) * S(tol) * np.dot(b.astype(S), b.astype(S))
@@ -202,12 +202,13 @@ def power_reference(P, v0, steps, dtype=None):
 
 
 # ---- the GPU side -------------------------------------------------------------------------------------
-def _problem(name, dtype, base, A=None):
-    """(Problem, handle): the scaled matrix of test_gpu_pcg_steps.py; the inverse blocks from the handle"""
+def _problem(name, dtype, base, A=None, block=3):
+    """(Problem, handle): the scaled matrix of test_gpu_pcg_steps.py ("rotated<bs>": rotated_node_blocks(bs) as it
+    is); the inverse blocks of `block` rows from the handle"""
     import torch
     import cfs_spmv_amd as cfs
-    if name == "rotated3":
-        n, rp, ci, va, _ = rotated_node_blocks(3)
+    if name.startswith("rotated"):
+        n, rp, ci, va, _ = rotated_node_blocks(int(name[7:]))
         va = va.astype(dtype)
     else:
         n, rp, ci, va = _matrix(name)
@@ -216,25 +217,26 @@ def _problem(name, dtype, base, A=None):
         A = cfs.SymMatrix(n, rp, ci, va)
     minv = None
     if base == "block_jacobi":
-        minv = A.block_inverse(3)
+        minv = A.block_inverse(block)
         torch.cuda.synchronize()
         minv = minv.cpu().numpy()
     return Problem(n, rp, ci, va, base, minv), A
 
 
-def _apply_gpu(A, r, base, degree, lmin, lmax):
+def _apply_gpu(A, r, base, degree, lmin, lmax, block=3):
     import torch
     rd = torch.from_numpy(r).cuda()
     z = torch.full_like(rd, float("nan"))
-    A.cheb_apply(z, rd, lmin, lmax, base=base, block=3, degree=degree)
+    A.cheb_apply(z, rd, lmin, lmax, base=base, block=block, degree=degree)
     torch.cuda.synchronize()
     return z.cpu().numpy()
 
 
-def _native(A, b, **kw):
+def _native(A, b, x0=None, **kw):
     import torch
     from cfs_spmv_amd.solver import pcg_cheb_native
-    u, it, res, used = pcg_cheb_native(A, torch.from_numpy(b).cuda(), **kw)
+    x0 = None if x0 is None else torch.from_numpy(x0).cuda()
+    u, it, res, used = pcg_cheb_native(A, torch.from_numpy(b).cuda(), x0=x0, **kw)
     torch.cuda.synchronize()
     return u.cpu().numpy(), it, res, used
 
@@ -275,10 +277,10 @@ def test_cheb_apply_against_the_long_double_recurrence(name, dtype):
 
 
 # ---- 2. the iterates ----------------------------------------------------------------------------------
-def _check_iterates(name, P, b, dtype, degree, lmin, lmax, run, label="", ks=KS):
-    """run(k) -> (u_k, iterations) on the GPU; asserts every k of ks against the long-double iterate"""
-    ref = pcg_cheb_reference(P, b, degree, lmin, lmax, ks)
-    work = pcg_cheb_reference(P, b, degree, lmin, lmax, ks, dtype)
+def _check_iterates(name, P, b, dtype, degree, lmin, lmax, run, label="", ks=KS, x0=None):
+    """run(k) -> (u_k, iterations) on the GPU from u = x0 (0); asserts every k of ks against the long-double iterate"""
+    ref = pcg_cheb_reference(P, b, degree, lmin, lmax, ks, x0=x0)
+    work = pcg_cheb_reference(P, b, degree, lmin, lmax, ks, dtype, x0=x0)
     errors = []
     for k in ks:
         u_ref, _ = ref[k]
@@ -290,7 +292,7 @@ def _check_iterates(name, P, b, dtype, degree, lmin, lmax, run, label="", ks=KS)
               f"allowed={allowed:.3e} it={it}")
         # fewer than k iterations only where the recurrence's residual can vanish: the Krylov space is exhausted
         # (after n iterations -- or after the first when a single block makes M the matrix itself)
-        if not (it == k if k < P.n and (P.base != "block_jacobi" or P.n > 3) else 1 <= it <= k):
+        if not (it == k if k < P.n and (P.base != "block_jacobi" or P.minv.shape[0] > 1) else 1 <= it <= k):
             errors.append(f"k={k}: {it} iterations")
         if not g <= allowed:
             errors.append(f"k={k}: deviation {g:.3e} from the long-double iterate, allowed {allowed:.3e} (d_k = {d:.3e})")
