@@ -1486,6 +1486,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
 #include "cfs_solver_eigs.hpp" // thick-restart Lanczos for extreme eigenpairs: tall-skinny algebra against a resident basis
 #include "cfs_solver_lobpcg.hpp" // LOBPCG for the smallest eigenpairs with the PCG preconditioners: a small SYRK per iteration
 #include "cfs_solver_cheb.hpp" // a Chebyshev polynomial in M^-1 A as the PCG preconditioner, and the power method for its bound
+#include "cfs_solver_amg.hpp" // an aggregation multigrid V-cycle as the PCG preconditioner: the hierarchy on the host, the cycle on the device
 #include "cfs_multi.hpp"   // one host thread, N devices: MultiSym, its create and cfs_hip_sym_multi_*
 
 
@@ -2228,6 +2229,131 @@ int cfs_hip_debug_cheb_coeffs(int degree, double lmin, double lmax, double *thet
   int rc = check_cheb_args("cheb_coeffs", 0, degree, lmin, lmax, true);
   if (rc) return rc;
   cfs_solver::cheb_coeffs(degree, lmin, lmax, theta, c1, c2);
+  return 0;
+}
+
+// ---- aggregation multigrid (cfs_solver_amg.hpp) ------------------------------------------------------
+template <typename V>
+static int amg_create(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const V *values, const cfs_hip_amg_options *opt,
+                      cfs_hip_amg_t *out) {
+  if (out) *out = nullptr;
+  if (!h || !out || !rowptr || n < 0 || (n > 0 && rowptr[n] > 0 && (!colind || !values)))
+    return set_err(CFS_HIP_ERR_ARG, "amg_create: null argument");
+  const int passes = opt && opt->passes ? opt->passes : 2, degree = opt && opt->degree ? opt->degree : 1;
+  const int coarse_max = opt && opt->coarse_max ? opt->coarse_max : 512;
+  const double ratio = opt && opt->ratio != 0.0 ? opt->ratio : 4.0;
+  if (passes < 1 || passes > 3) return set_err(CFS_HIP_ERR_ARG, "amg_create: passes must lie in [1, 3], got " + std::to_string(passes));
+  if (degree < 1 || degree > 4) return set_err(CFS_HIP_ERR_ARG, "amg_create: the degree must lie in [1, 4], got " + std::to_string(degree));
+  if (!std::isfinite(ratio) || !(ratio > 1.0))
+    return set_err(CFS_HIP_ERR_ARG, "amg_create: the ratio lmax / lmin must be finite and > 1, got " + std::to_string(ratio));
+  if (coarse_max < 1 || coarse_max > CFS_HIP_AMG_MAX_COARSE)
+    return set_err(CFS_HIP_ERR_ARG, "amg_create: coarse_max must lie in [1, " + std::to_string(CFS_HIP_AMG_MAX_COARSE) + "], got " +
+                                        std::to_string(coarse_max));
+  SymMatrix<V> *m = dynamic_cast<SymMatrix<V> *>(h);
+  if (!h->send_rows().empty() || h->rows() != h->n())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "amg_create: a handle of the whole matrix, not a shard");
+  int ngpus = 1;
+  if (cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "amg_create: the whole matrix on one device, not a multi-device handle");
+  if (h->value_bytes != (int)sizeof(V) || !m)
+    return set_err(CFS_HIP_ERR_ARG, "amg_create: the handle holds values of " + std::to_string(h->value_bytes) + " bytes, the CSR of " +
+                                        std::to_string(sizeof(V)));
+  if (n != h->n()) return set_err(CFS_HIP_ERR_ARG, "amg_create: n = " + std::to_string(n) + ", the handle has " + std::to_string(h->n()) + " rows");
+  DeviceGuard g(h->device);
+  std::unique_ptr<cfs_solver::Amg<V>> a(new cfs_solver::Amg<V>());
+  a->passes = passes, a->degree = degree, a->coarse_max = coarse_max, a->ratio = ratio, a->device = h->device;
+  const int flags = CFS_HIP_FLAG_NO_CALIBRATE | (m->P.deterministic ? CFS_HIP_FLAG_DETERMINISTIC : 0);
+  h->ok_x = h->ok_y = nullptr;
+  int rc = a->build(h, n, rowptr, colind, values, flags,
+                    [](int ln, const int *rp, const int *ci, const V *va, int fl, cfs_hip_sym_s **lh) {
+                      cfs_hip_options o = {0, 0, 0, fl};
+                      return sym_create<V>(ln, rp, ci, va, 1, 0, nullptr, &o, lh);
+                    });
+  if (rc) return rc; // (the levels built so far go with `a`)
+  *out = a.release();
+  return 0;
+}
+int cfs_hip_amg_create_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
+                           const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create<double>(h, n, rowptr, colind, values, opt, out);
+}
+int cfs_hip_amg_create_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
+                           const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create<float>(h, n, rowptr, colind, values, opt, out);
+}
+int cfs_hip_amg_destroy(cfs_hip_amg_t a) {
+  delete a;
+  return 0;
+}
+int cfs_hip_amg_info(cfs_hip_amg_t a, cfs_hip_amg_info_t *out) {
+  if (!a || !out) return set_err(CFS_HIP_ERR_ARG, "amg_info: null argument");
+  return a->info(out);
+}
+int cfs_hip_amg_level_aggregates(cfs_hip_amg_t a, int level, int *agg, void *w) {
+  if (!a) return set_err(CFS_HIP_ERR_ARG, "amg_level_aggregates: null argument");
+  return a->level_aggregates(level, agg, w);
+}
+int cfs_hip_amg_level_matrix(cfs_hip_amg_t a, int level, int *rowptr, int *colind, void *values) {
+  if (!a) return set_err(CFS_HIP_ERR_ARG, "amg_level_matrix: null argument");
+  return a->level_matrix(level, rowptr, colind, values);
+}
+int cfs_hip_amg_coarse_inverse(cfs_hip_amg_t a, void *inv) {
+  if (!a || !inv) return set_err(CFS_HIP_ERR_ARG, "amg_coarse_inverse: null argument");
+  return a->coarse_inverse(inv);
+}
+int cfs_hip_amg_apply(cfs_hip_amg_t a, void *z_dev, const void *r_dev, void *stream) {
+  if (!a || !z_dev || !r_dev) return set_err(CFS_HIP_ERR_ARG, "amg_apply: null argument");
+  if (z_dev == r_dev) return set_err(CFS_HIP_ERR_ARG, "amg_apply: z and r must be different vectors");
+  if ((((uintptr_t)z_dev) | ((uintptr_t)r_dev)) & 15) return set_err(CFS_HIP_ERR_ARG, "amg_apply: z and r must be 16-byte aligned");
+  cfs_hip_sym_t h = a->fine;
+  int rc = check_placement(h, z_dev, r_dev);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  return a->apply(z_dev, r_dev, (hipStream_t)stream);
+}
+int cfs_hip_sym_pcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const void *b_dev, double tol, int maxiter, int check_every,
+                        int *iterations, double *relres, void *stream) {
+  (void)check_every; // (the host looks after every iteration: cfs_hip.h)
+  if (!h || !a || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (iterations) *iterations = 0;
+  if (relres) *relres = 0.0;
+  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg_amg: u and b must be different vectors");
+  if ((((uintptr_t)u_dev) | ((uintptr_t)b_dev)) & 15) return set_err(CFS_HIP_ERR_ARG, "pcg_amg: u and b must be 16-byte aligned");
+  if (maxiter < 0 || !(tol >= 0.0)) return set_err(CFS_HIP_ERR_ARG, "pcg_amg: bad tolerance / iteration limit");
+  if (!h->send_rows().empty() || h->rows() != h->n())
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_amg: a handle of the whole matrix, not a shard");
+  int ngpus = 1;
+  if (cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_amg: the whole matrix on one device, not a multi-device handle");
+  if (a->fine != h) return set_err(CFS_HIP_ERR_ARG, "pcg_amg: the hierarchy was created on another handle");
+  int rc = check_placement(h, u_dev, b_dev);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  DeviceGuard g(h->device);
+  return a->pcg(u_dev, b_dev, tol, maxiter, iterations, relres, (hipStream_t)stream);
+}
+int cfs_hip_debug_amg_coarsen(int n, const int *rowptr, const int *colind, const double *values, int passes, int *agg, double *w,
+                              int *nc, int *c_rowptr, int *c_colind, double *c_values, long long capacity, long long *c_nnz) {
+  if (n < 0 || !rowptr || !agg || !w || !nc || !c_rowptr || !c_nnz || (n > 0 && rowptr[n] > 0 && (!colind || !values)))
+    return set_err(CFS_HIP_ERR_ARG, "amg_coarsen: null argument");
+  if (passes < 1 || passes > 3) return set_err(CFS_HIP_ERR_ARG, "amg_coarsen: passes must lie in [1, 3], got " + std::to_string(passes));
+  cfs_solver::AmgCsr low, coarse;
+  cfs_solver::amg_lower(n, rowptr, colind, values, low);
+  std::vector<int> ag;
+  std::vector<double> wv;
+  long long bad = 0;
+  if (cfs_solver::amg_coarsen(low, passes, ag, wv, coarse, &bad))
+    return set_err(CFS_HIP_ERR_ARG, "amg_coarsen: Jacobi needs a positive diagonal, " + std::to_string(bad) + " of " + std::to_string(n) +
+                                        " entries are zero, negative or not finite");
+  *nc = coarse.n;
+  *c_nnz = coarse.nnz();
+  for (int i = 0; i < n; ++i) agg[i] = ag[i], w[i] = wv[i];
+  for (int i = 0; i <= coarse.n; ++i) c_rowptr[i] = (int)coarse.rp[i];
+  if (coarse.nnz() > capacity || (coarse.nnz() > 0 && (!c_colind || !c_values)))
+    return set_err(CFS_HIP_ERR_ARG, "amg_coarsen: the coarse matrix has " + std::to_string(coarse.nnz()) + " entries, room for " +
+                                        std::to_string(capacity));
+  for (long long k = 0; k < coarse.nnz(); ++k) c_colind[k] = coarse.ci[k], c_values[k] = coarse.va[k];
   return 0;
 }
 

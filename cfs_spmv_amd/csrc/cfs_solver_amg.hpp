@@ -1,0 +1,724 @@
+// cfs_solver_amg.hpp -- an aggregation multigrid V-cycle as the preconditioner of the native PCG
+// (cfs_hip_sym_pcg_amg), the cycle alone (cfs_hip_amg_apply) and the set-up of its hierarchy
+// (cfs_hip_amg_create_*, cfs_hip_debug_amg_coarsen).
+//
+// SET-UP (host, fp64).  Per level l with matrix A_l (A_0 = the caller's CSR, entries with col <= row):
+//   w_i = 1 / sqrt(a_ii);  B = W A_l W                      (unit diagonal up to rounding)
+//   `passes` rounds of pairwise matching on B: the rows in ascending order, an unmatched row i takes the unmatched
+//   neighbour j != i with the largest s_ij = |b_ij| / sqrt(b_ii b_jj) > 0 (ties: the smallest j) -- the pair is the next
+//   aggregate, a row without a candidate a singleton -- then B <- Q^T B Q, every coarse entry the fp64 sum of its
+//   contributions in ascending (row, column) order (the lower triangle is summed, the upper one is its mirror)
+//   agg_l = the composition of the rounds;  P_l = W Q_1 .. Q_p;  A_{l+1} = the last B = P_l^T A_l P_l
+// The weights make the hierarchy invariant under a symmetric scaling of A: B does not see it.  A_{l+1} is rounded to the
+// value type V before it is coarsened further, so every level is the Galerkin product of the matrix its handle holds.
+// The hierarchy ends with a DENSE level (n_l <= coarse_max; or the coarsening stalled, n_{l+1} > 0.9 n_l, or level 16
+// is reached, at n_l <= 1024), whose inverse -- Cholesky in fp64, solves, symmetrised, rounded to V -- is kept as an
+// n_L x n_L array, or else with a SMOOTHER-ONLY level: a stalled hierarchy degrades to the Chebyshev preconditioner.
+// Levels 1 .. L are handles of the library's own create path (no measured alternatives; deterministic when the fine
+// handle is); level 0 is the caller's handle.  Per non-dense level: dinv as cg_dinv_kernel stores it, the bound
+// lmax = 1.1 x cheb_power (Jacobi, 16 steps, the fixed start vector), lmin = lmax / ratio, the coefficient pairs.
+//
+// ONE CYCLE z = M^-1 r, S_l the level's Chebyshev polynomial of degree m in D^-1 A_l (cfs_solver_cheb.hpp):
+//   dense level:          z = (V)(A_L^-1 r)                                   amg_dense_kernel               1 launch
+//   smoother-only level:  z = S_l r                                           cheb_start_kernel + cheb_chain 1 + 3 (m - 1)
+//   otherwise:            z = S_l r                                                                          1 + 3 (m - 1)
+//                         t = A_l z;  rc_I = (V)(sum_{i in I} w_i (r_i - t_i))  product + amg_restrict_kernel  3
+//                         ec = cycle(l + 1, rc)
+//                         z_i = (V)(z_i + w_i ec_agg(i))                        amg_prolong_kernel             1
+//                         t = A_l z;  d = (V)((1/theta) D^-1 (r - t));  z = (V)(z + d)
+//                                                                             product + amg_restart_kernel   3
+//                         the m - 1 steps of cheb_chain, unchanged                                           3 (m - 1)
+// 8 + 6 (m - 1) launches per multigrid level.  cheb_chain forms r - A z_j from the full iterate, so the Chebyshev
+// iteration from a nonzero start is the same recurrence and post-smoothing needs only the start kernel that takes t.
+// Pre- and post-smoother are the same symmetric polynomial and restriction is the transpose of prolongation with the
+// same stored w: M^-1 is symmetric, and positive definite while every level's spectrum of D^-1 A_l lies in
+// (0, lmin + lmax) -- the margin of cfs_hip_sym_pcg_cheb, here (1 + 1 / ratio) x 1.1 = 1.375 x the estimate at ratio 4.
+//
+// The outer PCG (cg_amg) is cg_cheb with the chain replaced by the cycle:
+//   tile kernel + fold   q = A p
+//   cg_pq_kernel         pq = p . q
+//   amg_update_kernel    u += (rz/pq) p;  r -= (rz/pq) q;  rr' = r . r
+//   the cycle            z = M^-1 r
+//   amg_dot_kernel       rz' = r . z of the stored r and the stored final z
+//   cheb_direction_kernel  p = z + (rz'/rz) p;  iteration count;  converged?  (rr' <= tol^2 b.b)
+// 6 launches and the cycle; a cycle exceeds what may be enqueued between two host looks, so the host looks at the
+// convergence flag after every iteration.
+//
+// Rounding: vectors are stored in V; every update is computed in fp64 from the stored operands and rounded once; the
+// restriction sums its members in ascending order, the dense rows in a fixed lane order; all scalars are the
+// fixed-order partial sums of cfs_solver.hpp.  No atomics: on a deterministic handle the solve is bit-reproducible.
+#pragma once
+
+#include <algorithm>
+#include <chrono>
+#include <memory>
+#include <utility>
+
+// what cfs_hip_amg_t points to
+struct cfs_hip_amg_s {
+  int value_bytes = 8;
+  cfs_hip_sym_s *fine = nullptr; // the handle the hierarchy was created on (level 0; not owned)
+  virtual ~cfs_hip_amg_s() {}
+  virtual int info(cfs_hip_amg_info_t *out) = 0;
+  virtual int level_aggregates(int level, int *agg, void *w) = 0;
+  virtual int level_matrix(int level, int *rowptr, int *colind, void *values) = 0;
+  virtual int coarse_inverse(void *inv) = 0;
+  virtual int apply(void *z_dev, const void *r_dev, hipStream_t st) = 0;
+  virtual int pcg(void *u_dev, const void *b_dev, double tol, int maxiter, int *iterations, double *relres, hipStream_t st) = 0;
+};
+
+namespace cfs_solver {
+
+// ---- set-up on the host ----------------------------------------------------------------------------
+// a CSR in fp64 with 64-bit row pointers: the lower triangle + diagonal of a level, or both triangles of B
+struct AmgCsr {
+  int n = 0;
+  std::vector<long long> rp;
+  std::vector<int> ci;
+  std::vector<double> va;
+  long long nnz() const { return rp.empty() ? 0 : rp.back(); }
+};
+
+// the entries with col <= row of the caller's CSR, columns ascending, duplicates summed in the order given
+template <typename T> inline void amg_lower(int n, const int *rowptr, const int *colind, const T *values, AmgCsr &out) {
+  out.n = n;
+  out.rp.assign((size_t)n + 1, 0);
+  out.ci.clear();
+  out.va.clear();
+  std::vector<std::pair<int, double>> row;
+  for (int i = 0; i < n; ++i) {
+    row.clear();
+    bool sorted = true;
+    for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+      const int j = colind[k];
+      if (j < 0 || j > i) continue;
+      if (!row.empty() && row.back().first >= j) sorted = false;
+      row.emplace_back(j, (double)values[k]);
+    }
+    if (!sorted) std::stable_sort(row.begin(), row.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    for (size_t k = 0; k < row.size(); ++k) {
+      if (k > 0 && row[k].first == row[k - 1].first) {
+        out.va.back() += row[k].second;
+      } else {
+        out.ci.push_back(row[k].first);
+        out.va.push_back(row[k].second);
+      }
+    }
+    out.rp[(size_t)i + 1] = (long long)out.ci.size();
+  }
+}
+
+// both triangles of a symmetric matrix from its lower triangle + diagonal, columns ascending; scale: the entry
+// (i, j) becomes (scale_i a_ij) scale_j, computed once and mirrored (nullptr: the entries as they are)
+inline void amg_mirror(const AmgCsr &low, const double *scale, AmgCsr &full) {
+  const int n = low.n;
+  full.n = n;
+  full.rp.assign((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i)
+    for (long long k = low.rp[i]; k < low.rp[i + 1]; ++k) {
+      full.rp[(size_t)i + 1] += 1;
+      if (low.ci[k] != i) full.rp[(size_t)low.ci[k] + 1] += 1;
+    }
+  for (int i = 0; i < n; ++i) full.rp[(size_t)i + 1] += full.rp[i];
+  full.ci.assign((size_t)full.rp[n], 0);
+  full.va.assign((size_t)full.rp[n], 0.0);
+  std::vector<long long> pos(full.rp.begin(), full.rp.end() - 1);
+  auto value = [&](int i, long long k) { return scale ? (scale[i] * low.va[k]) * scale[low.ci[k]] : low.va[k]; };
+  for (int i = 0; i < n; ++i) // the columns up to the diagonal ...
+    for (long long k = low.rp[i]; k < low.rp[i + 1]; ++k) {
+      full.ci[pos[i]] = low.ci[k];
+      full.va[pos[i]++] = value(i, k);
+    }
+  for (int i = 0; i < n; ++i) // ... then those behind it, rows ascending
+    for (long long k = low.rp[i]; k < low.rp[i + 1]; ++k) {
+      const int j = low.ci[k];
+      if (j == i) continue;
+      full.ci[pos[j]] = i;
+      full.va[pos[j]++] = value(i, k);
+    }
+}
+
+// the diagonal of a lower triangle + diagonal; returns the number of entries that are missing, zero, negative or not finite
+inline long long amg_diagonal(const AmgCsr &low, std::vector<double> &diag) {
+  long long bad = 0;
+  diag.assign((size_t)low.n, 0.0);
+  for (int i = 0; i < low.n; ++i) {
+    const long long e = low.rp[(size_t)i + 1];
+    const double a = (e > low.rp[i] && low.ci[e - 1] == i) ? low.va[e - 1] : 0.0;
+    diag[i] = a;
+    // (!(a > 0): a NaN counts too)
+    if (!(a > 0.0) || a * 0.0 != 0.0) bad += 1;
+  }
+  return bad;
+}
+
+// one round of pairwise matching on B (both triangles): q[i] = the aggregate of row i, numbered in order of creation
+inline int amg_match(const AmgCsr &B, std::vector<int> &q) {
+  const int n = B.n;
+  std::vector<double> diag((size_t)n, 0.0);
+  for (int i = 0; i < n; ++i)
+    for (long long k = B.rp[i]; k < B.rp[i + 1]; ++k)
+      if (B.ci[k] == i) diag[i] = B.va[k];
+  q.assign((size_t)n, -1);
+  int nc = 0;
+  for (int i = 0; i < n; ++i) {
+    if (q[i] >= 0) continue;
+    int best = -1;
+    double sbest = 0.0;
+    for (long long k = B.rp[i]; k < B.rp[i + 1]; ++k) {
+      const int j = B.ci[k];
+      if (j == i || q[j] >= 0) continue;
+      const double s = std::fabs(B.va[k]) / std::sqrt(diag[i] * diag[j]);
+      if (s > sbest) best = j, sbest = s; // (columns ascending and a strict comparison: a tie keeps the smallest j)
+    }
+    q[i] = nc;
+    if (best >= 0) q[best] = nc;
+    ++nc;
+  }
+  return nc;
+}
+
+// the lower triangle + diagonal of Q^T B Q: every entry the sum of its contributions in ascending (row, column) order
+inline void amg_galerkin(const AmgCsr &B, const std::vector<int> &q, int nc, AmgCsr &out) {
+  const int n = B.n;
+  std::vector<int> first((size_t)nc, -1), second((size_t)nc, -1);
+  for (int i = 0; i < n; ++i) (first[q[i]] < 0 ? first[q[i]] : second[q[i]]) = i;
+  out.n = nc;
+  out.rp.assign((size_t)nc + 1, 0);
+  out.ci.clear();
+  out.va.clear();
+  std::vector<long long> where((size_t)nc, -1);
+  std::vector<std::pair<int, double>> row;
+  for (int I = 0; I < nc; ++I) {
+    const long long start = (long long)out.ci.size();
+    for (int m : {first[I], second[I]}) {
+      if (m < 0) continue;
+      for (long long k = B.rp[m]; k < B.rp[m + 1]; ++k) {
+        const int J = q[B.ci[k]];
+        if (J > I) continue;
+        if (where[J] < start) {
+          where[J] = (long long)out.ci.size();
+          out.ci.push_back(J);
+          out.va.push_back(B.va[k]);
+        } else {
+          out.va[where[J]] += B.va[k];
+        }
+      }
+    }
+    const long long end = (long long)out.ci.size();
+    row.clear();
+    for (long long k = start; k < end; ++k) row.emplace_back(out.ci[k], out.va[k]);
+    std::sort(row.begin(), row.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    for (long long k = start; k < end; ++k) out.ci[k] = row[k - start].first, out.va[k] = row[k - start].second, where[out.ci[k]] = -1;
+    out.rp[(size_t)I + 1] = end;
+  }
+}
+
+// one level: agg, w and the lower triangle + diagonal of A_{l+1} from that of A_l.  *bad: diagonal entries that are not positive
+inline int amg_coarsen(const AmgCsr &low, int passes, std::vector<int> &agg, std::vector<double> &w, AmgCsr &coarse, long long *bad) {
+  const int n = low.n;
+  std::vector<double> diag;
+  *bad = amg_diagonal(low, diag);
+  if (*bad) return -1;
+  w.resize((size_t)n);
+  for (int i = 0; i < n; ++i) w[i] = 1.0 / std::sqrt(diag[i]);
+  AmgCsr B, next;
+  amg_mirror(low, w.data(), B);
+  agg.resize((size_t)n);
+  for (int i = 0; i < n; ++i) agg[i] = i;
+  std::vector<int> q;
+  for (int p = 0; p < passes; ++p) {
+    const int nc = amg_match(B, q);
+    amg_galerkin(B, q, nc, next);
+    for (int i = 0; i < n; ++i) agg[i] = q[agg[i]];
+    if (p + 1 < passes) amg_mirror(next, nullptr, B);
+  }
+  coarse = std::move(next);
+  return 0;
+}
+
+// the inverse of a dense level from its lower triangle + diagonal: A = L L^T in fp64, the columns by two triangular
+// solves each, then (X + X^T) / 2.  Returns the first pivot that is not finite and > 0, or -1
+inline int amg_dense_inverse(const AmgCsr &low, std::vector<double> &inv) {
+  const int n = low.n;
+  std::vector<double> a((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i)
+    for (long long k = low.rp[i]; k < low.rp[i + 1]; ++k) a[(size_t)i * n + low.ci[k]] = low.va[k];
+  for (int j = 0; j < n; ++j) { // a <- L, column by column (the order of cg_binv_kernel)
+    double dj = a[(size_t)j * n + j];
+    for (int c = 0; c < j; ++c) dj -= a[(size_t)j * n + c] * a[(size_t)j * n + c];
+    if (!(dj > 0.0) || dj * 0.0 != 0.0) return j;
+    const double l = std::sqrt(dj);
+    a[(size_t)j * n + j] = l;
+#pragma omp parallel for schedule(static) if (n - j > 256)
+    for (int i = j + 1; i < n; ++i) {
+      double v = a[(size_t)i * n + j];
+      for (int c = 0; c < j; ++c) v -= a[(size_t)i * n + c] * a[(size_t)j * n + c];
+      a[(size_t)i * n + j] = v / l;
+    }
+  }
+  std::vector<double> x((size_t)n * n, 0.0); // x[j * n + i] = column j of the inverse
+#pragma omp parallel for schedule(dynamic, 8) if (n > 128)
+  for (int j = 0; j < n; ++j) {
+    double *y = &x[(size_t)j * n];
+    for (int i = j; i < n; ++i) { // L y = e_j (y_i = 0 above j)
+      double v = i == j ? 1.0 : 0.0;
+      for (int c = j; c < i; ++c) v -= a[(size_t)i * n + c] * y[c];
+      y[i] = v / a[(size_t)i * n + i];
+    }
+    for (int i = n - 1; i >= 0; --i) { // L^T x = y, in place
+      const double xi = y[i] / a[(size_t)i * n + i];
+      y[i] = xi;
+      for (int c = 0; c < i; ++c) y[c] -= a[(size_t)i * n + c] * xi;
+    }
+  }
+  inv.resize((size_t)n * n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) inv[(size_t)i * n + j] = 0.5 * (x[(size_t)j * n + i] + x[(size_t)i * n + j]);
+  return -1;
+}
+
+// ---- the kernels of the cycle ----------------------------------------------------------------------
+// rc_I = (V)(sum over the members i of aggregate I, ascending, of w_i (r_i - t_i)): one thread per aggregate
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    amg_restrict_kernel(V *__restrict__ rc, const V *__restrict__ r, const V *__restrict__ t, const V *__restrict__ w,
+                        const int *__restrict__ aggptr, const int *__restrict__ aggidx, long long nc, const int *__restrict__ ic) {
+  if (ic[I_DONE]) return;
+  for (long long I = (long long)blockIdx.x * kThreads + threadIdx.x; I < nc; I += (long long)gridDim.x * kThreads) {
+    double s = 0.0;
+    for (int k = aggptr[I]; k < aggptr[I + 1]; ++k) {
+      const int i = aggidx[k];
+      s += (double)w[i] * ((double)r[i] - (double)t[i]);
+    }
+    rc[I] = (V)s;
+  }
+}
+
+// z_i = (V)(z_i + w_i ec_agg(i))
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    amg_prolong_kernel(V *__restrict__ z, const V *__restrict__ ec, const V *__restrict__ w, const int *__restrict__ agg, long long n,
+                       const int *__restrict__ ic) {
+  if (ic[I_DONE]) return;
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads)
+    z[i] = (V)((double)z[i] + (double)w[i] * (double)ec[agg[i]]);
+}
+
+// cheb_start_kernel from a nonzero z, t = A z given:  d = (V)((1 / theta) dinv (r - t));  z = (V)(z + d)
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    amg_restart_kernel(V *__restrict__ z, V *__restrict__ d, const V *__restrict__ r, const V *__restrict__ t, long long n,
+                       double inv_theta, const V *__restrict__ dinv, const int *__restrict__ ic) {
+  if (ic[I_DONE]) return;
+  constexpr int W = Vec16<V>::W;
+  typedef typename Vec16<V>::type VT;
+  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+  for (long long i = t0; i < nv; i += stride) {
+    const VT rv = reinterpret_cast<const VT *>(r)[i], tv = reinterpret_cast<const VT *>(t)[i], mv = reinterpret_cast<const VT *>(dinv)[i];
+    VT zv = reinterpret_cast<VT *>(z)[i], dv;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      dv[k] = (V)(inv_theta * (((double)rv[k] - (double)tv[k]) * (double)mv[k]));
+      zv[k] = (V)((double)zv[k] + (double)dv[k]);
+    }
+    reinterpret_cast<VT *>(d)[i] = dv;
+    reinterpret_cast<VT *>(z)[i] = zv;
+  }
+  for (long long i = nv * W + t0; i < n; i += stride) {
+    const V di = (V)(inv_theta * (((double)r[i] - (double)t[i]) * (double)dinv[i]));
+    d[i] = di;
+    z[i] = (V)((double)z[i] + (double)di);
+  }
+}
+
+// z = (V)(inv r) on the dense level: one wave per row, the lanes stride over the columns, a fixed-order sum
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    amg_dense_kernel(V *__restrict__ z, const V *__restrict__ inv, const V *__restrict__ r, int n, const int *__restrict__ ic) {
+  if (ic[I_DONE]) return;
+  const int lane = threadIdx.x & 63, nwaves = gridDim.x * (kThreads / 64);
+  for (int i = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); i < n; i += nwaves) { // (uniform over the wave)
+    const V *row = inv + (size_t)i * n;
+    double s = 0.0;
+    for (int j = lane; j < n; j += 64) s += (double)row[j] * (double)r[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    if (lane == 0) z[i] = (V)s;
+  }
+}
+
+// cg_update_kernel with alpha = rz / pq and z elsewhere:  u += alpha p;  r -= alpha q;  part[rr'] <- r . r
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    amg_update_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q, long long n,
+                      double *__restrict__ part, const int *__restrict__ ic, int it) {
+  if (ic[I_DONE]) return;
+  const double pq = slot_sum(part, P_PQ), rz_old = slot_sum(part, P_RZ0 + (it & 1));
+  const double alpha = pq != 0.0 ? rz_old / pq : 0.0;
+  constexpr int W = Vec16<V>::W;
+  typedef typename Vec16<V>::type VT;
+  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+  double s = 0.0;
+  for (long long i = t0; i < nv; i += stride) {
+    VT uv = reinterpret_cast<VT *>(u)[i], rv = reinterpret_cast<VT *>(r)[i];
+    const VT pv = reinterpret_cast<const VT *>(p)[i], qv = reinterpret_cast<const VT *>(q)[i];
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      uv[k] = (V)((double)uv[k] + alpha * (double)pv[k]);
+      const double ri = (double)rv[k] - alpha * (double)qv[k];
+      rv[k] = (V)ri;
+      s += ri * ri;
+    }
+    reinterpret_cast<VT *>(u)[i] = uv;
+    reinterpret_cast<VT *>(r)[i] = rv;
+  }
+  for (long long i = nv * W + t0; i < n; i += stride) {
+    u[i] = (V)((double)u[i] + alpha * (double)p[i]);
+    const double ri = (double)r[i] - alpha * (double)q[i];
+    r[i] = (V)ri;
+    s += ri * ri;
+  }
+  s = block_sum(s);
+  if (threadIdx.x == 0) part[(P_RR0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = s;
+}
+
+// part[slot] <- a . b of the stored values
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    amg_dot_kernel(const V *__restrict__ a, const V *__restrict__ b, long long n, double *__restrict__ part, int slot,
+                   const int *__restrict__ ic) {
+  if (ic[I_DONE]) return;
+  constexpr int W = Vec16<V>::W;
+  typedef typename Vec16<V>::type VT;
+  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+  double s = 0.0;
+  for (long long i = t0; i < nv; i += stride) {
+    const VT av = reinterpret_cast<const VT *>(a)[i], bv = reinterpret_cast<const VT *>(b)[i];
+#pragma unroll
+    for (int k = 0; k < W; ++k) s += (double)av[k] * (double)bv[k];
+  }
+  for (long long i = nv * W + t0; i < n; i += stride) s += (double)a[i] * (double)b[i];
+  s = block_sum(s);
+  if (threadIdx.x == 0) part[slot * kGrid + blockIdx.x] = s;
+}
+
+// ---- the hierarchy on the device -------------------------------------------------------------------
+enum AmgKind { AMG_MULTIGRID = 0, AMG_SMOOTHER = 1, AMG_DENSE = 2 };
+
+template <typename V> struct AmgLevel {
+  int n = 0, nc = 0, kind = AMG_MULTIGRID;
+  long long nnz = 0;
+  double lmin = 0.0, lmax = 0.0, theta = 1.0, c1[kChebMaxDegree], c2[kChebMaxDegree];
+  cfs_hip_sym_s *h = nullptr;
+  bool owned = false;
+  cfs_rt::DevBuf dinv, aggptr, aggidx, agg, w, r, z, d, t, inv;
+  // the CSR the level's handle was created from (levels >= 1): lower triangle + diagonal, values in V
+  std::vector<int> rp, ci;
+  std::vector<V> va;
+  ~AmgLevel() {
+    if (owned) delete h;
+  }
+  size_t bytes() const {
+    return dinv.bytes + aggptr.bytes + aggidx.bytes + agg.bytes + w.bytes + r.bytes + z.bytes + d.bytes + t.bytes + inv.bytes;
+  }
+};
+
+template <typename V> struct Amg : cfs_hip_amg_s {
+  using Level = AmgLevel<V>;
+  std::vector<std::unique_ptr<Level>> lv;
+  cfs_rt::DevBuf part, cnt; // the partial-sum slots the smoother's kernels are handed, and a done flag that is never set
+  int passes = 2, degree = 1, coarse_max = 512, device = 0;
+  double ratio = 4.0, setup_seconds = 0.0, handles_seconds = 0.0;
+
+  ~Amg() override {
+    cfs_rt::DeviceGuard g(device);
+    lv.clear();
+  }
+
+  // mk(n, rowptr, colind, values, flags, &handle): the library's own create path
+  template <class Make>
+  int build(cfs_hip_sym_s *h, int n, const int *rowptr, const int *colind, const V *values, int flags, Make &&mk) {
+    using clock = std::chrono::steady_clock;
+    const auto t_begin = clock::now();
+    fine = h;
+    value_bytes = (int)sizeof(V);
+    hipStream_t st = nullptr;
+    int rc;
+    if ((rc = part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) || (rc = cnt.alloc(I_COUNT * sizeof(int)))) return rc;
+    HIPCHK(hipMemset(part.p, 0, (size_t)P_COUNT * kGrid * sizeof(double)));
+    HIPCHK(hipMemset(cnt.p, 0, I_COUNT * sizeof(int)));
+    AmgCsr cur, next;
+    amg_lower(n, rowptr, colind, values, cur);
+    std::vector<int> agg;
+    std::vector<double> w, inv;
+    for (int l = 0;; ++l) {
+      lv.emplace_back(new Level());
+      Level &L = *lv.back();
+      L.n = cur.n;
+      L.nnz = cur.nnz();
+      long long bad = 0;
+      std::vector<double> diag;
+      if ((bad = amg_diagonal(cur, diag)))
+        return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_create: Jacobi needs a positive diagonal, " + std::to_string(bad) + " of " +
+                                                    std::to_string(cur.n) + " entries are zero, negative or not finite (level " +
+                                                    std::to_string(l) + ")");
+      if (l == 0) {
+        L.h = h;
+      } else { // the level as a handle of its own, from the values rounded to V (which `cur` already holds)
+        L.rp.resize((size_t)cur.n + 1);
+        for (int i = 0; i <= cur.n; ++i) L.rp[i] = (int)cur.rp[i];
+        L.ci = cur.ci;
+        L.va.resize(cur.va.size());
+        for (size_t k = 0; k < cur.va.size(); ++k) L.va[k] = (V)cur.va[k];
+        const auto t0 = clock::now();
+        if ((rc = mk(cur.n, L.rp.data(), L.ci.data(), L.va.data(), flags, &L.h))) return rc;
+        L.owned = true;
+        handles_seconds += std::chrono::duration<double>(clock::now() - t0).count();
+      }
+      // how the hierarchy goes on
+      bool last = cur.n <= coarse_max;
+      L.kind = last ? AMG_DENSE : AMG_MULTIGRID;
+      if (!last) {
+        if (amg_coarsen(cur, passes, agg, w, next, &bad)) return cfs_rt::set_err(CFS_HIP_ERR_INTERNAL, "amg_create: the diagonal changed");
+        if ((double)next.n > 0.9 * (double)cur.n || l + 1 == CFS_HIP_AMG_MAX_LEVELS) {
+          last = true;
+          L.kind = cur.n <= CFS_HIP_AMG_MAX_COARSE ? AMG_DENSE : AMG_SMOOTHER;
+        }
+      }
+      if (L.kind == AMG_DENSE) {
+        const int piv = amg_dense_inverse(cur, inv);
+        if (piv >= 0)
+          return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_create: the matrix of level " + std::to_string(l) + " (" + std::to_string(cur.n) +
+                                                      " rows) is not positive definite: pivot " + std::to_string(piv) +
+                                                      " of its Cholesky factorisation is zero, negative or not finite");
+        std::vector<V> iv(inv.size());
+        for (size_t k = 0; k < inv.size(); ++k) iv[k] = (V)inv[k];
+        if ((rc = L.inv.upload(iv.data(), iv.size() * sizeof(V)))) return rc;
+      } else {
+        if ((rc = setup_smoother(L, st))) return rc;
+      }
+      if (l > 0 && ((rc = L.r.alloc((size_t)L.n * sizeof(V) + 64)) || (rc = L.z.alloc((size_t)L.n * sizeof(V) + 64)))) return rc;
+      if (last) break;
+      // the transfer to the next level
+      L.nc = next.n;
+      std::vector<int> ptr((size_t)next.n + 1, 0), idx((size_t)cur.n);
+      for (int i = 0; i < cur.n; ++i) ptr[(size_t)agg[i] + 1] += 1;
+      for (int I = 0; I < next.n; ++I) ptr[(size_t)I + 1] += ptr[I];
+      {
+        std::vector<int> pos(ptr.begin(), ptr.end() - 1);
+        for (int i = 0; i < cur.n; ++i) idx[pos[agg[i]]++] = i; // (rows ascending: members ascending)
+      }
+      std::vector<V> wv((size_t)cur.n);
+      for (int i = 0; i < cur.n; ++i) wv[i] = (V)w[i];
+      if ((rc = L.aggptr.upload(ptr.data(), ptr.size() * sizeof(int))) || (rc = L.aggidx.upload(idx.data(), idx.size() * sizeof(int))) ||
+          (rc = L.agg.upload(agg.data(), agg.size() * sizeof(int))) || (rc = L.w.upload(wv.data(), wv.size() * sizeof(V))))
+        return rc;
+      for (double &v : next.va) v = (double)(V)v; // the next level is what its handle will hold
+      cur = std::move(next);
+    }
+    HIPCHK(hipDeviceSynchronize());
+    setup_seconds = std::chrono::duration<double>(clock::now() - t_begin).count();
+    return 0;
+  }
+
+  // dinv, the work vectors and the bounds of a level that smooths
+  int setup_smoother(Level &L, hipStream_t st) {
+    const long long n = L.n;
+    double *pp = (double *)part.p;
+    int rc;
+    if ((rc = L.dinv.alloc((size_t)n * sizeof(V) + 64)) || (rc = L.d.alloc((size_t)n * sizeof(V) + 64)) ||
+        (rc = L.t.alloc((size_t)n * sizeof(V) + 64)) || (rc = L.h->diagonal(L.dinv.p, st)))
+      return rc;
+    hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)L.dinv.p, n, pp);
+    HIPCHK(hipGetLastError());
+    cfs_rt::DevBuf vbuf, lbuf;
+    if ((rc = vbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = lbuf.alloc((size_t)L_COUNT * kGrid * sizeof(double)))) return rc;
+    HIPCHK(hipMemsetAsync(lbuf.p, 0, (size_t)L_COUNT * kGrid * sizeof(double), st));
+    hipLaunchKernelGGL((cheb_lmax_start_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)L.d.p, (const V *)nullptr, n);
+    double est = 0.0;
+    if ((rc = cheb_power<V, 1>(L.h, (V *)L.d.p, (V *)L.t.p, (V *)vbuf.p, n, 16, (double *)lbuf.p, (const V *)L.dinv.p, 0LL, &est, st)))
+      return rc;
+    std::vector<double> hb(kGrid);
+    HIPCHK(hipMemcpy(hb.data(), pp + (size_t)P_BAD * kGrid, kGrid * sizeof(double), hipMemcpyDeviceToHost));
+    double bad = 0.0;
+    for (int g = 0; g < kGrid; g++) bad += hb[g];
+    if (bad != 0.0) return ChebBase<V, 1>::refuse("amg_create", bad, n, 0);
+    if (!(est > 0.0) || est * 0.0 != 0.0)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_create: the power method gave no positive estimate of lambda_max(D^-1 A) on a level of " +
+                                                  std::to_string(n) + " rows (" + std::to_string(est) + ")");
+    L.lmax = 1.1 * est;
+    L.lmin = L.lmax / ratio;
+    cheb_coeffs(degree, L.lmin, L.lmax, &L.theta, L.c1, L.c2);
+    return 0;
+  }
+
+  // z = M^-1 r from level l down, on `st`; ic: the done flag the kernels look at
+  int cycle(int l, V *z, const V *r, const int *ic, hipStream_t st) {
+    Level &L = *lv[l];
+    const long long n = L.n;
+    double *pp = (double *)part.p;
+    if (L.kind == AMG_DENSE) {
+      hipLaunchKernelGGL((amg_dense_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, (const V *)L.inv.p, r, L.n, ic);
+      return 0;
+    }
+    V *d = (V *)L.d.p, *t = (V *)L.t.p;
+    const V *dinv = (const V *)L.dinv.p;
+    int rc;
+    hipLaunchKernelGGL((cheb_start_kernel<V, 1>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, n, 1.0 / L.theta, -1, pp, dinv, 0LL);
+    if ((rc = cheb_chain<V, 1>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, 0LL, st))) return rc;
+    if (L.kind == AMG_SMOOTHER) return 0;
+    Level &C = *lv[l + 1];
+    if ((rc = L.h->spmv_local(t, z, nullptr, st))) return rc;
+    hipLaunchKernelGGL((amg_restrict_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)C.r.p, r, (const V *)t, (const V *)L.w.p,
+                       (const int *)L.aggptr.p, (const int *)L.aggidx.p, (long long)L.nc, ic);
+    if ((rc = cycle(l + 1, (V *)C.z.p, (const V *)C.r.p, ic, st))) return rc;
+    hipLaunchKernelGGL((amg_prolong_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, (const V *)C.z.p, (const V *)L.w.p,
+                       (const int *)L.agg.p, n, ic);
+    if ((rc = L.h->spmv_local(t, z, nullptr, st))) return rc;
+    hipLaunchKernelGGL((amg_restart_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, (const V *)t, n, 1.0 / L.theta, dinv, ic);
+    return cheb_chain<V, 1>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, 0LL, st);
+  }
+
+  int apply(void *z_dev, const void *r_dev, hipStream_t st) override {
+    int rc = cycle(0, (V *)z_dev, (const V *)r_dev, (const int *)cnt.p, st);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+
+  int info(cfs_hip_amg_info_t *o) override {
+    memset(o, 0, sizeof *o);
+    o->levels = (int)lv.size();
+    o->passes = passes;
+    o->degree = degree;
+    o->coarse_max = coarse_max;
+    o->ratio = ratio;
+    o->setup_seconds = setup_seconds;
+    o->handles_seconds = handles_seconds;
+    long long bytes = (long long)(part.bytes + cnt.bytes);
+    for (size_t l = 0; l < lv.size(); ++l) {
+      const Level &L = *lv[l];
+      o->n[l] = L.n;
+      o->nnz[l] = L.nnz;
+      o->lmin[l] = L.lmin;
+      o->lmax[l] = L.lmax;
+      o->kind[l] = L.kind;
+      bytes += (long long)L.bytes();
+      if (L.owned) {
+        cfs_hip_sym_stats s;
+        memset(&s, 0, sizeof s);
+        L.h->stats(&s);
+        bytes += s.device_bytes;
+      }
+    }
+    o->device_bytes = bytes;
+    return 0;
+  }
+
+  int level_aggregates(int level, int *agg, void *w) override {
+    if (level < 0 || level + 1 >= (int)lv.size())
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_level_aggregates: level " + std::to_string(level) + " has no coarser level (" +
+                                                  std::to_string(lv.size()) + " levels)");
+    const Level &L = *lv[level];
+    cfs_rt::DeviceGuard g(device);
+    if (agg) HIPCHK(hipMemcpy(agg, L.agg.p, (size_t)L.n * sizeof(int), hipMemcpyDeviceToHost));
+    if (w) HIPCHK(hipMemcpy(w, L.w.p, (size_t)L.n * sizeof(V), hipMemcpyDeviceToHost));
+    return 0;
+  }
+
+  int level_matrix(int level, int *rowptr, int *colind, void *values) override {
+    if (level < 1 || level >= (int)lv.size())
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_level_matrix: level " + std::to_string(level) + " is not one of 1 .. " +
+                                                  std::to_string((int)lv.size() - 1) + " (level 0 is the caller's matrix)");
+    const Level &L = *lv[level];
+    if (rowptr) memcpy(rowptr, L.rp.data(), L.rp.size() * sizeof(int));
+    if (colind) memcpy(colind, L.ci.data(), L.ci.size() * sizeof(int));
+    if (values) memcpy(values, L.va.data(), L.va.size() * sizeof(V));
+    return 0;
+  }
+
+  int coarse_inverse(void *inv) override {
+    const Level &L = *lv.back();
+    if (L.kind != AMG_DENSE) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_coarse_inverse: the hierarchy ends with a smoother-only level");
+    cfs_rt::DeviceGuard g(device);
+    HIPCHK(hipMemcpy(inv, L.inv.p, (size_t)L.n * L.n * sizeof(V), hipMemcpyDeviceToHost));
+    return 0;
+  }
+
+  // cfs_hip_sym_pcg_amg.  u: in = first guess, out = solution
+  int pcg(void *u_dev, const void *b_dev, double tol, int maxiter, int *iterations, double *relres, hipStream_t st) override {
+    using cfs_rt::DevBuf;
+    cfs_hip_sym_s *h = fine;
+    const long long n = h->n();
+    V *u = (V *)u_dev;
+    const V *b = (const V *)b_dev;
+    DevBuf rbuf, pbuf, qbuf, zbuf, pbuf_part, cbuf;
+    int rc;
+    if ((rc = rbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf.alloc((size_t)n * sizeof(V) + 64)) ||
+        (rc = qbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = zbuf.alloc((size_t)n * sizeof(V) + 64)) ||
+        (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) || (rc = cbuf.alloc(I_COUNT * sizeof(int))))
+      return rc;
+    V *r = (V *)rbuf.p, *p = (V *)pbuf.p, *q = (V *)qbuf.p, *z = (V *)zbuf.p;
+    double *pp = (double *)pbuf_part.p;
+    int *ic = (int *)cbuf.p;
+    std::vector<double> hp((size_t)P_COUNT * kGrid);
+    auto read_slot = [&](int slot, double *out) -> int { // (synchronises the stream)
+      HIPCHK(hipMemcpyAsync(hp.data(), pp, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      double s = 0.0;
+      for (int g = 0; g < kGrid; g++) s += hp[(size_t)slot * kGrid + g];
+      *out = s;
+      return 0;
+    };
+    HIPCHK(hipMemsetAsync(pp, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(ic, 0, I_COUNT * sizeof(int), st));
+    // r = b - A u, rr[0] = r . r, bb = b . b: the residual kernel of the plain iteration, the same bits
+    if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
+    hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, n, pp,
+                       (int)P_RR0, 1, (const V *)nullptr);
+    HIPCHK(hipGetLastError());
+    double rr0 = 0.0, bb = 0.0;
+    if ((rc = read_slot(P_RR0, &rr0))) return rc;
+    for (int g = 0; g < kGrid; g++) bb += hp[(size_t)P_BB * kGrid + g];
+    const double stop = tol * tol * bb;
+    bool done = !(rr0 > stop); // the first guess already solves it (or b = 0)
+    int host_ic[I_COUNT] = {0, 0};
+    int it = 0;
+    if (!done && maxiter > 0) { // z = M^-1 r, rz[0] = r . z, p = z
+      if ((rc = cycle(0, z, (const V *)r, (const int *)ic, st))) return rc;
+      hipLaunchKernelGGL((amg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, n, pp, (int)P_RZ0,
+                         (const int *)ic);
+      HIPCHK(hipMemcpyAsync(p, z, (size_t)n * sizeof(V), hipMemcpyDeviceToDevice, st));
+    }
+    while (!done && it < maxiter) { // (one look per iteration: a cycle is more than may be enqueued ahead of the GPU)
+      if ((rc = h->spmv_local(q, p, nullptr, st))) return rc;
+      hipLaunchKernelGGL((cg_pq_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, pp, (const int *)ic);
+      hipLaunchKernelGGL((amg_update_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n, pp,
+                         (const int *)ic, it);
+      if ((rc = cycle(0, z, (const V *)r, (const int *)ic, st))) return rc;
+      hipLaunchKernelGGL((amg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, n, pp,
+                         (int)P_RZ0 + ((it + 1) & 1), (const int *)ic);
+      hipLaunchKernelGGL((cheb_direction_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, n, (const double *)pp, ic, it,
+                         stop);
+      ++it;
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      done = host_ic[I_DONE] != 0;
+    }
+    // the true residual of what is returned
+    if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
+    hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b, (const V *)q, n,
+                       pp, (int)P_RES, 0, (const V *)nullptr);
+    HIPCHK(hipGetLastError());
+    double res2 = 0.0;
+    if ((rc = read_slot(P_RES, &res2))) return rc;
+    HIPCHK(hipMemcpy(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost));
+    if (iterations) *iterations = host_ic[I_ITER];
+    if (relres) *relres = bb > 0.0 ? std::sqrt(res2 / bb) : std::sqrt(res2);
+    return 0;
+  }
+};
+
+} // namespace cfs_solver

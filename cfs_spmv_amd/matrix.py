@@ -390,6 +390,23 @@ class SymMatrix:
                                                         _stream_ptr(stream)))
         return est.value
 
+    def amg(self, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512):
+        """the aggregation multigrid hierarchy of this matrix (cfs_hip_amg_create_*), an Amg: rowptr, colind, values
+        are the CSR the handle was created from (only entries with col <= row are read; the caller vouches that it is
+        this handle's matrix).  passes 1 .. 3 rounds of pairwise matching per level, degree 1 .. 4 of the Chebyshev
+        smoother, ratio = lmax / lmin of its interval, coarse_max <= 1024 the largest dense last level.  A whole-matrix
+        handle on one device.  The hierarchy holds the values of now: after update_values() make a new one."""
+        return Amg(self, rowptr, colind, values, passes=passes, degree=degree, ratio=ratio, coarse_max=coarse_max)
+
+    def pcg_amg(self, u, b, amg, tol=1e-10, maxiter=1000, check_every=1, stream=None):
+        """PCG with one V-cycle of `amg` (self.amg(...)) as the preconditioner (cfs_hip_sym_pcg_amg): like
+        pcg_cheb(), the polynomial replaced by the cycle; the host looks at the convergence flag after every
+        iteration whatever check_every says.  Returns (iterations, ||b - A u|| / ||b||)."""
+        it, res = C.c_int(), C.c_double()
+        _lib.check(_lib.load().cfs_hip_sym_pcg_amg(self._h, amg._a, _ptr(u), _ptr(b), float(tol), int(maxiter),
+                                                   int(check_every), C.byref(it), C.byref(res), _stream_ptr(stream)))
+        return it.value, res.value
+
     def minres(self, u, b, precond="none", shift=0.0, tol=1e-10, maxiter=1000, check_every=8, stream=None):
         """MINRES inside the library (cfs_hip_sym_minres): u (device tensor) holds the first guess and
         receives the solution of (A - shift I) u = b, A symmetric and possibly indefinite; five launches per
@@ -569,6 +586,87 @@ class SymMatrix:
             self.close()
         except Exception:
             pass
+
+
+class Amg:
+    """The aggregation multigrid hierarchy of a SymMatrix (cfs_hip_amg_create_*) and its V-cycle.  Keeps a reference
+    to its matrix, which must stay open for as long as the hierarchy is used."""
+
+    def __init__(self, A, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512):
+        lib = _lib.load()
+        rowptr, colind = _np_i32(rowptr), _np_i32(colind)
+        values = np.ascontiguousarray(values, dtype=A.dtype)
+        self.A, self.dtype = A, A.dtype
+        self._a = C.c_void_p()
+        opt = _lib.AmgOptions(int(passes), int(degree), int(coarse_max), 0, float(ratio))
+        suf = "f64" if self.dtype == np.float64 else "f32"
+        _lib.check(getattr(lib, "cfs_hip_amg_create_" + suf)(A._h, A.n, rowptr.ctypes.data, colind.ctypes.data,
+                                                             values.ctypes.data, C.byref(opt), C.byref(self._a)))
+
+    def info(self):
+        """dict: levels, the options used, device_bytes, setup_seconds (of which handles_seconds for the create path
+        of the level handles), and per level n, nnz (stored), lmin, lmax, kind (0 multigrid, 1 smoother-only,
+        2 dense)"""
+        out = _lib.AmgInfo()
+        _lib.check(_lib.load().cfs_hip_amg_info(self._a, C.byref(out)))
+        return out.asdict()
+
+    def aggregates(self, level):
+        """(agg, w) of a level that has a coarser one, as the device holds them: the aggregate of every row and the
+        weights in the value type"""
+        n = self.info()["n"][level] if 0 <= level < self.info()["levels"] else 0
+        agg, w = np.zeros(n, np.int32), np.zeros(n, self.dtype)
+        _lib.check(_lib.load().cfs_hip_amg_level_aggregates(self._a, int(level), agg.ctypes.data, w.ctypes.data))
+        return agg, w
+
+    def level_matrix(self, level):
+        """(n, rowptr, colind, values) of level >= 1: the lower triangle + diagonal its handle was created from"""
+        inf = self.info()
+        ok = 1 <= level < inf["levels"]
+        n, nnz = (inf["n"][level], inf["nnz"][level]) if ok else (0, 0)
+        rp, ci, va = np.zeros(n + 1, np.int32), np.zeros(nnz, np.int32), np.zeros(nnz, self.dtype)
+        _lib.check(_lib.load().cfs_hip_amg_level_matrix(self._a, int(level), rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
+        return n, rp, ci, va
+
+    def coarse_inverse(self):
+        """the (n_L, n_L) inverse of the dense last level as the device holds it"""
+        inf = self.info()
+        n = inf["n"][-1]
+        inv = np.zeros((n, n), self.dtype)
+        _lib.check(_lib.load().cfs_hip_amg_coarse_inverse(self._a, inv.ctypes.data))
+        return inv
+
+    def apply(self, z, r, stream=None):
+        """z <- M^-1 r, one cycle (cfs_hip_amg_apply): device tensors of n values.  Returns z."""
+        _lib.check(_lib.load().cfs_hip_amg_apply(self._a, _ptr(z), _ptr(r), _stream_ptr(stream)))
+        return z
+
+    def close(self):
+        if getattr(self, "_a", None) and self._a.value:
+            _lib.load().cfs_hip_amg_destroy(self._a)
+            self._a = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def coarsen(n, rowptr, colind, values, passes=2):
+    """host only: one level of the multigrid set-up (cfs_hip_debug_amg_coarsen).  Returns (agg, w, (nc, rowptr, colind,
+    values)): the aggregate of every row, the weights 1 / sqrt(a_ii) and the lower triangle + diagonal of the coarse
+    matrix, all in fp64"""
+    rowptr, colind = _np_i32(rowptr), _np_i32(colind)
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    cap = int(rowptr[n]) if n > 0 else 0
+    agg, w = np.zeros(n, np.int32), np.zeros(n, np.float64)
+    crp, cci, cva = np.zeros(n + 1, np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float64)
+    nc, nnz = C.c_int(), C.c_longlong()
+    _lib.check(_lib.load().cfs_hip_debug_amg_coarsen(n, rowptr.ctypes.data, colind.ctypes.data, values.ctypes.data, int(passes),
+                                                     agg.ctypes.data, w.ctypes.data, C.byref(nc), crp.ctypes.data, cci.ctypes.data,
+                                                     cva.ctypes.data, cap, C.byref(nnz)))
+    return agg, w, (nc.value, crp[:nc.value + 1].copy(), cci[:nnz.value].copy(), cva[:nnz.value].copy())
 
 
 class MixedSym:

@@ -216,6 +216,53 @@ def pcg_cheb_native(A, b, base="jacobi", block=3, degree=4, lmin=None, lmax=None
     return u, it, res, used
 
 
+def pcg_amg(A, b, amg, tol=1e-10, maxiter=1000, x0=None):
+    """PCG with the multigrid V-cycle as the preconditioner, host-driven: the recurrence and the rounding rules of
+    cfs_hip_sym_pcg_amg with torch operations and amg.apply() as M^-1 (amg = A.amg(...)) -- u, r, p stored in the
+    value type, every update computed in fp64 from the stored operands and rounded once, the dots in fp64 over the
+    stored values, r.r from the unrounded update.  The model of the native loop and its baseline.  Returns (u,
+    iterations, relative residual)."""
+    import torch
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    q = torch.empty_like(b)
+    z = torch.empty_like(b)
+    A.dense_vector_multiply(q, u)
+    r = b - q
+    rr = float(torch.dot(r.double(), r.double()))
+    bb = float(torch.dot(b.double(), b.double()))
+    bnorm = math.sqrt(bb) or 1.0
+    it = 0
+    if maxiter > 0 and rr > tol * tol * bb:
+        amg.apply(z, r)
+        p = z.clone()
+        rz = float(torch.dot(r.double(), z.double()))
+    while it < maxiter and rr > tol * tol * bb:
+        A.dense_vector_multiply(q, p)          # the hot path
+        pq = float(torch.dot(p.double(), q.double()))
+        alpha = rz / pq if pq != 0.0 else 0.0
+        u = (u.double() + alpha * p.double()).to(b.dtype)
+        rs = r.double() - alpha * q.double()
+        rr = float(torch.dot(rs, rs))
+        r = rs.to(b.dtype)
+        amg.apply(z, r)
+        rz_new = float(torch.dot(r.double(), z.double()))
+        p = (z.double() + (rz_new / rz if rz != 0.0 else 0.0) * p.double()).to(b.dtype)
+        rz = rz_new
+        it += 1
+    A.dense_vector_multiply(q, u)
+    res = math.sqrt(float(torch.dot((b - q).double(), (b - q).double()))) / bnorm
+    return u, it, res
+
+
+def pcg_amg_native(A, b, amg, tol=1e-10, maxiter=1000, x0=None, check_every=1):
+    """the same iteration inside the library (cfs_hip_sym_pcg_amg): the product, four vector kernels and one cycle
+    per iteration, one host look per iteration.  Returns (u, iterations, relative residual), like pcg_amg()."""
+    import torch
+    u = torch.zeros_like(b) if x0 is None else x0.clone()
+    it, res = A.pcg_amg(u, b, amg, tol=tol, maxiter=maxiter, check_every=check_every)
+    return u, it, res
+
+
 def pcg_mixed(M, b, tol=1e-10, delta=0.1, maxiter=1000, x0=None, precond="jacobi", block=3, check_every=8):
     """mixed-precision PCG, host-driven: the recurrence of cfs_hip_sym_pcg_mixed on a MixedSym.  One CG
     recurrence in float32 (r, p, q and the correction xlo; the products on M.A32; dots and z = M^-1 r in

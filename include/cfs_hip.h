@@ -471,6 +471,109 @@ int cfs_hip_sym_precond_lmax(cfs_hip_sym_t h, int block_rows, int steps, const v
  * inner steps for these bounds, c1[j-1] = rho_j rho_{j-1} and c2[j-1] = 2 rho_j / delta for j = 1 .. degree - 1
  * (c1, c2: degree - 1 doubles each; may be NULL at degree 1).  Both bounds required, 0 < lmin < lmax.          */
 int cfs_hip_debug_cheb_coeffs(int degree, double lmin, double lmax, double *theta, double *c1, double *c2);
+/* ---- aggregation multigrid: a V-cycle as the preconditioner of the native PCG ------------------------------------
+ * For scalar problems whose condition number, not their size, is the cost: the iteration count of every solver above
+ * grows with its square root, a multilevel cycle removes the low end of the spectrum.  (Block / node smoothers are not
+ * part of it: on a multi-dof matrix whose couplings inside a node are as strong as the diagonal, block Jacobi does
+ * better.)  CFS_HIP_ABI_VERSION is unchanged; callers detect the symbols.
+ * THE HIERARCHY, built on the host in fp64 from the caller's CSR (as for cfs_hip_sym_create_*: only entries with
+ * col <= row are read).  Per level l, A_0 = A:  w_i = 1 / sqrt(a_ii), B = W A_l W;  `passes` rounds of pairwise
+ * matching on B -- the rows in ascending order, an unmatched row i takes the unmatched neighbour j != i with the largest
+ * s_ij = |b_ij| / sqrt(b_ii b_jj) > 0, ties to the smallest j; the pair is the next aggregate, a row without a candidate
+ * a singleton -- each followed by B <- Q^T B Q, every coarse entry the fp64 sum of its contributions in ascending
+ * (row, column) order.  agg_l is the composition of the rounds (at most 2^passes members per aggregate),
+ * P_l = W Q_1 .. Q_p and A_{l+1} = P_l^T A_l P_l, rounded to the value type before it is coarsened further.  The weights
+ * make the hierarchy invariant under a symmetric scaling of A.  Level l is the last one, DENSE, when n_l <= coarse_max;
+ * otherwise, when the coarsening stalls (n_{l+1} > 0.9 n_l) or l + 1 == CFS_HIP_AMG_MAX_LEVELS, it is the last one,
+ * dense when n_l <= CFS_HIP_AMG_MAX_COARSE and SMOOTHER-ONLY otherwise: a stalled hierarchy degrades to the Chebyshev
+ * preconditioner, never to an error.  The dense level keeps the inverse (Cholesky in fp64, solves, symmetrised, rounded
+ * to the value type) as an n_L x n_L device array.  Levels 1 .. L are handles of the library's own create path
+ * (CFS_HIP_FLAG_NO_CALIBRATE, plus CFS_HIP_FLAG_DETERMINISTIC when h has it); level 0 is h itself, not copied.
+ * Every other level smooths with the Chebyshev polynomial of `degree` in D^-1 A_l on [lmax / ratio, lmax],
+ * lmax = 1.1 x the power-method estimate (Jacobi, 16 steps, the fixed start vector), made at create.
+ * THE CYCLE z = M^-1 r:  dense level: z = A_L^-1 r, one kernel; smoother-only level: z = S_l r; otherwise z = S_l r,
+ * t = A_l z, rc_I = sum_{i in I} w_i (r_i - t_i), ec = cycle(l + 1, rc), z_i += w_i ec_agg(i), then the Chebyshev
+ * iteration again from that z.  8 + 6 (degree - 1) launches per multigrid level, 1 + 3 (degree - 1) on a
+ * smoother-only level, 1 on the dense one.  Vectors are stored in the value type, every update is computed in fp64
+ * from the stored operands and rounded once, all sums have a fixed order.  M^-1 is symmetric; it is positive definite
+ * while every level's spectrum of D^-1 A_l lies in (0, lmin + lmax), the margin of cfs_hip_sym_pcg_cheb:
+ * 1.375 x the estimate at ratio 4.
+ * MEMORY: per level dinv, w, the aggregate lists, the work vectors r, z, d, t and the level's handle
+ * (cfs_hip_amg_info reports the bytes).                                                                          */
+#define CFS_HIP_AMG_MAX_LEVELS 16
+#define CFS_HIP_AMG_MAX_COARSE 1024
+typedef struct cfs_hip_amg_s *cfs_hip_amg_t;
+typedef struct {
+  int passes;     /* rounds of pairwise matching per level, 1 .. 3 (0: 2)          */
+  int degree;     /* of the smoother, 1 .. 4 (0: 1)                                */
+  int coarse_max; /* largest dense last level, 1 .. CFS_HIP_AMG_MAX_COARSE (0: 512) */
+  int reserved_;
+  double ratio;   /* lmax / lmin of the smoother, finite and > 1 (0: 4)            */
+} cfs_hip_amg_options; /* 0 = default */
+#define CFS_HIP_AMG_KIND_MULTIGRID 0
+#define CFS_HIP_AMG_KIND_SMOOTHER 1
+#define CFS_HIP_AMG_KIND_DENSE 2
+typedef struct {
+  int levels, passes, degree, coarse_max; /* the options as used */
+  double ratio;
+  long long device_bytes;  /* held by the object: the level handles, the transfer lists, the vectors, the inverse  */
+  double setup_seconds;    /* the whole create ...                                                                  */
+  double handles_seconds;  /* ... of which the create path of the level handles                                     */
+  int n[CFS_HIP_AMG_MAX_LEVELS];
+  long long nnz[CFS_HIP_AMG_MAX_LEVELS]; /* stored: lower triangle + diagonal */
+  double lmin[CFS_HIP_AMG_MAX_LEVELS], lmax[CFS_HIP_AMG_MAX_LEVELS]; /* 0 on a dense level */
+  int kind[CFS_HIP_AMG_MAX_LEVELS]; /* CFS_HIP_AMG_KIND_* */
+} cfs_hip_amg_info_t;
+/* The hierarchy of the matrix behind h.  h: a whole-matrix handle on one device of the matching value type and n (a
+ * shard or a multi-device handle: CFS_HIP_ERR_UNSUPPORTED); it must outlive the object, and the caller vouches that the
+ * CSR is h's matrix.  THE HIERARCHY HOLDS THE VALUES AT CREATE: after cfs_hip_sym_update_values_* the caller destroys it
+ * and creates a new one.  CFS_HIP_ERR_ARG, before any device work and in this order: a null pointer (h, rowptr, out;
+ * colind / values when there are entries), passes outside 1 .. 3, degree outside 1 .. 4, a ratio that is not finite and
+ * > 1, coarse_max outside 1 .. CFS_HIP_AMG_MAX_COARSE (0 is the default in each).  Then, from the handle: a shard or a
+ * multi-device handle (CFS_HIP_ERR_UNSUPPORTED), a value type or an n different from h's (CFS_HIP_ERR_ARG).  A diagonal entry of any level that is zero, missing, negative or not finite: CFS_HIP_ERR_ARG in
+ * the words of cfs_hip_sym_pcg; a dense level whose Cholesky factorisation meets a pivot that is not finite and > 0:
+ * CFS_HIP_ERR_ARG ("not positive definite").  On any error *out = NULL and nothing stays allocated.             */
+int cfs_hip_amg_create_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
+                           const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_create_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
+                           const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_destroy(cfs_hip_amg_t a); /* NULL is allowed */
+/* The readers: what the launches read.  info: the level count and per level n, the stored nonzeros, the bounds and
+ * the kind, the options used, the device bytes held and the set-up seconds.  level_aggregates (level < levels - 1):
+ * agg[n_l], the aggregate of every row, and w[n_l] in the value type, both copied back from the device (either may be
+ * NULL).  level_matrix (1 <= level < levels): the lower triangle + diagonal CSR the level's handle was created from,
+ * rowptr[n_l + 1], colind[nnz_l], values[nnz_l] in the value type (any may be NULL).  coarse_inverse: the n_L x n_L
+ * values of the dense level, copied back from the device; a hierarchy that ends smoother-only: CFS_HIP_ERR_ARG.   */
+int cfs_hip_amg_info(cfs_hip_amg_t a, cfs_hip_amg_info_t *out);
+int cfs_hip_amg_level_aggregates(cfs_hip_amg_t a, int level, int *agg, void *w);
+int cfs_hip_amg_level_matrix(cfs_hip_amg_t a, int level, int *rowptr, int *colind, void *values);
+int cfs_hip_amg_coarse_inverse(cfs_hip_amg_t a, void *inv);
+/* One cycle, z = M^-1 r, enqueued on `stream`.  z_dev (fully overwritten) and r_dev: different device vectors of n
+ * values of the value type on the handle's device, 16-byte aligned; nothing else of the caller's is written.  The work
+ * vectors belong to the object: one cycle of an object at a time.  CFS_HIP_ERR_ARG: a null pointer, z == r, a pointer
+ * that is not 16-byte aligned, a host pointer or one on another device.                                          */
+int cfs_hip_amg_apply(cfs_hip_amg_t a, void *z_dev, const void *r_dev, void *stream);
+/* cfs_hip_sym_pcg_cheb with the polynomial replaced by the cycle of `a`, which must have been created on h (otherwise
+ * CFS_HIP_ERR_ARG): the same residual kernel, the same stopping rule on the UNPRECONDITIONED residual, r.r <= tol^2 b.b;
+ * a NaN ends the solve; *relres is RECOMPUTED from the returned u; r.z sums the stored r and the stored final z; all
+ * scalars are fixed-order partial sums, so a solve on a CFS_HIP_FLAG_DETERMINISTIC handle is bit-reproducible.  Per
+ * iteration: the product, four vector kernels and the cycle.  A cycle is more than may be enqueued between two host
+ * looks, so the host looks at the convergence flag after EVERY iteration; check_every is accepted and not used.
+ * Argument checks as for cfs_hip_sym_pcg_cheb: CFS_HIP_ERR_ARG for a null pointer (first), u == b, u or b not 16-byte
+ * aligned, tol < 0, maxiter < 0; CFS_HIP_ERR_UNSUPPORTED for a shard or a multi-device handle; then CFS_HIP_ERR_ARG
+ * for a hierarchy of another handle, a host pointer or a pointer on another device.  In each case u is untouched and
+ * *iterations = 0.                                                                                                */
+int cfs_hip_sym_pcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const void *b_dev, double tol, int maxiter,
+                        int check_every, int *iterations, double *relres, void *stream);
+/* Host only, no device work: one level of the set-up above.  In: the CSR of A_l (entries with col <= row are read),
+ * passes (1 .. 3).  Out: agg[n], w[n] (fp64), *nc, and the lower triangle + diagonal CSR of A_{l+1} in fp64,
+ * c_rowptr[*nc + 1] (at least n + 1 ints: *nc is not known before), c_colind / c_values with room for `capacity`
+ * entries, *c_nnz the number written.  The coarse matrix never has more stored entries than the lower triangle +
+ * diagonal of the input, so capacity = nnz always suffices; too little room: CFS_HIP_ERR_ARG with *c_nnz set to what
+ * is needed.  A diagonal entry that is zero, missing, negative or not finite: CFS_HIP_ERR_ARG as above.           */
+int cfs_hip_debug_amg_coarsen(int n, const int *rowptr, const int *colind, const double *values, int passes,
+                              int *agg, double *w, int *nc, int *c_rowptr, int *c_colind, double *c_values,
+                              long long capacity, long long *c_nnz);
 /* MINRES (Paige & Saunders) for (A - shift I) u = b: A symmetric, possibly INDEFINITE, or singular with a
  * consistent b -- saddle-point matrices (a zero diagonal block), shifted operators, mixed-sign diagonals, on
  * which the conjugate gradients above promise nothing (on [[0, K], [K, 0]] with b = [f; 0] their first p.q is

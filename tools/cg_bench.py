@@ -17,7 +17,11 @@ the base, beside the block-Jacobi PCG): solves down to TOL at degrees 2 and 4, i
 rounds, the best wall time of each; outer iterations, products (the estimate's 16 and the two residuals included) and the
 time per outer iteration.  The default bounds are estimated inside the timed call; "_bounds_given" passes the bounds of
 an earlier call, as a caller with many right-hand sides would.
-usage: python tools/cg_bench.py [--only-cheb] [matrix[:scale] | lap2dNXxNY ...]"""
+The multigrid-preconditioned PCG (cfs_hip_sym_pcg_amg, --only-amg) sits beside the native Jacobi PCG and the Chebyshev degree-4
+PCG of the same build: solves down to TOL at smoother degrees 1 and 2 with the default hierarchy, interleaved, AMG_ROUNDS rounds,
+the best wall time of each; iterations, ms per solve, and per hierarchy the levels, the device bytes and the set-up seconds (the
+whole create, and of it the create path of the level handles).  The hierarchy is built once, outside the timed solves.
+usage: python tools/cg_bench.py [--only-cheb | --only-amg] [matrix[:scale] | lap2dNXxNY ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -26,6 +30,7 @@ import cfs_spmv_amd as cfs
 from cfs_spmv_amd import synth
 from cfs_spmv_amd.solver import cg, cg_native, minres, minres_native, pcg, pcg_native, pcg_mixed_native
 from cfs_spmv_amd.solver import pcg_cheb_native
+from cfs_spmv_amd.solver import pcg_amg_native
 
 HAVE_PCG = hasattr(cfs.load(), "cfs_hip_sym_pcg")
 HAVE_BLOCK = hasattr(cfs.load(), "cfs_hip_sym_pcg_block")
@@ -33,6 +38,9 @@ HAVE_MIXED = hasattr(cfs.load(), "cfs_hip_sym_pcg_mixed")
 HAVE_MINRES = hasattr(cfs.load(), "cfs_hip_sym_minres")
 HAVE_CHEB = hasattr(cfs.load(), "cfs_hip_sym_pcg_cheb")
 ONLY_CHEB = "--only-cheb" in sys.argv
+HAVE_AMG = hasattr(cfs.load(), "cfs_hip_sym_pcg_amg")
+ONLY_AMG = "--only-amg" in sys.argv
+AMG_DEGREES, AMG_ROUNDS = (1, 2), 3
 CHEB_DEGREES, CHEB_ROUNDS = (2, 4), 3
 BLOCK, TOL, MAXITER = 3, 1e-8, 5000
 MIXED_TOL, MIXED_MAXITER = 1e-10, 20000
@@ -77,6 +85,42 @@ def cheb_section(A, b, res):
                 res[f"cheb{m}_{tag}{suffix}_over_pcg_{tag}_time"] = round(best[f"cheb{m}_{tag}{suffix}"][0] / best[f"pcg_{tag}"][0], 4)
 
 
+def amg_section(A, b, res, rp, ci, va):
+    """solves down to TOL: Jacobi PCG, Chebyshev degree 4 on Jacobi, and the V-cycle at AMG_DEGREES, interleaved"""
+    loops = {"pcg_jacobi": lambda: pcg_native(A, b, precond="jacobi", tol=TOL, maxiter=MAXITER, check_every=16)[1:3],
+             "cheb4_jacobi": lambda: pcg_cheb_native(A, b, degree=4, tol=TOL, maxiter=MAXITER, check_every=16)[1:3]}
+    hierarchies = {}
+    for m in AMG_DEGREES:
+        hierarchies[m] = G = A.amg(rp, ci, va, degree=m)
+        inf = G.info()
+        res[f"amg{m}_levels"] = inf["n"]
+        res[f"amg{m}_kinds"] = inf["kind"]
+        res[f"amg{m}_device_bytes"] = inf["device_bytes"]
+        res[f"amg{m}_setup_seconds"] = round(inf["setup_seconds"], 4)
+        res[f"amg{m}_setup_seconds_level_handles"] = round(inf["handles_seconds"], 4)
+        loops[f"amg{m}"] = (lambda G=G: pcg_amg_native(A, b, G, tol=TOL, maxiter=MAXITER)[1:3])
+    res["matrix_device_bytes"] = A.stats()["device_bytes"]
+    best = {}
+    for _ in range(AMG_ROUNDS):
+        for label, fn in loops.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            it, rel = fn()
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            if t < best.get(label, (float("inf"),))[0]:
+                best[label] = (t, it, rel)
+    res["amg_tolerance"], res["amg_rounds"] = TOL, AMG_ROUNDS
+    for label, (t, it, rel) in best.items():
+        res[label + "_ms_to_tolerance"] = round(t * 1e3, 3)
+        res[label + "_iterations"] = it
+        res[label + "_relres"] = rel
+    for m in AMG_DEGREES:
+        res[f"amg{m}_over_pcg_jacobi_time"] = round(best[f"amg{m}"][0] / best["pcg_jacobi"][0], 4)
+        res[f"amg{m}_over_cheb4_jacobi_time"] = round(best[f"amg{m}"][0] / best["cheb4_jacobi"][0], 4)
+        hierarchies[m].close()
+
+
 out = {}
 for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ldoor", "Flan_1565"]):
     name, _, sc = spec.partition(":")
@@ -102,8 +146,11 @@ for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ld
     spmv_us = (time.perf_counter() - t0) / 200 * 1e6
     K = 200
     res = {"n": n, "spmv_us": round(spmv_us, 2)}
-    if ONLY_CHEB:
-        cheb_section(A, b, res)
+    if ONLY_CHEB or ONLY_AMG:
+        if ONLY_CHEB:
+            cheb_section(A, b, res)
+        if ONLY_AMG:
+            amg_section(A, b, res, rp, ci, va)
         out[spec] = res
         A.close()
         continue
@@ -200,6 +247,8 @@ for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ld
                                                                      check_every=16)[1]
     if HAVE_CHEB:
         cheb_section(A, b, res)
+    if HAVE_AMG:
+        amg_section(A, b, res, rp, ci, va)
     out[spec] = res
     A.close()
 print(json.dumps(out))
