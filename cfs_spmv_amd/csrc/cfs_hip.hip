@@ -1945,41 +1945,97 @@ int cfs_hip_sym_spmv_async(cfs_hip_sym_t h, void *y, const void *x, void *stream
   return h->spmv_local(y, x, nullptr, (hipStream_t)stream);
 }
 
+// ---- the solve entry points ------------------------------------------------------------------------
+// What each of them checks of its (u, b) or (z, r) pair, in one order.  check_solve_args: what needs no look at the
+// handle -- null, the outputs zeroed, u != b, 16-byte alignment, tol / maxiter (tol = nullptr: the entry point has
+// none).  Then the entry point's own arguments.  Then check_solve_handle: a handle of the whole matrix, on one device
+// where that is required, the placement of the pair, and ok_x = ok_y = nullptr (the iteration's own vectors are
+// library memory on the handle's device).
+//   who: the prefix of the refusals;  inner: that of the alignment and tolerance refusals (cfs_hip_sym_pcg and
+//   _pcg_block have always answered those with cg's);  pair: "u and b" / "z and r"
+static int check_solve_args(const char *who, const char *inner, const char *pair, bool any_null, const void *u, const void *b,
+                            const double *tol, int maxiter, int *iterations, int *replacements, double *relres,
+                            const char *null_text = "null argument") {
+  if (any_null) return set_err(CFS_HIP_ERR_ARG, null_text);
+  if (iterations) *iterations = 0;
+  if (replacements) *replacements = 0;
+  if (relres) *relres = 0.0;
+  if (u == b) return set_err(CFS_HIP_ERR_ARG, std::string(who) + ": " + pair + " must be different vectors");
+  if ((((uintptr_t)u) | ((uintptr_t)b)) & 15) return set_err(CFS_HIP_ERR_ARG, std::string(inner) + ": " + pair + " must be 16-byte aligned");
+  if (tol && (maxiter < 0 || !(*tol >= 0.0))) return set_err(CFS_HIP_ERR_ARG, std::string(inner) + ": bad tolerance / iteration limit");
+  return 0;
+}
+static std::string not_a_shard(const char *who) { return std::string(who) + ": a handle of the whole matrix, not a shard"; }
+// the refusal of a multi-device handle where node blocks are used ("": block_rows < 2, any handle of the whole matrix)
+static std::string blocks_on_one_device(const char *who, int block_rows) {
+  if (block_rows < 2) return "";
+  return std::string(who) + ": block Jacobi needs the whole matrix on one device (blocks straddle the row splits of a multi-device handle)";
+}
+// shard: the refusal of a handle that is not of the whole matrix (rows_too: a row block without sends counts);
+// one_device: the refusal of a multi-device handle, or "" where one is accepted
+static int check_whole_matrix(cfs_hip_sym_t h, const std::string &shard, bool rows_too, const std::string &one_device) {
+  if (!h->send_rows().empty() || (rows_too && h->rows() != h->n())) return set_err(CFS_HIP_ERR_UNSUPPORTED, shard);
+  int ngpus = 1;
+  if (!one_device.empty() && cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1) return set_err(CFS_HIP_ERR_UNSUPPORTED, one_device);
+  return 0;
+}
+static int check_solve_handle(cfs_hip_sym_t h, const void *u, const void *b, const std::string &shard, bool rows_too,
+                              const std::string &one_device) {
+  int rc = check_whole_matrix(h, shard, rows_too, one_device);
+  if (rc || (rc = check_placement(h, u, b))) return rc;
+  h->ok_x = h->ok_y = nullptr;
+  return 0;
+}
+
+static bool block_rows_ok(int bs) { return bs == 1 || bs == 2 || bs == 3 || bs == 4 || bs == 6; }
+// f(V(), std::integral_constant<int, BS>()) for the handle's value type and a stored M^-1 of 0 (none), 1 (Jacobi) or
+// node blocks of 2, 3, 4 or 6 rows: the BS of cfs_solver::Precond
+template <class F> static int with_precond(int value_bytes, int bs, F &&f) {
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    switch (bs) {
+    case 0: return f(v, std::integral_constant<int, 0>());
+    case 1: return f(v, std::integral_constant<int, 1>());
+    case 2: return f(v, std::integral_constant<int, 2>());
+    case 3: return f(v, std::integral_constant<int, 3>());
+    case 4: return f(v, std::integral_constant<int, 4>());
+    default: return f(v, std::integral_constant<int, 6>());
+    }
+  });
+}
+// the handles an entry point with a stored M^-1 accepts: those of cfs_hip_sym_pcg (0, 1) or of cfs_hip_sym_pcg_block
+static int check_precond_handle(cfs_hip_sym_t h, int block_rows, const char *who) {
+  return check_whole_matrix(h, not_a_shard(who), true, blocks_on_one_device(who, block_rows));
+}
+
+// cfs_hip_sym_cg (block_rows 0), _pcg (1) and _pcg_block (2, 3, 4, 6) behind their checks: one code path
+static int run_cg(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int block_rows, double tol, int maxiter, int check_every,
+                  int *iterations, double *relres, void *stream) {
+  DeviceGuard g(h->device);
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::cg<decltype(v), decltype(bs)::value>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres,
+                                                            (hipStream_t)stream);
+  });
+}
+
 int cfs_hip_sym_cg(cfs_hip_sym_t h, void *u_dev, const void *b_dev, double tol, int maxiter, int check_every,
                    int *iterations, double *relres, void *stream) {
-  if (!h || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "cg: u and b must be different vectors");
-  if (iterations) *iterations = 0;
-  if (relres) *relres = 0.0;
-  if (!h->send_rows().empty())
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, "cg: a handle of the whole matrix (a loop over shards of several processes: cfs_spmv_amd/solver.py)");
-  int rc = check_placement(h, u_dev, b_dev);
-  if (rc) return rc;
-  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
-  DeviceGuard g(h->device);
-  if (h->value_bytes == 8)
-    return cfs_solver::cg<double>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, (hipStream_t)stream);
-  return cfs_solver::cg<float>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, (hipStream_t)stream);
+  int rc = check_solve_args("cg", "cg", "u and b", !h || !u_dev || !b_dev, u_dev, b_dev, &tol, maxiter, iterations, nullptr, relres);
+  if (rc || (rc = check_solve_handle(h, u_dev, b_dev,
+                                     "cg: a handle of the whole matrix (a loop over shards of several processes: cfs_spmv_amd/solver.py)",
+                                     false, "")))
+    return rc;
+  return run_cg(h, u_dev, b_dev, 0, tol, maxiter, check_every, iterations, relres, stream);
 }
 
 int cfs_hip_sym_pcg(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int precond, double tol, int maxiter,
                     int check_every, int *iterations, double *relres, void *stream) {
   if (precond == CFS_HIP_PRECOND_NONE) // the plain iteration: the same code path, the same bits
     return cfs_hip_sym_cg(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, stream);
-  if (!h || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  if (iterations) *iterations = 0;
-  if (relres) *relres = 0.0;
-  if (precond != CFS_HIP_PRECOND_JACOBI) return set_err(CFS_HIP_ERR_ARG, "pcg: unknown preconditioner " + std::to_string(precond));
-  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg: u and b must be different vectors");
-  if (!h->send_rows().empty())
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg: a handle of the whole matrix, not a shard");
-  int rc = check_placement(h, u_dev, b_dev);
+  int rc = check_solve_args("pcg", "cg", "u and b", !h || !u_dev || !b_dev, u_dev, b_dev, &tol, maxiter, iterations, nullptr, relres);
   if (rc) return rc;
-  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
-  DeviceGuard g(h->device);
-  if (h->value_bytes == 8)
-    return cfs_solver::cg<double, true>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, (hipStream_t)stream);
-  return cfs_solver::cg<float, true>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres, (hipStream_t)stream);
+  if (precond != CFS_HIP_PRECOND_JACOBI) return set_err(CFS_HIP_ERR_ARG, "pcg: unknown preconditioner " + std::to_string(precond));
+  if ((rc = check_solve_handle(h, u_dev, b_dev, not_a_shard("pcg"), false, ""))) return rc;
+  return run_cg(h, u_dev, b_dev, 1, tol, maxiter, check_every, iterations, relres, stream);
 }
 
 int cfs_hip_sym_diagonal_async(cfs_hip_sym_t h, void *d_dev, void *stream) {
@@ -1993,18 +2049,6 @@ int cfs_hip_sym_diagonal_async(cfs_hip_sym_t h, void *d_dev, void *stream) {
   return h->diagonal(d_dev, (hipStream_t)stream);
 }
 
-static bool block_rows_ok(int bs) { return bs == 1 || bs == 2 || bs == 3 || bs == 4 || bs == 6; }
-// f(V(), std::integral_constant<int, BS>()) for the handle's value type and a block size of 2, 3, 4 or 6
-template <class F> static int with_block(int value_bytes, int bs, F &&f) {
-  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
-    switch (bs) {
-    case 2: return f(v, std::integral_constant<int, 2>());
-    case 3: return f(v, std::integral_constant<int, 3>());
-    case 4: return f(v, std::integral_constant<int, 4>());
-    default: return f(v, std::integral_constant<int, 6>());
-    }
-  });
-}
 // the output of the two block entry points: a device pointer on the handle's device
 static int check_block_out(cfs_hip_sym_t h, const void *p, const char *who) {
   const cfs_rt::PtrInfo di = cfs_rt::classify(p);
@@ -2032,102 +2076,67 @@ int cfs_hip_sym_block_inverse_async(cfs_hip_sym_t h, int block_rows, void *minv_
   int rc = check_block_out(h, minv_dev, "cfs_hip_sym_block_inverse_async");
   if (rc) return rc;
   DeviceGuard g(h->device);
-  if (block_rows == 1)
-    return cfs_rt::with_value_type(h->value_bytes, [&](auto v) {
-      return cfs_solver::block_inverse<decltype(v), 1>(h, minv_dev, (hipStream_t)stream);
-    });
-  return with_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
-    return cfs_solver::block_inverse<decltype(v), decltype(bs)::value>(h, minv_dev, (hipStream_t)stream);
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    constexpr int BS = decltype(bs)::value;
+    if constexpr (BS == 0) // (block_rows_ok: not reached)
+      return set_err(CFS_HIP_ERR_INTERNAL, "block inverse: no blocks");
+    else
+      return cfs_solver::block_inverse<decltype(v), BS>(h, minv_dev, (hipStream_t)stream);
   });
 }
 
 int cfs_hip_sym_pcg_block(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int block_rows, double tol, int maxiter,
                           int check_every, int *iterations, double *relres, void *stream) {
-  if (!h || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  if (iterations) *iterations = 0;
-  if (relres) *relres = 0.0;
+  int rc = check_solve_args("pcg", "cg", "u and b", !h || !u_dev || !b_dev, u_dev, b_dev, &tol, maxiter, iterations, nullptr, relres);
+  if (rc) return rc;
   if (!block_rows_ok(block_rows))
     return set_err(CFS_HIP_ERR_ARG, "pcg: block_rows " + std::to_string(block_rows) + " is not one of 1, 2, 3, 4, 6");
   if (block_rows == 1) // Jacobi: the same code path, the same bits
     return cfs_hip_sym_pcg(h, u_dev, b_dev, CFS_HIP_PRECOND_JACOBI, tol, maxiter, check_every, iterations, relres, stream);
-  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg: u and b must be different vectors");
-  if (!h->send_rows().empty() || h->rows() != h->n())
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg: a handle of the whole matrix, not a shard");
-  int ngpus = 1;
-  if (cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg: block Jacobi needs the whole matrix on one device (blocks straddle the "
-                                            "row splits of a multi-device handle)");
-  int rc = check_placement(h, u_dev, b_dev);
-  if (rc) return rc;
-  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
-  DeviceGuard g(h->device);
-  return with_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
-    return cfs_solver::cg<decltype(v), true, decltype(bs)::value>(h, u_dev, b_dev, tol, maxiter, check_every, iterations, relres,
-                                                                  (hipStream_t)stream);
-  });
+  if ((rc = check_solve_handle(h, u_dev, b_dev, not_a_shard("pcg"), true, blocks_on_one_device("pcg", block_rows)))) return rc;
+  return run_cg(h, u_dev, b_dev, block_rows, tol, maxiter, check_every, iterations, relres, stream);
 }
 
 int cfs_hip_sym_pcg_mixed(cfs_hip_sym_t h64, cfs_hip_sym_t h32, void *u_dev, const void *b_dev, int block_rows, double tol,
                           double delta, int maxiter, int check_every, int *iterations, int *replacements, double *relres,
                           void *stream) {
-  if (!h64 || !h32 || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  if (iterations) *iterations = 0;
-  if (replacements) *replacements = 0;
-  if (relres) *relres = 0.0;
+  int rc = check_solve_args("pcg_mixed", "pcg_mixed", "u and b", !h64 || !h32 || !u_dev || !b_dev, u_dev, b_dev, &tol, maxiter,
+                            iterations, replacements, relres);
+  if (rc) return rc;
   if (block_rows != 0 && !block_rows_ok(block_rows))
     return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: block_rows " + std::to_string(block_rows) + " is not one of 0, 1, 2, 3, 4, 6");
   if (delta == 0.0) delta = 0.1;
   if (!(delta > 0.0 && delta < 1.0)) return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: delta must lie in (0, 1) (0: the default, 0.1)");
-  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: u and b must be different vectors");
   if (h64->value_bytes != 8 || h32->value_bytes != 4)
     return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: the first handle must hold fp64 values and the second fp32 values (got " +
                                         std::to_string(h64->value_bytes) + " and " + std::to_string(h32->value_bytes) + " bytes)");
   if (h64->n() != h32->n())
     return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: the handles hold matrices of " + std::to_string(h64->n()) + " and " +
                                         std::to_string(h32->n()) + " rows");
-  for (cfs_hip_sym_t h : {h64, h32}) {
-    if (!h->send_rows().empty() || h->rows() != h->n())
-      return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_mixed: handles of the whole matrix, not shards");
-    int ngpus = 1;
-    if (cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
-      return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_mixed: both matrices on one device (the multi-device form is not built)");
-  }
+  for (cfs_hip_sym_t h : {h64, h32})
+    if ((rc = check_whole_matrix(h, "pcg_mixed: handles of the whole matrix, not shards", true,
+                                 "pcg_mixed: both matrices on one device (the multi-device form is not built)")))
+      return rc;
   if (h64->device != h32->device)
     return set_err(CFS_HIP_ERR_ARG, "pcg_mixed: the fp64 matrix lives on device " + std::to_string(h64->device) +
                                         ", the fp32 matrix on device " + std::to_string(h32->device));
-  int rc = check_placement(h64, u_dev, b_dev);
-  if (rc) return rc;
-  // (the iteration's own vectors are library memory on the handles' device)
-  h64->ok_x = h64->ok_y = h32->ok_x = h32->ok_y = nullptr;
+  if ((rc = check_placement(h64, u_dev, b_dev))) return rc;
+  h64->ok_x = h64->ok_y = h32->ok_x = h32->ok_y = nullptr; // (as check_solve_handle, for both)
   DeviceGuard g(h64->device);
-  hipStream_t st = (hipStream_t)stream;
-  if (block_rows == 0)
-    return cfs_solver::cg_mixed<false, 0>(h64, h32, u_dev, b_dev, tol, delta, maxiter, check_every, iterations, replacements, relres, st);
-  if (block_rows == 1)
-    return cfs_solver::cg_mixed<true, 0>(h64, h32, u_dev, b_dev, tol, delta, maxiter, check_every, iterations, replacements, relres, st);
-  return with_block(4, block_rows, [&](auto, auto bs) {
-    return cfs_solver::cg_mixed<true, decltype(bs)::value>(h64, h32, u_dev, b_dev, tol, delta, maxiter, check_every, iterations,
-                                                           replacements, relres, st);
+  return with_precond(4, block_rows, [&](auto, auto bs) {
+    return cfs_solver::cg_mixed<decltype(bs)::value>(h64, h32, u_dev, b_dev, tol, delta, maxiter, check_every, iterations,
+                                                     replacements, relres, (hipStream_t)stream);
   });
 }
 
 int cfs_hip_sym_minres(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int precond, double shift, double tol, int maxiter,
                        int check_every, int *iterations, double *relres, void *stream) {
-  if (!h || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  if (iterations) *iterations = 0;
-  if (relres) *relres = 0.0;
+  int rc = check_solve_args("minres", "minres", "u and b", !h || !u_dev || !b_dev, u_dev, b_dev, &tol, maxiter, iterations, nullptr, relres);
+  if (rc) return rc;
   if (precond != CFS_HIP_PRECOND_NONE && precond != CFS_HIP_PRECOND_JACOBI)
     return set_err(CFS_HIP_ERR_ARG, "minres: unknown preconditioner " + std::to_string(precond));
-  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "minres: u and b must be different vectors");
-  if ((((uintptr_t)u_dev) | ((uintptr_t)b_dev)) & 15)
-    return set_err(CFS_HIP_ERR_ARG, "minres: u and b must be 16-byte aligned");
-  if (maxiter < 0 || !(tol >= 0.0)) return set_err(CFS_HIP_ERR_ARG, "minres: bad tolerance / iteration limit");
   if (!std::isfinite(shift)) return set_err(CFS_HIP_ERR_ARG, "minres: the shift must be finite");
-  if (!h->send_rows().empty() || h->rows() != h->n())
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, "minres: a handle of the whole matrix, not a shard");
-  int rc = check_placement(h, u_dev, b_dev);
-  if (rc) return rc;
-  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  if ((rc = check_solve_handle(h, u_dev, b_dev, not_a_shard("minres"), true, ""))) return rc;
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)stream;
   return cfs_rt::with_value_type(h->value_bytes, [&](auto v) {
@@ -2138,24 +2147,6 @@ int cfs_hip_sym_minres(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int prec
   });
 }
 
-// f(V(), std::integral_constant<int, BS>()) for the handle's value type and a base of 0 (none), 1 (Jacobi), 2, 3, 4 or 6
-template <class F> static int with_cheb_base(int value_bytes, int bs, F &&f) {
-  if (bs >= 2) return with_block(value_bytes, bs, f);
-  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
-    if (bs == 1) return f(v, std::integral_constant<int, 1>());
-    return f(v, std::integral_constant<int, 0>());
-  });
-}
-// the handles a Chebyshev entry point accepts: those of cfs_hip_sym_pcg (base 0, 1) or of cfs_hip_sym_pcg_block
-static int check_cheb_handle(cfs_hip_sym_t h, int block_rows, const char *who) {
-  if (!h->send_rows().empty() || h->rows() != h->n())
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, std::string(who) + ": a handle of the whole matrix, not a shard");
-  int ngpus = 1;
-  if (block_rows >= 2 && cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, std::string(who) + ": block Jacobi needs the whole matrix on one device (blocks straddle "
-                                                               "the row splits of a multi-device handle)");
-  return 0;
-}
 // degree and the bounds of the Chebyshev entry points; need_both: both bounds must be given (> 0)
 static int check_cheb_args(const char *who, int block_rows, int degree, double lmin, double lmax, bool need_both) {
   if (block_rows != 0 && !block_rows_ok(block_rows))
@@ -2173,17 +2164,13 @@ static int check_cheb_args(const char *who, int block_rows, int degree, double l
 int cfs_hip_sym_pcg_cheb(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int block_rows, int degree, double lmin, double lmax,
                          double tol, int maxiter, int check_every, int *iterations, double *relres, double *bounds_used,
                          void *stream) {
-  if (!h || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  if (iterations) *iterations = 0;
-  if (relres) *relres = 0.0;
-  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg_cheb: u and b must be different vectors");
-  if ((((uintptr_t)u_dev) | ((uintptr_t)b_dev)) & 15) return set_err(CFS_HIP_ERR_ARG, "pcg_cheb: u and b must be 16-byte aligned");
-  if (maxiter < 0 || !(tol >= 0.0)) return set_err(CFS_HIP_ERR_ARG, "pcg_cheb: bad tolerance / iteration limit");
-  int rc = check_cheb_args("pcg_cheb", block_rows, degree, lmin, lmax, false);
-  if (rc || (rc = check_cheb_handle(h, block_rows, "pcg_cheb")) || (rc = check_placement(h, u_dev, b_dev))) return rc;
-  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  const char *who = "pcg_cheb";
+  int rc = check_solve_args(who, who, "u and b", !h || !u_dev || !b_dev, u_dev, b_dev, &tol, maxiter, iterations, nullptr, relres);
+  if (rc || (rc = check_cheb_args(who, block_rows, degree, lmin, lmax, false)) ||
+      (rc = check_solve_handle(h, u_dev, b_dev, not_a_shard(who), true, blocks_on_one_device(who, block_rows))))
+    return rc;
   DeviceGuard g(h->device);
-  return with_cheb_base(h->value_bytes, block_rows, [&](auto v, auto bs) {
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
     return cfs_solver::cg_cheb<decltype(v), decltype(bs)::value>(h, u_dev, b_dev, degree, lmin, lmax, tol, maxiter, check_every,
                                                                  iterations, relres, bounds_used, (hipStream_t)stream);
   });
@@ -2191,14 +2178,13 @@ int cfs_hip_sym_pcg_cheb(cfs_hip_sym_t h, void *u_dev, const void *b_dev, int bl
 
 int cfs_hip_sym_cheb_apply(cfs_hip_sym_t h, int block_rows, int degree, double lmin, double lmax, void *z_dev, const void *r_dev,
                            void *stream) {
-  if (!h || !z_dev || !r_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  if (z_dev == r_dev) return set_err(CFS_HIP_ERR_ARG, "cheb_apply: z and r must be different vectors");
-  if ((((uintptr_t)z_dev) | ((uintptr_t)r_dev)) & 15) return set_err(CFS_HIP_ERR_ARG, "cheb_apply: z and r must be 16-byte aligned");
-  int rc = check_cheb_args("cheb_apply", block_rows, degree, lmin, lmax, true);
-  if (rc || (rc = check_cheb_handle(h, block_rows, "cheb_apply")) || (rc = check_placement(h, z_dev, r_dev))) return rc;
-  h->ok_x = h->ok_y = nullptr;
+  const char *who = "cheb_apply";
+  int rc = check_solve_args(who, who, "z and r", !h || !z_dev || !r_dev, z_dev, r_dev, nullptr, 0, nullptr, nullptr, nullptr);
+  if (rc || (rc = check_cheb_args(who, block_rows, degree, lmin, lmax, true)) ||
+      (rc = check_solve_handle(h, z_dev, r_dev, not_a_shard(who), true, blocks_on_one_device(who, block_rows))))
+    return rc;
   DeviceGuard g(h->device);
-  return with_cheb_base(h->value_bytes, block_rows, [&](auto v, auto bs) {
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
     return cfs_solver::cheb_apply<decltype(v), decltype(bs)::value>(h, degree, lmin, lmax, z_dev, r_dev, (hipStream_t)stream);
   });
 }
@@ -2208,7 +2194,7 @@ int cfs_hip_sym_precond_lmax(cfs_hip_sym_t h, int block_rows, int steps, const v
   *estimate = 0.0;
   if (block_rows != 0 && !block_rows_ok(block_rows))
     return set_err(CFS_HIP_ERR_ARG, "precond_lmax: block_rows " + std::to_string(block_rows) + " is not one of 0, 1, 2, 3, 4, 6");
-  int rc = check_cheb_handle(h, block_rows, "precond_lmax");
+  int rc = check_precond_handle(h, block_rows, "precond_lmax");
   if (rc) return rc;
   if (v0_dev) {
     const cfs_rt::PtrInfo pi = cfs_rt::classify(v0_dev);
@@ -2219,7 +2205,7 @@ int cfs_hip_sym_precond_lmax(cfs_hip_sym_t h, int block_rows, int steps, const v
   }
   h->ok_x = h->ok_y = nullptr;
   DeviceGuard g(h->device);
-  return with_cheb_base(h->value_bytes, block_rows, [&](auto v, auto bs) {
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
     return cfs_solver::cheb_lmax<decltype(v), decltype(bs)::value>(h, steps, v0_dev, estimate, (hipStream_t)stream);
   });
 }
@@ -2302,34 +2288,24 @@ int cfs_hip_amg_coarse_inverse(cfs_hip_amg_t a, void *inv) {
   return a->coarse_inverse(inv);
 }
 int cfs_hip_amg_apply(cfs_hip_amg_t a, void *z_dev, const void *r_dev, void *stream) {
-  if (!a || !z_dev || !r_dev) return set_err(CFS_HIP_ERR_ARG, "amg_apply: null argument");
-  if (z_dev == r_dev) return set_err(CFS_HIP_ERR_ARG, "amg_apply: z and r must be different vectors");
-  if ((((uintptr_t)z_dev) | ((uintptr_t)r_dev)) & 15) return set_err(CFS_HIP_ERR_ARG, "amg_apply: z and r must be 16-byte aligned");
-  cfs_hip_sym_t h = a->fine;
-  int rc = check_placement(h, z_dev, r_dev);
-  if (rc) return rc;
-  h->ok_x = h->ok_y = nullptr;
+  const char *who = "amg_apply";
+  int rc = check_solve_args(who, who, "z and r", !a || !z_dev || !r_dev, z_dev, r_dev, nullptr, 0, nullptr, nullptr, nullptr,
+                            "amg_apply: null argument");
+  cfs_hip_sym_t h = rc ? nullptr : a->fine; // (a handle cfs_hip_amg_create_* accepted: the whole matrix on one device)
+  if (rc || (rc = check_solve_handle(h, z_dev, r_dev, not_a_shard(who), true, ""))) return rc;
   DeviceGuard g(h->device);
   return a->apply(z_dev, r_dev, (hipStream_t)stream);
 }
 int cfs_hip_sym_pcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const void *b_dev, double tol, int maxiter, int check_every,
                         int *iterations, double *relres, void *stream) {
   (void)check_every; // (the host looks after every iteration: cfs_hip.h)
-  if (!h || !a || !u_dev || !b_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
-  if (iterations) *iterations = 0;
-  if (relres) *relres = 0.0;
-  if (u_dev == b_dev) return set_err(CFS_HIP_ERR_ARG, "pcg_amg: u and b must be different vectors");
-  if ((((uintptr_t)u_dev) | ((uintptr_t)b_dev)) & 15) return set_err(CFS_HIP_ERR_ARG, "pcg_amg: u and b must be 16-byte aligned");
-  if (maxiter < 0 || !(tol >= 0.0)) return set_err(CFS_HIP_ERR_ARG, "pcg_amg: bad tolerance / iteration limit");
-  if (!h->send_rows().empty() || h->rows() != h->n())
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_amg: a handle of the whole matrix, not a shard");
-  int ngpus = 1;
-  if (cfs_hip_sym_num_gpus(h, &ngpus) == 0 && ngpus != 1)
-    return set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_amg: the whole matrix on one device, not a multi-device handle");
+  const char *who = "pcg_amg";
+  int rc = check_solve_args(who, who, "u and b", !h || !a || !u_dev || !b_dev, u_dev, b_dev, &tol, maxiter, iterations, nullptr, relres);
+  if (rc || (rc = check_whole_matrix(h, not_a_shard(who), true, "pcg_amg: the whole matrix on one device, not a multi-device handle")))
+    return rc;
   if (a->fine != h) return set_err(CFS_HIP_ERR_ARG, "pcg_amg: the hierarchy was created on another handle");
-  int rc = check_placement(h, u_dev, b_dev);
-  if (rc) return rc;
-  h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
+  if ((rc = check_placement(h, u_dev, b_dev))) return rc;
+  h->ok_x = h->ok_y = nullptr; // (as check_solve_handle)
   DeviceGuard g(h->device);
   return a->pcg(u_dev, b_dev, tol, maxiter, iterations, relres, (hipStream_t)stream);
 }
@@ -2466,14 +2442,6 @@ int cfs_hip_debug_eigs_combine(void *out_dev, long long ldo, const void *basis_d
 }
 
 // ---- LOBPCG ----
-// f(V(), std::integral_constant<int, BS>()) for the handle's value type and block_rows 0, 1, 2, 3, 4 or 6
-template <class F> static int with_lobpcg_block(int value_bytes, int bs, F &&f) {
-  if (bs >= 2) return with_block(value_bytes, bs, f);
-  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
-    if (bs == 1) return f(v, std::integral_constant<int, 1>());
-    return f(v, std::integral_constant<int, 0>());
-  });
-}
 // the checks that cfs_hip_sym_lobpcg and cfs_hip_sym_debug_lobpcg share, from "bad k" on, in the documented order
 static int check_lobpcg(cfs_hip_sym_t h, int k, int block_rows, bool tol_ok, const void *x0_dev, long long ld0, const void *vectors_dev,
                         long long ld) {
@@ -2517,7 +2485,7 @@ int cfs_hip_sym_lobpcg(cfs_hip_sym_t h, int k, int block_rows, double tol, doubl
   h->ok_x = h->ok_y = nullptr; // (the iteration's own vectors are library memory on the handle's device)
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)stream;
-  return with_lobpcg_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
     return cfs_solver::lobpcg<decltype(v), decltype(bs)::value>(h, k, tol, scale, maxiter, -1, x0_dev, ld0, eigenvalues, vectors_dev, ld,
                                                                 residuals, nconv, iterations, products, st);
   });
@@ -2531,7 +2499,7 @@ int cfs_hip_sym_debug_lobpcg(cfs_hip_sym_t h, int k, int block_rows, const void 
   h->ok_x = h->ok_y = nullptr;
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)stream;
-  return with_lobpcg_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
     return cfs_solver::lobpcg<decltype(v), decltype(bs)::value>(h, k, 0.0, 1.0, 0, iters, x0_dev, ld0, theta, vectors_dev, ld, resnorms,
                                                                 nullptr, nullptr, nullptr, st);
   });
@@ -2662,7 +2630,7 @@ int cfs_hip_sym_debug_lobpcg_residual(cfs_hip_sym_t h, int block_rows, const voi
   h->ok_x = h->ok_y = nullptr;
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)stream;
-  return with_lobpcg_block(h->value_bytes, block_rows, [&](auto v, auto bs) {
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
     return cfs_solver::debug_residual<decltype(v), decltype(bs)::value>(h, x_dev, ax_dev, w_dev, ld, k, theta, active, sums, st);
   });
 }

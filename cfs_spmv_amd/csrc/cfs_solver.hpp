@@ -8,7 +8,7 @@
 // synchronisation (20-30 us), more than a whole SpMV of a small matrix.  Here an iteration
 // is five launches on one stream and no host round trip:
 //   tile kernel + fold            q = A p                        (cfs_hip.hip)
-//   cg_pq_kernel                  pq = p . q
+//   cg_dot_kernel                 pq = p . q
 //   cg_update_kernel              u += (rr/pq) p;  r -= (rr/pq) q;  rr' = r . r   (one pass)
 //   cg_direction_kernel           p = r + (rr'/rr) p;  converged?
 // The scalars live in device memory as 512 partial sums each (one per workgroup of the kernel
@@ -20,7 +20,7 @@
 // kernels enqueued behind a converged iteration return at once.  cfs_hip_sym_cg recomputes the
 // true residual ||b - A u|| / ||b|| at the end.
 //
-// Jacobi (cfs_hip_sym_pcg, PRE = true below): the same five launches.  dinv_i = (V)(1 / a_ii) is
+// Jacobi (cfs_hip_sym_pcg; BS = 1 on the host, PRE = true in the kernels below): the same five launches.  dinv_i = (V)(1 / a_ii) is
 // built once from the handle's own diagonal (cfs_diag_gather_kernel, then cg_dinv_kernel);
 // z = D^-1 r is never stored: z_i = (double)r_i * (double)dinv_i, with r_i the rounded value in
 // memory, is formed in fp64 where it is needed --
@@ -81,7 +81,7 @@ __device__ __forceinline__ double slot_sum(const double *part, int slot) {
 
 // The vector kernels move 16 bytes per lane and load (two doubles / four floats) over the part of
 // the vectors that is a multiple of that -- every vector here is 16-byte aligned: library memory, or
-// checked by cg() -- and single values over the rest; grid-stride.
+// checked by the entry point -- and single values over the rest; grid-stride.
 template <typename V> struct Vec16 {
   static constexpr int W = 16 / (int)sizeof(V);
   typedef V type __attribute__((ext_vector_type(16 / sizeof(V))));
@@ -153,35 +153,37 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-// part[P_PQ] <- p . q
+// part[slot] <- a . b of the stored values (p . q into P_PQ; r . z where z is stored: cfs_solver_amg.hpp)
 template <typename V>
 __global__ void __launch_bounds__(kThreads)
-    cg_pq_kernel(const V *__restrict__ p, const V *__restrict__ q, long long n, double *__restrict__ part,
-                 const int *__restrict__ ic) {
+    cg_dot_kernel(const V *__restrict__ a, const V *__restrict__ b, long long n, double *__restrict__ part, int slot,
+                  const int *__restrict__ ic) {
   if (ic[I_DONE]) return;
   constexpr int W = Vec16<V>::W;
   typedef typename Vec16<V>::type VT;
   const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
   double s = 0.0;
   for (long long i = t0; i < nv; i += stride) {
-    const VT pv = reinterpret_cast<const VT *>(p)[i], qv = reinterpret_cast<const VT *>(q)[i];
+    const VT av = reinterpret_cast<const VT *>(a)[i], bv = reinterpret_cast<const VT *>(b)[i];
 #pragma unroll
-    for (int k = 0; k < W; ++k) s += (double)pv[k] * (double)qv[k];
+    for (int k = 0; k < W; ++k) s += (double)av[k] * (double)bv[k];
   }
-  for (long long i = nv * W + t0; i < n; i += stride) s += (double)p[i] * (double)q[i];
+  for (long long i = nv * W + t0; i < n; i += stride) s += (double)a[i] * (double)b[i];
   s = block_sum(s);
-  if (threadIdx.x == 0) part[P_PQ * kGrid + blockIdx.x] = s;
+  if (threadIdx.x == 0) part[slot * kGrid + blockIdx.x] = s;
 }
 
 // alpha = rr / pq;  u += alpha p;  r -= alpha q;  part[rr of the next iteration] <- r . r
 // PRE: alpha = rz / pq, and part[rz of the next iteration] <- r . z with z = dinv r of the ROUNDED r
-template <typename V, bool PRE = false>
+// ALPHA: the first of the two slots alpha's numerator alternates between (PRE = false with P_RZ0: z is stored
+// elsewhere and r . z comes from cg_dot_kernel, cfs_solver_amg.hpp)
+template <typename V, bool PRE = false, int ALPHA = PRE ? P_RZ0 : P_RR0>
 __global__ void __launch_bounds__(kThreads)
     cg_update_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q,
                      long long n, double *__restrict__ part, const int *__restrict__ ic, int it,
                      const V *__restrict__ dinv = nullptr) {
   if (ic[I_DONE]) return;
-  const double pq = slot_sum(part, P_PQ), rr_old = slot_sum(part, (PRE ? P_RZ0 : P_RR0) + (it & 1));
+  const double pq = slot_sum(part, P_PQ), rr_old = slot_sum(part, ALPHA + (it & 1));
   const double alpha = pq != 0.0 ? rr_old / pq : 0.0;
   constexpr int W = Vec16<V>::W;
   typedef typename Vec16<V>::type VT;
@@ -461,108 +463,216 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// ---- host: what every solver behind the C ABI shares ---------------------------------------------
+// n values of V (+ 64 bytes) in each of the buffers
+template <typename V> inline int alloc_vectors(long long n, std::initializer_list<cfs_rt::DevBuf *> bufs) {
+  for (cfs_rt::DevBuf *b : bufs)
+    if (int rc = b->alloc((size_t)n * sizeof(V) + 64)) return rc;
+  return 0;
+}
+
+// the host side of partial-sum slots, part[nslots][kGrid] (P_*, M_* of MINRES, L_* of the power method): the device
+// array, its mirror and the stream it is read on
+struct Slots {
+  cfs_rt::DevBuf buf;
+  std::vector<double> host;
+  hipStream_t st = nullptr;
+  double *dev() const { return (double *)buf.p; }
+  int alloc(int nslots, hipStream_t stream) {
+    st = stream;
+    host.assign((size_t)nslots * kGrid, 0.0);
+    return buf.alloc(host.size() * sizeof(double));
+  }
+  int zero() {
+    HIPCHK(hipMemsetAsync(buf.p, 0, host.size() * sizeof(double), st));
+    return 0;
+  }
+  // a host look: every slot in one copy, one synchronisation of the stream
+  int fetch() {
+    HIPCHK(hipMemcpyAsync(host.data(), buf.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  // the scalar a slot held at the last fetch(): its partial sums added in the order g = 0 .. kGrid - 1 (the order
+  // fixes bb, stop and relres: it is not free to change)
+  double sum(int slot) const {
+    double s = 0.0;
+    for (int g = 0; g < kGrid; g++) s += host[(size_t)slot * kGrid + g];
+    return s;
+  }
+};
+
+// the stored M^-1 of one call, from the handle's own entries: nothing (BS = 0), dinv = (V)(1 / a_ii) (BS = 1) or the
+// packed inverse node blocks (BS = 2, 3, 4, 6).  The kernels' PRE is BS == 1.
+template <typename V, int BS> struct Precond {
+  static_assert(BS == 0 || BS == 1 || BS == 2 || BS == 3 || BS == 4 || BS == 6, "the block sizes of cfs_hip.h");
+  cfs_rt::DevBuf dbuf, blkbuf; // the inverse; the gathered full blocks (BS >= 2)
+  long long nb = 0;            // node blocks (BS >= 2)
+  const V *minv() const { return (const V *)dbuf.p; }
+  // enqueues gather and inversion; entries / blocks that are not positive (definite) are counted into part[P_BAD],
+  // which the caller has zeroed.  gathered: room for the full blocks of the caller's own (cfs_hip_sym_block_inverse_async,
+  // BS = 1 included: block_diagonal and cg_binv_kernel then)
+  template <class Handle> int setup(Handle *h, double *part, hipStream_t st, void *gathered = nullptr) {
+    if constexpr (BS >= 1) {
+      const long long n = h->n(), nblk = (n + BS - 1) / BS;
+      int rc;
+      if (BS >= 2 || gathered) {
+        if (BS >= 2) nb = nblk;
+        if ((rc = dbuf.alloc((size_t)nblk * tri_words(BS) * sizeof(V) + 64)) ||
+            (!gathered && (rc = blkbuf.alloc((size_t)nblk * BS * BS * sizeof(V) + 64))))
+          return rc;
+        void *blocks = gathered ? gathered : blkbuf.p;
+        if ((rc = h->block_diagonal(blocks, BS, st))) return rc;
+        hipLaunchKernelGGL((cg_binv_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)blocks, (V *)dbuf.p, nblk, n, part);
+      } else {
+        if ((rc = dbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = h->diagonal(dbuf.p, st))) return rc;
+        hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)dbuf.p, n, part);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    return 0;
+  }
+  static int refuse(const char *who, double bad, long long n, long long nb) {
+    if (BS >= 2)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, std::string(who) + ": block Jacobi needs positive definite diagonal blocks, " +
+                                                  std::to_string((long long)bad) + " of " + std::to_string(nb) + " blocks of " +
+                                                  std::to_string(BS) + " rows have a pivot that is zero, negative or not finite");
+    return cfs_rt::set_err(CFS_HIP_ERR_ARG, std::string(who) + ": Jacobi needs a positive diagonal, " + std::to_string((long long)bad) +
+                                                " of " + std::to_string(n) + " entries are zero, negative or not finite");
+  }
+  // after a fetch() of the slots set-up counted into: 0, or the refusal
+  int check(const char *who, const Slots &part, long long n) const {
+    const double bad = BS >= 1 ? part.sum(P_BAD) : 0.0;
+    return bad != 0.0 ? refuse(who, bad, n, nb) : 0;
+  }
+};
+
 // the inverse blocks cfs_hip_sym_pcg_block would use now, as nb full row-major blocks
-// (cfs_hip_sym_block_inverse_async): the solver's gather and cg_binv_kernel, then the unpack
+// (cfs_hip_sym_block_inverse_async): the solver's set-up, gathering into the caller's memory, then the unpack
 template <typename V, int BS, class Handle> int block_inverse(Handle *h, void *minv_dev, hipStream_t st) {
-  using cfs_rt::DevBuf;
-  const long long n = h->n(), nb = (n + BS - 1) / BS;
-  DevBuf packed, pbuf_part; // (freed on return: hipFree waits for the kernels that use them)
+  Precond<V, BS> pre; // (freed on return: hipFree waits for the kernels that use them)
+  cfs_rt::DevBuf part;
   int rc;
-  if ((rc = packed.alloc((size_t)nb * tri_words(BS) * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))))
-    return rc;
-  if ((rc = h->block_diagonal(minv_dev, BS, st))) return rc;
-  hipLaunchKernelGGL((cg_binv_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)minv_dev, (V *)packed.p, nb, n,
-                     (double *)pbuf_part.p);
-  hipLaunchKernelGGL((cg_bunpack_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)minv_dev, (const V *)packed.p, nb);
+  if ((rc = part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) || (rc = pre.setup(h, (double *)part.p, st, minv_dev))) return rc;
+  hipLaunchKernelGGL((cg_bunpack_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)minv_dev, pre.minv(),
+                     (h->n() + BS - 1) / BS);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-// u: in = first guess, out = solution.  Returns 0 / an error code; *iterations, *relres as documented in cfs_hip.h
-// PRE: Jacobi (cfs_hip_sym_pcg); PRE = false is cfs_hip_sym_cg, launch for launch
-// BS >= 2 (with PRE): block Jacobi on BS x BS blocks (cfs_hip_sym_pcg_block); dbuf then holds the packed inverses
-template <typename V, bool PRE = false, int BS = 0, class Handle>
+// check_every as the windowed solvers use it: < 1 means 8, and never more than `cap` iterations between two looks
+// (more than ~100 launches enqueued ahead of the GPU make the runtime stall: pwtk stand-in, 64 iterations = 320
+// launches between two looks, 187 us per iteration instead of 32)
+inline int look_window(int check_every, int cap = 16) { return std::min(check_every < 1 ? 8 : check_every, cap); }
+
+// The host side of preconditioned CG, the part cg(), cg_cheb() and Amg::pcg() share: r, p, q, the slots and the
+// counters; the first residual and the first look; the looks at the counters between windows of iterations; the true
+// residual of what is returned.  A solver calls these in order and enqueues its own recurrence between them:
+//   begin;  [its set-up of M^-1];  first_residual (or product_u, a residual kernel of its own, first_look);
+//   [its refusals: u has not been written];  if (live()) [its start];
+//   while (live()) { until = window_end(w);  [iterations it .. until - 1, ++it each];  look(); }   finish
+template <typename V, class Handle> struct Pcg {
+  Handle *h = nullptr;
+  V *u = nullptr;
+  const V *b = nullptr;
+  long long n = 0;
+  hipStream_t st = nullptr;
+  int maxiter = 0;
+  double tol = 0.0, bb = 0.0, stop = 0.0;
+  cfs_rt::DevBuf rbuf, pbuf, qbuf, cnt;
+  Slots part;
+  V *r = nullptr, *p = nullptr, *q = nullptr;
+  int *ic = nullptr;
+  int host_ic[I_COUNT] = {0, 0};
+  int it = 0;        // iterations enqueued
+  bool done = false; // the device has raised ic[I_DONE], or the first guess already solves it (or b = 0)
+
+  int begin(const char *who, Handle *handle, void *u_dev, const void *b_dev, double tolerance, int max_iterations, hipStream_t stream) {
+    h = handle, u = (V *)u_dev, b = (const V *)b_dev, n = h->n(), st = stream, tol = tolerance, maxiter = max_iterations;
+    if (h->rows() != h->n())
+      return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, std::string(who) + ": the handle holds a row block, not the whole matrix");
+    int rc;
+    if ((rc = alloc_vectors<V>(n, {&rbuf, &pbuf, &qbuf})) || (rc = part.alloc(P_COUNT, st)) || (rc = cnt.alloc(I_COUNT * sizeof(int))))
+      return rc;
+    r = (V *)rbuf.p, p = (V *)pbuf.p, q = (V *)qbuf.p, ic = (int *)cnt.p;
+    if ((rc = part.zero())) return rc;
+    HIPCHK(hipMemsetAsync(ic, 0, I_COUNT * sizeof(int), st));
+    return 0;
+  }
+  int product_u() { return h->spmv_local(q, u, nullptr, st); } // q = A u
+  // behind a residual kernel that left r . r in P_RR0 and b . b in P_BB
+  int first_look() {
+    HIPCHK(hipGetLastError());
+    if (int rc = part.fetch()) return rc;
+    bb = part.sum(P_BB);
+    stop = tol * tol * bb;
+    done = !(part.sum(P_RR0) > stop);
+    return 0;
+  }
+  // r = b - A u, rr[0] = r . r, bb = b . b by the residual kernel of the plain iteration (the same bits), and the look
+  int first_residual() {
+    if (int rc = product_u()) return rc;
+    hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, n,
+                       part.dev(), (int)P_RR0, 1, (const V *)nullptr);
+    return first_look();
+  }
+  bool live() const { return !done && it < maxiter; } // (maxiter = 0 behaves like done)
+  int window_end(int window) const { return std::min(maxiter, it + window); }
+  int look() { // one 8-byte copy + synchronisation
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    done = host_ic[I_DONE] != 0;
+    return 0;
+  }
+  // the true residual of what is returned; *iterations from the device's counter; relres absolute when bb = 0
+  int finish(int *iterations, double *relres) {
+    int rc;
+    if ((rc = product_u())) return rc;
+    hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b,
+                       (const V *)q, n, part.dev(), (int)P_RES, 0, (const V *)nullptr);
+    HIPCHK(hipGetLastError());
+    if ((rc = part.fetch())) return rc;
+    const double res2 = part.sum(P_RES);
+    HIPCHK(hipMemcpy(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost));
+    if (iterations) *iterations = host_ic[I_ITER];
+    if (relres) *relres = bb > 0.0 ? std::sqrt(res2 / bb) : std::sqrt(res2);
+    return 0;
+  }
+};
+
+// cfs_hip_sym_cg (BS = 0), cfs_hip_sym_pcg (1), cfs_hip_sym_pcg_block (2, 3, 4, 6).  u: in = first guess, out = solution.
+// Returns 0 / an error code; *iterations, *relres as documented in cfs_hip.h
+template <typename V, int BS = 0, class Handle>
 int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int check_every, int *iterations,
        double *relres, hipStream_t st) {
-  using cfs_rt::DevBuf;
-  const long long n = h->n();
-  if (h->rows() != h->n()) return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "cg: the handle holds a row block, not the whole matrix");
-  if (maxiter < 0 || !(tol >= 0.0)) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "cg: bad tolerance / iteration limit");
-  if (check_every < 1) check_every = 8;
-  // (more than ~100 launches enqueued ahead of the GPU make the runtime stall: pwtk stand-in, 64
-  // iterations = 320 launches between two looks, 187 us per iteration instead of 32)
-  check_every = std::min(check_every, 16);
+  constexpr bool PRE = BS == 1, BLK = BS >= 2;
+  check_every = look_window(check_every);
   const char *eg = getenv("CFS_HIP_CG_GRAPH");
   const bool use_graph = eg && atoi(eg) != 0;
-  if ((((uintptr_t)u_dev) | ((uintptr_t)b_dev)) & 15)
-    return cfs_rt::set_err(CFS_HIP_ERR_ARG, "cg: u and b must be 16-byte aligned");
-  V *u = (V *)u_dev;
-  const V *b = (const V *)b_dev;
-  static_assert(BS == 0 || (PRE && BS >= 2), "block Jacobi is a preconditioner; BS = 1 is Jacobi");
-  constexpr bool BLK = BS >= 2;
-  const long long nb = BLK ? (n + BS - 1) / BS : 0;
-  DevBuf rbuf, pbuf, qbuf, pbuf_part, cnt, dbuf, blkbuf;
+  Pcg<V, Handle> s;
+  Precond<V, BS> pre;
   int rc;
-  if (BLK && ((rc = dbuf.alloc((size_t)nb * tri_words(BS) * sizeof(V) + 64)) || (rc = blkbuf.alloc((size_t)nb * BS * BS * sizeof(V) + 64))))
-    return rc;
-  if (PRE && !BLK && (rc = dbuf.alloc((size_t)n * sizeof(V) + 64))) return rc;
-  const V *dinv = (const V *)dbuf.p;
-  if ((rc = rbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf.alloc((size_t)n * sizeof(V) + 64)) ||
-      (rc = qbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) ||
-      (rc = cnt.alloc(I_COUNT * sizeof(int))))
-    return rc;
-  V *r = (V *)rbuf.p, *p = (V *)pbuf.p, *q = (V *)qbuf.p;
-  double *part = (double *)pbuf_part.p;
-  int *ic = (int *)cnt.p;
-  std::vector<double> hp((size_t)P_COUNT * kGrid);
-  auto read_slot = [&](int slot, double *out) -> int { // (synchronises the stream)
-    HIPCHK(hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    double s = 0.0;
-    for (int g = 0; g < kGrid; g++) s += hp[(size_t)slot * kGrid + g];
-    *out = s;
-    return 0;
-  };
-  HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
-  HIPCHK(hipMemsetAsync(ic, 0, I_COUNT * sizeof(int), st));
-  if constexpr (BLK) { // the inverse blocks from the handle's own blocks; blocks that are not positive definite are counted
-    if ((rc = h->block_diagonal(blkbuf.p, BS, st))) return rc;
-    hipLaunchKernelGGL((cg_binv_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)blkbuf.p, (V *)dbuf.p, nb, n, part);
-  } else if (PRE) { // dinv from the handle's own diagonal; entries that are not finite and > 0 are counted
-    if ((rc = h->diagonal(dbuf.p, st))) return rc;
-    hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)dbuf.p, n, part);
-  }
-  // r = b - A u, p = r, rr[0] = r . r, bb = b . b  (PRE: p = dinv r, rz[0] = r . p)
-  if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
+  if ((rc = s.begin("cg", h, u_dev, b_dev, tol, maxiter, st)) || (rc = pre.setup(h, s.part.dev(), st))) return rc;
+  V *u = s.u, *r = s.r, *p = s.p, *q = s.q;
+  const long long n = s.n, nb = pre.nb;
+  double *part = s.part.dev();
+  int *ic = s.ic;
+  const V *dinv = pre.minv();
+  // r = b - A u, p = r, rr[0] = r . r, bb = b . b  (PRE: p = dinv r, rz[0] = r . p), in one pass
+  if ((rc = s.product_u())) return rc;
   if constexpr (BLK)
-    hipLaunchKernelGGL((cg_residual_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, p, b, (const V *)q, n, part,
+    hipLaunchKernelGGL((cg_residual_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, p, s.b, (const V *)q, n, part,
                        dinv, nb);
   else
-    hipLaunchKernelGGL((cg_residual_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, r, p, b, (const V *)q, n, part,
+    hipLaunchKernelGGL((cg_residual_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, r, p, s.b, (const V *)q, n, part,
                        (int)P_RR0, 1, dinv);
-  HIPCHK(hipGetLastError());
-  double rr0 = 0.0, bb = 0.0;
-  if ((rc = read_slot(P_RR0, &rr0))) return rc;
-  for (int g = 0; g < kGrid; g++) bb += hp[(size_t)P_BB * kGrid + g];
-  if (PRE) { // (read with the first host look: u has not been touched yet)
-    double bad = 0.0;
-    for (int g = 0; g < kGrid; g++) bad += hp[(size_t)P_BAD * kGrid + g];
-    if (BLK && bad != 0.0)
-      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg: block Jacobi needs positive definite diagonal blocks, " +
-                                                  std::to_string((long long)bad) + " of " + std::to_string(nb) + " blocks of " +
-                                                  std::to_string(BS) + " rows have a pivot that is zero, negative or not finite");
-    if (bad != 0.0)
-      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg: Jacobi needs a positive diagonal, " + std::to_string((long long)bad) +
-                                                  " of " + std::to_string(n) + " entries are zero, negative or not finite");
-  }
-  const double stop = tol * tol * bb;
-  bool done = !(rr0 > stop); // the first guess already solves it (or b = 0)
-  int host_ic[I_COUNT] = {0, 0};
-  int it = 0;
+  if ((rc = s.first_look()) || (rc = pre.check("pcg", s.part, n))) return rc; // (u has not been touched yet)
+  const double stop = s.stop;
   auto iteration = [&](int k) -> int {
     int r2 = h->spmv_local(q, p, nullptr, st);
     if (r2) return r2;
-    hipLaunchKernelGGL((cg_pq_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part,
+    hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part, (int)P_PQ,
                        (const int *)ic);
     if constexpr (BLK) {
       hipLaunchKernelGGL((cg_update_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q,
@@ -591,7 +701,7 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
       if (g) (void)hipGraphDestroy(g);
     }
   } graph_guard{graph, gexec};
-  if (use_graph && !done && maxiter >= 2 && st != nullptr) {
+  if (use_graph && !s.done && maxiter >= 2 && st != nullptr) {
     bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
     if (ok) {
       const int r0 = iteration(0), r1 = r0 ? r0 : iteration(1);
@@ -603,33 +713,20 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
       gexec = nullptr;
     }
   }
-  while (!done && it < maxiter) {
-    const int until = std::min(maxiter, it + check_every);
-    while (it < until) {
-      if (gexec && (it & 1) == 0 && it + 2 <= until) {
+  while (s.live()) {
+    const int until = s.window_end(check_every);
+    while (s.it < until) {
+      if (gexec && (s.it & 1) == 0 && s.it + 2 <= until) {
         HIPCHK(hipGraphLaunch(gexec, st));
-        it += 2;
+        s.it += 2;
       } else {
-        if ((rc = iteration(it))) return rc;
-        ++it;
+        if ((rc = iteration(s.it))) return rc;
+        ++s.it;
       }
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    done = host_ic[I_DONE] != 0;
+    if ((rc = s.look())) return rc;
   }
-  // the true residual of what is returned
-  if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
-  hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b,
-                     (const V *)q, n, part, (int)P_RES, 0, (const V *)nullptr);
-  HIPCHK(hipGetLastError());
-  double res2 = 0.0;
-  if ((rc = read_slot(P_RES, &res2))) return rc;
-  HIPCHK(hipMemcpy(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost));
-  if (iterations) *iterations = host_ic[I_ITER];
-  if (relres) *relres = bb > 0.0 ? std::sqrt(res2 / bb) : std::sqrt(res2);
-  return 0;
+  return s.finish(iterations, relres);
 }
 
 } // namespace cfs_solver

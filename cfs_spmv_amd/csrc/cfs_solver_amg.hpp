@@ -36,10 +36,10 @@
 //
 // The outer PCG (cg_amg) is cg_cheb with the chain replaced by the cycle:
 //   tile kernel + fold   q = A p
-//   cg_pq_kernel         pq = p . q
-//   amg_update_kernel    u += (rz/pq) p;  r -= (rz/pq) q;  rr' = r . r
+//   cg_dot_kernel        pq = p . q
+//   cg_update_kernel<V, false, P_RZ0>   u += (rz/pq) p;  r -= (rz/pq) q;  rr' = r . r
 //   the cycle            z = M^-1 r
-//   amg_dot_kernel       rz' = r . z of the stored r and the stored final z
+//   cg_dot_kernel        rz' = r . z of the stored r and the stored final z
 //   cheb_direction_kernel  p = z + (rz'/rz) p;  iteration count;  converged?  (rr' <= tol^2 b.b)
 // 6 launches and the cycle; a cycle exceeds what may be enqueued between two host looks, so the host looks at the
 // convergence flag after every iteration.
@@ -348,61 +348,6 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-// cg_update_kernel with alpha = rz / pq and z elsewhere:  u += alpha p;  r -= alpha q;  part[rr'] <- r . r
-template <typename V>
-__global__ void __launch_bounds__(kThreads)
-    amg_update_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q, long long n,
-                      double *__restrict__ part, const int *__restrict__ ic, int it) {
-  if (ic[I_DONE]) return;
-  const double pq = slot_sum(part, P_PQ), rz_old = slot_sum(part, P_RZ0 + (it & 1));
-  const double alpha = pq != 0.0 ? rz_old / pq : 0.0;
-  constexpr int W = Vec16<V>::W;
-  typedef typename Vec16<V>::type VT;
-  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  double s = 0.0;
-  for (long long i = t0; i < nv; i += stride) {
-    VT uv = reinterpret_cast<VT *>(u)[i], rv = reinterpret_cast<VT *>(r)[i];
-    const VT pv = reinterpret_cast<const VT *>(p)[i], qv = reinterpret_cast<const VT *>(q)[i];
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      uv[k] = (V)((double)uv[k] + alpha * (double)pv[k]);
-      const double ri = (double)rv[k] - alpha * (double)qv[k];
-      rv[k] = (V)ri;
-      s += ri * ri;
-    }
-    reinterpret_cast<VT *>(u)[i] = uv;
-    reinterpret_cast<VT *>(r)[i] = rv;
-  }
-  for (long long i = nv * W + t0; i < n; i += stride) {
-    u[i] = (V)((double)u[i] + alpha * (double)p[i]);
-    const double ri = (double)r[i] - alpha * (double)q[i];
-    r[i] = (V)ri;
-    s += ri * ri;
-  }
-  s = block_sum(s);
-  if (threadIdx.x == 0) part[(P_RR0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = s;
-}
-
-// part[slot] <- a . b of the stored values
-template <typename V>
-__global__ void __launch_bounds__(kThreads)
-    amg_dot_kernel(const V *__restrict__ a, const V *__restrict__ b, long long n, double *__restrict__ part, int slot,
-                   const int *__restrict__ ic) {
-  if (ic[I_DONE]) return;
-  constexpr int W = Vec16<V>::W;
-  typedef typename Vec16<V>::type VT;
-  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  double s = 0.0;
-  for (long long i = t0; i < nv; i += stride) {
-    const VT av = reinterpret_cast<const VT *>(a)[i], bv = reinterpret_cast<const VT *>(b)[i];
-#pragma unroll
-    for (int k = 0; k < W; ++k) s += (double)av[k] * (double)bv[k];
-  }
-  for (long long i = nv * W + t0; i < n; i += stride) s += (double)a[i] * (double)b[i];
-  s = block_sum(s);
-  if (threadIdx.x == 0) part[slot * kGrid + blockIdx.x] = s;
-}
-
 // ---- the hierarchy on the device -------------------------------------------------------------------
 enum AmgKind { AMG_MULTIGRID = 0, AMG_SMOOTHER = 1, AMG_DENSE = 2 };
 
@@ -412,7 +357,8 @@ template <typename V> struct AmgLevel {
   double lmin = 0.0, lmax = 0.0, theta = 1.0, c1[kChebMaxDegree], c2[kChebMaxDegree];
   cfs_hip_sym_s *h = nullptr;
   bool owned = false;
-  cfs_rt::DevBuf dinv, aggptr, aggidx, agg, w, r, z, d, t, inv;
+  Precond<V, 1> pre; // dinv of a level that smooths
+  cfs_rt::DevBuf aggptr, aggidx, agg, w, r, z, d, t, inv;
   // the CSR the level's handle was created from (levels >= 1): lower triangle + diagonal, values in V
   std::vector<int> rp, ci;
   std::vector<V> va;
@@ -420,14 +366,15 @@ template <typename V> struct AmgLevel {
     if (owned) delete h;
   }
   size_t bytes() const {
-    return dinv.bytes + aggptr.bytes + aggidx.bytes + agg.bytes + w.bytes + r.bytes + z.bytes + d.bytes + t.bytes + inv.bytes;
+    return pre.dbuf.bytes + aggptr.bytes + aggidx.bytes + agg.bytes + w.bytes + r.bytes + z.bytes + d.bytes + t.bytes + inv.bytes;
   }
 };
 
 template <typename V> struct Amg : cfs_hip_amg_s {
   using Level = AmgLevel<V>;
   std::vector<std::unique_ptr<Level>> lv;
-  cfs_rt::DevBuf part, cnt; // the partial-sum slots the smoother's kernels are handed, and a done flag that is never set
+  Slots part;         // the partial-sum slots the smoother's kernels are handed
+  cfs_rt::DevBuf cnt; // a done flag that is never set
   int passes = 2, degree = 1, coarse_max = 512, device = 0;
   double ratio = 4.0, setup_seconds = 0.0, handles_seconds = 0.0;
 
@@ -445,8 +392,7 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     value_bytes = (int)sizeof(V);
     hipStream_t st = nullptr;
     int rc;
-    if ((rc = part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) || (rc = cnt.alloc(I_COUNT * sizeof(int)))) return rc;
-    HIPCHK(hipMemset(part.p, 0, (size_t)P_COUNT * kGrid * sizeof(double)));
+    if ((rc = part.alloc(P_COUNT, st)) || (rc = cnt.alloc(I_COUNT * sizeof(int))) || (rc = part.zero())) return rc;
     HIPCHK(hipMemset(cnt.p, 0, I_COUNT * sizeof(int)));
     AmgCsr cur, next;
     amg_lower(n, rowptr, colind, values, cur);
@@ -525,25 +471,14 @@ template <typename V> struct Amg : cfs_hip_amg_s {
   // dinv, the work vectors and the bounds of a level that smooths
   int setup_smoother(Level &L, hipStream_t st) {
     const long long n = L.n;
-    double *pp = (double *)part.p;
-    int rc;
-    if ((rc = L.dinv.alloc((size_t)n * sizeof(V) + 64)) || (rc = L.d.alloc((size_t)n * sizeof(V) + 64)) ||
-        (rc = L.t.alloc((size_t)n * sizeof(V) + 64)) || (rc = L.h->diagonal(L.dinv.p, st)))
-      return rc;
-    hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)L.dinv.p, n, pp);
-    HIPCHK(hipGetLastError());
-    cfs_rt::DevBuf vbuf, lbuf;
-    if ((rc = vbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = lbuf.alloc((size_t)L_COUNT * kGrid * sizeof(double)))) return rc;
-    HIPCHK(hipMemsetAsync(lbuf.p, 0, (size_t)L_COUNT * kGrid * sizeof(double), st));
-    hipLaunchKernelGGL((cheb_lmax_start_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)L.d.p, (const V *)nullptr, n);
+    cfs_rt::DevBuf vbuf;
+    Slots lpart;
     double est = 0.0;
-    if ((rc = cheb_power<V, 1>(L.h, (V *)L.d.p, (V *)L.t.p, (V *)vbuf.p, n, 16, (double *)lbuf.p, (const V *)L.dinv.p, 0LL, &est, st)))
+    int rc;
+    if ((rc = alloc_vectors<V>(n, {&L.d, &L.t})) || (rc = L.pre.setup(L.h, part.dev(), st)) || (rc = alloc_vectors<V>(n, {&vbuf})) ||
+        (rc = cheb_power<V, 1>(L.h, (V *)L.d.p, (V *)L.t.p, (V *)vbuf.p, (const V *)nullptr, n, 16, lpart, L.pre.minv(), 0LL, &est, st)) ||
+        (rc = part.fetch()) || (rc = L.pre.check("amg_create", part, n)))
       return rc;
-    std::vector<double> hb(kGrid);
-    HIPCHK(hipMemcpy(hb.data(), pp + (size_t)P_BAD * kGrid, kGrid * sizeof(double), hipMemcpyDeviceToHost));
-    double bad = 0.0;
-    for (int g = 0; g < kGrid; g++) bad += hb[g];
-    if (bad != 0.0) return ChebBase<V, 1>::refuse("amg_create", bad, n, 0);
     if (!(est > 0.0) || est * 0.0 != 0.0)
       return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_create: the power method gave no positive estimate of lambda_max(D^-1 A) on a level of " +
                                                   std::to_string(n) + " rows (" + std::to_string(est) + ")");
@@ -557,13 +492,13 @@ template <typename V> struct Amg : cfs_hip_amg_s {
   int cycle(int l, V *z, const V *r, const int *ic, hipStream_t st) {
     Level &L = *lv[l];
     const long long n = L.n;
-    double *pp = (double *)part.p;
+    double *pp = part.dev();
     if (L.kind == AMG_DENSE) {
       hipLaunchKernelGGL((amg_dense_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, (const V *)L.inv.p, r, L.n, ic);
       return 0;
     }
     V *d = (V *)L.d.p, *t = (V *)L.t.p;
-    const V *dinv = (const V *)L.dinv.p;
+    const V *dinv = L.pre.minv();
     int rc;
     hipLaunchKernelGGL((cheb_start_kernel<V, 1>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, n, 1.0 / L.theta, -1, pp, dinv, 0LL);
     if ((rc = cheb_chain<V, 1>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, 0LL, st))) return rc;
@@ -596,7 +531,7 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     o->ratio = ratio;
     o->setup_seconds = setup_seconds;
     o->handles_seconds = handles_seconds;
-    long long bytes = (long long)(part.bytes + cnt.bytes);
+    long long bytes = (long long)(part.buf.bytes + cnt.bytes);
     for (size_t l = 0; l < lv.size(); ++l) {
       const Level &L = *lv[l];
       o->n[l] = L.n;
@@ -648,76 +583,38 @@ template <typename V> struct Amg : cfs_hip_amg_s {
 
   // cfs_hip_sym_pcg_amg.  u: in = first guess, out = solution
   int pcg(void *u_dev, const void *b_dev, double tol, int maxiter, int *iterations, double *relres, hipStream_t st) override {
-    using cfs_rt::DevBuf;
-    cfs_hip_sym_s *h = fine;
-    const long long n = h->n();
-    V *u = (V *)u_dev;
-    const V *b = (const V *)b_dev;
-    DevBuf rbuf, pbuf, qbuf, zbuf, pbuf_part, cbuf;
+    Pcg<V, cfs_hip_sym_s> s;
+    cfs_rt::DevBuf zbuf;
     int rc;
-    if ((rc = rbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf.alloc((size_t)n * sizeof(V) + 64)) ||
-        (rc = qbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = zbuf.alloc((size_t)n * sizeof(V) + 64)) ||
-        (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) || (rc = cbuf.alloc(I_COUNT * sizeof(int))))
+    if ((rc = s.begin("pcg_amg", fine, u_dev, b_dev, tol, maxiter, st)) || (rc = alloc_vectors<V>(s.n, {&zbuf})) || (rc = s.first_residual()))
       return rc;
-    V *r = (V *)rbuf.p, *p = (V *)pbuf.p, *q = (V *)qbuf.p, *z = (V *)zbuf.p;
-    double *pp = (double *)pbuf_part.p;
-    int *ic = (int *)cbuf.p;
-    std::vector<double> hp((size_t)P_COUNT * kGrid);
-    auto read_slot = [&](int slot, double *out) -> int { // (synchronises the stream)
-      HIPCHK(hipMemcpyAsync(hp.data(), pp, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      double s = 0.0;
-      for (int g = 0; g < kGrid; g++) s += hp[(size_t)slot * kGrid + g];
-      *out = s;
+    V *u = s.u, *r = s.r, *p = s.p, *q = s.q, *z = (V *)zbuf.p;
+    const long long n = s.n;
+    double *pp = s.part.dev();
+    int *ic = s.ic;
+    // z = M^-1 r;  part[slot] <- r . z of the stored r and the stored final z
+    auto cycle_and_dot = [&](int slot) -> int {
+      if (int r2 = cycle(0, z, (const V *)r, (const int *)ic, st)) return r2;
+      hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, n, pp, slot, (const int *)ic);
       return 0;
     };
-    HIPCHK(hipMemsetAsync(pp, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
-    HIPCHK(hipMemsetAsync(ic, 0, I_COUNT * sizeof(int), st));
-    // r = b - A u, rr[0] = r . r, bb = b . b: the residual kernel of the plain iteration, the same bits
-    if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
-    hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, n, pp,
-                       (int)P_RR0, 1, (const V *)nullptr);
-    HIPCHK(hipGetLastError());
-    double rr0 = 0.0, bb = 0.0;
-    if ((rc = read_slot(P_RR0, &rr0))) return rc;
-    for (int g = 0; g < kGrid; g++) bb += hp[(size_t)P_BB * kGrid + g];
-    const double stop = tol * tol * bb;
-    bool done = !(rr0 > stop); // the first guess already solves it (or b = 0)
-    int host_ic[I_COUNT] = {0, 0};
-    int it = 0;
-    if (!done && maxiter > 0) { // z = M^-1 r, rz[0] = r . z, p = z
-      if ((rc = cycle(0, z, (const V *)r, (const int *)ic, st))) return rc;
-      hipLaunchKernelGGL((amg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, n, pp, (int)P_RZ0,
-                         (const int *)ic);
+    if (s.live()) { // z = M^-1 r, rz[0] = r . z, p = z
+      if ((rc = cycle_and_dot((int)P_RZ0))) return rc;
       HIPCHK(hipMemcpyAsync(p, z, (size_t)n * sizeof(V), hipMemcpyDeviceToDevice, st));
     }
-    while (!done && it < maxiter) { // (one look per iteration: a cycle is more than may be enqueued ahead of the GPU)
-      if ((rc = h->spmv_local(q, p, nullptr, st))) return rc;
-      hipLaunchKernelGGL((cg_pq_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, pp, (const int *)ic);
-      hipLaunchKernelGGL((amg_update_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n, pp,
-                         (const int *)ic, it);
-      if ((rc = cycle(0, z, (const V *)r, (const int *)ic, st))) return rc;
-      hipLaunchKernelGGL((amg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, n, pp,
-                         (int)P_RZ0 + ((it + 1) & 1), (const int *)ic);
+    while (s.live()) { // (a window of one: a cycle is more than may be enqueued ahead of the GPU)
+      const int it = s.it;
+      if ((rc = fine->spmv_local(q, p, nullptr, st))) return rc;
+      hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, pp, (int)P_PQ, (const int *)ic);
+      hipLaunchKernelGGL((cg_update_kernel<V, false, P_RZ0>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n, pp,
+                         (const int *)ic, it, (const V *)nullptr);
+      if ((rc = cycle_and_dot((int)P_RZ0 + ((it + 1) & 1)))) return rc;
       hipLaunchKernelGGL((cheb_direction_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, n, (const double *)pp, ic, it,
-                         stop);
-      ++it;
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      done = host_ic[I_DONE] != 0;
+                         s.stop);
+      ++s.it;
+      if ((rc = s.look())) return rc;
     }
-    // the true residual of what is returned
-    if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
-    hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b, (const V *)q, n,
-                       pp, (int)P_RES, 0, (const V *)nullptr);
-    HIPCHK(hipGetLastError());
-    double res2 = 0.0;
-    if ((rc = read_slot(P_RES, &res2))) return rc;
-    HIPCHK(hipMemcpy(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost));
-    if (iterations) *iterations = host_ic[I_ITER];
-    if (relres) *relres = bb > 0.0 ? std::sqrt(res2 / bb) : std::sqrt(res2);
-    return 0;
+    return s.finish(iterations, relres);
   }
 };
 

@@ -20,7 +20,7 @@
 // The pairs (rho_j rho_{j-1}, 2 rho_j / delta) are computed on the host in fp64 (cheb_coeffs) and passed as
 // kernel arguments: an inner step has no dot product and reads no device scalar.  An outer iteration:
 //   tile kernel + fold            q = A p
-//   cg_pq_kernel                  pq = p . q                                      (cfs_solver.hpp, unchanged)
+//   cg_dot_kernel                 pq = p . q                                      (cfs_solver.hpp, unchanged)
 //   cheb_update_kernel            u += (rz/pq) p;  r -= (rz/pq) q;  rr' = r . r;  z = d = (1/theta) M^-1 r
 //                                 (degree 1: also rz' = r . z)
 //   m - 1 times:  tile kernel + fold   t = A z        (t lives in the q buffer: q = A p has been consumed)
@@ -356,37 +356,7 @@ __global__ void __launch_bounds__(kThreads)
 }
 
 // ---- host ----------------------------------------------------------------------------------------
-// the stored M^-1 of one call: nothing (BS = 0), dinv (1) or the packed inverse blocks (>= 2); entries or
-// blocks that are not positive are counted into part[P_BAD] (which the caller has zeroed)
-template <typename V, int BS> struct ChebBase {
-  cfs_rt::DevBuf dbuf, blkbuf;
-  long long nb = 0;
-  const V *minv() const { return (const V *)dbuf.p; }
-  template <class Handle> int setup(Handle *h, double *part, hipStream_t st) {
-    const long long n = h->n();
-    int rc;
-    if constexpr (BS >= 2) {
-      nb = (n + BS - 1) / BS;
-      if ((rc = dbuf.alloc((size_t)nb * tri_words(BS) * sizeof(V) + 64)) || (rc = blkbuf.alloc((size_t)nb * BS * BS * sizeof(V) + 64)) ||
-          (rc = h->block_diagonal(blkbuf.p, BS, st)))
-        return rc;
-      hipLaunchKernelGGL((cg_binv_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)blkbuf.p, (V *)dbuf.p, nb, n, part);
-    } else if constexpr (BS == 1) {
-      if ((rc = dbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = h->diagonal(dbuf.p, st))) return rc;
-      hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)dbuf.p, n, part);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  static int refuse(const char *who, double bad, long long n, long long nb) {
-    if (BS >= 2)
-      return cfs_rt::set_err(CFS_HIP_ERR_ARG, std::string(who) + ": block Jacobi needs positive definite diagonal blocks, " +
-                                                  std::to_string((long long)bad) + " of " + std::to_string(nb) + " blocks of " +
-                                                  std::to_string(BS) + " rows have a pivot that is zero, negative or not finite");
-    return cfs_rt::set_err(CFS_HIP_ERR_ARG, std::string(who) + ": Jacobi needs a positive diagonal, " + std::to_string((long long)bad) +
-                                                " of " + std::to_string(n) + " entries are zero, negative or not finite");
-  }
-};
+// (the stored M^-1 of a call is Precond<V, BS> of cfs_solver.hpp)
 
 // the m - 1 inner steps behind a z = d = z_1 that is already enqueued; t: n values of scratch
 template <typename V, int BS, class Handle>
@@ -401,25 +371,25 @@ int cheb_chain(Handle *h, V *z, V *d, V *t, const V *r, long long n, int degree,
   return 0;
 }
 
-// `steps` power steps on M^-1 A from v (already stored); v, t, w: n values each.  No host look before the last step.
+// `steps` power steps on M^-1 A from the start vector v0 (nullptr: that of cfs_hip_sym_eigs); v, t, w: n values each.
+// One host look, after the last step.  lpart: the caller's, not yet allocated (it lives as long as the caller's buffers)
 template <typename V, int BS, class Handle>
-int cheb_power(Handle *h, V *v, V *t, V *w, long long n, int steps, double *lpart, const V *minv, long long nb, double *estimate,
-               hipStream_t st) {
+int cheb_power(Handle *h, V *v, V *t, V *w, const V *v0, long long n, int steps, Slots &lpart, const V *minv, long long nb,
+               double *estimate, hipStream_t st) {
+  int rc;
+  if ((rc = lpart.alloc(L_COUNT, st)) || (rc = lpart.zero())) return rc;
+  hipLaunchKernelGGL((cheb_lmax_start_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, v, v0, n);
   for (int s = 0; s < steps; ++s) {
-    int rc = h->spmv_local(t, v, nullptr, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL((cheb_lmax_apply_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, w, (const V *)t, (const V *)v, n, lpart,
-                       minv, nb);
+    if ((rc = h->spmv_local(t, v, nullptr, st))) return rc;
+    hipLaunchKernelGGL((cheb_lmax_apply_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, w, (const V *)t, (const V *)v, n,
+                       lpart.dev(), minv, nb);
     if (s + 1 < steps)
-      hipLaunchKernelGGL((cheb_lmax_normalise_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, v, (const V *)w, n, (const double *)lpart);
+      hipLaunchKernelGGL((cheb_lmax_normalise_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, v, (const V *)w, n,
+                         (const double *)lpart.dev());
   }
   HIPCHK(hipGetLastError());
-  std::vector<double> hp((size_t)L_COUNT * kGrid);
-  HIPCHK(hipMemcpyAsync(hp.data(), lpart, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  double wt = 0.0, vt = 0.0;
-  for (int g = 0; g < kGrid; g++) wt += hp[(size_t)L_WT * kGrid + g], vt += hp[(size_t)L_VT * kGrid + g];
-  *estimate = wt / vt;
+  if ((rc = lpart.fetch())) return rc;
+  *estimate = lpart.sum(L_WT) / lpart.sum(L_VT);
   return 0;
 }
 
@@ -430,26 +400,16 @@ int cheb_lmax(Handle *h, int steps, const void *v0_dev, double *estimate, hipStr
   const long long n = h->n();
   if (h->rows() != h->n()) return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "precond_lmax: the handle holds a row block, not the whole matrix");
   if (steps <= 0) steps = 16;
-  DevBuf vbuf, tbuf, wbuf, pbuf_part, lbuf;
-  ChebBase<V, BS> base;
+  DevBuf vbuf, tbuf, wbuf;
+  Slots part, lpart;
+  Precond<V, BS> pre;
   int rc;
-  if ((rc = vbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = tbuf.alloc((size_t)n * sizeof(V) + 64)) ||
-      (rc = wbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) ||
-      (rc = lbuf.alloc((size_t)L_COUNT * kGrid * sizeof(double))))
+  if ((rc = alloc_vectors<V>(n, {&vbuf, &tbuf, &wbuf})) || (rc = part.alloc(P_COUNT, st)) || (rc = part.zero()) ||
+      (rc = pre.setup(h, part.dev(), st)) ||
+      (rc = cheb_power<V, BS>(h, (V *)vbuf.p, (V *)tbuf.p, (V *)wbuf.p, (const V *)v0_dev, n, steps, lpart, pre.minv(), pre.nb, estimate, st)) ||
+      (rc = part.fetch()))
     return rc;
-  double *part = (double *)pbuf_part.p;
-  HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
-  HIPCHK(hipMemsetAsync(lbuf.p, 0, (size_t)L_COUNT * kGrid * sizeof(double), st));
-  if ((rc = base.setup(h, part, st))) return rc;
-  hipLaunchKernelGGL((cheb_lmax_start_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)vbuf.p, (const V *)v0_dev, n);
-  if ((rc = cheb_power<V, BS>(h, (V *)vbuf.p, (V *)tbuf.p, (V *)wbuf.p, n, steps, (double *)lbuf.p, base.minv(), base.nb, estimate, st)))
-    return rc;
-  std::vector<double> hb(kGrid);
-  HIPCHK(hipMemcpy(hb.data(), part + (size_t)P_BAD * kGrid, kGrid * sizeof(double), hipMemcpyDeviceToHost));
-  double bad = 0.0;
-  for (int g = 0; g < kGrid; g++) bad += hb[g];
-  if (bad != 0.0) return ChebBase<V, BS>::refuse("precond_lmax", bad, n, base.nb);
-  return 0;
+  return pre.check("precond_lmax", part, n);
 }
 
 // cfs_hip_sym_cheb_apply: z = P_m r
@@ -458,85 +418,49 @@ int cheb_apply(Handle *h, int degree, double lmin, double lmax, void *z_dev, con
   using cfs_rt::DevBuf;
   const long long n = h->n();
   if (h->rows() != h->n()) return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "cheb_apply: the handle holds a row block, not the whole matrix");
-  DevBuf dvec, tvec, pbuf_part, cnt;
-  ChebBase<V, BS> base;
+  DevBuf dvec, tvec, cnt;
+  Slots part;
+  Precond<V, BS> pre;
   int rc;
-  if ((rc = dvec.alloc((size_t)n * sizeof(V) + 64)) || (rc = tvec.alloc((size_t)n * sizeof(V) + 64)) ||
-      (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) || (rc = cnt.alloc(I_COUNT * sizeof(int))))
+  if ((rc = alloc_vectors<V>(n, {&dvec, &tvec})) || (rc = part.alloc(P_COUNT, st)) || (rc = cnt.alloc(I_COUNT * sizeof(int))) ||
+      (rc = part.zero()))
     return rc;
-  double *part = (double *)pbuf_part.p;
-  HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
   HIPCHK(hipMemsetAsync(cnt.p, 0, I_COUNT * sizeof(int), st));
-  if ((rc = base.setup(h, part, st))) return rc;
+  if ((rc = pre.setup(h, part.dev(), st))) return rc;
   double theta, c1[kChebMaxDegree], c2[kChebMaxDegree];
   cheb_coeffs(degree, lmin, lmax, &theta, c1, c2);
   hipLaunchKernelGGL((cheb_start_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)z_dev, (V *)dvec.p, (const V *)r_dev, n,
-                     1.0 / theta, -1, part, base.minv(), base.nb);
-  if ((rc = cheb_chain<V, BS>(h, (V *)z_dev, (V *)dvec.p, (V *)tvec.p, (const V *)r_dev, n, degree, c1, c2, -1, part,
-                              (const int *)cnt.p, base.minv(), base.nb, st)))
+                     1.0 / theta, -1, part.dev(), pre.minv(), pre.nb);
+  if ((rc = cheb_chain<V, BS>(h, (V *)z_dev, (V *)dvec.p, (V *)tvec.p, (const V *)r_dev, n, degree, c1, c2, -1, part.dev(),
+                              (const int *)cnt.p, pre.minv(), pre.nb, st)))
     return rc;
   HIPCHK(hipGetLastError());
-  std::vector<double> hb(kGrid);
-  HIPCHK(hipMemcpyAsync(hb.data(), part + (size_t)P_BAD * kGrid, kGrid * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  double bad = 0.0;
-  for (int g = 0; g < kGrid; g++) bad += hb[g];
-  if (bad != 0.0) return ChebBase<V, BS>::refuse("cheb_apply", bad, n, base.nb);
-  return 0;
+  if ((rc = part.fetch())) return rc;
+  return pre.check("cheb_apply", part, n);
 }
 
 // cfs_hip_sym_pcg_cheb.  u: in = first guess, out = solution; lmin / lmax <= 0: the defaults (cfs_hip.h)
 template <typename V, int BS, class Handle>
 int cg_cheb(Handle *h, void *u_dev, const void *b_dev, int degree, double lmin, double lmax, double tol, int maxiter, int check_every,
             int *iterations, double *relres, double *bounds_used, hipStream_t st) {
-  using cfs_rt::DevBuf;
-  const long long n = h->n();
-  if (h->rows() != h->n()) return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_cheb: the handle holds a row block, not the whole matrix");
-  if (check_every < 1) check_every = 8;
-  // (the cap of cg(): about 100 enqueued launches stall the runtime; an iteration here is 5 + 3 (m - 1) of them)
-  check_every = std::min(std::min(check_every, 16), std::max(1, 80 / (5 + 3 * (degree - 1))));
-  V *u = (V *)u_dev;
-  const V *b = (const V *)b_dev;
-  DevBuf rbuf, pbuf, qbuf, zbuf, dvec, pbuf_part, cnt, lbuf;
-  ChebBase<V, BS> base;
+  // (the cap of cg(); an iteration here is 5 + 3 (m - 1) launches)
+  check_every = look_window(check_every, std::min(16, std::max(1, 80 / (5 + 3 * (degree - 1)))));
+  Pcg<V, Handle> s;
+  Precond<V, BS> pre;
+  cfs_rt::DevBuf zbuf, dvec;
+  Slots lpart;
   int rc;
-  if ((rc = rbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf.alloc((size_t)n * sizeof(V) + 64)) ||
-      (rc = qbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = zbuf.alloc((size_t)n * sizeof(V) + 64)) ||
-      (rc = dvec.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) ||
-      (rc = cnt.alloc(I_COUNT * sizeof(int))))
-    return rc;
-  V *r = (V *)rbuf.p, *p = (V *)pbuf.p, *q = (V *)qbuf.p, *z = (V *)zbuf.p, *d = (V *)dvec.p;
-  double *part = (double *)pbuf_part.p;
-  int *ic = (int *)cnt.p;
-  std::vector<double> hp((size_t)P_COUNT * kGrid);
-  auto read_slot = [&](int slot, double *out) -> int { // (synchronises the stream)
-    HIPCHK(hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    double s = 0.0;
-    for (int g = 0; g < kGrid; g++) s += hp[(size_t)slot * kGrid + g];
-    *out = s;
-    return 0;
-  };
-  HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
-  HIPCHK(hipMemsetAsync(ic, 0, I_COUNT * sizeof(int), st));
-  if ((rc = base.setup(h, part, st))) return rc;
-  const V *minv = base.minv();
-  const long long nb = base.nb;
-  // r = b - A u, rr[0] = r . r, bb = b . b: the residual kernel of the plain iteration, the same bits
-  if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
-  hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, n, part,
-                     (int)P_RR0, 1, (const V *)nullptr);
-  HIPCHK(hipGetLastError());
-  double rr0 = 0.0, bb = 0.0, bad = 0.0;
-  if ((rc = read_slot(P_RR0, &rr0))) return rc;
-  for (int g = 0; g < kGrid; g++) bb += hp[(size_t)P_BB * kGrid + g], bad += hp[(size_t)P_BAD * kGrid + g];
-  if (bad != 0.0) return ChebBase<V, BS>::refuse("pcg_cheb", bad, n, nb); // (u has not been touched yet)
+  if ((rc = s.begin("pcg_cheb", h, u_dev, b_dev, tol, maxiter, st)) || (rc = alloc_vectors<V>(s.n, {&zbuf, &dvec})) ||
+      (rc = pre.setup(h, s.part.dev(), st)) || (rc = s.first_residual()) || (rc = pre.check("pcg_cheb", s.part, s.n)))
+    return rc; // (u has not been touched yet)
+  V *u = s.u, *r = s.r, *p = s.p, *q = s.q, *z = (V *)zbuf.p, *d = (V *)dvec.p;
+  const long long n = s.n, nb = pre.nb;
+  double *part = s.part.dev();
+  int *ic = s.ic;
+  const V *minv = pre.minv();
   if (!(lmax > 0.0)) { // the power method, in the buffers the iteration does not use yet
-    if ((rc = lbuf.alloc((size_t)L_COUNT * kGrid * sizeof(double)))) return rc;
-    HIPCHK(hipMemsetAsync(lbuf.p, 0, (size_t)L_COUNT * kGrid * sizeof(double), st));
-    hipLaunchKernelGGL((cheb_lmax_start_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)nullptr, n);
     double est = 0.0;
-    if ((rc = cheb_power<V, BS>(h, p, q, z, n, 16, (double *)lbuf.p, minv, nb, &est, st))) return rc;
+    if ((rc = cheb_power<V, BS>(h, p, q, z, (const V *)nullptr, n, 16, lpart, minv, nb, &est, st))) return rc;
     if (!(est > 0.0) || est * 0.0 != 0.0)
       return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg_cheb: the power method gave no positive estimate of lambda_max(M^-1 A) (" +
                                                   std::to_string(est) + "): pass lmax");
@@ -549,12 +473,8 @@ int cg_cheb(Handle *h, void *u_dev, const void *b_dev, int degree, double lmin, 
   if (bounds_used) bounds_used[0] = lmin, bounds_used[1] = lmax;
   double theta, c1[kChebMaxDegree], c2[kChebMaxDegree];
   cheb_coeffs(degree, lmin, lmax, &theta, c1, c2);
-  const double inv_theta = 1.0 / theta;
-  const double stop = tol * tol * bb;
-  bool done = !(rr0 > stop); // the first guess already solves it (or b = 0)
-  int host_ic[I_COUNT] = {0, 0};
-  int it = 0;
-  if (!done && maxiter > 0) { // z = P_m r, rz[0] = r . z, p = z
+  const double inv_theta = 1.0 / theta, stop = s.stop;
+  if (s.live()) { // z = P_m r, rz[0] = r . z, p = z
     hipLaunchKernelGGL((cheb_start_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, z, d, (const V *)r, n, inv_theta,
                        degree == 1 ? (int)P_RZ0 : -1, part, minv, nb);
     if ((rc = cheb_chain<V, BS>(h, z, d, q, (const V *)r, n, degree, c1, c2, (int)P_RZ0, part, (const int *)ic, minv, nb, st)))
@@ -564,7 +484,8 @@ int cg_cheb(Handle *h, void *u_dev, const void *b_dev, int degree, double lmin, 
   auto iteration = [&](int k) -> int {
     int r2 = h->spmv_local(q, p, nullptr, st);
     if (r2) return r2;
-    hipLaunchKernelGGL((cg_pq_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part, (const int *)ic);
+    hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part, (int)P_PQ,
+                       (const int *)ic);
     hipLaunchKernelGGL((cheb_update_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, z, d, n, part,
                        (const int *)ic, k, inv_theta, degree == 1 ? 1 : 0, minv, nb);
     if ((r2 = cheb_chain<V, BS>(h, z, d, q, (const V *)r, n, degree, c1, c2, (int)P_RZ0 + ((k + 1) & 1), part, (const int *)ic, minv,
@@ -574,26 +495,12 @@ int cg_cheb(Handle *h, void *u_dev, const void *b_dev, int degree, double lmin, 
                        stop);
     return 0;
   };
-  while (!done && it < maxiter) {
-    const int until = std::min(maxiter, it + check_every);
-    for (; it < until; ++it)
-      if ((rc = iteration(it))) return rc;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    done = host_ic[I_DONE] != 0;
+  while (s.live()) {
+    for (const int until = s.window_end(check_every); s.it < until; ++s.it)
+      if ((rc = iteration(s.it))) return rc;
+    if ((rc = s.look())) return rc;
   }
-  // the true residual of what is returned
-  if ((rc = h->spmv_local(q, u, nullptr, st))) return rc;
-  hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b, (const V *)q, n,
-                     part, (int)P_RES, 0, (const V *)nullptr);
-  HIPCHK(hipGetLastError());
-  double res2 = 0.0;
-  if ((rc = read_slot(P_RES, &res2))) return rc;
-  HIPCHK(hipMemcpy(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost));
-  if (iterations) *iterations = host_ic[I_ITER];
-  if (relres) *relres = bb > 0.0 ? std::sqrt(res2 / bb) : std::sqrt(res2);
-  return 0;
+  return s.finish(iterations, relres);
 }
 
 } // namespace cfs_solver

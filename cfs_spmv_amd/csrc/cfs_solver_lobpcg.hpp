@@ -387,41 +387,18 @@ int lobpcg_update(V *sbuf, V *asbuf, long long ld, long long n, const LobpcgCols
   return 0;
 }
 
-// The preconditioner of the iteration, exactly as cfs_hip_sym_pcg / _pcg_block build theirs: dbuf <- the inverse
-// diagonal (BS = 1, cg_dinv_kernel) or the packed inverse node blocks (BS >= 2, cg_binv_kernel); a diagonal entry or a
-// block that is not positive (definite) is refused.  BS = 0: nothing.  part: P_COUNT x kGrid doubles, zeroed, on `st`.
-template <typename V, int BS, class Handle> int lobpcg_precond(Handle *h, cfs_rt::DevBuf &dbuf, double *part, hipStream_t st) {
+// The preconditioner of the iteration, exactly as cfs_hip_sym_pcg / _pcg_block build theirs (Precond, cfs_solver.hpp); a
+// diagonal entry or a block that is not positive (definite) is refused after a look of its own, and the gathered blocks
+// are freed with it.  BS = 0: nothing, and no look.  part: kLobSlots slots, zeroed.
+constexpr int kLobSlots = P_COUNT > 2 * kLobK ? (int)P_COUNT : 2 * kLobK;
+template <typename V, int BS, class Handle> int lobpcg_precond(Handle *h, Precond<V, BS> &pre, Slots &part) {
   if constexpr (BS >= 1) {
-    const long long n = h->n();
-    constexpr int B = BS;
-    const long long nb = (n + B - 1) / B;
-    cfs_rt::DevBuf blkbuf;
     int rc;
-    if ((rc = dbuf.alloc((size_t)nb * tri_words(B) * sizeof(V) + 64))) return rc;
-    if constexpr (BS >= 2) {
-      if ((rc = blkbuf.alloc((size_t)nb * BS * BS * sizeof(V) + 64)) || (rc = h->block_diagonal(blkbuf.p, BS, st))) return rc;
-      hipLaunchKernelGGL((cg_binv_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)blkbuf.p, (V *)dbuf.p, nb, n, part);
-    } else {
-      if ((rc = h->diagonal(dbuf.p, st))) return rc;
-      hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)dbuf.p, n, part);
-    }
-    HIPCHK(hipGetLastError());
-    std::vector<double> hp(kGrid);
-    HIPCHK(hipMemcpyAsync(hp.data(), part + (size_t)P_BAD * kGrid, kGrid * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    double bad = 0.0;
-    for (int g = 0; g < kGrid; g++) bad += hp[g];
-    if (BS >= 2 && bad != 0.0)
-      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "lobpcg: block Jacobi needs positive definite diagonal blocks, " +
-                                                  std::to_string((long long)bad) + " of " + std::to_string(nb) + " blocks of " +
-                                                  std::to_string(BS) + " rows have a pivot that is zero, negative or not finite");
-    if (bad != 0.0)
-      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "lobpcg: Jacobi needs a positive diagonal, " + std::to_string((long long)bad) + " of " +
-                                                  std::to_string(n) + " entries are zero, negative or not finite");
+    if ((rc = pre.setup(h, part.dev(), part.st)) || (rc = part.fetch()) || (rc = pre.check("lobpcg", part, h->n()))) return rc;
+    pre.blkbuf = cfs_rt::DevBuf();
   }
   return 0;
 }
-inline size_t lobpcg_part_bytes() { return (size_t)std::max<int>(P_COUNT, 2 * kLobK) * kGrid * sizeof(double); }
 
 // step 4 and the host's look: sums[2 i] = R_i . R_i, sums[2 i + 1] = X_i . X_i (host, 2 k doubles); W_i written for the
 // bits set in `active`.  x, ax, w: column 0 of X, AX and W;  out_dev: 2 k doubles.  Waits for the stream.
@@ -474,14 +451,16 @@ int debug_update(void *s_dev, void *as_dev, long long ld, long long n, int k, in
 template <typename V, int BS, class Handle>
 int debug_residual(Handle *h, const void *x_dev, const void *ax_dev, void *w_dev, long long ld, int k, const double *theta,
                    unsigned active, double *sums, hipStream_t st) {
-  cfs_rt::DevBuf dbuf, pbuf, nout;
+  cfs_rt::DevBuf nout;
+  Slots part;
+  Precond<V, BS> pre;
   int rc;
-  if ((rc = pbuf.alloc(lobpcg_part_bytes())) || (rc = nout.alloc((size_t)2 * kLobK * sizeof(double)))) return rc;
-  HIPCHK(hipMemsetAsync(pbuf.p, 0, pbuf.bytes, st));
-  if ((rc = lobpcg_precond<V, BS>(h, dbuf, (double *)pbuf.p, st))) return rc;
+  if ((rc = part.alloc(kLobSlots, st)) || (rc = nout.alloc((size_t)2 * kLobK * sizeof(double))) || (rc = part.zero()) ||
+      (rc = lobpcg_precond<V, BS>(h, pre, part)))
+    return rc;
   std::vector<double> hn(2 * kLobK);
-  if ((rc = lobpcg_residual<V, BS>((const V *)x_dev, (const V *)ax_dev, (V *)w_dev, ld, h->n(), k, theta, active, (const V *)dbuf.p,
-                                   (double *)pbuf.p, (double *)nout.p, hn.data(), st)))
+  if ((rc = lobpcg_residual<V, BS>((const V *)x_dev, (const V *)ax_dev, (V *)w_dev, ld, h->n(), k, theta, active, pre.minv(),
+                                   part.dev(), (double *)nout.p, hn.data(), st)))
     return rc;
   std::copy(hn.begin(), hn.begin() + 2 * k, sums);
   return 0;
@@ -499,20 +478,22 @@ int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_it
   const long long ld = (n + Vec16<V>::W - 1) / Vec16<V>::W * Vec16<V>::W; // columns 16-byte aligned
   const int mmax = 3 * k;
   const double unit = sizeof(V) == 8 ? 0x1p-53 : 0x1p-24, drop = 64.0 * unit;
-  DevBuf sb, asb, dbuf, pbuf, gpart, gout, cdev, nout;
+  DevBuf sb, asb, gpart, gout, cdev, nout;
+  Slots slots;
+  Precond<V, BS> pre;
   int rc;
   if ((rc = sb.alloc((size_t)mmax * ld * sizeof(V) + 64)) || (rc = asb.alloc((size_t)mmax * ld * sizeof(V) + 64)) ||
-      (rc = pbuf.alloc(lobpcg_part_bytes())) || (rc = gpart.alloc(lobpcg_gram_part_bytes(mmax))) ||
+      (rc = slots.alloc(kLobSlots, st)) || (rc = gpart.alloc(lobpcg_gram_part_bytes(mmax))) ||
       (rc = gout.alloc((size_t)2 * mmax * mmax * sizeof(double))) || (rc = cdev.alloc((size_t)mmax * 2 * k * sizeof(double))) ||
       (rc = nout.alloc((size_t)2 * kLobK * sizeof(double))))
     return rc;
   V *S = (V *)sb.p, *AS = (V *)asb.p;
-  double *part = (double *)pbuf.p;
+  double *part = slots.dev();
   auto col = [&](V *base, int c) { return base + (long long)c * ld; };
-  HIPCHK(hipMemsetAsync(part, 0, pbuf.bytes, st));
+  if ((rc = slots.zero())) return rc;
   // the preconditioner; refused before anything else happens
-  if ((rc = lobpcg_precond<V, BS>(h, dbuf, part, st))) return rc;
-  const V *minv = (const V *)dbuf.p;
+  if ((rc = lobpcg_precond<V, BS>(h, pre, slots))) return rc;
+  const V *minv = pre.minv();
   int products = 0, it = 0;
   auto product = [&](int c) -> int { // AS[:, c] = A S[:, c]
     ++products;

@@ -299,34 +299,20 @@ int minres(Handle *h, void *u_dev, const void *b_dev, double shift, double tol, 
   const long long n = h->n();
   if (h->rows() != h->n())
     return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "minres: the handle holds a row block, not the whole matrix");
-  if (check_every < 1) check_every = 8;
-  check_every = std::min(check_every, 16); // (as cg(): more launches enqueued ahead make the runtime stall)
+  check_every = look_window(check_every);
   V *u = (V *)u_dev;
   const V *b = (const V *)b_dev;
-  DevBuf vbuf, qbuf, rbuf[2], wbuf[2], pbuf_part, sbuf, dbuf;
+  DevBuf vbuf, qbuf, rbuf[2], wbuf[2], sbuf, dbuf;
+  Slots slots;
   int rc;
-  if (PRE && (rc = dbuf.alloc((size_t)n * sizeof(V) + 64))) return rc;
+  if (PRE && (rc = alloc_vectors<V>(n, {&dbuf}))) return rc;
   const V *dinv = (const V *)dbuf.p;
-  const size_t vec = (size_t)n * sizeof(V) + 64;
-  if ((rc = vbuf.alloc(vec)) || (rc = qbuf.alloc(vec)) || (rc = rbuf[0].alloc(vec)) || (rc = rbuf[1].alloc(vec)) ||
-      (rc = wbuf[0].alloc(vec)) || (rc = wbuf[1].alloc(vec)) || (rc = pbuf_part.alloc((size_t)M_COUNT * kGrid * sizeof(double))) ||
-      (rc = sbuf.alloc(2 * S_COUNT * sizeof(double))))
+  if ((rc = alloc_vectors<V>(n, {&vbuf, &qbuf, &rbuf[0], &rbuf[1], &wbuf[0], &wbuf[1]})) || (rc = slots.alloc(M_COUNT, st)) ||
+      (rc = sbuf.alloc(2 * S_COUNT * sizeof(double))) || (rc = slots.zero()))
     return rc;
   V *v = (V *)vbuf.p, *q = (V *)qbuf.p;
   V *r[2] = {(V *)rbuf[0].p, (V *)rbuf[1].p}, *w[2] = {(V *)wbuf[0].p, (V *)wbuf[1].p};
-  double *part = (double *)pbuf_part.p, *state = (double *)sbuf.p;
-  std::vector<double> hp((size_t)M_COUNT * kGrid);
-  auto read_parts = [&]() -> int { // (synchronises the stream)
-    HIPCHK(hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
-  };
-  auto host_sum = [&](int slot) {
-    double s = 0.0;
-    for (int g = 0; g < kGrid; g++) s += hp[(size_t)slot * kGrid + g];
-    return s;
-  };
-  HIPCHK(hipMemsetAsync(part, 0, (size_t)M_COUNT * kGrid * sizeof(double), st));
+  double *part = slots.dev(), *state = (double *)sbuf.p;
   HIPCHK(hipMemsetAsync(state, 0, 2 * S_COUNT * sizeof(double), st));
   if (PRE) { // dinv from the handle's own diagonal; entries whose |a_ii - shift| is zero or not finite are counted
     if ((rc = h->diagonal(dbuf.p, st))) return rc;
@@ -337,15 +323,15 @@ int minres(Handle *h, void *u_dev, const void *b_dev, double shift, double tol, 
   hipLaunchKernelGGL((minres_residual_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, r[0], r[1], b, (const V *)q,
                      (const V *)u, shift, n, part, 1, dinv);
   HIPCHK(hipGetLastError());
-  if ((rc = read_parts())) return rc;
+  if ((rc = slots.fetch())) return rc;
   if (PRE) { // (read with the first host look: u has not been touched yet)
-    const double bad = host_sum(M_BAD);
+    const double bad = slots.sum(M_BAD);
     if (bad != 0.0)
       return cfs_rt::set_err(CFS_HIP_ERR_ARG, "minres: Jacobi needs a nonzero diagonal of A - shift I, " +
                                                   std::to_string((long long)bad) + " of " + std::to_string(n) +
                                                   " entries are zero (or not stored) or not finite");
   }
-  const double bb = host_sum(M_BB), beta1 = std::sqrt(host_sum(M_R0)), stop = tol * std::sqrt(host_sum(M_BM));
+  const double bb = slots.sum(M_BB), beta1 = std::sqrt(slots.sum(M_R0)), stop = tol * std::sqrt(slots.sum(M_BM));
   // the first guess already solves it (or b = 0, or a NaN)
   bool done = !(beta1 > stop) || !(beta1 > 0.0);
   int it = 0, counted = 0;
@@ -384,8 +370,8 @@ int minres(Handle *h, void *u_dev, const void *b_dev, double shift, double tol, 
   hipLaunchKernelGGL((minres_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b,
                      (const V *)q, (const V *)u, shift, n, part, 0, (const V *)nullptr);
   HIPCHK(hipGetLastError());
-  if ((rc = read_parts())) return rc;
-  const double res2 = host_sum(M_RES);
+  if ((rc = slots.fetch())) return rc;
+  const double res2 = slots.sum(M_RES);
   if (iterations) *iterations = counted;
   if (relres) *relres = bb > 0.0 ? std::sqrt(res2 / bb) : std::sqrt(res2);
   return 0;

@@ -16,7 +16,7 @@
 // delta^2 against the largest r . r seen at a host look since the last one (or below the stopping rule),
 // so about once per decade of the residual.  The device decides that at every iteration, see `thr` below;
 // the host acts on the flag at its next look.  Between replacements an iteration is the five fp32 launches of
-// cfs_solver::cg<float, PRE, BS>, one single-workgroup launch that raises the flag, and no host round trip.
+// cfs_solver::cg<float, BS>, one single-workgroup launch that raises the flag, and no host round trip.
 //
 // The scalars are the partial-sum slots of cfs_solver.hpp (no atomics, fixed order): on two deterministic
 // handles the whole solve is bit-reproducible.  z = M^-1 r is formed in fp64 from the ROUNDED r and the fp32
@@ -156,59 +156,37 @@ __global__ void __launch_bounds__(kThreads) cg_pause_kernel(const double *__rest
 }
 
 // u (fp64): in = first guess, out = solution.  h64 / h32: the same matrix in fp64 / fp32, whole-matrix handles on
-// one device.  PRE / BS as in cg().  *iterations: fp32 iterations done;  *replacements: replacements made inside
+// one device.  BS as in cg().  *iterations: fp32 iterations done;  *replacements: replacements made inside
 // the loop (neither the first residual nor the closing one after maxiter counts);  *relres: the fp64 true
 // residual of the returned u.
-template <bool PRE, int BS, class Handle>
+template <int BS, class Handle>
 int cg_mixed(Handle *h64, Handle *h32, void *u_dev, const void *b_dev, double tol, double delta, int maxiter, int check_every,
              int *iterations, int *replacements, double *relres, hipStream_t st) {
   using cfs_rt::DevBuf;
   typedef float V;
+  constexpr bool PRE = BS == 1, BLK = BS >= 2;
   const long long n = h64->n();
   if (h64->rows() != h64->n() || h32->rows() != h32->n())
     return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_mixed: the handles hold a row block, not the whole matrix");
-  if (maxiter < 0 || !(tol >= 0.0)) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg_mixed: bad tolerance / iteration limit");
-  if (check_every < 1) check_every = 8;
-  check_every = std::min(check_every, 16); // (as cg(): more launches enqueued ahead make the runtime stall)
-  if ((((uintptr_t)u_dev) | ((uintptr_t)b_dev)) & 15)
-    return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg_mixed: u and b must be 16-byte aligned");
+  check_every = look_window(check_every);
   double *u = (double *)u_dev;
   const double *b = (const double *)b_dev;
-  static_assert(BS == 0 || (PRE && BS >= 2), "block Jacobi is a preconditioner; BS = 1 is Jacobi");
-  constexpr bool BLK = BS >= 2;
-  const long long nb = BLK ? (n + BS - 1) / BS : 0;
-  DevBuf q64buf, rbuf, pbuf, qbuf, xbuf, pbuf_part, cnt, dbuf, blkbuf;
+  DevBuf q64buf, rbuf, pbuf, qbuf, xbuf, cnt;
+  Slots slots;
+  Precond<V, BS> pre; // from the fp32 handle's own blocks / diagonal, by the fp32 path of cg()
   int rc;
-  if (BLK && ((rc = dbuf.alloc((size_t)nb * tri_words(BS) * sizeof(V) + 64)) || (rc = blkbuf.alloc((size_t)nb * BS * BS * sizeof(V) + 64))))
-    return rc;
-  if (PRE && !BLK && (rc = dbuf.alloc((size_t)n * sizeof(V) + 64))) return rc;
-  const V *dinv = (const V *)dbuf.p;
-  if ((rc = q64buf.alloc((size_t)n * sizeof(double) + 64)) || (rc = rbuf.alloc((size_t)n * sizeof(V) + 64)) ||
-      (rc = pbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = qbuf.alloc((size_t)n * sizeof(V) + 64)) ||
-      (rc = xbuf.alloc((size_t)n * sizeof(V) + 64)) || (rc = pbuf_part.alloc((size_t)P_COUNT * kGrid * sizeof(double))) ||
-      (rc = cnt.alloc(I_COUNT * sizeof(int))))
+  if ((rc = alloc_vectors<double>(n, {&q64buf})) || (rc = alloc_vectors<V>(n, {&rbuf, &pbuf, &qbuf, &xbuf})) ||
+      (rc = slots.alloc(P_COUNT, st)) || (rc = cnt.alloc(I_COUNT * sizeof(int))) || (rc = slots.zero()))
     return rc;
   double *q64 = (double *)q64buf.p;
   V *r = (V *)rbuf.p, *p = (V *)pbuf.p, *q = (V *)qbuf.p, *xlo = (V *)xbuf.p;
-  double *part = (double *)pbuf_part.p;
+  double *part = slots.dev();
   int *ic = (int *)cnt.p;
-  std::vector<double> hp((size_t)P_COUNT * kGrid);
-  auto host_sum = [&](int slot) {
-    double s = 0.0;
-    for (int g = 0; g < kGrid; g++) s += hp[(size_t)slot * kGrid + g];
-    return s;
-  };
-  HIPCHK(hipMemsetAsync(part, 0, (size_t)P_COUNT * kGrid * sizeof(double), st));
   HIPCHK(hipMemsetAsync(ic, 0, I_COUNT * sizeof(int), st));
   HIPCHK(hipMemsetAsync(xlo, 0, (size_t)n * sizeof(V), st));
-  // the preconditioner from the fp32 handle's own blocks / diagonal, by the fp32 path of cg()
-  if constexpr (BLK) {
-    if ((rc = h32->block_diagonal(blkbuf.p, BS, st))) return rc;
-    hipLaunchKernelGGL((cg_binv_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)blkbuf.p, (V *)dbuf.p, nb, n, part);
-  } else if (PRE) {
-    if ((rc = h32->diagonal(dbuf.p, st))) return rc;
-    hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)dbuf.p, n, part);
-  }
+  if ((rc = pre.setup(h32, part, st))) return rc;
+  const V *dinv = pre.minv();
+  const long long nb = pre.nb;
   // q64 = A u, then r = (float)(b - q64) and the scalars for the fp32 iteration number `k` that comes next;
   // `first`: p = z (or r) and b . b as well.  Synchronises; returns the true r . r in *rr_true.
   auto true_residual = [&](int k, bool first, double *rr_true) -> int {
@@ -222,30 +200,20 @@ int cg_mixed(Handle *h64, Handle *h32, void *u_dev, const void *b_dev, double to
       hipLaunchKernelGGL((cg_replace_kernel<PRE>), dim3(kGrid), dim3(kThreads), 0, st, r, first ? p : (V *)nullptr, b,
                          (const double *)q64, n, part, slot_rr, slot_rz, first ? 1 : 0, dinv);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    *rr_true = host_sum(slot_rr);
+    if ((r2 = slots.fetch())) return r2;
+    *rr_true = slots.sum(slot_rr);
     return 0;
   };
   double rr_true = 0.0;
   if ((rc = true_residual(0, true, &rr_true))) return rc;
-  const double bb = host_sum(P_BB);
-  if (PRE) { // (read with the first host look: u has not been touched yet)
-    const double bad = host_sum(P_BAD);
-    if (BLK && bad != 0.0)
-      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg: block Jacobi needs positive definite diagonal blocks, " +
-                                                  std::to_string((long long)bad) + " of " + std::to_string(nb) + " blocks of " +
-                                                  std::to_string(BS) + " rows have a pivot that is zero, negative or not finite");
-    if (bad != 0.0)
-      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg: Jacobi needs a positive diagonal, " + std::to_string((long long)bad) +
-                                                  " of " + std::to_string(n) + " entries are zero, negative or not finite");
-  }
+  const double bb = slots.sum(P_BB);
+  if ((rc = pre.check("pcg", slots, n))) return rc; // (read with the first host look: u has not been touched yet)
   const double stop = tol * tol * bb, drop = delta * delta;
   bool done = !(rr_true > stop); // the first guess already solves it (or b = 0, or a NaN)
   bool folded = true;            // u holds everything: xlo = 0
   double rr_ref = rr_true;
   int it = 0, nrep = 0;
-  // the launches of cg<float, PRE, BS>, with xlo in the place of u, and cg_pause_kernel behind them.  The
+  // the launches of cg<float, BS>, with xlo in the place of u, and cg_pause_kernel behind them.  The
   // direction kernels get a stop that only a NaN trips (r . r >= 0 > -1): their flag is written by workgroup 0
   // while other workgroups of the same launch may not have started, which is harmless where p is dead once the
   // flag is up, but here p is KEPT across a replacement -- a workgroup that saw the flag and returned would
@@ -257,7 +225,7 @@ int cg_mixed(Handle *h64, Handle *h32, void *u_dev, const void *b_dev, double to
   auto iteration = [&](int k, double thr) -> int {
     int r2 = h32->spmv_local(q, p, nullptr, st);
     if (r2) return r2;
-    hipLaunchKernelGGL((cg_pq_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part,
+    hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part, (int)P_PQ,
                        (const int *)ic);
     if constexpr (BLK) {
       hipLaunchKernelGGL((cg_update_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, xlo, r, (const V *)p, (const V *)q,
@@ -273,12 +241,7 @@ int cg_mixed(Handle *h64, Handle *h32, void *u_dev, const void *b_dev, double to
     hipLaunchKernelGGL(cg_pause_kernel, dim3(1), dim3(kThreads), 0, st, (const double *)part, ic, k, thr);
     return 0;
   };
-  // host look: the counters and both r . r slots in one synchronisation
-  struct Look {
-    int ic[I_COUNT];
-    double rr[2][kGrid];
-  };
-  std::vector<Look> look(1);
+  int host_ic[I_COUNT] = {0, 0};
   while (!done && it < maxiter) {
     const int until = std::min(maxiter, it + check_every);
     const double thr = std::max(stop, drop * rr_ref);
@@ -286,17 +249,16 @@ int cg_mixed(Handle *h64, Handle *h32, void *u_dev, const void *b_dev, double to
       if ((rc = iteration(k, thr))) return rc;
     folded = false;
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(look[0].ic, ic, sizeof look[0].ic, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(look[0].rr, part + (size_t)P_RR0 * kGrid, sizeof look[0].rr, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    // host look: the counters and the slots in one synchronisation
+    HIPCHK(hipMemcpyAsync(host_ic, ic, sizeof host_ic, hipMemcpyDeviceToHost, st));
+    if ((rc = slots.fetch())) return rc;
     // (iterations enqueued behind a converged one did nothing: the device's count is the one that holds, and
     // its parity names the slots the next iteration reads)
-    it = look[0].ic[I_ITER];
-    double rr = 0.0;
-    for (int g = 0; g < kGrid; g++) rr += look[0].rr[it & 1][g];
+    it = host_ic[I_ITER];
+    const double rr = slots.sum(P_RR0 + (it & 1));
     if (rr > rr_ref) rr_ref = rr;
     // (!(x >= y): a NaN also asks for the true residual, which then ends the solve)
-    if (look[0].ic[I_DONE] || !(rr >= drop * rr_ref)) {
+    if (host_ic[I_DONE] || !(rr >= drop * rr_ref)) {
       hipLaunchKernelGGL(cg_fold_kernel, dim3(kGrid), dim3(kThreads), 0, st, u, xlo, n);
       if ((rc = true_residual(it, false, &rr_true))) return rc;
       folded = true;
