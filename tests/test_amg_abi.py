@@ -14,7 +14,13 @@ before anything touches a device, in the documented order; and one level of the 
   scaling of A -- the coarse matrix of D A D equals that of A within the same bound, with the same aggregates.
 
   lap2d(40, 33) with 2 passes: 330 aggregates of 4 (a numpy model of the algorithm gave exactly 330 / 1320 before
-  the library did), asserted as nc <= 0.30 n."""
+  the library did), asserted as nc <= 0.30 n.
+
+  The rule itself: _model_coarsen restates the text of include/cfs_hip.h in plain Python, and cfs.coarsen must give
+  its aggregates, weights, pattern and coarse values in every bit (6 matrices and an isotropic Laplacian, where ties
+  between free neighbours really occur; 1, 2, 3 passes).  What the reading of the caller's CSR promises: entries above
+  the diagonal ignored, unsorted rows sorted, duplicates summed -- a CSR disturbed in all three ways coarsens to the
+  same bits."""
 import ctypes as C
 import os
 import re
@@ -229,3 +235,144 @@ def test_a_diagonal_that_is_not_positive_is_refused(value):
     with pytest.raises(_lib.CfsHipError, match="positive diagonal, 1 of 63") as e:
         cfs.coarsen(n, rp, ci, va, 2)
     assert e.value.code == _lib.ERR_ARG
+
+
+# ---- the set-up restated from the text of cfs_hip.h, and what the reading of the caller's CSR promises ----------------
+def _model_coarsen(n, rp, ci, va, passes, ties=None):
+    """One level as include/cfs_hip.h words it, in plain Python floats (IEEE double, sqrt and division correctly
+    rounded) on dictionaries {row: {column: value}} -- a restatement of the rules, not of the library's loops:
+      w_i = 1 / sqrt(a_ii);  b_ij = (w_i a_ij) w_j from the entries with col <= row, mirrored
+      per pass: the rows ascending; an unmatched row takes the unmatched neighbour with the largest
+      |b_ij| / sqrt(b_ii b_jj) > 0, the columns ascending and the comparison strict (a tie keeps the smallest j);
+      aggregates numbered as they are made;  then C = Q^T B Q: the entries with J <= I, each the sum of its
+      contributions in ascending (row, column) order, and the upper triangle their mirror.
+    Returns what cfs.coarsen returns.  The CSR must have no duplicate entries.  ties (a list): receives (pass, row) of
+    every row that had two or more unmatched neighbours of the same, largest strength -- where the tie rule decided."""
+    import math
+    rp, ci, va = rp.tolist(), ci.tolist(), va.tolist()
+    diag = {ci[k]: va[k] for i in range(n) for k in range(rp[i], rp[i + 1]) if ci[k] == i}
+    w = [1.0 / math.sqrt(diag[i]) for i in range(n)]
+    B = {i: {} for i in range(n)}
+    for i in range(n):
+        for k in range(rp[i], rp[i + 1]):
+            if ci[k] <= i:
+                assert ci[k] not in B[i]
+                B[i][ci[k]] = B[ci[k]][i] = (w[i] * va[k]) * w[ci[k]]
+    agg = list(range(n))
+    for p in range(passes):
+        q, made = {}, 0
+        for i in sorted(B):
+            if i in q:
+                continue
+            best, sbest, tied = None, 0.0, False
+            for j in sorted(B[i]):
+                if j != i and j not in q:
+                    s = abs(B[i][j]) / math.sqrt(B[i][i] * B[j][j])
+                    if s > sbest:
+                        best, sbest, tied = j, s, False
+                    elif s == sbest and best is not None:
+                        tied = True
+            if tied and ties is not None:
+                ties.append((p, i))
+            q[i] = made
+            if best is not None:
+                q[best] = made
+            made += 1
+        Cm = {I: {} for I in range(made)}
+        for i in sorted(B):
+            for j in sorted(B[i]):
+                I, J = q[i], q[j]
+                if J <= I:
+                    Cm[I][J] = Cm[I][J] + B[i][j] if J in Cm[I] else B[i][j]
+        for I in sorted(Cm):
+            for J in Cm[I]:
+                Cm[J][I] = Cm[I][J]
+        agg, B = [q[a] for a in agg], Cm
+    nc = len(B)
+    low = [[(J, B[I][J]) for J in sorted(B[I]) if J <= I] for I in range(nc)]
+    crp = np.cumsum([0] + [len(r) for r in low]).astype(np.int32)
+    return (np.array(agg, np.int32), np.array(w, np.float64),
+            (nc, crp, np.array([J for r in low for J, _ in r], np.int32), np.array([v for r in low for _, v in r], np.float64)))
+
+
+def _same_level(got, want):
+    """agg, w, the pattern and the coarse values: equal in every bit"""
+    (agg, w, (nc, crp, cci, cva)), (agg2, w2, (nc2, crp2, cci2, cva2)) = got, want
+    return (nc == nc2 and np.array_equal(agg, agg2) and np.array_equal(w.view(np.uint8), w2.view(np.uint8)) and
+            np.array_equal(crp, crp2) and np.array_equal(cci, cci2) and cva.dtype == cva2.dtype == np.float64 and
+            np.array_equal(cva.view(np.uint8), cva2.view(np.uint8)))
+
+
+def _iso2d(nx, ny):
+    """kron(I, T_nx) + kron(T_ny, I), T = tridiag(-1, 2, -1): the five-point Laplacian, every coupling equally strong"""
+    import scipy.sparse as sp
+    T = lambda n: sp.diags([-np.ones(n - 1), 2 * np.ones(n), -np.ones(n - 1)], [-1, 0, 1])
+    A = (sp.kron(sp.identity(ny), T(nx)) + sp.kron(T(ny), sp.identity(nx))).tocsr()
+    A.sort_indices()
+    return A.shape[0], A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float64)
+
+
+@pytest.mark.parametrize("passes", (1, 2, 3))
+@pytest.mark.parametrize("name", MATRICES + ("iso2d13x11",))
+def test_the_set_up_is_the_documented_one_bit_for_bit(name, passes):
+    """cfs.coarsen against _model_coarsen: the same aggregates, weights, pattern and coarse VALUES in every bit -- the
+    matching rule (strongest neighbour, ties to the smallest j) and the order of every sum are the documented ones, not
+    merely some valid partition with its own P^T A P.
+    Where the tie rule decides: the rows of lap2d have two equally strong neighbours, i - 1 and i + 1, but i - 1 is
+    always matched already when row i has its turn, and the same holds on its coarse grids: the model counts NO row of
+    lap2d40x33, in any pass, at which two free neighbours tie (the count is printed) -- a matching that broke ties
+    towards the largest j passes every lap2d and rand case.  In the isotropic iso2d13x11 a row whose right and lower
+    neighbours are both free has a tie between them (the strengths are exactly 1/4: w = 1/2 and b_ij = -1/4 are
+    exact): 60 of its 143 rows in the first pass.  That is asserted, so that a change of the matrix cannot silently
+    empty the case."""
+    n, rp, ci, va = _iso2d(13, 11) if name.startswith("iso2d") else matrix(name)
+    ties = []
+    got, want = cfs.coarsen(n, rp, ci, va, passes), _model_coarsen(n, rp, ci, va, passes, ties)
+    sizes = np.bincount(np.bincount(want[0]), minlength=2 ** passes + 1)[1:]
+    per_pass = [sum(1 for p, _ in ties if p == k) for k in range(passes)]
+    print(f"amg-model {name} passes={passes}: n={n} nc={want[2][0]} aggregates of 1 .. {2 ** passes} rows: "
+          + "/".join(str(int(s)) for s in sizes) + f"; rows where a tie was broken, per pass: {per_pass}")
+    assert int(sizes.sum()) == want[2][0] and int((sizes * np.arange(1, len(sizes) + 1)).sum()) == n
+    if name == "iso2d13x11":
+        assert per_pass[0] >= n // 4, per_pass
+    assert np.array_equal(got[0], want[0]), "the aggregates differ from the documented matching"
+    assert _same_level(got, want)
+
+
+def _disturbed(n, rp, ci, va, seed):
+    """the same matrix as amg_lower has to read it: every entry above the diagonal replaced by a random value, about
+    half of those with col <= row split into two equal halves (v / 2 + v / 2 is exact), every row's columns shuffled"""
+    rng = np.random.default_rng(seed)
+    nrp, nci, nva = [0], [], []
+    for i in range(n):
+        cols, vals = [], []
+        for k in range(rp[i], rp[i + 1]):
+            j, v = int(ci[k]), float(va[k])
+            if j > i:
+                cols.append(j), vals.append(float(rng.uniform(-5, 5)))
+            elif rng.random() < 0.5:
+                assert v / 2 + v / 2 == v
+                cols += [j, j]
+                vals += [v / 2, v / 2]
+            else:
+                cols.append(j), vals.append(v)
+        order = rng.permutation(len(cols))
+        nci += [cols[k] for k in order]
+        nva += [vals[k] for k in order]
+        nrp.append(len(nci))
+    return np.array(nrp, np.int32), np.array(nci, np.int32), np.array(nva, np.float64)
+
+
+@pytest.mark.parametrize("passes", (1, 2, 3))
+@pytest.mark.parametrize("name", ("rand63", "rand1026", "lap2d40x33-scaled"))
+def test_entries_above_the_diagonal_duplicates_and_unsorted_rows(name, passes):
+    """what the reading of the caller's CSR promises: entries with col > row are ignored, rows need not be sorted,
+    duplicates are summed -- cfs.coarsen of the disturbed CSR equals that of the clean one in every bit"""
+    n, rp, ci, va = matrix(name)
+    rp2, ci2, va2 = _disturbed(n, rp, ci, va, seed=n + passes)
+    rows, rows2 = np.repeat(np.arange(n), np.diff(rp)), np.repeat(np.arange(n), np.diff(rp2))
+    # the disturbance is there: more entries, other values above the diagonal, rows that are not ascending
+    assert len(ci2) > len(ci) + int((ci <= rows).sum()) // 4
+    assert not np.array_equal(np.sort(va2[ci2 > rows2]), np.sort(va[ci > rows]))
+    assert int(((np.diff(ci2) < 0) & (np.diff(rows2) == 0)).sum()) > n // 4
+    assert _same_level(cfs.coarsen(n, rp2, ci2, va2, passes), cfs.coarsen(n, rp, ci, va, passes))

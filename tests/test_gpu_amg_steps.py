@@ -386,9 +386,9 @@ def test_the_stored_inverse_against_a_long_double_inverse(name, coarse_max, dtyp
 
 
 # ---- 3. the iterates ----------------------------------------------------------------------------------------
-def _check_iterates(name, H, b, dtype, run, label="", ks=KS):
-    """run(k) -> (u_k, iterations) on the GPU from u = 0; asserts every k of ks against the long-double iterate"""
-    ref, work = H.pcg(b, ks), H.pcg(b, ks, dtype)
+def _check_iterates(name, H, b, dtype, run, label="", ks=KS, x0=None):
+    """run(k) -> (u_k, iterations) on the GPU from u = x0 (0); asserts every k of ks against the long-double iterate"""
+    ref, work = H.pcg(b, ks, x0=x0), H.pcg(b, ks, dtype, x0=x0)
     errors = []
     for k in ks:
         u_ref, _ = ref[k]
