@@ -13,4 +13,4 @@ directory is `cfs_spmv_amd`.)
 """
 from ._lib import CfsHipError, load, lib_path  # noqa: F401
 from .matrix import (EXCHANGE_REDUCE_SCATTER, Amg, EXCHANGE_SPARSE, FLAG_HOST_PLAN, FLAG_KEEP_VALUE_MAP, FLAG_SHARD_EXCHANGE, CsrMatrix, Format, Kernel, MixedSym, SpDMV, SymMatrix, Tuning,  # noqa: F401
-                     balanced_splits, coarsen, make_options, plan_check, plan_send_info, plan_file_info, plan_save)
+                     balanced_splits, coarsen, recoarsen, make_options, plan_check, plan_send_info, plan_file_info, plan_save)

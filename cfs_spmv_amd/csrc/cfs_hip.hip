@@ -1021,6 +1021,7 @@ struct cfs_hip_sym_s {
                                                     "straddle the row splits of a multi-device handle)");
   }
   int device = 0; // the device this handle's arrays live on (current device at create)
+  unsigned long long values_epoch = 0; // cfs_hip_sym_update_values_* so far: a refreshable hierarchy sees that level 0 changed
   std::string plan_note; // why the device builder handed the schedule to the host builder ("" = it did not)
   HostStage stage; // host-pointer callers
   // the last (y, x) pair whose placement was validated (async entry points)
@@ -1439,6 +1440,7 @@ template <typename V> struct SymMatrix : cfs_hip_sym_s {
     go(fvals, fval_map);
     go(diag, diag_map);
     HIPCHK(hipGetLastError());
+    values_epoch += 1;
     return 0;
   }
   int diagonal(void *d_dev, hipStream_t st) override {
@@ -2221,7 +2223,7 @@ int cfs_hip_debug_cheb_coeffs(int degree, double lmin, double lmax, double *thet
 // ---- aggregation multigrid (cfs_solver_amg.hpp) ------------------------------------------------------
 template <typename V>
 static int amg_create(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const V *values, const cfs_hip_amg_options *opt,
-                      cfs_hip_amg_t *out) {
+                      cfs_hip_amg_t *out, bool refreshable = false) {
   if (out) *out = nullptr;
   if (!h || !out || !rowptr || n < 0 || (n > 0 && rowptr[n] > 0 && (!colind || !values)))
     return set_err(CFS_HIP_ERR_ARG, "amg_create: null argument");
@@ -2245,10 +2247,15 @@ static int amg_create(cfs_hip_sym_t h, int n, const int *rowptr, const int *coli
     return set_err(CFS_HIP_ERR_ARG, "amg_create: the handle holds values of " + std::to_string(h->value_bytes) + " bytes, the CSR of " +
                                         std::to_string(sizeof(V)));
   if (n != h->n()) return set_err(CFS_HIP_ERR_ARG, "amg_create: n = " + std::to_string(n) + ", the handle has " + std::to_string(h->n()) + " rows");
+  if (refreshable && m->P.deterministic)
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "amg_create_refreshable: a deterministic handle's levels are deterministic, and those refuse "
+                                            "update_values (their fixed-point scale depends on the values)");
   DeviceGuard g(h->device);
   std::unique_ptr<cfs_solver::Amg<V>> a(new cfs_solver::Amg<V>());
   a->passes = passes, a->degree = degree, a->coarse_max = coarse_max, a->ratio = ratio, a->device = h->device;
-  const int flags = CFS_HIP_FLAG_NO_CALIBRATE | (m->P.deterministic ? CFS_HIP_FLAG_DETERMINISTIC : 0);
+  a->refreshable = refreshable;
+  const int flags = CFS_HIP_FLAG_NO_CALIBRATE | (m->P.deterministic ? CFS_HIP_FLAG_DETERMINISTIC : 0) |
+                    (refreshable ? CFS_HIP_FLAG_KEEP_VALUE_MAP : 0);
   h->ok_x = h->ok_y = nullptr;
   int rc = a->build(h, n, rowptr, colind, values, flags,
                     [](int ln, const int *rp, const int *ci, const V *va, int fl, cfs_hip_sym_s **lh) {
@@ -2266,6 +2273,82 @@ int cfs_hip_amg_create_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int 
 int cfs_hip_amg_create_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
                            const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
   return amg_create<float>(h, n, rowptr, colind, values, opt, out);
+}
+int cfs_hip_amg_create_refreshable_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
+                                       const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create<double>(h, n, rowptr, colind, values, opt, out, true);
+}
+int cfs_hip_amg_create_refreshable_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
+                                       const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create<float>(h, n, rowptr, colind, values, opt, out, true);
+}
+// cfs_hip_sym_update_values_* for a refreshable hierarchy: the same staging of a host array, the same stream
+static int amg_update_values(cfs_hip_amg_t a, const void *values, long long nnz, size_t vb) {
+  if (!a || !values) return set_err(CFS_HIP_ERR_ARG, "amg_update_values: null argument");
+  if ((size_t)a->value_bytes != vb) return set_err(CFS_HIP_ERR_ARG, "amg_update_values: value type differs from the hierarchy's");
+  int rc = a->update_check(nnz); // (not refreshable, another nnz: before any device work, and before a host array is read)
+  if (rc) return rc;
+  cfs_hip_sym_t h = a->fine;
+  cfs_rt::DevCtx *ctx;
+  if ((rc = cfs_rt::device_ctx(h->device, &ctx))) return rc;
+  DeviceGuard g(h->device);
+  const cfs_rt::PtrInfo vi = cfs_rt::classify(values);
+  if (vi.device && vi.dev != h->device) return set_err(CFS_HIP_ERR_ARG, "amg_update_values: values live on another device than the matrix");
+  DevBuf tmp;
+  const void *src = values;
+  if (!vi.device) {
+    if ((rc = tmp.alloc((size_t)nnz * vb))) return rc;
+    HIPCHK(hipMemcpyAsync(tmp.p, values, (size_t)nnz * vb, hipMemcpyHostToDevice, ctx->stream));
+    src = tmp.p;
+  }
+  h->ok_x = h->ok_y = nullptr;
+  rc = a->update_values(src, nnz, ctx->stream);
+  HIPCHK(hipStreamSynchronize(ctx->stream)); // tmp goes away; a cycle enqueued afterwards on any stream sees the hierarchy
+  return rc;
+}
+int cfs_hip_amg_update_values_f64(cfs_hip_amg_t a, const double *values, long long nnz) { return amg_update_values(a, values, nnz, 8); }
+int cfs_hip_amg_update_values_f32(cfs_hip_amg_t a, const float *values, long long nnz) { return amg_update_values(a, values, nnz, 4); }
+int cfs_hip_amg_refresh_info(cfs_hip_amg_t a, long long *map_bytes, int *refreshes, double *last_seconds) {
+  if (!a) return set_err(CFS_HIP_ERR_ARG, "amg_refresh_info: null argument");
+  return a->refresh_info(map_bytes, refreshes, last_seconds, nullptr);
+}
+int cfs_hip_debug_amg_refresh_split(cfs_hip_amg_t a, double *seconds) {
+  if (!a || !seconds) return set_err(CFS_HIP_ERR_ARG, "amg_refresh_split: null argument");
+  return a->refresh_info(nullptr, nullptr, nullptr, seconds);
+}
+int cfs_hip_debug_amg_recoarsen(int n, const int *rowptr, const int *colind, const double *values_at_create, const double *values_new,
+                                int passes, double *w, double *c_values, long long capacity, long long *c_nnz) {
+  if (n < 0 || !rowptr || !w || !c_nnz || (n > 0 && rowptr[n] > 0 && (!colind || !values_at_create || !values_new)))
+    return set_err(CFS_HIP_ERR_ARG, "amg_recoarsen: null argument");
+  if (passes < 1 || passes > 3) return set_err(CFS_HIP_ERR_ARG, "amg_recoarsen: passes must lie in [1, 3], got " + std::to_string(passes));
+  cfs_solver::AmgCsr low, coarse;
+  cfs_solver::amg_lower(n, rowptr, colind, values_at_create, low);
+  cfs_solver::AmgList lists;
+  cfs_solver::amg_lower_lists(n, rowptr, colind, lists);
+  cfs_solver::AmgFrozen frozen;
+  std::vector<int> ag;
+  std::vector<double> wv, a_new((size_t)low.nnz()), out;
+  long long bad = 0;
+  if (cfs_solver::amg_coarsen(low, passes, ag, wv, coarse, &bad, &frozen))
+    return set_err(CFS_HIP_ERR_ARG, "amg_recoarsen: Jacobi needs a positive diagonal, " + std::to_string(bad) + " of " + std::to_string(n) +
+                                        " entries (at create) are zero, negative or not finite");
+  if (frozen.overflow()) return set_err(CFS_HIP_ERR_UNSUPPORTED, "amg_recoarsen: the contributions of a round exceed the 32-bit indices of the lists");
+  cfs_solver::amg_eval_list(lists, values_new, a_new.data());
+  for (int i = 0; i < n; ++i) {
+    const double d = a_new[frozen.diag[i]];
+    if (!(d > 0.0) || d * 0.0 != 0.0) bad += 1;
+  }
+  if (bad)
+    return set_err(CFS_HIP_ERR_ARG, "amg_recoarsen: Jacobi needs a positive diagonal, " + std::to_string(bad) + " of " + std::to_string(n) +
+                                        " entries are zero, negative or not finite");
+  cfs_solver::amg_eval_frozen(frozen, low.ci, a_new.data(), wv, out);
+  *c_nnz = (long long)out.size();
+  for (int i = 0; i < n; ++i) w[i] = wv[i];
+  if ((long long)out.size() > capacity || (!out.empty() && !c_values))
+    return set_err(CFS_HIP_ERR_ARG, "amg_recoarsen: the coarse matrix has " + std::to_string(out.size()) + " entries, room for " +
+                                        std::to_string(capacity));
+  for (size_t k = 0; k < out.size(); ++k) c_values[k] = out[k];
+  return 0;
 }
 int cfs_hip_amg_destroy(cfs_hip_amg_t a) {
   delete a;

@@ -47,10 +47,28 @@
 // Rounding: vectors are stored in V; every update is computed in fp64 from the stored operands and rounded once; the
 // restriction sums its members in ascending order, the dense rows in a fixed lane order; all scalars are the
 // fixed-order partial sums of cfs_solver.hpp.  No atomics: on a deterministic handle the solve is bit-reproducible.
+//
+// REFRESH (cfs_hip_amg_create_refreshable_*, cfs_hip_amg_update_values_*): the arithmetic of the set-up with the matching
+// q of every round FROZEN, in the same order of operations, on the device over lists recorded at create --
+//   level 0:   a_k = the caller's values summed as amg_lower sums them         amg_gather_sum_kernel over amg_lower_lists
+//   per level: w_i = 1 / sqrt(a_ii) in fp64 on the device (correctly rounded division and sqrt: the bits of the host's;
+//              the test with unchanged values is the judge, and it found no differing bit), (V)w_i for the transfers,
+//              the entries that are not finite and > 0 counted                 amg_weight_kernel
+//              b_k = (w_row(k) a_k) w_col(k), the operand order of amg_mirror  amg_scale_kernel
+//              per round, every entry of Q^T B Q with J <= I as the sum of its contributions in the order amg_galerkin
+//              adds them; the last round writes (V)s and (double)(V)s           amg_gather_sum_kernel
+//              the pour into the next level's handle (update_values), then dinv, cheb_power and the pairs again
+//   dense level: its values to the host, amg_dense_inverse, the inverse back.
+// If a fresh set-up would choose the same aggregates the result equals it in every bit of w, the level matrices and the
+// inverse.  Kept between calls (map_bytes): the lists, row / column / diagonal position per stored entry of a level, every
+// level's values in V on the device (level_matrix() reads them back at its first call after a refresh), two fp64 arrays
+// of the longest level (the scaling is in place, the rounds go to and fro) and the fp64 weights.  Level 0 is the caller's
+// handle, poured by the caller: follow_fine().
 #pragma once
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <memory>
 #include <utility>
 
@@ -65,6 +83,9 @@ struct cfs_hip_amg_s {
   virtual int coarse_inverse(void *inv) = 0;
   virtual int apply(void *z_dev, const void *r_dev, hipStream_t st) = 0;
   virtual int pcg(void *u_dev, const void *b_dev, double tol, int maxiter, int *iterations, double *relres, hipStream_t st) = 0;
+  virtual int update_check(long long nnz) = 0;
+  virtual int update_values(const void *values_dev, long long nnz, hipStream_t st) = 0;
+  virtual int refresh_info(long long *map_bytes, int *refreshes, double *last_seconds, double *split) = 0;
 };
 
 namespace cfs_solver {
@@ -109,8 +130,9 @@ template <typename T> inline void amg_lower(int n, const int *rowptr, const int 
 }
 
 // both triangles of a symmetric matrix from its lower triangle + diagonal, columns ascending; scale: the entry
-// (i, j) becomes (scale_i a_ij) scale_j, computed once and mirrored (nullptr: the entries as they are)
-inline void amg_mirror(const AmgCsr &low, const double *scale, AmgCsr &full) {
+// (i, j) becomes (scale_i a_ij) scale_j, computed once and mirrored (nullptr: the entries as they are).  from (when
+// given): the position in `low` every entry of `full` was taken from
+inline void amg_mirror(const AmgCsr &low, const double *scale, AmgCsr &full, std::vector<int> *from = nullptr) {
   const int n = low.n;
   full.n = n;
   full.rp.assign((size_t)n + 1, 0);
@@ -122,11 +144,13 @@ inline void amg_mirror(const AmgCsr &low, const double *scale, AmgCsr &full) {
   for (int i = 0; i < n; ++i) full.rp[(size_t)i + 1] += full.rp[i];
   full.ci.assign((size_t)full.rp[n], 0);
   full.va.assign((size_t)full.rp[n], 0.0);
+  if (from) from->assign((size_t)full.rp[n], 0);
   std::vector<long long> pos(full.rp.begin(), full.rp.end() - 1);
   auto value = [&](int i, long long k) { return scale ? (scale[i] * low.va[k]) * scale[low.ci[k]] : low.va[k]; };
   for (int i = 0; i < n; ++i) // the columns up to the diagonal ...
     for (long long k = low.rp[i]; k < low.rp[i + 1]; ++k) {
       full.ci[pos[i]] = low.ci[k];
+      if (from) (*from)[pos[i]] = (int)k;
       full.va[pos[i]++] = value(i, k);
     }
   for (int i = 0; i < n; ++i) // ... then those behind it, rows ascending
@@ -134,6 +158,7 @@ inline void amg_mirror(const AmgCsr &low, const double *scale, AmgCsr &full) {
       const int j = low.ci[k];
       if (j == i) continue;
       full.ci[pos[j]] = i;
+      if (from) (*from)[pos[j]] = (int)k;
       full.va[pos[j]++] = value(i, k);
     }
 }
@@ -178,8 +203,53 @@ inline int amg_match(const AmgCsr &B, std::vector<int> &q) {
   return nc;
 }
 
-// the lower triangle + diagonal of Q^T B Q: every entry the sum of its contributions in ascending (row, column) order
-inline void amg_galerkin(const AmgCsr &B, const std::vector<int> &q, int nc, AmgCsr &out) {
+// what a refresh evaluates (cfs_hip_amg_update_values_*): output entry e is the sum of src[idx[k]], k = ptr[e] ..
+// ptr[e + 1] - 1, added in that order.  32-bit: a list that would not fit sets `overflow`
+struct AmgList {
+  std::vector<int> ptr, idx;
+  bool overflow = false;
+  long long entries() const { return ptr.empty() ? 0 : (long long)ptr.size() - 1; }
+};
+
+// the lists of amg_lower: per entry it writes, the positions in the caller's values[] it sums, in its order
+inline void amg_lower_lists(int n, const int *rowptr, const int *colind, AmgList &out) {
+  out.ptr.assign(1, 0);
+  out.idx.clear();
+  std::vector<std::pair<int, int>> row;
+  for (int i = 0; i < n; ++i) {
+    row.clear();
+    bool sorted = true;
+    for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+      const int j = colind[k];
+      if (j < 0 || j > i) continue;
+      if (!row.empty() && row.back().first >= j) sorted = false;
+      row.emplace_back(j, k);
+    }
+    if (!sorted) std::stable_sort(row.begin(), row.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    for (size_t k = 0; k < row.size(); ++k) {
+      out.idx.push_back(row[k].second);
+      if (k > 0 && row[k].first == row[k - 1].first)
+        out.ptr.back() = (int)out.idx.size();
+      else
+        out.ptr.push_back((int)out.idx.size());
+    }
+  }
+}
+
+// out[e] = the sum of list e over src, on the host in the order amg_gather_sum_kernel adds
+template <typename S> inline void amg_eval_list(const AmgList &li, const S *src, double *out) {
+  for (long long e = 0; e < li.entries(); ++e) {
+    double s = (double)src[li.idx[li.ptr[e]]];
+    for (int k = li.ptr[e] + 1; k < li.ptr[e + 1]; ++k) s += (double)src[li.idx[k]];
+    out[e] = s;
+  }
+}
+
+// the lower triangle + diagonal of Q^T B Q: every entry the sum of its contributions in ascending (row, column) order.
+// from + rec (when given): from[k] = where entry k of B sits in the lower-triangle array B was mirrored from; rec <- per
+// entry of `out`, as it stands after the sort of its row, those positions in the order the sum below adds them
+inline void amg_galerkin(const AmgCsr &B, const std::vector<int> &q, int nc, AmgCsr &out, const std::vector<int> *from = nullptr,
+                         AmgList *rec = nullptr) {
   const int n = B.n;
   std::vector<int> first((size_t)nc, -1), second((size_t)nc, -1);
   for (int i = 0; i < n; ++i) (first[q[i]] < 0 ? first[q[i]] : second[q[i]]) = i;
@@ -189,8 +259,12 @@ inline void amg_galerkin(const AmgCsr &B, const std::vector<int> &q, int nc, Amg
   out.va.clear();
   std::vector<long long> where((size_t)nc, -1);
   std::vector<std::pair<int, double>> row;
+  std::vector<std::pair<int, int>> added; // rec: (entry of the row before the sort, position in the source array)
+  std::vector<int> cnt;
+  if (rec) rec->ptr.assign(1, 0), rec->idx.clear(), rec->overflow = false;
   for (int I = 0; I < nc; ++I) {
     const long long start = (long long)out.ci.size();
+    added.clear();
     for (int m : {first[I], second[I]}) {
       if (m < 0) continue;
       for (long long k = B.rp[m]; k < B.rp[m + 1]; ++k) {
@@ -203,19 +277,69 @@ inline void amg_galerkin(const AmgCsr &B, const std::vector<int> &q, int nc, Amg
         } else {
           out.va[where[J]] += B.va[k];
         }
+        if (rec) added.emplace_back((int)(where[J] - start), (*from)[k]);
       }
     }
     const long long end = (long long)out.ci.size();
     row.clear();
     for (long long k = start; k < end; ++k) row.emplace_back(out.ci[k], out.va[k]);
     std::sort(row.begin(), row.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    if (rec) { // the lists follow their entries through the sort; inside a list the order of the sum stays
+      const size_t len = (size_t)(end - start), base = rec->idx.size();
+      if (base + added.size() > (size_t)INT_MAX) {
+        rec->overflow = true;
+        rec = nullptr;
+      } else {
+        cnt.assign(len + 1, 0);
+        for (const auto &c : added) cnt[(size_t)c.first + 1] += 1;
+        for (size_t k = 0; k < len; ++k) cnt[k + 1] += cnt[k];
+        std::vector<int> at(len); // where the list of the entry that was at `old` before the sort begins
+        for (size_t k = 0; k < len; ++k) {
+          const size_t old = (size_t)(where[row[k].first] - start);
+          at[old] = (int)rec->idx.size();
+          rec->idx.resize(rec->idx.size() + (size_t)(cnt[old + 1] - cnt[old]));
+          rec->ptr.push_back((int)rec->idx.size());
+        }
+        for (const auto &c : added) rec->idx[(size_t)at[c.first]++] = c.second;
+      }
+    }
     for (long long k = start; k < end; ++k) out.ci[k] = row[k - start].first, out.va[k] = row[k - start].second, where[out.ci[k]] = -1;
     out.rp[(size_t)I + 1] = end;
   }
 }
 
-// one level: agg, w and the lower triangle + diagonal of A_{l+1} from that of A_l.  *bad: diagonal entries that are not positive
-inline int amg_coarsen(const AmgCsr &low, int passes, std::vector<int> &agg, std::vector<double> &w, AmgCsr &coarse, long long *bad) {
+// one level with its matchings frozen, as a refresh evaluates it: w_i = 1 / sqrt(a[diag[i]]), b_k = (w_row[k] a_k) w_col[k]
+// over the lower-triangle array a (col: the pattern's colind), then rounds[p] over the array of the round before
+struct AmgFrozen {
+  std::vector<int> diag, row;
+  std::vector<AmgList> rounds;
+  bool overflow() const {
+    for (const AmgList &r : rounds)
+      if (r.overflow) return true;
+    return false;
+  }
+};
+
+// the frozen level for other values of the same pattern, on the host: a (the lower-triangle array) -> w and the values
+// of the last round, every operation in the order of the kernels (which is that of amg_coarsen)
+inline void amg_eval_frozen(const AmgFrozen &f, const std::vector<int> &col, const double *a, std::vector<double> &w, std::vector<double> &out) {
+  const size_t n = f.diag.size(), m = f.row.size();
+  w.resize(n);
+  for (size_t i = 0; i < n; ++i) w[i] = 1.0 / std::sqrt(a[f.diag[i]]);
+  std::vector<double> src(m), dst;
+  for (size_t k = 0; k < m; ++k) src[k] = (w[f.row[k]] * a[k]) * w[col[k]];
+  for (const AmgList &r : f.rounds) {
+    dst.resize((size_t)r.entries());
+    amg_eval_list(r, src.data(), dst.data());
+    src.swap(dst);
+  }
+  out = std::move(src);
+}
+
+// one level: agg, w and the lower triangle + diagonal of A_{l+1} from that of A_l.  *bad: diagonal entries that are not positive.
+// rec (when given): the level's lists, for a refresh
+inline int amg_coarsen(const AmgCsr &low, int passes, std::vector<int> &agg, std::vector<double> &w, AmgCsr &coarse, long long *bad,
+                       AmgFrozen *rec = nullptr) {
   const int n = low.n;
   std::vector<double> diag;
   *bad = amg_diagonal(low, diag);
@@ -223,15 +347,25 @@ inline int amg_coarsen(const AmgCsr &low, int passes, std::vector<int> &agg, std
   w.resize((size_t)n);
   for (int i = 0; i < n; ++i) w[i] = 1.0 / std::sqrt(diag[i]);
   AmgCsr B, next;
-  amg_mirror(low, w.data(), B);
+  std::vector<int> from;
+  if (rec) {
+    rec->diag.resize((size_t)n);
+    rec->row.resize((size_t)low.nnz());
+    for (int i = 0; i < n; ++i) {
+      rec->diag[i] = (int)low.rp[(size_t)i + 1] - 1; // (amg_diagonal found it there)
+      for (long long k = low.rp[i]; k < low.rp[(size_t)i + 1]; ++k) rec->row[k] = i;
+    }
+    rec->rounds.assign((size_t)passes, AmgList());
+  }
+  amg_mirror(low, w.data(), B, rec ? &from : nullptr);
   agg.resize((size_t)n);
   for (int i = 0; i < n; ++i) agg[i] = i;
   std::vector<int> q;
   for (int p = 0; p < passes; ++p) {
     const int nc = amg_match(B, q);
-    amg_galerkin(B, q, nc, next);
+    amg_galerkin(B, q, nc, next, rec ? &from : nullptr, rec ? &rec->rounds[p] : nullptr);
     for (int i = 0; i < n; ++i) agg[i] = q[agg[i]];
-    if (p + 1 < passes) amg_mirror(next, nullptr, B);
+    if (p + 1 < passes) amg_mirror(next, nullptr, B, rec ? &from : nullptr);
   }
   coarse = std::move(next);
   return 0;
@@ -348,8 +482,57 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// ---- the kernels of a refresh (see REFRESH at the end of the header comment) ------------------------
+// out[e] = src[idx[ptr[e]]] + src[idx[ptr[e] + 1]] + ... in fp64, in the order of the list: one thread per output entry.
+// LAST (the last round of a level): vout[e] = (V)s, what the next level's handle is poured, and out[e] = (double)(V)s,
+// what the next level is coarsened from.  Adds only: nothing for the compiler to contract
+template <typename S, typename V, bool LAST>
+__global__ void __launch_bounds__(kThreads)
+    amg_gather_sum_kernel(double *__restrict__ out, V *__restrict__ vout, const S *__restrict__ src, const int *__restrict__ ptr,
+                          const int *__restrict__ idx, long long m) {
+  for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < m; e += (long long)gridDim.x * kThreads) {
+    int k = ptr[e];
+    const int end = ptr[e + 1];
+    double s = (double)src[idx[k]];
+    for (++k; k < end; ++k) s += (double)src[idx[k]];
+    if (LAST) {
+      const V v = (V)s;
+      vout[e] = v;
+      out[e] = (double)v;
+    } else {
+      out[e] = s;
+    }
+  }
+}
+
+// w64_i = 1 / sqrt(a[diag[i]]) in fp64, w_i = (V)w64_i;  bad[workgroup] <- diagonal entries that are not finite and > 0
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    amg_weight_kernel(double *__restrict__ w64, V *__restrict__ w, const double *__restrict__ a, const int *__restrict__ diag, long long n,
+                      double *__restrict__ bad_out) {
+  double bad = 0.0;
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+    const double d = a[diag[i]];
+    if (!(d > 0.0) || d * 0.0 != 0.0) bad += 1.0;
+    const double wi = 1.0 / sqrt(d);
+    w64[i] = wi;
+    w[i] = (V)wi;
+  }
+  bad = block_sum(bad);
+  if (threadIdx.x == 0) bad_out[blockIdx.x] = bad;
+}
+
+// a_k <- b_k = (w_row(k) a_k) w_col(k), in place: the operand order of amg_mirror, the row the larger index
+__global__ void __launch_bounds__(kThreads)
+    amg_scale_kernel(double *__restrict__ a, const double *__restrict__ w64, const int *__restrict__ row, const int *__restrict__ col,
+                     long long m) {
+  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < m; k += (long long)gridDim.x * kThreads)
+    a[k] = (w64[row[k]] * a[k]) * w64[col[k]];
+}
+
 // ---- the hierarchy on the device -------------------------------------------------------------------
 enum AmgKind { AMG_MULTIGRID = 0, AMG_SMOOTHER = 1, AMG_DENSE = 2 };
+enum AmgPhase { AMG_T_GALERKIN = 0, AMG_T_POUR, AMG_T_POWER, AMG_T_DENSE, AMG_T_COUNT }; // the split of a refresh's time
 
 template <typename V> struct AmgLevel {
   int n = 0, nc = 0, kind = AMG_MULTIGRID;
@@ -362,11 +545,22 @@ template <typename V> struct AmgLevel {
   // the CSR the level's handle was created from (levels >= 1): lower triangle + diagonal, values in V
   std::vector<int> rp, ci;
   std::vector<V> va;
+  // a refreshable hierarchy only: the lists of amg_lower (level 0), the frozen level (a level with a coarser one) and
+  // vdev, the device image of va in V (levels >= 1): written by the level above, poured into h, read back into va on demand
+  cfs_rt::DevBuf lptr, lidx, fdiag, frow, fcol, rptr[3], ridx[3], vdev;
+  long long rout[3] = {0, 0, 0}; // entries round p writes
+  bool va_stale = false;
+  AmgCsr dense;                  // the pattern of a dense level, for amg_dense_inverse
   ~AmgLevel() {
     if (owned) delete h;
   }
   size_t bytes() const {
     return pre.dbuf.bytes + aggptr.bytes + aggidx.bytes + agg.bytes + w.bytes + r.bytes + z.bytes + d.bytes + t.bytes + inv.bytes;
+  }
+  size_t map_bytes() const {
+    size_t b = lptr.bytes + lidx.bytes + fdiag.bytes + frow.bytes + fcol.bytes + vdev.bytes;
+    for (int p = 0; p < 3; ++p) b += rptr[p].bytes + ridx[p].bytes;
+    return b;
   }
 };
 
@@ -377,9 +571,19 @@ template <typename V> struct Amg : cfs_hip_amg_s {
   cfs_rt::DevBuf cnt; // a done flag that is never set
   int passes = 2, degree = 1, coarse_max = 512, device = 0;
   double ratio = 4.0, setup_seconds = 0.0, handles_seconds = 0.0;
+  // a refreshable hierarchy (cfs_hip_amg_create_refreshable_*)
+  bool refreshable = false, stale = false;
+  int refreshes = 0;
+  long long nnz_caller = 0, value_map_bytes = 0; // ... of the level handles' value maps: 4 per stored entry, an ESTIMATE
+  unsigned long long fine_epoch = 0;             // fine->values_epoch when level 0's dinv and bound were last made
+  double last_seconds = 0.0, split[AMG_T_COUNT] = {0.0, 0.0, 0.0, 0.0};
+  cfs_rt::DevBuf rbuf[2], w64, pw; // kept: two fp64 arrays of the longest level, the fp64 weights, the power method's vector
+  Slots rpart, rlpart;             // P_COUNT slots of a level's smoother + one for amg_weight_kernel; the power method's, kept
+  std::vector<hipEvent_t> ev;
 
   ~Amg() override {
     cfs_rt::DeviceGuard g(device);
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     lv.clear();
   }
 
@@ -389,6 +593,7 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     using clock = std::chrono::steady_clock;
     const auto t_begin = clock::now();
     fine = h;
+    fine_epoch = h->values_epoch;
     value_bytes = (int)sizeof(V);
     hipStream_t st = nullptr;
     int rc;
@@ -398,11 +603,21 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     amg_lower(n, rowptr, colind, values, cur);
     std::vector<int> agg;
     std::vector<double> w, inv;
+    AmgFrozen frozen;
+    size_t longest = 0;
     for (int l = 0;; ++l) {
       lv.emplace_back(new Level());
       Level &L = *lv.back();
       L.n = cur.n;
       L.nnz = cur.nnz();
+      longest = std::max(longest, (size_t)L.nnz);
+      if (refreshable && l == 0) {
+        AmgList li;
+        amg_lower_lists(n, rowptr, colind, li);
+        nnz_caller = n > 0 ? rowptr[n] : 0;
+        if ((rc = L.lptr.upload(li.ptr.data(), li.ptr.size() * sizeof(int))) || (rc = L.lidx.upload(li.idx.data(), li.idx.size() * sizeof(int))))
+          return rc;
+      }
       long long bad = 0;
       std::vector<double> diag;
       if ((bad = amg_diagonal(cur, diag)))
@@ -420,13 +635,14 @@ template <typename V> struct Amg : cfs_hip_amg_s {
         const auto t0 = clock::now();
         if ((rc = mk(cur.n, L.rp.data(), L.ci.data(), L.va.data(), flags, &L.h))) return rc;
         L.owned = true;
+        if (refreshable && (rc = L.vdev.upload(L.va.data(), L.va.size() * sizeof(V)))) return rc;
         handles_seconds += std::chrono::duration<double>(clock::now() - t0).count();
       }
       // how the hierarchy goes on
       bool last = cur.n <= coarse_max;
       L.kind = last ? AMG_DENSE : AMG_MULTIGRID;
       if (!last) {
-        if (amg_coarsen(cur, passes, agg, w, next, &bad)) return cfs_rt::set_err(CFS_HIP_ERR_INTERNAL, "amg_create: the diagonal changed");
+        if (amg_coarsen(cur, passes, agg, w, next, &bad, refreshable ? &frozen : nullptr)) return cfs_rt::set_err(CFS_HIP_ERR_INTERNAL, "amg_create: the diagonal changed");
         if ((double)next.n > 0.9 * (double)cur.n || l + 1 == CFS_HIP_AMG_MAX_LEVELS) {
           last = true;
           L.kind = cur.n <= CFS_HIP_AMG_MAX_COARSE ? AMG_DENSE : AMG_SMOOTHER;
@@ -441,11 +657,27 @@ template <typename V> struct Amg : cfs_hip_amg_s {
         std::vector<V> iv(inv.size());
         for (size_t k = 0; k < inv.size(); ++k) iv[k] = (V)inv[k];
         if ((rc = L.inv.upload(iv.data(), iv.size() * sizeof(V)))) return rc;
+        if (refreshable) L.dense.n = cur.n, L.dense.rp = cur.rp, L.dense.ci = cur.ci;
       } else {
         if ((rc = setup_smoother(L, st))) return rc;
       }
       if (l > 0 && ((rc = L.r.alloc((size_t)L.n * sizeof(V) + 64)) || (rc = L.z.alloc((size_t)L.n * sizeof(V) + 64)))) return rc;
       if (last) break;
+      if (refreshable) { // the lists a refresh evaluates at this level
+        if (frozen.overflow())
+          return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "amg_create_refreshable: the contributions of a round of level " +
+                                                              std::to_string(l) + " exceed the 32-bit indices of the lists");
+        if ((rc = L.fdiag.upload(frozen.diag.data(), frozen.diag.size() * sizeof(int))) ||
+            (rc = L.frow.upload(frozen.row.data(), frozen.row.size() * sizeof(int))) ||
+            (rc = L.fcol.upload(cur.ci.data(), cur.ci.size() * sizeof(int))))
+          return rc;
+        for (int p = 0; p < passes; ++p) {
+          const AmgList &r = frozen.rounds[p];
+          L.rout[p] = r.entries();
+          if ((rc = L.rptr[p].upload(r.ptr.data(), r.ptr.size() * sizeof(int))) || (rc = L.ridx[p].upload(r.idx.data(), r.idx.size() * sizeof(int))))
+            return rc;
+        }
+      }
       // the transfer to the next level
       L.nc = next.n;
       std::vector<int> ptr((size_t)next.n + 1, 0), idx((size_t)cur.n);
@@ -463,8 +695,149 @@ template <typename V> struct Amg : cfs_hip_amg_s {
       for (double &v : next.va) v = (double)(V)v; // the next level is what its handle will hold
       cur = std::move(next);
     }
+    if (refreshable) {
+      for (int k = 0; k < 2; ++k)
+        if ((rc = rbuf[k].alloc(longest * sizeof(double) + 64))) return rc;
+      if ((rc = w64.alloc((size_t)n * sizeof(double) + 64)) || (rc = alloc_vectors<V>(n, {&pw})) || (rc = rpart.alloc(P_COUNT + 1, st)) ||
+          (rc = rlpart.alloc(L_COUNT, st)))
+        return rc;
+      for (size_t l = 1; l < lv.size(); ++l) value_map_bytes += 4 * lv[l]->nnz;
+    }
     HIPCHK(hipDeviceSynchronize());
     setup_seconds = std::chrono::duration<double>(clock::now() - t_begin).count();
+    return 0;
+  }
+
+  long long map_bytes() const {
+    long long b = (long long)(rbuf[0].bytes + rbuf[1].bytes + w64.bytes + pw.bytes + rpart.buf.bytes + rlpart.buf.bytes) + value_map_bytes;
+    for (const auto &L : lv) b += (long long)L->map_bytes();
+    return b;
+  }
+
+  // cfs_hip_amg_update_values_*: the arithmetic of build() with the matchings frozen, on `st`.  vals: the caller's
+  // values[] on the device.  Returns when the hierarchy is complete; on an error the object is stale
+  int refresh(const V *vals, hipStream_t st) {
+    using clock = std::chrono::steady_clock;
+    const auto t_begin = clock::now();
+    const int nl = (int)lv.size();
+    stale = true;
+    rpart.st = st;
+    if (ev.empty()) {
+      ev.resize((size_t)4 * nl);
+      for (hipEvent_t &e : ev) HIPCHK(hipEventCreate(&e));
+    }
+    // X: what the next kernel reads -- the level's lower-triangle array in fp64, B (scaled in place), a round's output;
+    // Y: what a round writes.  They change places after every round
+    double *X = (double *)rbuf[0].p, *Y = (double *)rbuf[1].p, *bad_dev = rpart.dev() + (size_t)P_COUNT * kGrid;
+    double dense_seconds = 0.0;
+    int rc, done = 0;
+    for (int l = 0; l < nl; ++l) {
+      Level &L = *lv[l];
+      HIPCHK(hipEventRecord(ev[4 * l + 0], st));
+      if (l == 0 && L.nnz > 0)
+        hipLaunchKernelGGL((amg_gather_sum_kernel<V, V, false>), dim3(kGrid), dim3(kThreads), 0, st, X, (V *)nullptr, vals,
+                           (const int *)L.lptr.p, (const int *)L.lidx.p, L.nnz);
+      if ((rc = rpart.zero())) return rc;
+      if (L.kind == AMG_MULTIGRID) {
+        Level &C = *lv[l + 1];
+        hipLaunchKernelGGL((amg_weight_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (double *)w64.p, (V *)L.w.p, (const double *)X,
+                           (const int *)L.fdiag.p, (long long)L.n, bad_dev);
+        hipLaunchKernelGGL(amg_scale_kernel, dim3(kGrid), dim3(kThreads), 0, st, X, (const double *)w64.p, (const int *)L.frow.p,
+                           (const int *)L.fcol.p, L.nnz);
+        for (int p = 0; p < passes; ++p) {
+          const int *ptr = (const int *)L.rptr[p].p, *idx = (const int *)L.ridx[p].p;
+          if (p + 1 < passes)
+            hipLaunchKernelGGL((amg_gather_sum_kernel<double, V, false>), dim3(kGrid), dim3(kThreads), 0, st, Y, (V *)nullptr,
+                               (const double *)X, ptr, idx, L.rout[p]);
+          else
+            hipLaunchKernelGGL((amg_gather_sum_kernel<double, V, true>), dim3(kGrid), dim3(kThreads), 0, st, Y, (V *)C.vdev.p,
+                               (const double *)X, ptr, idx, L.rout[p]);
+          std::swap(X, Y); // (what was written is the next round's source, and after the last round the next level's array)
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[4 * l + 1], st));
+        C.va_stale = true;
+        if ((rc = C.h->update_values(C.vdev.p, C.nnz, st))) return rc;
+      } else {
+        HIPCHK(hipEventRecord(ev[4 * l + 1], st));
+      }
+      HIPCHK(hipEventRecord(ev[4 * l + 2], st));
+      if (L.kind == AMG_DENSE) {
+        HIPCHK(hipEventRecord(ev[4 * l + 3], st));
+        const auto t0 = clock::now();
+        L.dense.va.resize((size_t)L.nnz);
+        HIPCHK(hipMemcpyAsync(L.dense.va.data(), X, (size_t)L.nnz * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        std::vector<double> inv;
+        const int piv = amg_dense_inverse(L.dense, inv);
+        if (piv >= 0)
+          return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_update_values: the matrix of level " + std::to_string(l) + " (" + std::to_string(L.n) +
+                                                      " rows) is not positive definite: pivot " + std::to_string(piv) +
+                                                      " of its Cholesky factorisation is zero, negative or not finite");
+        std::vector<V> iv(inv.size());
+        for (size_t k = 0; k < inv.size(); ++k) iv[k] = (V)inv[k];
+        HIPCHK(hipMemcpyAsync(L.inv.p, iv.data(), iv.size() * sizeof(V), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        dense_seconds = std::chrono::duration<double>(clock::now() - t0).count();
+      } else {
+        rc = refresh_smoother(L, l, st); // (the level's host look)
+        HIPCHK(hipEventRecord(ev[4 * l + 3], st));
+        if (rc) return rc;
+      }
+      done = l + 1;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < AMG_T_COUNT; ++k) split[k] = 0.0;
+    for (int l = 0; l < done; ++l)
+      for (int k = 0; k < 3; ++k) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, ev[4 * l + k], ev[4 * l + k + 1]));
+        split[k] += 1e-3 * (double)ms;
+      }
+    split[AMG_T_DENSE] = dense_seconds;
+    stale = false;
+    refreshes += 1;
+    last_seconds = std::chrono::duration<double>(clock::now() - t_begin).count();
+    return 0;
+  }
+
+  // Level 0 is the caller's handle, and the caller pours its values: dinv and the bound of level 0 are made from what h
+  // holds during the refresh and, when h has been poured since (cfs_hip_sym_update_values_* AFTER the refresh), once
+  // more by the next apply or pcg, on its stream (info() only reports: until then it shows the bound of the refresh)
+  int follow_fine(hipStream_t st) {
+    if (!refreshable || lv.empty() || lv[0]->kind == AMG_DENSE || fine_epoch == fine->values_epoch) return 0;
+    rpart.st = st;
+    int rc = rpart.zero();
+    if (!rc) rc = refresh_smoother(*lv[0], 0, st);
+    if (rc) {
+      stale = true;
+      return rc;
+    }
+    return 0;
+  }
+
+  // the numbers of setup_smoother again, into the buffers it allocated: dinv from the level's handle, the bound, the pairs
+  int refresh_smoother(Level &L, int l, hipStream_t st) {
+    const long long n = L.n;
+    double est = 0.0;
+    int rc;
+    if (l == 0) fine_epoch = fine->values_epoch;
+    if ((rc = L.h->diagonal(L.pre.dbuf.p, st))) return rc;
+    hipLaunchKernelGGL((cg_dinv_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)L.pre.dbuf.p, n, rpart.dev());
+    if ((rc = cheb_power<V, 1>(L.h, (V *)L.d.p, (V *)L.t.p, (V *)pw.p, (const V *)nullptr, n, 16, rlpart, L.pre.minv(), 0LL, &est, st)) ||
+        (rc = rpart.fetch()))
+      return rc;
+    const double bad = std::max(rpart.sum(P_BAD), L.kind == AMG_MULTIGRID ? rpart.sum(P_COUNT) : 0.0);
+    if (bad != 0.0)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_update_values: Jacobi needs a positive diagonal, " + std::to_string((long long)bad) +
+                                                  " of " + std::to_string(n) + " entries are zero, negative or not finite (level " +
+                                                  std::to_string(l) + ")");
+    if (!(est > 0.0) || est * 0.0 != 0.0)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_update_values: the power method gave no positive estimate of lambda_max(D^-1 A) on a level of " +
+                                                  std::to_string(n) + " rows (" + std::to_string(est) + ")");
+    L.lmax = 1.1 * est;
+    L.lmin = L.lmax / ratio;
+    cheb_coeffs(degree, L.lmin, L.lmax, &L.theta, L.c1, L.c2);
     return 0;
   }
 
@@ -516,7 +889,10 @@ template <typename V> struct Amg : cfs_hip_amg_s {
   }
 
   int apply(void *z_dev, const void *r_dev, hipStream_t st) override {
-    int rc = cycle(0, (V *)z_dev, (const V *)r_dev, (const int *)cnt.p, st);
+    if (stale) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_apply: the last refresh failed");
+    int rc = follow_fine(st);
+    if (rc) return rc;
+    rc = cycle(0, (V *)z_dev, (const V *)r_dev, (const int *)cnt.p, st);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;
@@ -547,7 +923,7 @@ template <typename V> struct Amg : cfs_hip_amg_s {
         bytes += s.device_bytes;
       }
     }
-    o->device_bytes = bytes;
+    o->device_bytes = bytes + (refreshable ? map_bytes() - value_map_bytes : 0); // (the handles' stats count their maps)
     return 0;
   }
 
@@ -566,7 +942,12 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     if (level < 1 || level >= (int)lv.size())
       return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_level_matrix: level " + std::to_string(level) + " is not one of 1 .. " +
                                                   std::to_string((int)lv.size() - 1) + " (level 0 is the caller's matrix)");
-    const Level &L = *lv[level];
+    Level &L = *lv[level];
+    if (values && L.va_stale) { // a refresh wrote the values on the device: read them back at the first look
+      cfs_rt::DeviceGuard g(device);
+      HIPCHK(hipMemcpy(L.va.data(), L.vdev.p, L.va.size() * sizeof(V), hipMemcpyDeviceToHost));
+      L.va_stale = false;
+    }
     if (rowptr) memcpy(rowptr, L.rp.data(), L.rp.size() * sizeof(int));
     if (colind) memcpy(colind, L.ci.data(), L.ci.size() * sizeof(int));
     if (values) memcpy(values, L.va.data(), L.va.size() * sizeof(V));
@@ -581,11 +962,36 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     return 0;
   }
 
+  int update_check(long long nnz) override {
+    if (!refreshable)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_update_values: the hierarchy was made by cfs_hip_amg_create_*, not by "
+                                              "cfs_hip_amg_create_refreshable_*");
+    if (nnz != nnz_caller)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_update_values: " + std::to_string(nnz) + " values, the CSR at create had " +
+                                                  std::to_string(nnz_caller));
+    return 0;
+  }
+  int update_values(const void *values_dev, long long nnz, hipStream_t st) override {
+    if (int rc = update_check(nnz)) return rc;
+    return refresh((const V *)values_dev, st);
+  }
+
+  int refresh_info(long long *mb, int *count, double *seconds, double *parts) override {
+    if (mb) *mb = refreshable ? map_bytes() : 0;
+    if (count) *count = refreshes;
+    if (seconds) *seconds = last_seconds;
+    if (parts)
+      for (int k = 0; k < AMG_T_COUNT; ++k) parts[k] = split[k];
+    return 0;
+  }
+
   // cfs_hip_sym_pcg_amg.  u: in = first guess, out = solution
   int pcg(void *u_dev, const void *b_dev, double tol, int maxiter, int *iterations, double *relres, hipStream_t st) override {
+    if (stale) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg_amg: the last refresh failed");
     Pcg<V, cfs_hip_sym_s> s;
     cfs_rt::DevBuf zbuf;
     int rc;
+    if ((rc = follow_fine(st))) return rc;
     if ((rc = s.begin("pcg_amg", fine, u_dev, b_dev, tol, maxiter, st)) || (rc = alloc_vectors<V>(s.n, {&zbuf})) || (rc = s.first_residual()))
       return rc;
     V *u = s.u, *r = s.r, *p = s.p, *q = s.q, *z = (V *)zbuf.p;

@@ -372,12 +372,17 @@ int cheb_chain(Handle *h, V *z, V *d, V *t, const V *r, long long n, int degree,
 }
 
 // `steps` power steps on M^-1 A from the start vector v0 (nullptr: that of cfs_hip_sym_eigs); v, t, w: n values each.
-// One host look, after the last step.  lpart: the caller's, not yet allocated (it lives as long as the caller's buffers)
+// One host look, after the last step.  lpart: the caller's (it lives as long as the caller's buffers), allocated here
+// unless an earlier call has done so
 template <typename V, int BS, class Handle>
 int cheb_power(Handle *h, V *v, V *t, V *w, const V *v0, long long n, int steps, Slots &lpart, const V *minv, long long nb,
                double *estimate, hipStream_t st) {
   int rc;
-  if ((rc = lpart.alloc(L_COUNT, st)) || (rc = lpart.zero())) return rc;
+  if (lpart.buf.p && lpart.host.size() == (size_t)L_COUNT * kGrid)
+    lpart.st = st;
+  else if ((rc = lpart.alloc(L_COUNT, st)))
+    return rc;
+  if ((rc = lpart.zero())) return rc;
   hipLaunchKernelGGL((cheb_lmax_start_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, v, v0, n);
   for (int s = 0; s < steps; ++s) {
     if ((rc = h->spmv_local(t, v, nullptr, st))) return rc;

@@ -390,13 +390,16 @@ class SymMatrix:
                                                         _stream_ptr(stream)))
         return est.value
 
-    def amg(self, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512):
+    def amg(self, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512, refreshable=False):
         """the aggregation multigrid hierarchy of this matrix (cfs_hip_amg_create_*), an Amg: rowptr, colind, values
         are the CSR the handle was created from (only entries with col <= row are read; the caller vouches that it is
         this handle's matrix).  passes 1 .. 3 rounds of pairwise matching per level, degree 1 .. 4 of the Chebyshev
         smoother, ratio = lmax / lmin of its interval, coarse_max <= 1024 the largest dense last level.  A whole-matrix
-        handle on one device.  The hierarchy holds the values of now: after update_values() make a new one."""
-        return Amg(self, rowptr, colind, values, passes=passes, degree=degree, ratio=ratio, coarse_max=coarse_max)
+        handle on one device.  The hierarchy holds the values of now: to follow update_values() make it with
+        refreshable=True (cfs_hip_amg_create_refreshable_*; the matrix needs FLAG_KEEP_VALUE_MAP) and call
+        Amg.update_values() with the same array."""
+        return Amg(self, rowptr, colind, values, passes=passes, degree=degree, ratio=ratio, coarse_max=coarse_max,
+                   refreshable=refreshable)
 
     def pcg_amg(self, u, b, amg, tol=1e-10, maxiter=1000, check_every=1, stream=None):
         """PCG with one V-cycle of `amg` (self.amg(...)) as the preconditioner (cfs_hip_sym_pcg_amg): like
@@ -592,7 +595,7 @@ class Amg:
     """The aggregation multigrid hierarchy of a SymMatrix (cfs_hip_amg_create_*) and its V-cycle.  Keeps a reference
     to its matrix, which must stay open for as long as the hierarchy is used."""
 
-    def __init__(self, A, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512):
+    def __init__(self, A, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512, refreshable=False):
         lib = _lib.load()
         rowptr, colind = _np_i32(rowptr), _np_i32(colind)
         values = np.ascontiguousarray(values, dtype=A.dtype)
@@ -600,8 +603,9 @@ class Amg:
         self._a = C.c_void_p()
         opt = _lib.AmgOptions(int(passes), int(degree), int(coarse_max), 0, float(ratio))
         suf = "f64" if self.dtype == np.float64 else "f32"
-        _lib.check(getattr(lib, "cfs_hip_amg_create_" + suf)(A._h, A.n, rowptr.ctypes.data, colind.ctypes.data,
-                                                             values.ctypes.data, C.byref(opt), C.byref(self._a)))
+        self.refreshable = bool(refreshable)
+        create = getattr(lib, "cfs_hip_amg_create_" + ("refreshable_" if refreshable else "") + suf)
+        _lib.check(create(A._h, A.n, rowptr.ctypes.data, colind.ctypes.data, values.ctypes.data, C.byref(opt), C.byref(self._a)))
 
     def info(self):
         """dict: levels, the options used, device_bytes, setup_seconds (of which handles_seconds for the create path
@@ -610,6 +614,32 @@ class Amg:
         out = _lib.AmgInfo()
         _lib.check(_lib.load().cfs_hip_amg_info(self._a, C.byref(out)))
         return out.asdict()
+
+    def update_values(self, values):
+        """new values, same sparsity pattern, for a refreshable hierarchy (cfs_hip_amg_update_values_*): a numpy array or
+        a contiguous device tensor of the hierarchy's value type, in the order of the CSR given at construction.  The
+        aggregates stay; every level's weights, matrix, bounds and the dense inverse are made again on the device."""
+        suf = "f64" if self.dtype == np.float64 else "f32"
+        if isinstance(values, np.ndarray):
+            values = np.ascontiguousarray(values, dtype=self.dtype)
+            ptr, cnt = values.ctypes.data, values.size
+        else:
+            if values.element_size() != np.dtype(self.dtype).itemsize or not values.is_floating_point():
+                raise TypeError(f"the hierarchy holds {np.dtype(self.dtype).name} values, the tensor is {values.dtype}")
+            if not values.is_contiguous():
+                raise ValueError("a device tensor of values must be contiguous")
+            ptr, cnt = values.data_ptr(), values.numel()
+        _lib.check(getattr(_lib.load(), "cfs_hip_amg_update_values_" + suf)(self._a, ptr, cnt))
+
+    def refresh_info(self):
+        """dict: map_bytes (the device bytes being refreshable adds), refreshes (successful ones), last_seconds, and
+        split_seconds of the last one: galerkin, pour, power, dense"""
+        mb, cnt, sec, split = C.c_longlong(), C.c_int(), C.c_double(), (C.c_double * 4)()
+        lib = _lib.load()
+        _lib.check(lib.cfs_hip_amg_refresh_info(self._a, C.byref(mb), C.byref(cnt), C.byref(sec)))
+        _lib.check(lib.cfs_hip_debug_amg_refresh_split(self._a, split))
+        return dict(map_bytes=mb.value, refreshes=cnt.value, last_seconds=sec.value,
+                    split_seconds=dict(zip(("galerkin", "pour", "power", "dense"), list(split))))
 
     def aggregates(self, level):
         """(agg, w) of a level that has a coarser one, as the device holds them: the aggregate of every row and the
@@ -667,6 +697,21 @@ def coarsen(n, rowptr, colind, values, passes=2):
                                                      agg.ctypes.data, w.ctypes.data, C.byref(nc), crp.ctypes.data, cci.ctypes.data,
                                                      cva.ctypes.data, cap, C.byref(nnz)))
     return agg, w, (nc.value, crp[:nc.value + 1].copy(), cci[:nnz.value].copy(), cva[:nnz.value].copy())
+
+
+def recoarsen(n, rowptr, colind, values_at_create, values_new, passes=2):
+    """host only: one level of a refresh (cfs_hip_debug_amg_recoarsen) -- the matchings of values_at_create, frozen, the
+    sums evaluated for values_new in the order the kernels add.  Returns (w, coarse values) in fp64, the values in the
+    pattern coarsen() returns for values_at_create"""
+    rowptr, colind = _np_i32(rowptr), _np_i32(colind)
+    old, new = (np.ascontiguousarray(v, dtype=np.float64) for v in (values_at_create, values_new))
+    cap = int(rowptr[n]) if n > 0 else 0
+    assert old.size == new.size == cap
+    w, cva = np.zeros(n, np.float64), np.zeros(max(cap, 1), np.float64)
+    nnz = C.c_longlong()
+    _lib.check(_lib.load().cfs_hip_debug_amg_recoarsen(n, rowptr.ctypes.data, colind.ctypes.data, old.ctypes.data, new.ctypes.data,
+                                                       int(passes), w.ctypes.data, cva.ctypes.data, cap, C.byref(nnz)))
+    return w, cva[:nnz.value].copy()
 
 
 class MixedSym:

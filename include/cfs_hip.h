@@ -526,8 +526,9 @@ typedef struct {
 } cfs_hip_amg_info_t;
 /* The hierarchy of the matrix behind h.  h: a whole-matrix handle on one device of the matching value type and n (a
  * shard or a multi-device handle: CFS_HIP_ERR_UNSUPPORTED); it must outlive the object, and the caller vouches that the
- * CSR is h's matrix.  THE HIERARCHY HOLDS THE VALUES AT CREATE: after cfs_hip_sym_update_values_* the caller destroys it
- * and creates a new one.  CFS_HIP_ERR_ARG, before any device work and in this order: a null pointer (h, rowptr, out;
+ * CSR is h's matrix.  THE HIERARCHY HOLDS THE VALUES AT CREATE: to follow cfs_hip_sym_update_values_* make it with
+ * cfs_hip_amg_create_refreshable_* and call cfs_hip_amg_update_values_* (below).
+ * CFS_HIP_ERR_ARG, before any device work and in this order: a null pointer (h, rowptr, out;
  * colind / values when there are entries), passes outside 1 .. 3, degree outside 1 .. 4, a ratio that is not finite and
  * > 1, coarse_max outside 1 .. CFS_HIP_AMG_MAX_COARSE (0 is the default in each).  Then, from the handle: a shard or a
  * multi-device handle (CFS_HIP_ERR_UNSUPPORTED), a value type or an n different from h's (CFS_HIP_ERR_ARG).  A diagonal entry of any level that is zero, missing, negative or not finite: CFS_HIP_ERR_ARG in
@@ -538,6 +539,60 @@ int cfs_hip_amg_create_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int 
 int cfs_hip_amg_create_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
                            const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
 int cfs_hip_amg_destroy(cfs_hip_amg_t a); /* NULL is allowed */
+/* ---- a hierarchy that follows cfs_hip_sym_update_values_*: the numeric re-set-up with the aggregates kept ---------
+ * cfs_hip_amg_create_refreshable_*: the arguments and rules of cfs_hip_amg_create_*, and the same hierarchy bit for
+ * bit; the level handles are created with CFS_HIP_FLAG_KEEP_VALUE_MAP and the object keeps, on the device, what a refresh
+ * evaluates (below).  In addition: a CFS_HIP_FLAG_DETERMINISTIC handle is CFS_HIP_ERR_UNSUPPORTED (its levels would
+ * be deterministic, and those refuse update_values), a level whose contributions per round exceed 32-bit indices
+ * CFS_HIP_ERR_UNSUPPORTED.
+ * cfs_hip_amg_create_* itself is unchanged, in behaviour and in the bytes it holds.
+ * cfs_hip_amg_update_values_*: `values` is the caller's full CSR value array in the order of the rowptr / colind given
+ * at create, nnz entries, host or device pointer, as for cfs_hip_sym_update_values_*.  The call runs on the library's
+ * stream of the handle's device and returns when the hierarchy is complete: a cfs_hip_sym_pcg_amg or cfs_hip_amg_apply
+ * enqueued afterwards, on any stream, sees the new one.  THE REFRESH is the arithmetic of create with the matchings of
+ * every round FROZEN, in the same order of operations, in HIP kernels over lists built at create:
+ *   level 0: the lower triangle of `values`, duplicates summed in the order amg_lower reads them (gather-sum lists);
+ *   per level: w_i = 1 / sqrt(a_ii) in fp64 ON THE DEVICE (division and sqrt are correctly rounded: the same bits as
+ *   the host's at create), b_k = (w_row a_k) w_col per stored entry, then per round every entry of Q^T B Q as the fp64
+ *   sum of its contributions in the order create adds them -- the members of the aggregate ascending, each member's
+ *   row of the full B by ascending column, an entry above the diagonal read from its mirror (amg_gather_sum_kernel,
+ *   one thread per output entry); the last round rounds to the value type;  the values are poured into the next
+ *   level's handle through its update_values;  dinv, the power method (16 steps, the fixed start vector),
+ *   lmax = 1.1 x the estimate, lmin and the coefficient pairs are made again per level;  the dense last level is
+ *   brought to the host, inverted by the code of create and uploaded.
+ * If a fresh create on the new values would choose the same aggregates, the refreshed hierarchy equals it in every
+ * bit of w, of every level matrix and of the dense inverse (lmax: within the run-to-run spread of the product's
+ * atomics).  agg, every pattern, the schedules of the level handles and the options stay.  Level 0 is h, not a
+ * copy: the caller pours h's own array into h with cfs_hip_sym_update_values_*, before or after this call and before
+ * the next cycle, and vouches, as at create, that the two arrays are one matrix.  Level 0's dinv and bound are taken
+ * from h: they are made during the refresh from what h holds then and, when h has been poured since, once more by the
+ * next cfs_hip_amg_apply or cfs_hip_sym_pcg_amg, on its stream (pouring h first saves that second power method;
+ * cfs_hip_amg_info only reports, and until that cycle shows level 0's bound as the refresh made it).
+ * cfs_hip_amg_level_matrix reads a refreshed level's values back from the device at its first call after a refresh.
+ * CFS_HIP_ERR_ARG, the hierarchy untouched: a null argument, an object of cfs_hip_amg_create_*, the other value
+ * type's entry point, another nnz -- these before any device work -- or `values` on another device.
+ * FAILURE INSIDE A REFRESH -- a diagonal entry of a level that is zero, negative or not finite (counted on the device,
+ * read at the level's host look), a power method without a positive estimate, a dense level that is not positive
+ * definite: CFS_HIP_ERR_ARG in the words of create.  The object is then STALE: cfs_hip_amg_apply and
+ * cfs_hip_sym_pcg_amg return CFS_HIP_ERR_ARG ("the last refresh failed") until a refresh succeeds; nothing is leaked
+ * and the object can be destroyed.
+ * cfs_hip_amg_refresh_info: *map_bytes = the device bytes the capability adds (the lists, two fp64 arrays of the
+ * longest level and the fp64 weights, kept between calls, the levels' values on the device, and for each level
+ * handle's value map 4 bytes per stored entry of the level -- that last part an ESTIMATE: the handle's own count,
+ * which covers the padding of its format, is inside its device bytes), also counted in
+ * cfs_hip_amg_info().device_bytes (there with the handles' own count of their maps); 0 for an object of
+ * cfs_hip_amg_create_*.  *refreshes = successful refreshes, *last_seconds = the wall time of the last one.  Any of the
+ * three may be NULL.  cfs_hip_debug_amg_refresh_split: seconds[4] of the last successful refresh -- the Galerkin
+ * kernels (gather, weights, scaling, rounds), the pours, dinv + power method with its host look (all three between
+ * events on the stream), the dense inverse with its two copies (host clock).                                        */
+int cfs_hip_amg_create_refreshable_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
+                                       const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_create_refreshable_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
+                                       const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_update_values_f64(cfs_hip_amg_t a, const double *values, long long nnz);
+int cfs_hip_amg_update_values_f32(cfs_hip_amg_t a, const float *values, long long nnz);
+int cfs_hip_amg_refresh_info(cfs_hip_amg_t a, long long *map_bytes, int *refreshes, double *last_seconds);
+int cfs_hip_debug_amg_refresh_split(cfs_hip_amg_t a, double *seconds);
 /* The readers: what the launches read.  info: the level count and per level n, the stored nonzeros, the bounds and
  * the kind, the options used, the device bytes held and the set-up seconds.  level_aggregates (level < levels - 1):
  * agg[n_l], the aggregate of every row, and w[n_l] in the value type, both copied back from the device (either may be
@@ -574,6 +629,14 @@ int cfs_hip_sym_pcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const voi
 int cfs_hip_debug_amg_coarsen(int n, const int *rowptr, const int *colind, const double *values, int passes,
                               int *agg, double *w, int *nc, int *c_rowptr, int *c_colind, double *c_values,
                               long long capacity, long long *c_nnz);
+/* Host only, no device work: one level of a REFRESH.  The lists are built from values_at_create by the code
+ * cfs_hip_amg_create_refreshable_* uses (the matchings of that array, frozen), then evaluated for values_new -- the
+ * same CSR pattern -- in a host loop that adds in the order the kernels add.  Out: w[n] (fp64) and the coarse values in
+ * the pattern cfs_hip_debug_amg_coarsen returns for values_at_create, room for `capacity`, *c_nnz written (too little
+ * room: CFS_HIP_ERR_ARG with *c_nnz set).  A diagonal of either array that is not positive: CFS_HIP_ERR_ARG.      */
+int cfs_hip_debug_amg_recoarsen(int n, const int *rowptr, const int *colind, const double *values_at_create,
+                                const double *values_new, int passes, double *w, double *c_values, long long capacity,
+                                long long *c_nnz);
 /* MINRES (Paige & Saunders) for (A - shift I) u = b: A symmetric, possibly INDEFINITE, or singular with a
  * consistent b -- saddle-point matrices (a zero diagonal block), shifted operators, mixed-sign diagonals, on
  * which the conjugate gradients above promise nothing (on [[0, K], [K, 0]] with b = [f; 0] their first p.q is

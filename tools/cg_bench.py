@@ -21,7 +21,14 @@ The multigrid-preconditioned PCG (cfs_hip_sym_pcg_amg, --only-amg) sits beside t
 PCG of the same build: solves down to TOL at smoother degrees 1 and 2 with the default hierarchy, interleaved, AMG_ROUNDS rounds,
 the best wall time of each; iterations, ms per solve, and per hierarchy the levels, the device bytes and the set-up seconds (the
 whole create, and of it the create path of the level handles).  The hierarchy is built once, outside the timed solves.
-usage: python tools/cg_bench.py [--only-cheb | --only-amg] [matrix[:scale] | lap2dNXxNY ...]"""
+With --only-amg also the REFRESH of a hierarchy (cfs_hip_amg_update_values_*): a refreshable hierarchy of the default options,
+its set-up seconds (the number to beat: the create path is unchanged code) and device bytes beside map_bytes, then one warm-up
+refresh and REFRESH_TIMED timed ones alternating between two value arrays on the device (the second: every diagonal entry times
+1 + uniform(0, 1)), the host clock around the call, which ends in a synchronise; the handle is poured first, outside the timed
+call, and its pour timed by itself.  Minimum and median, the split of the fastest one (Galerkin kernels, pours, dinv + power
+methods, dense inverse) and, with handle and hierarchy refreshed to the SECOND array, the iterations of a solve beside those
+of a fresh create on that array.  --only-amg-refresh: that part alone, without the solves above.
+usage: python tools/cg_bench.py [--only-cheb | --only-amg | --only-amg-refresh] [matrix[:scale] | lap2dNXxNY ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -39,7 +46,10 @@ HAVE_MINRES = hasattr(cfs.load(), "cfs_hip_sym_minres")
 HAVE_CHEB = hasattr(cfs.load(), "cfs_hip_sym_pcg_cheb")
 ONLY_CHEB = "--only-cheb" in sys.argv
 HAVE_AMG = hasattr(cfs.load(), "cfs_hip_sym_pcg_amg")
-ONLY_AMG = "--only-amg" in sys.argv
+ONLY_REFRESH = "--only-amg-refresh" in sys.argv
+ONLY_AMG = "--only-amg" in sys.argv or ONLY_REFRESH
+HAVE_REFRESH = hasattr(cfs.load(), "cfs_hip_amg_update_values_f64")
+REFRESH_TIMED = 5
 AMG_DEGREES, AMG_ROUNDS = (1, 2), 3
 CHEB_DEGREES, CHEB_ROUNDS = (2, 4), 3
 BLOCK, TOL, MAXITER = 3, 1e-8, 5000
@@ -85,8 +95,53 @@ def cheb_section(A, b, res):
                 res[f"cheb{m}_{tag}{suffix}_over_pcg_{tag}_time"] = round(best[f"cheb{m}_{tag}{suffix}"][0] / best[f"pcg_{tag}"][0], 4)
 
 
+def refresh_section(A, b, res, rp, ci, va):
+    """a refreshable hierarchy followed through REFRESH_TIMED + 1 value updates; A was made with FLAG_KEEP_VALUE_MAP"""
+    n = A.n
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    vb = va.copy()
+    d = rows == ci
+    vb[d] *= 1.0 + np.random.default_rng(7).uniform(0.0, 1.0, n)[rows[d]]
+    dev = [torch.from_numpy(va).cuda(), torch.from_numpy(vb).cuda()]
+    G = A.amg(rp, ci, va, refreshable=True)
+    inf = G.info()
+    res["refresh_levels"], res["refresh_kinds"] = inf["n"], inf["kind"]
+    res["refresh_create_setup_seconds"] = round(inf["setup_seconds"], 4)
+    res["refresh_create_setup_seconds_level_handles"] = round(inf["handles_seconds"], 4)
+    res["refresh_device_bytes"], res["refresh_map_bytes"] = inf["device_bytes"], G.refresh_info()["map_bytes"]
+    times, pours, splits = [], [], []
+    for k in range(REFRESH_TIMED + 1):  # (the first one is the warm-up)
+        v = dev[(k + 1) % 2]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        A.update_values(v)
+        t1 = time.perf_counter()
+        G.update_values(v)
+        t2 = time.perf_counter()
+        if k > 0:
+            pours.append(t1 - t0), times.append(t2 - t1), splits.append(G.refresh_info()["split_seconds"])
+    res["refresh_ms_min"], res["refresh_ms_median"] = round(min(times) * 1e3, 3), round(float(np.median(times)) * 1e3, 3)
+    res["refresh_handle_pour_ms_min"] = round(min(pours) * 1e3, 3)
+    res["refresh_split_ms"] = {k: round(v * 1e3, 3) for k, v in splits[int(np.argmin(times))].items()}
+    res["refresh_over_create"] = round(min(times) / inf["setup_seconds"], 5)
+    # what frozen aggregates cost: handle and hierarchy on the PERTURBED array vb, against a fresh create on vb
+    A.update_values(dev[1])
+    G.update_values(dev[1])
+    it, rel = pcg_amg_native(A, b, G, tol=TOL, maxiter=MAXITER)[1:3]
+    F = A.amg(rp, ci, vb)
+    res["refresh_solve_values"] = "perturbed: every diagonal entry times 1 + uniform(0, 1), default_rng(7)"
+    itf, relf = pcg_amg_native(A, b, F, tol=TOL, maxiter=MAXITER)[1:3]
+    res.update(refresh_solve_iterations=it, refresh_solve_relres=rel, fresh_create_solve_iterations=itf, fresh_create_solve_relres=relf,
+               fresh_create_setup_seconds=round(F.info()["setup_seconds"], 4))
+    F.close()
+    G.close()
+    A.update_values(dev[0])
+
+
 def amg_section(A, b, res, rp, ci, va):
     """solves down to TOL: Jacobi PCG, Chebyshev degree 4 on Jacobi, and the V-cycle at AMG_DEGREES, interleaved"""
+    if ONLY_REFRESH:
+        return refresh_section(A, b, res, rp, ci, va)
     loops = {"pcg_jacobi": lambda: pcg_native(A, b, precond="jacobi", tol=TOL, maxiter=MAXITER, check_every=16)[1:3],
              "cheb4_jacobi": lambda: pcg_cheb_native(A, b, degree=4, tol=TOL, maxiter=MAXITER, check_every=16)[1:3]}
     hierarchies = {}
@@ -119,6 +174,8 @@ def amg_section(A, b, res, rp, ci, va):
         res[f"amg{m}_over_pcg_jacobi_time"] = round(best[f"amg{m}"][0] / best["pcg_jacobi"][0], 4)
         res[f"amg{m}_over_cheb4_jacobi_time"] = round(best[f"amg{m}"][0] / best["cheb4_jacobi"][0], 4)
         hierarchies[m].close()
+    if ONLY_AMG and HAVE_REFRESH:
+        refresh_section(A, b, res, rp, ci, va)
 
 
 out = {}
@@ -133,7 +190,8 @@ for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ld
         n, rp, ci, va = L.shape[0], L.indptr.astype(np.int32), L.indices.astype(np.int32), L.data
     else:
         n, rp, ci, va, _ = synth.generate(name, float(sc or 1.0))
-    A = cfs.SymMatrix(n, rp, ci, va)
+    # (--only-amg: the refresh part pours new values into the handle)
+    A = cfs.SymMatrix(n, rp, ci, va, options=cfs.make_options(flags=cfs.FLAG_KEEP_VALUE_MAP) if ONLY_AMG and HAVE_REFRESH else None)
     b = torch.from_numpy(synth.make_x(n, 11)).cuda()
     y = torch.empty_like(b)
     for _ in range(50):
