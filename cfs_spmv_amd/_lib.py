@@ -66,6 +66,7 @@ class PlanFileInfo(C.Structure):
 
 
 AMG_MAX_LEVELS, AMG_MAX_COARSE = 16, 1024  # CFS_HIP_AMG_MAX_LEVELS, CFS_HIP_AMG_MAX_COARSE
+AMG_MATCHING_GREEDY, AMG_MATCHING_DOMINANT, AMG_MATCH_ROUNDS = 0, 1, 64  # CFS_HIP_AMG_MATCHING_*, CFS_HIP_AMG_MATCH_ROUNDS
 
 
 class AmgOptions(C.Structure):
@@ -97,7 +98,9 @@ SYMBOLS = [
     "cfs_hip_comm_allgather", "cfs_hip_comm_alltoallv", "cfs_hip_comm_wait_consumed", "cfs_hip_sym_num_gpus", "cfs_hip_sym_multi_set_xmode", "cfs_hip_sym_multi_set_exchange", "cfs_hip_sym_multi_exchange_info", "cfs_hip_sym_multi_devices", "cfs_hip_sym_balanced_splits", "cfs_hip_sym_destroy", "cfs_hip_sym_update_values_f64", "cfs_hip_sym_update_values_f32", "cfs_hip_sym_spmv",
     "cfs_hip_sym_spmv_async", "cfs_hip_sym_cg", "cfs_hip_sym_pcg", "cfs_hip_sym_diagonal_async", "cfs_hip_sym_block_diagonal_async",
     "cfs_hip_sym_pcg_block", "cfs_hip_sym_block_inverse_async", "cfs_hip_sym_pcg_mixed", "cfs_hip_sym_minres", "cfs_hip_sym_pcg_cheb", "cfs_hip_sym_cheb_apply", "cfs_hip_sym_precond_lmax", "cfs_hip_debug_cheb_coeffs",
-    "cfs_hip_amg_create_f64", "cfs_hip_amg_create_f32", "cfs_hip_amg_destroy", "cfs_hip_amg_info", "cfs_hip_amg_level_aggregates", "cfs_hip_amg_level_matrix", "cfs_hip_amg_coarse_inverse", "cfs_hip_amg_apply", "cfs_hip_sym_pcg_amg", "cfs_hip_debug_amg_coarsen", "cfs_hip_amg_create_refreshable_f64", "cfs_hip_amg_create_refreshable_f32", "cfs_hip_amg_update_values_f64", "cfs_hip_amg_update_values_f32", "cfs_hip_amg_refresh_info", "cfs_hip_debug_amg_refresh_split", "cfs_hip_debug_amg_recoarsen", "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_debug_gram_cols", "cfs_hip_debug_lobpcg_update_cols", "cfs_hip_sym_debug_lobpcg_residual", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
+    "cfs_hip_amg_create_f64", "cfs_hip_amg_create_f32", "cfs_hip_amg_destroy", "cfs_hip_amg_info", "cfs_hip_amg_level_aggregates", "cfs_hip_amg_level_matrix", "cfs_hip_amg_coarse_inverse", "cfs_hip_amg_apply", "cfs_hip_sym_pcg_amg", "cfs_hip_debug_amg_coarsen", "cfs_hip_amg_create_refreshable_f64", "cfs_hip_amg_create_refreshable_f32", "cfs_hip_amg_update_values_f64", "cfs_hip_amg_update_values_f32", "cfs_hip_amg_refresh_info", "cfs_hip_debug_amg_refresh_split", "cfs_hip_debug_amg_recoarsen",
+    "cfs_hip_amg_create_dominant_f64", "cfs_hip_amg_create_dominant_f32", "cfs_hip_amg_create_device_f64", "cfs_hip_amg_create_device_f32",
+    "cfs_hip_amg_setup_info", "cfs_hip_debug_amg_coarsen_dominant", "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_debug_gram_cols", "cfs_hip_debug_lobpcg_update_cols", "cfs_hip_sym_debug_lobpcg_residual", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
     "cfs_hip_sym_shard_set_recv", "cfs_hip_sym_spmv_local_async",
     "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_fold_lists", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
     "cfs_hip_sym_plan_check_f32", "cfs_hip_sym_plan_send_info_f64",
@@ -237,6 +240,14 @@ def load():
         lib.cfs_hip_sym_pcg_amg.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int, C.c_int, ip, dp, vp]
         lib.cfs_hip_debug_amg_coarsen.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, ip, vp, vp, vp, C.c_longlong,
                                                   C.POINTER(C.c_longlong)]
+    if hasattr(lib, "cfs_hip_amg_create_device_f64"):  # (absent from older builds loaded through CFS_HIP_LIB)
+        dp = C.POINTER(C.c_double)
+        for suf in ("f64", "f32"):
+            for kind in ("dominant_", "device_"):
+                getattr(lib, "cfs_hip_amg_create_" + kind + suf).argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(AmgOptions), C.POINTER(vp)]
+        lib.cfs_hip_amg_setup_info.argtypes = [vp, ip, ip, ip, dp, C.POINTER(C.c_longlong)]
+        lib.cfs_hip_debug_amg_coarsen_dominant.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, ip, vp, vp, vp, C.c_longlong,
+                                                           C.POINTER(C.c_longlong), ip]
     if hasattr(lib, "cfs_hip_amg_update_values_f64"):  # (absent from older builds loaded through CFS_HIP_LIB)
         for suf in ("f64", "f32"):
             getattr(lib, "cfs_hip_amg_create_refreshable_" + suf).argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(AmgOptions),

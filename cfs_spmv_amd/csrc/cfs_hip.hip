@@ -2223,7 +2223,7 @@ int cfs_hip_debug_cheb_coeffs(int degree, double lmin, double lmax, double *thet
 // ---- aggregation multigrid (cfs_solver_amg.hpp) ------------------------------------------------------
 template <typename V>
 static int amg_create(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const V *values, const cfs_hip_amg_options *opt,
-                      cfs_hip_amg_t *out, bool refreshable = false) {
+                      cfs_hip_amg_t *out, bool refreshable = false, int matching = CFS_HIP_AMG_MATCHING_GREEDY, bool on_device = false) {
   if (out) *out = nullptr;
   if (!h || !out || !rowptr || n < 0 || (n > 0 && rowptr[n] > 0 && (!colind || !values)))
     return set_err(CFS_HIP_ERR_ARG, "amg_create: null argument");
@@ -2250,10 +2250,13 @@ static int amg_create(cfs_hip_sym_t h, int n, const int *rowptr, const int *coli
   if (refreshable && m->P.deterministic)
     return set_err(CFS_HIP_ERR_UNSUPPORTED, "amg_create_refreshable: a deterministic handle's levels are deterministic, and those refuse "
                                             "update_values (their fixed-point scale depends on the values)");
+  if (on_device && n > 0 && 2 * (long long)rowptr[n] > (long long)INT_MAX)
+    return set_err(CFS_HIP_ERR_UNSUPPORTED, "amg_create_device: 2 nnz = " + std::to_string(2 * (long long)rowptr[n]) +
+                                                " exceeds the 32-bit positions of the records");
   DeviceGuard g(h->device);
   std::unique_ptr<cfs_solver::Amg<V>> a(new cfs_solver::Amg<V>());
   a->passes = passes, a->degree = degree, a->coarse_max = coarse_max, a->ratio = ratio, a->device = h->device;
-  a->refreshable = refreshable;
+  a->refreshable = refreshable, a->matching = matching, a->on_device = on_device ? 1 : 0;
   const int flags = CFS_HIP_FLAG_NO_CALIBRATE | (m->P.deterministic ? CFS_HIP_FLAG_DETERMINISTIC : 0) |
                     (refreshable ? CFS_HIP_FLAG_KEEP_VALUE_MAP : 0);
   h->ok_x = h->ok_y = nullptr;
@@ -2281,6 +2284,26 @@ int cfs_hip_amg_create_refreshable_f64(cfs_hip_sym_t h, int n, const int *rowptr
 int cfs_hip_amg_create_refreshable_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
                                        const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
   return amg_create<float>(h, n, rowptr, colind, values, opt, out, true);
+}
+int cfs_hip_amg_create_dominant_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
+                                    const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create<double>(h, n, rowptr, colind, values, opt, out, false, CFS_HIP_AMG_MATCHING_DOMINANT);
+}
+int cfs_hip_amg_create_dominant_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
+                                    const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create<float>(h, n, rowptr, colind, values, opt, out, false, CFS_HIP_AMG_MATCHING_DOMINANT);
+}
+int cfs_hip_amg_create_device_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
+                                  const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create<double>(h, n, rowptr, colind, values, opt, out, false, CFS_HIP_AMG_MATCHING_DOMINANT, true);
+}
+int cfs_hip_amg_create_device_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
+                                  const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create<float>(h, n, rowptr, colind, values, opt, out, false, CFS_HIP_AMG_MATCHING_DOMINANT, true);
+}
+int cfs_hip_amg_setup_info(cfs_hip_amg_t a, int *matching, int *on_device, int *rounds, double *seconds, long long *scratch_bytes) {
+  if (!a) return set_err(CFS_HIP_ERR_ARG, "amg_setup_info: null argument");
+  return a->setup_info(matching, on_device, rounds, seconds, scratch_bytes);
 }
 // cfs_hip_sym_update_values_* for a refreshable hierarchy: the same staging of a host array, the same stream
 static int amg_update_values(cfs_hip_amg_t a, const void *values, long long nnz, size_t vb) {
@@ -2392,9 +2415,10 @@ int cfs_hip_sym_pcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const voi
   DeviceGuard g(h->device);
   return a->pcg(u_dev, b_dev, tol, maxiter, iterations, relres, (hipStream_t)stream);
 }
-int cfs_hip_debug_amg_coarsen(int n, const int *rowptr, const int *colind, const double *values, int passes, int *agg, double *w,
-                              int *nc, int *c_rowptr, int *c_colind, double *c_values, long long capacity, long long *c_nnz) {
-  if (n < 0 || !rowptr || !agg || !w || !nc || !c_rowptr || !c_nnz || (n > 0 && rowptr[n] > 0 && (!colind || !values)))
+static int amg_coarsen_entry(int n, const int *rowptr, const int *colind, const double *values, int passes, int *agg, double *w, int *nc,
+                             int *c_rowptr, int *c_colind, double *c_values, long long capacity, long long *c_nnz, int matching, int *rounds) {
+  if (n < 0 || !rowptr || !agg || !w || !nc || !c_rowptr || !c_nnz || (n > 0 && rowptr[n] > 0 && (!colind || !values)) ||
+      (matching == CFS_HIP_AMG_MATCHING_DOMINANT && !rounds))
     return set_err(CFS_HIP_ERR_ARG, "amg_coarsen: null argument");
   if (passes < 1 || passes > 3) return set_err(CFS_HIP_ERR_ARG, "amg_coarsen: passes must lie in [1, 3], got " + std::to_string(passes));
   cfs_solver::AmgCsr low, coarse;
@@ -2402,7 +2426,7 @@ int cfs_hip_debug_amg_coarsen(int n, const int *rowptr, const int *colind, const
   std::vector<int> ag;
   std::vector<double> wv;
   long long bad = 0;
-  if (cfs_solver::amg_coarsen(low, passes, ag, wv, coarse, &bad))
+  if (cfs_solver::amg_coarsen(low, passes, ag, wv, coarse, &bad, nullptr, matching, rounds))
     return set_err(CFS_HIP_ERR_ARG, "amg_coarsen: Jacobi needs a positive diagonal, " + std::to_string(bad) + " of " + std::to_string(n) +
                                         " entries are zero, negative or not finite");
   *nc = coarse.n;
@@ -2414,6 +2438,17 @@ int cfs_hip_debug_amg_coarsen(int n, const int *rowptr, const int *colind, const
                                         std::to_string(capacity));
   for (long long k = 0; k < coarse.nnz(); ++k) c_colind[k] = coarse.ci[k], c_values[k] = coarse.va[k];
   return 0;
+}
+int cfs_hip_debug_amg_coarsen(int n, const int *rowptr, const int *colind, const double *values, int passes, int *agg, double *w,
+                              int *nc, int *c_rowptr, int *c_colind, double *c_values, long long capacity, long long *c_nnz) {
+  return amg_coarsen_entry(n, rowptr, colind, values, passes, agg, w, nc, c_rowptr, c_colind, c_values, capacity, c_nnz,
+                           CFS_HIP_AMG_MATCHING_GREEDY, nullptr);
+}
+int cfs_hip_debug_amg_coarsen_dominant(int n, const int *rowptr, const int *colind, const double *values, int passes, int *agg, double *w,
+                                       int *nc, int *c_rowptr, int *c_colind, double *c_values, long long capacity, long long *c_nnz,
+                                       int *rounds) {
+  return amg_coarsen_entry(n, rowptr, colind, values, passes, agg, w, nc, c_rowptr, c_colind, c_values, capacity, c_nnz,
+                           CFS_HIP_AMG_MATCHING_DOMINANT, rounds);
 }
 
 // a vector argument of the eigensolver entry points: device memory on the handle's device

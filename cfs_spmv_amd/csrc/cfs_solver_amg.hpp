@@ -64,6 +64,13 @@
 // level's values in V on the device (level_matrix() reads them back at its first call after a refresh), two fp64 arrays
 // of the longest level (the scaling is in place, the rounds go to and fro) and the fp64 weights.  Level 0 is the caller's
 // handle, poured by the caller: follow_fine().
+//
+// THE LOCALLY DOMINANT MATCHING (cfs_hip_amg_create_dominant_*, amg_match_dominant) replaces the sweep in row order by
+// synchronous rounds over a total order of the edges (strength, parity of the smaller endpoint, a hash, the indices):
+// parallel by definition and deterministic, everything else of a level unchanged.  With it the whole set-up runs ON THE
+// DEVICE (cfs_hip_amg_create_device_*, cfs_solver_amg_setup.hpp) and gives the host's hierarchy in every bit; build()
+// below is one loop over the levels for both, the host keeping what it kept: the level handles' create path, the dense
+// inverse and the power method's look.
 #pragma once
 
 #include <algorithm>
@@ -86,6 +93,7 @@ struct cfs_hip_amg_s {
   virtual int update_check(long long nnz) = 0;
   virtual int update_values(const void *values_dev, long long nnz, hipStream_t st) = 0;
   virtual int refresh_info(long long *map_bytes, int *refreshes, double *last_seconds, double *split) = 0;
+  virtual int setup_info(int *matching, int *on_device, int *rounds, double *seconds, long long *scratch_bytes) = 0;
 };
 
 namespace cfs_solver {
@@ -198,6 +206,75 @@ inline int amg_match(const AmgCsr &B, std::vector<int> &q) {
     }
     q[i] = nc;
     if (best >= 0) q[best] = nc;
+    ++nc;
+  }
+  return nc;
+}
+
+// ---- the locally dominant matching (CFS_HIP_AMG_MATCHING_DOMINANT): parallel by definition, host and device ----
+// the 32-bit mix of an edge's endpoints, lo < hi: it decides between edges of equal strength and equal parity
+__host__ __device__ inline unsigned amg_edge_hash(unsigned lo, unsigned hi) {
+  unsigned x = (lo * 0x9E3779B1u) ^ (hi * 0x85EBCA77u);
+  x ^= x >> 15;
+  x *= 0x2C1B3C6Du;
+  x ^= x >> 12;
+  x *= 0x297A2D39u;
+  x ^= x >> 15;
+  return x;
+}
+
+// the total order of the candidate edges: does (i, j1) of strength s1 come before (i, j2) of strength s2?  Larger s,
+// then an even smaller endpoint, then the smaller hash, then the smaller (lo, hi)
+__host__ __device__ inline bool amg_edge_before(double s1, int i, int j1, double s2, int j2) {
+  if (s1 != s2) return s1 > s2;
+  const int lo1 = i < j1 ? i : j1, hi1 = i < j1 ? j1 : i, lo2 = i < j2 ? i : j2, hi2 = i < j2 ? j2 : i;
+  if ((lo1 & 1) != (lo2 & 1)) return !(lo1 & 1);
+  const unsigned h1 = amg_edge_hash((unsigned)lo1, (unsigned)hi1), h2 = amg_edge_hash((unsigned)lo2, (unsigned)hi2);
+  if (h1 != h2) return h1 < h2;
+  return lo1 != lo2 ? lo1 < lo2 : hi1 < hi2;
+}
+
+// one round of pairwise matching on B (both triangles) by synchronous rounds: every free row points to its first free
+// neighbour in the total order, computed from the state at the start of the round; rows that point at each other pair.
+// The rounds end with one that forms no pair, or after CFS_HIP_AMG_MATCH_ROUNDS; *rounds = the rounds run.  q[i] = the
+// aggregate of row i, numbered by smallest member
+inline int amg_match_dominant(const AmgCsr &B, std::vector<int> &q, int *rounds) {
+  const int n = B.n;
+  std::vector<double> diag((size_t)n, 0.0);
+  for (int i = 0; i < n; ++i)
+    for (long long k = B.rp[i]; k < B.rp[i + 1]; ++k)
+      if (B.ci[k] == i) diag[i] = B.va[k];
+  std::vector<int> mate((size_t)n, -1), to((size_t)n, -1);
+  int r = 0;
+  while (r < CFS_HIP_AMG_MATCH_ROUNDS) {
+    ++r;
+    for (int i = 0; i < n; ++i) {
+      int best = -1;
+      double sbest = 0.0;
+      if (mate[i] < 0)
+        for (long long k = B.rp[i]; k < B.rp[i + 1]; ++k) {
+          const int j = B.ci[k];
+          if (j == i || mate[j] >= 0) continue;
+          const double s = std::fabs(B.va[k]) / std::sqrt(diag[i] * diag[j]);
+          if (!(s > 0.0)) continue;
+          if (best < 0 || amg_edge_before(s, i, j, sbest, best)) best = j, sbest = s;
+        }
+      to[i] = best;
+    }
+    int made = 0;
+    for (int i = 0; i < n; ++i) {
+      const int j = to[i];
+      if (j >= 0 && to[j] == i) mate[i] = j, made += i < j;
+    }
+    if (!made) break;
+  }
+  if (rounds) *rounds = r;
+  q.assign((size_t)n, -1);
+  int nc = 0;
+  for (int i = 0; i < n; ++i) {
+    if (q[i] >= 0) continue;
+    q[i] = nc;
+    if (mate[i] >= 0) q[mate[i]] = nc;
     ++nc;
   }
   return nc;
@@ -337,9 +414,10 @@ inline void amg_eval_frozen(const AmgFrozen &f, const std::vector<int> &col, con
 }
 
 // one level: agg, w and the lower triangle + diagonal of A_{l+1} from that of A_l.  *bad: diagonal entries that are not positive.
-// rec (when given): the level's lists, for a refresh
+// rec (when given): the level's lists, for a refresh.  matching: CFS_HIP_AMG_MATCHING_*; rounds (when given, dominant
+// only): the rounds every pass ran
 inline int amg_coarsen(const AmgCsr &low, int passes, std::vector<int> &agg, std::vector<double> &w, AmgCsr &coarse, long long *bad,
-                       AmgFrozen *rec = nullptr) {
+                       AmgFrozen *rec = nullptr, int matching = CFS_HIP_AMG_MATCHING_GREEDY, int *rounds = nullptr) {
   const int n = low.n;
   std::vector<double> diag;
   *bad = amg_diagonal(low, diag);
@@ -362,7 +440,7 @@ inline int amg_coarsen(const AmgCsr &low, int passes, std::vector<int> &agg, std
   for (int i = 0; i < n; ++i) agg[i] = i;
   std::vector<int> q;
   for (int p = 0; p < passes; ++p) {
-    const int nc = amg_match(B, q);
+    const int nc = matching == CFS_HIP_AMG_MATCHING_DOMINANT ? amg_match_dominant(B, q, rounds ? rounds + p : nullptr) : amg_match(B, q);
     amg_galerkin(B, q, nc, next, rec ? &from : nullptr, rec ? &rec->rounds[p] : nullptr);
     for (int i = 0; i < n; ++i) agg[i] = q[agg[i]];
     if (p + 1 < passes) amg_mirror(next, nullptr, B, rec ? &from : nullptr);
@@ -564,6 +642,10 @@ template <typename V> struct AmgLevel {
   }
 };
 
+} // namespace cfs_solver
+#include "cfs_solver_amg_setup.hpp" // a level coarsened on the device: AmgDeviceSetup
+namespace cfs_solver {
+
 template <typename V> struct Amg : cfs_hip_amg_s {
   using Level = AmgLevel<V>;
   std::vector<std::unique_ptr<Level>> lv;
@@ -580,6 +662,11 @@ template <typename V> struct Amg : cfs_hip_amg_s {
   cfs_rt::DevBuf rbuf[2], w64, pw; // kept: two fp64 arrays of the longest level, the fp64 weights, the power method's vector
   Slots rpart, rlpart;             // P_COUNT slots of a level's smoother + one for amg_weight_kernel; the power method's, kept
   std::vector<hipEvent_t> ev;
+  // how the hierarchy was made (cfs_hip_amg_setup_info): the matching, where (0 host, 1 device, 2 device after amg_lower
+  // on the host), the rounds every pass of every level ran, the split of a device set-up and its scratch
+  int matching = CFS_HIP_AMG_MATCHING_GREEDY, on_device = 0, rounds[CFS_HIP_AMG_MAX_LEVELS][3] = {};
+  double setup_split[4] = {0.0, 0.0, 0.0, 0.0};
+  long long scratch_bytes = 0;
 
   ~Amg() override {
     cfs_rt::DeviceGuard g(device);
@@ -600,7 +687,22 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     if ((rc = part.alloc(P_COUNT, st)) || (rc = cnt.alloc(I_COUNT * sizeof(int))) || (rc = part.zero())) return rc;
     HIPCHK(hipMemset(cnt.p, 0, I_COUNT * sizeof(int)));
     AmgCsr cur, next;
-    amg_lower(n, rowptr, colind, values, cur);
+    // a device set-up holds the level on the device; `cur` is then the coarse CSR it brought down (levels >= 1), or
+    // amg_lower's when level 0 is the last one
+    std::unique_ptr<AmgDeviceSetup<V>> dev;
+    if (on_device && n > coarse_max) {
+      dev.reset(new AmgDeviceSetup<V>());
+      if ((rc = dev->begin(n, rowptr, colind, values, st))) return rc;
+      if (dev->host_lower) on_device = 2;
+      scratch_bytes = dev->scratch_bytes;
+    } else {
+      amg_lower(n, rowptr, colind, values, cur);
+    }
+    auto bad_diagonal = [](long long bad, int rows, int l) {
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_create: Jacobi needs a positive diagonal, " + std::to_string(bad) + " of " +
+                                                  std::to_string(rows) + " entries are zero, negative or not finite (level " +
+                                                  std::to_string(l) + ")");
+    };
     std::vector<int> agg;
     std::vector<double> w, inv;
     AmgFrozen frozen;
@@ -608,8 +710,9 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     for (int l = 0;; ++l) {
       lv.emplace_back(new Level());
       Level &L = *lv.back();
-      L.n = cur.n;
-      L.nnz = cur.nnz();
+      const bool resident0 = dev && l == 0; // level 0 of a device set-up: only the device holds its lower triangle
+      L.n = resident0 ? dev->n : cur.n;
+      L.nnz = resident0 ? dev->m : cur.nnz();
       longest = std::max(longest, (size_t)L.nnz);
       if (refreshable && l == 0) {
         AmgList li;
@@ -620,10 +723,7 @@ template <typename V> struct Amg : cfs_hip_amg_s {
       }
       long long bad = 0;
       std::vector<double> diag;
-      if ((bad = amg_diagonal(cur, diag)))
-        return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_create: Jacobi needs a positive diagonal, " + std::to_string(bad) + " of " +
-                                                    std::to_string(cur.n) + " entries are zero, negative or not finite (level " +
-                                                    std::to_string(l) + ")");
+      if (!resident0 && (bad = amg_diagonal(cur, diag))) return bad_diagonal(bad, cur.n, l);
       if (l == 0) {
         L.h = h;
       } else { // the level as a handle of its own, from the values rounded to V (which `cur` already holds)
@@ -639,13 +739,19 @@ template <typename V> struct Amg : cfs_hip_amg_s {
         handles_seconds += std::chrono::duration<double>(clock::now() - t0).count();
       }
       // how the hierarchy goes on
-      bool last = cur.n <= coarse_max;
+      bool last = L.n <= coarse_max;
       L.kind = last ? AMG_DENSE : AMG_MULTIGRID;
       if (!last) {
-        if (amg_coarsen(cur, passes, agg, w, next, &bad, refreshable ? &frozen : nullptr)) return cfs_rt::set_err(CFS_HIP_ERR_INTERNAL, "amg_create: the diagonal changed");
-        if ((double)next.n > 0.9 * (double)cur.n || l + 1 == CFS_HIP_AMG_MAX_LEVELS) {
+        if (dev) {
+          if ((rc = dev->coarsen(L, passes, &bad, next, rounds[l]))) return rc == 1 ? bad_diagonal(bad, L.n, l) : rc;
+        } else if (amg_coarsen(cur, passes, agg, w, next, &bad, refreshable ? &frozen : nullptr, matching, rounds[l])) {
+          return cfs_rt::set_err(CFS_HIP_ERR_INTERNAL, "amg_create: the diagonal changed");
+        }
+        if ((double)next.n > 0.9 * (double)L.n || l + 1 == CFS_HIP_AMG_MAX_LEVELS) {
           last = true;
-          L.kind = cur.n <= CFS_HIP_AMG_MAX_COARSE ? AMG_DENSE : AMG_SMOOTHER;
+          L.kind = L.n <= CFS_HIP_AMG_MAX_COARSE ? AMG_DENSE : AMG_SMOOTHER;
+          if (resident0 && L.kind == AMG_DENSE) amg_lower(n, rowptr, colind, values, cur); // (at most 1024 rows)
+          if (dev) L.agg = cfs_rt::DevBuf(), L.w = cfs_rt::DevBuf(), L.aggptr = cfs_rt::DevBuf(), L.aggidx = cfs_rt::DevBuf();
         }
       }
       if (L.kind == AMG_DENSE) {
@@ -680,6 +786,10 @@ template <typename V> struct Amg : cfs_hip_amg_s {
       }
       // the transfer to the next level
       L.nc = next.n;
+      if (dev) { // (agg, the lists and w are on the device already)
+        cur = std::move(next);
+        continue;
+      }
       std::vector<int> ptr((size_t)next.n + 1, 0), idx((size_t)cur.n);
       for (int i = 0; i < cur.n; ++i) ptr[(size_t)agg[i] + 1] += 1;
       for (int I = 0; I < next.n; ++I) ptr[(size_t)I + 1] += ptr[I];
@@ -704,7 +814,22 @@ template <typename V> struct Amg : cfs_hip_amg_s {
       for (size_t l = 1; l < lv.size(); ++l) value_map_bytes += 4 * lv[l]->nnz;
     }
     HIPCHK(hipDeviceSynchronize());
+    if (dev)
+      for (int k = 0; k < 4; ++k) setup_split[k] = dev->seconds[k];
+    dev.reset(); // (the scratch goes before the call returns)
     setup_seconds = std::chrono::duration<double>(clock::now() - t_begin).count();
+    return 0;
+  }
+
+  int setup_info(int *mt, int *where, int *rnd, double *seconds, long long *scratch) override {
+    if (mt) *mt = matching;
+    if (where) *where = on_device;
+    if (rnd)
+      for (size_t l = 0; l < lv.size(); ++l)
+        for (int p = 0; p < 3; ++p) rnd[3 * l + p] = rounds[l][p];
+    if (seconds)
+      for (int k = 0; k < 4; ++k) seconds[k] = setup_split[k];
+    if (scratch) *scratch = scratch_bytes;
     return 0;
   }
 

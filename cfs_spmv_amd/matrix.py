@@ -390,16 +390,22 @@ class SymMatrix:
                                                         _stream_ptr(stream)))
         return est.value
 
-    def amg(self, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512, refreshable=False):
+    def amg(self, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512, refreshable=False, matching="greedy",
+            setup="host"):
         """the aggregation multigrid hierarchy of this matrix (cfs_hip_amg_create_*), an Amg: rowptr, colind, values
         are the CSR the handle was created from (only entries with col <= row are read; the caller vouches that it is
         this handle's matrix).  passes 1 .. 3 rounds of pairwise matching per level, degree 1 .. 4 of the Chebyshev
         smoother, ratio = lmax / lmin of its interval, coarse_max <= 1024 the largest dense last level.  A whole-matrix
         handle on one device.  The hierarchy holds the values of now: to follow update_values() make it with
         refreshable=True (cfs_hip_amg_create_refreshable_*; the matrix needs FLAG_KEEP_VALUE_MAP) and call
-        Amg.update_values() with the same array."""
+        Amg.update_values() with the same array.
+        matching: "greedy" (the rows in ascending order, each takes its strongest free neighbour) or "dominant" (the
+        locally dominant matching of cfs_hip.h, parallel by definition: usually more iterations, and the only one with
+        setup="device", where the hierarchy is built by kernels on the device -- the hierarchy of matching="dominant",
+        setup="host" in every bit, in a fraction of the time).  setup="device" with matching="greedy" and a refreshable
+        hierarchy with matching="dominant" do not exist: ValueError."""
         return Amg(self, rowptr, colind, values, passes=passes, degree=degree, ratio=ratio, coarse_max=coarse_max,
-                   refreshable=refreshable)
+                   refreshable=refreshable, matching=matching, setup=setup)
 
     def pcg_amg(self, u, b, amg, tol=1e-10, maxiter=1000, check_every=1, stream=None):
         """PCG with one V-cycle of `amg` (self.amg(...)) as the preconditioner (cfs_hip_sym_pcg_amg): like
@@ -595,7 +601,14 @@ class Amg:
     """The aggregation multigrid hierarchy of a SymMatrix (cfs_hip_amg_create_*) and its V-cycle.  Keeps a reference
     to its matrix, which must stay open for as long as the hierarchy is used."""
 
-    def __init__(self, A, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512, refreshable=False):
+    def __init__(self, A, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512, refreshable=False,
+                 matching="greedy", setup="host"):
+        if matching not in ("greedy", "dominant") or setup not in ("host", "device"):
+            raise ValueError(f'matching is "greedy" or "dominant" and setup "host" or "device", got {matching!r}, {setup!r}')
+        if setup == "device" and matching == "greedy":
+            raise ValueError('setup="device" needs matching="dominant": the greedy matching has no parallel form')
+        if refreshable and matching != "greedy":
+            raise ValueError("a refreshable hierarchy is made with the greedy matching on the host")
         lib = _lib.load()
         rowptr, colind = _np_i32(rowptr), _np_i32(colind)
         values = np.ascontiguousarray(values, dtype=A.dtype)
@@ -604,7 +617,8 @@ class Amg:
         opt = _lib.AmgOptions(int(passes), int(degree), int(coarse_max), 0, float(ratio))
         suf = "f64" if self.dtype == np.float64 else "f32"
         self.refreshable = bool(refreshable)
-        create = getattr(lib, "cfs_hip_amg_create_" + ("refreshable_" if refreshable else "") + suf)
+        kind = "refreshable_" if refreshable else "device_" if setup == "device" else "dominant_" if matching == "dominant" else ""
+        create = getattr(lib, "cfs_hip_amg_create_" + kind + suf)
         _lib.check(create(A._h, A.n, rowptr.ctypes.data, colind.ctypes.data, values.ctypes.data, C.byref(opt), C.byref(self._a)))
 
     def info(self):
@@ -614,6 +628,19 @@ class Amg:
         out = _lib.AmgInfo()
         _lib.check(_lib.load().cfs_hip_amg_info(self._a, C.byref(out)))
         return out.asdict()
+
+    def setup_info(self):
+        """dict (cfs_hip_amg_setup_info): matching ("greedy" / "dominant"), setup ("host" / "device"), lower_on_host (a
+        device set-up whose level 0 was read on the host: unsorted rows or duplicates), rounds (per level that has a
+        coarser one, the rounds of every pass), split_seconds of a device set-up (lower, matching, galerkin, download)
+        and scratch_bytes, the device scratch it held"""
+        inf = self.info()
+        mt, dev, sb = C.c_int(), C.c_int(), C.c_longlong()
+        rounds, sec = (C.c_int * (3 * _lib.AMG_MAX_LEVELS))(), (C.c_double * 4)()
+        _lib.check(_lib.load().cfs_hip_amg_setup_info(self._a, C.byref(mt), C.byref(dev), rounds, sec, C.byref(sb)))
+        return dict(matching=("greedy", "dominant")[mt.value], setup="device" if dev.value else "host", lower_on_host=dev.value == 2,
+                    rounds=[list(rounds[3 * l:3 * l + inf["passes"]]) for l in range(inf["levels"] - 1)],
+                    split_seconds=dict(zip(("lower", "matching", "galerkin", "download"), list(sec))), scratch_bytes=sb.value)
 
     def update_values(self, values):
         """new values, same sparsity pattern, for a refreshable hierarchy (cfs_hip_amg_update_values_*): a numpy array or
@@ -683,19 +710,28 @@ class Amg:
             pass
 
 
-def coarsen(n, rowptr, colind, values, passes=2):
-    """host only: one level of the multigrid set-up (cfs_hip_debug_amg_coarsen).  Returns (agg, w, (nc, rowptr, colind,
-    values)): the aggregate of every row, the weights 1 / sqrt(a_ii) and the lower triangle + diagonal of the coarse
-    matrix, all in fp64"""
+def coarsen(n, rowptr, colind, values, passes=2, matching="greedy", rounds=None):
+    """host only: one level of the multigrid set-up (cfs_hip_debug_amg_coarsen, or cfs_hip_debug_amg_coarsen_dominant
+    with matching="dominant").  Returns (agg, w, (nc, rowptr, colind, values)): the aggregate of every row, the weights
+    1 / sqrt(a_ii) and the lower triangle + diagonal of the coarse matrix, all in fp64.  rounds (a list, dominant only):
+    receives the rounds every pass ran"""
+    if matching not in ("greedy", "dominant"):
+        raise ValueError(f'matching is "greedy" or "dominant", got {matching!r}')
     rowptr, colind = _np_i32(rowptr), _np_i32(colind)
     values = np.ascontiguousarray(values, dtype=np.float64)
     cap = int(rowptr[n]) if n > 0 else 0
     agg, w = np.zeros(n, np.int32), np.zeros(n, np.float64)
     crp, cci, cva = np.zeros(n + 1, np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float64)
     nc, nnz = C.c_int(), C.c_longlong()
-    _lib.check(_lib.load().cfs_hip_debug_amg_coarsen(n, rowptr.ctypes.data, colind.ctypes.data, values.ctypes.data, int(passes),
-                                                     agg.ctypes.data, w.ctypes.data, C.byref(nc), crp.ctypes.data, cci.ctypes.data,
-                                                     cva.ctypes.data, cap, C.byref(nnz)))
+    args = (n, rowptr.ctypes.data, colind.ctypes.data, values.ctypes.data, int(passes), agg.ctypes.data, w.ctypes.data, C.byref(nc),
+            crp.ctypes.data, cci.ctypes.data, cva.ctypes.data, cap, C.byref(nnz))
+    if matching == "dominant":
+        rnd = (C.c_int * 3)()
+        _lib.check(_lib.load().cfs_hip_debug_amg_coarsen_dominant(*args, rnd))
+        if rounds is not None:
+            rounds[:] = list(rnd)[:int(passes)]
+    else:
+        _lib.check(_lib.load().cfs_hip_debug_amg_coarsen(*args))
     return agg, w, (nc.value, crp[:nc.value + 1].copy(), cci[:nnz.value].copy(), cva[:nnz.value].copy())
 
 

@@ -539,6 +539,56 @@ int cfs_hip_amg_create_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int 
 int cfs_hip_amg_create_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
                            const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
 int cfs_hip_amg_destroy(cfs_hip_amg_t a); /* NULL is allowed */
+/* ---- the LOCALLY DOMINANT matching, and the set-up on the device --------------------------------------------------
+ * The matching above is sequential by definition (row i's choice depends on row i - 2's on a chain).  The second
+ * matching is parallel by definition and deterministic; everything else of a level -- w, B = W A W, B <- Q^T B Q with
+ * the sums in the same order, the rounding to the value type, the rules that end a hierarchy, the smoother, the dense
+ * inverse and the cycle -- is unchanged.  One round of pairwise matching on B:
+ *   CANDIDATE EDGES: every off-diagonal entry with s_ij = |b_ij| / sqrt(b_ii b_jj) > 0, the fp64 expression above (the
+ *   product b_ii b_jj and the stored b_ij = b_ji give both endpoints the same bits).
+ *   TOTAL ORDER of the edges: (1) the larger s first; (2) at equal s (compared as doubles) the edge whose smaller
+ *   endpoint lo = min(i, j) is even; (3) then the smaller h(lo, hi); (4) then the smaller (lo, hi).  h is this 32-bit
+ *   mix, all arithmetic mod 2^32:
+ *     x = (lo * 0x9E3779B1u) ^ (hi * 0x85EBCA77u);  x ^= x >> 15;  x *= 0x2C1B3C6Du;  x ^= x >> 12;  x *= 0x297A2D39u;
+ *     x ^= x >> 15
+ *   SYNCHRONOUS ROUNDS: every free row that has a free neighbour over a candidate edge points to the first such edge in
+ *   the total order; all pointers are computed from the state at the start of the round; rows that point at each
+ *   other become a pair.  The rounds end with a round that forms no pair (it is counted), or after
+ *   CFS_HIP_AMG_MATCH_ROUNDS rounds; the rows still free are singletons.
+ *   NUMBERING: the aggregates by their smallest member, ascending.
+ * Below the cap the result is the matching of a sequential pass over the edges in the total order (take an edge when
+ * both ends are free), whatever the schedule of the rounds.  The hash keeps the number of rounds logarithmic on chains of
+ * equal weights (ties to the smallest index would need n / 2); the parity key lets naturally ordered grids match
+ * perfectly in one round.  Heaviest-edge-first leaves more singletons on structured grids than the sweep in index
+ * order: expect more iterations than with the greedy hierarchy (README), against a set-up that runs on the device.
+ * cfs_hip_amg_create_dominant_*: the arguments, checks, messages and their order of cfs_hip_amg_create_*; the set-up on
+ * the host with this matching; not refreshable.
+ * cfs_hip_amg_create_device_*: the same arguments and checks, and THE SAME HIERARCHY IN EVERY BIT -- aggregates, w, every
+ * level's pattern and values, the inverse -- built by HIP kernels, hipcub sorts and scans on the handle's device: level
+ * 0's lower triangle from one upload of the caller's CSR (rows whose kept columns do not ascend strictly: read on the host,
+ * as above, and uploaded), per level the weights, the scaling, both triangles by a stable sort of (row, col) records,
+ * the rounds (one host look per round), Q^T B Q as lists over the stably sorted (I, J) records summed one thread per
+ * coarse entry, the transfer; the coarse CSR comes to the host once per level for the level's handle and the dense
+ * inverse.  In addition: a CSR with 2 nnz beyond 32-bit positions is CFS_HIP_ERR_UNSUPPORTED, before any device work;
+ * a failed allocation returns the device error.  The scratch (cfs_hip_amg_setup_info) is freed before the call returns.
+ * cfs_hip_amg_setup_info, for every hierarchy: *matching = CFS_HIP_AMG_MATCHING_*; *on_device = 0 (host), 1 (device) or
+ * 2 (device, level 0's lower triangle read on the host); rounds[3 * level + pass] = the rounds of every pass (levels x 3
+ * ints, 0 where none ran); seconds[4] of a device set-up: level 0's lower triangle with the upload, the matching, the
+ * mirror + Galerkin product + transfer, the downloads; *scratch_bytes = the device scratch a device set-up held.  Greedy,
+ * 0 and zeros for the entry points above.  Any of the five may be NULL.                                            */
+#define CFS_HIP_AMG_MATCHING_GREEDY 0
+#define CFS_HIP_AMG_MATCHING_DOMINANT 1
+#define CFS_HIP_AMG_MATCH_ROUNDS 64
+int cfs_hip_amg_create_dominant_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
+                                    const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_create_dominant_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
+                                    const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_create_device_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
+                                  const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_create_device_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
+                                  const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_setup_info(cfs_hip_amg_t a, int *matching, int *on_device, int *rounds, double *seconds,
+                           long long *scratch_bytes);
 /* ---- a hierarchy that follows cfs_hip_sym_update_values_*: the numeric re-set-up with the aggregates kept ---------
  * cfs_hip_amg_create_refreshable_*: the arguments and rules of cfs_hip_amg_create_*, and the same hierarchy bit for
  * bit; the level handles are created with CFS_HIP_FLAG_KEEP_VALUE_MAP and the object keeps, on the device, what a refresh
@@ -629,6 +679,10 @@ int cfs_hip_sym_pcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const voi
 int cfs_hip_debug_amg_coarsen(int n, const int *rowptr, const int *colind, const double *values, int passes,
                               int *agg, double *w, int *nc, int *c_rowptr, int *c_colind, double *c_values,
                               long long capacity, long long *c_nnz);
+/* The same with the locally dominant matching; rounds[passes]: the rounds every pass ran.                         */
+int cfs_hip_debug_amg_coarsen_dominant(int n, const int *rowptr, const int *colind, const double *values, int passes,
+                                       int *agg, double *w, int *nc, int *c_rowptr, int *c_colind, double *c_values,
+                                       long long capacity, long long *c_nnz, int *rounds);
 /* Host only, no device work: one level of a REFRESH.  The lists are built from values_at_create by the code
  * cfs_hip_amg_create_refreshable_* uses (the matchings of that array, frozen), then evaluated for values_new -- the
  * same CSR pattern -- in a host loop that adds in the order the kernels add.  Out: w[n] (fp64) and the coarse values in

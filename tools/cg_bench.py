@@ -28,7 +28,12 @@ refresh and REFRESH_TIMED timed ones alternating between two value arrays on the
 call, and its pour timed by itself.  Minimum and median, the split of the fastest one (Galerkin kernels, pours, dinv + power
 methods, dense inverse) and, with handle and hierarchy refreshed to the SECOND array, the iterations of a solve beside those
 of a fresh create on that array.  --only-amg-refresh: that part alone, without the solves above.
-usage: python tools/cg_bench.py [--only-cheb | --only-amg | --only-amg-refresh] [matrix[:scale] | lap2dNXxNY ...]"""
+--only-amg-setup: what the SET-UP of a hierarchy costs and what its matching costs in iterations -- greedy / host,
+dominant / host and dominant / device (cfs_hip_amg_create_device_*), SETUP_CREATES creates each, interleaved: minimum and
+median of setup_seconds, of handles_seconds and of their difference (the level handles' create path is the same code in
+all three); the split and the scratch of the device set-up (cfs_hip_amg_setup_info); the levels and device_bytes; then
+pcg_amg to TOL on the greedy and the dominant hierarchy, interleaved as above.
+usage: python tools/cg_bench.py [--only-cheb | --only-amg | --only-amg-refresh | --only-amg-setup] [matrix[:scale] | lap2dNXxNY ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -49,6 +54,8 @@ HAVE_AMG = hasattr(cfs.load(), "cfs_hip_sym_pcg_amg")
 ONLY_REFRESH = "--only-amg-refresh" in sys.argv
 ONLY_AMG = "--only-amg" in sys.argv or ONLY_REFRESH
 HAVE_REFRESH = hasattr(cfs.load(), "cfs_hip_amg_update_values_f64")
+ONLY_SETUP = "--only-amg-setup" in sys.argv
+SETUP_CREATES = 3
 REFRESH_TIMED = 5
 AMG_DEGREES, AMG_ROUNDS = (1, 2), 3
 CHEB_DEGREES, CHEB_ROUNDS = (2, 4), 3
@@ -138,6 +145,53 @@ def refresh_section(A, b, res, rp, ci, va):
     A.update_values(dev[0])
 
 
+def setup_section(A, b, res, rp, ci, va):
+    """the three ways to a hierarchy, SETUP_CREATES creates each, interleaved; then the solves on greedy and dominant"""
+    ways = {"greedy_host": dict(), "dominant_host": dict(matching="dominant"), "dominant_device": dict(matching="dominant", setup="device")}
+    seen = {w: [] for w in ways}
+    kept = {}
+    for k in range(SETUP_CREATES):
+        for w, kw in ways.items():
+            G = A.amg(rp, ci, va, **kw)
+            inf = G.info()
+            seen[w].append((inf["setup_seconds"], inf["handles_seconds"], G.setup_info()))
+            if k + 1 == SETUP_CREATES:
+                kept[w] = G
+                res[f"{w}_levels"], res[f"{w}_kinds"], res[f"{w}_device_bytes"] = inf["n"], inf["kind"], inf["device_bytes"]
+            else:
+                G.close()
+    for w, runs in seen.items():
+        total, handles = np.array([r[0] for r in runs]), np.array([r[1] for r in runs])
+        for label, v in (("setup_seconds", total), ("handles_seconds", handles), ("setup_minus_handles_seconds", total - handles)):
+            res[f"{w}_{label}_min"], res[f"{w}_{label}_median"] = round(float(v.min()), 5), round(float(np.median(v)), 5)
+    best = seen["dominant_device"][int(np.argmin([r[0] for r in seen["dominant_device"]]))][2]
+    res["dominant_device_split_ms"] = {k: round(v * 1e3, 3) for k, v in best["split_seconds"].items()}
+    res["dominant_device_scratch_bytes"], res["dominant_device_lower_on_host"] = best["scratch_bytes"], best["lower_on_host"]
+    res["dominant_rounds"] = best["rounds"]
+    res["device_over_greedy_host_setup"] = round(res["dominant_device_setup_seconds_min"] / res["greedy_host_setup_seconds_min"], 4)
+    res["device_over_greedy_host_setup_minus_handles"] = round(res["dominant_device_setup_minus_handles_seconds_min"] /
+                                                               res["greedy_host_setup_minus_handles_seconds_min"], 4)
+    loops = {w: (lambda G=kept[w]: pcg_amg_native(A, b, G, tol=TOL, maxiter=MAXITER)[1:3]) for w in ("greedy_host", "dominant_device")}
+    solved = {}
+    for _ in range(AMG_ROUNDS):
+        for label, fn in loops.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            it, rel = fn()
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            if t < solved.get(label, (float("inf"),))[0]:
+                solved[label] = (t, it, rel)
+    res["amg_tolerance"], res["amg_rounds"], res["setup_creates"] = TOL, AMG_ROUNDS, SETUP_CREATES
+    for label, (t, it, rel) in solved.items():
+        tag = label.split("_")[0]
+        res[f"{tag}_ms_to_tolerance"], res[f"{tag}_iterations"], res[f"{tag}_relres"] = round(t * 1e3, 3), it, rel
+    res["dominant_over_greedy_iterations"] = round(res["dominant_iterations"] / max(res["greedy_iterations"], 1), 3)
+    res["dominant_over_greedy_time"] = round(res["dominant_ms_to_tolerance"] / res["greedy_ms_to_tolerance"], 4)
+    for G in kept.values():
+        G.close()
+
+
 def amg_section(A, b, res, rp, ci, va):
     """solves down to TOL: Jacobi PCG, Chebyshev degree 4 on Jacobi, and the V-cycle at AMG_DEGREES, interleaved"""
     if ONLY_REFRESH:
@@ -204,7 +258,9 @@ for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ld
     spmv_us = (time.perf_counter() - t0) / 200 * 1e6
     K = 200
     res = {"n": n, "spmv_us": round(spmv_us, 2)}
-    if ONLY_CHEB or ONLY_AMG:
+    if ONLY_CHEB or ONLY_AMG or ONLY_SETUP:
+        if ONLY_SETUP:
+            setup_section(A, b, res, rp, ci, va)
         if ONLY_CHEB:
             cheb_section(A, b, res)
         if ONLY_AMG:
