@@ -100,7 +100,9 @@ SYMBOLS = [
     "cfs_hip_sym_pcg_block", "cfs_hip_sym_block_inverse_async", "cfs_hip_sym_pcg_mixed", "cfs_hip_sym_minres", "cfs_hip_sym_pcg_cheb", "cfs_hip_sym_cheb_apply", "cfs_hip_sym_precond_lmax", "cfs_hip_debug_cheb_coeffs",
     "cfs_hip_amg_create_f64", "cfs_hip_amg_create_f32", "cfs_hip_amg_destroy", "cfs_hip_amg_info", "cfs_hip_amg_level_aggregates", "cfs_hip_amg_level_matrix", "cfs_hip_amg_coarse_inverse", "cfs_hip_amg_apply", "cfs_hip_sym_pcg_amg", "cfs_hip_debug_amg_coarsen", "cfs_hip_amg_create_refreshable_f64", "cfs_hip_amg_create_refreshable_f32", "cfs_hip_amg_update_values_f64", "cfs_hip_amg_update_values_f32", "cfs_hip_amg_refresh_info", "cfs_hip_debug_amg_refresh_split", "cfs_hip_debug_amg_recoarsen",
     "cfs_hip_amg_create_dominant_f64", "cfs_hip_amg_create_dominant_f32", "cfs_hip_amg_create_device_f64", "cfs_hip_amg_create_device_f32",
-    "cfs_hip_amg_setup_info", "cfs_hip_debug_amg_coarsen_dominant", "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_debug_gram_cols", "cfs_hip_debug_lobpcg_update_cols", "cfs_hip_sym_debug_lobpcg_residual", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
+    "cfs_hip_amg_setup_info", "cfs_hip_debug_amg_coarsen_dominant",
+    "cfs_hip_amg_create_block_f64", "cfs_hip_amg_create_block_f32", "cfs_hip_amg_block", "cfs_hip_amg_level_node_weights", "cfs_hip_debug_amg_coarsen_block",
+    "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_debug_gram_cols", "cfs_hip_debug_lobpcg_update_cols", "cfs_hip_sym_debug_lobpcg_residual", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
     "cfs_hip_sym_shard_set_recv", "cfs_hip_sym_spmv_local_async",
     "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_fold_lists", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
     "cfs_hip_sym_plan_check_f32", "cfs_hip_sym_plan_send_info_f64",
@@ -256,6 +258,14 @@ def load():
         lib.cfs_hip_amg_refresh_info.argtypes = [vp, C.POINTER(C.c_longlong), ip, C.POINTER(C.c_double)]
         lib.cfs_hip_debug_amg_refresh_split.argtypes = [vp, C.POINTER(C.c_double)]
         lib.cfs_hip_debug_amg_recoarsen.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    if hasattr(lib, "cfs_hip_amg_create_block_f64"):  # (absent from older builds loaded through CFS_HIP_LIB)
+        for suf in ("f64", "f32"):
+            getattr(lib, "cfs_hip_amg_create_block_" + suf).argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.POINTER(AmgOptions),
+                                                                        C.POINTER(vp)]
+        lib.cfs_hip_amg_block.argtypes = [vp, ip]
+        lib.cfs_hip_amg_level_node_weights.argtypes = [vp, C.c_int, vp]
+        lib.cfs_hip_debug_amg_coarsen_block.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, ip, vp, vp, vp,
+                                                        C.c_longlong, C.POINTER(C.c_longlong), ip]
     if hasattr(lib, "cfs_hip_sym_eigs"):  # (absent from older builds loaded through CFS_HIP_LIB)
         dp = C.POINTER(C.c_double)
         lib.cfs_hip_sym_eigs.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, dp, vp, C.c_longlong, dp,

@@ -2223,7 +2223,8 @@ int cfs_hip_debug_cheb_coeffs(int degree, double lmin, double lmax, double *thet
 // ---- aggregation multigrid (cfs_solver_amg.hpp) ------------------------------------------------------
 template <typename V>
 static int amg_create(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const V *values, const cfs_hip_amg_options *opt,
-                      cfs_hip_amg_t *out, bool refreshable = false, int matching = CFS_HIP_AMG_MATCHING_GREEDY, bool on_device = false) {
+                      cfs_hip_amg_t *out, bool refreshable = false, int matching = CFS_HIP_AMG_MATCHING_GREEDY, bool on_device = false,
+                      int block = 1) {
   if (out) *out = nullptr;
   if (!h || !out || !rowptr || n < 0 || (n > 0 && rowptr[n] > 0 && (!colind || !values)))
     return set_err(CFS_HIP_ERR_ARG, "amg_create: null argument");
@@ -2254,20 +2255,61 @@ static int amg_create(cfs_hip_sym_t h, int n, const int *rowptr, const int *coli
     return set_err(CFS_HIP_ERR_UNSUPPORTED, "amg_create_device: 2 nnz = " + std::to_string(2 * (long long)rowptr[n]) +
                                                 " exceeds the 32-bit positions of the records");
   DeviceGuard g(h->device);
-  std::unique_ptr<cfs_solver::Amg<V>> a(new cfs_solver::Amg<V>());
-  a->passes = passes, a->degree = degree, a->coarse_max = coarse_max, a->ratio = ratio, a->device = h->device;
-  a->refreshable = refreshable, a->matching = matching, a->on_device = on_device ? 1 : 0;
   const int flags = CFS_HIP_FLAG_NO_CALIBRATE | (m->P.deterministic ? CFS_HIP_FLAG_DETERMINISTIC : 0) |
                     (refreshable ? CFS_HIP_FLAG_KEEP_VALUE_MAP : 0);
   h->ok_x = h->ok_y = nullptr;
-  int rc = a->build(h, n, rowptr, colind, values, flags,
-                    [](int ln, const int *rp, const int *ci, const V *va, int fl, cfs_hip_sym_s **lh) {
-                      cfs_hip_options o = {0, 0, 0, fl};
-                      return sym_create<V>(ln, rp, ci, va, 1, 0, nullptr, &o, lh);
-                    });
-  if (rc) return rc; // (the levels built so far go with `a`)
-  *out = a.release();
+  auto make = [&](auto *obj) -> int { // obj: a new cfs_solver::Amg<V, BS>
+    std::unique_ptr<std::remove_pointer_t<decltype(obj)>> a(obj);
+    a->passes = passes, a->degree = degree, a->coarse_max = coarse_max, a->ratio = ratio, a->device = h->device;
+    a->refreshable = refreshable, a->matching = matching, a->on_device = on_device ? 1 : 0;
+    int rc = a->build(h, n, rowptr, colind, values, flags,
+                      [](int ln, const int *rp, const int *ci, const V *va, int fl, cfs_hip_sym_s **lh) {
+                        cfs_hip_options o = {0, 0, 0, fl};
+                        return sym_create<V>(ln, rp, ci, va, 1, 0, nullptr, &o, lh);
+                      });
+    if (rc) return rc; // (the levels built so far go with `a`)
+    *out = a.release();
+    return 0;
+  };
+  switch (block) { // (cfs_hip_amg_create_block_* has checked it)
+  case 2: return make(new cfs_solver::Amg<V, 2>());
+  case 3: return make(new cfs_solver::Amg<V, 3>());
+  case 4: return make(new cfs_solver::Amg<V, 4>());
+  case 6: return make(new cfs_solver::Amg<V, 6>());
+  default: return make(new cfs_solver::Amg<V, 1>());
+  }
+}
+// block = 1: the scalar create with that matching itself
+template <typename V>
+static int amg_create_block(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const V *values, int block, int matching,
+                            const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  if (out) *out = nullptr;
+  if (block != 1 && block != 2 && block != 3 && block != 4 && block != 6)
+    return set_err(CFS_HIP_ERR_ARG, "amg_create_block: block must be 1, 2, 3, 4 or 6, got " + std::to_string(block));
+  if (matching != CFS_HIP_AMG_MATCHING_GREEDY && matching != CFS_HIP_AMG_MATCHING_DOMINANT)
+    return set_err(CFS_HIP_ERR_ARG, "amg_create_block: matching must be CFS_HIP_AMG_MATCHING_GREEDY (0) or CFS_HIP_AMG_MATCHING_DOMINANT (1), got " +
+                                        std::to_string(matching));
+  if (n > 0 && n % block != 0)
+    return set_err(CFS_HIP_ERR_ARG, "amg_create_block: n = " + std::to_string(n) + " is not a multiple of block = " + std::to_string(block) +
+                                        " (a trailing partial node)");
+  return amg_create<V>(h, n, rowptr, colind, values, opt, out, false, matching, false, block);
+}
+int cfs_hip_amg_create_block_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values, int block, int matching,
+                                 const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create_block<double>(h, n, rowptr, colind, values, block, matching, opt, out);
+}
+int cfs_hip_amg_create_block_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values, int block, int matching,
+                                 const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
+  return amg_create_block<float>(h, n, rowptr, colind, values, block, matching, opt, out);
+}
+int cfs_hip_amg_block(cfs_hip_amg_t a, int *block) {
+  if (!a || !block) return set_err(CFS_HIP_ERR_ARG, "amg_block: null argument");
+  *block = a->block();
   return 0;
+}
+int cfs_hip_amg_level_node_weights(cfs_hip_amg_t a, int level, void *W) {
+  if (!a || !W) return set_err(CFS_HIP_ERR_ARG, "amg_level_node_weights: null argument");
+  return a->level_node_weights(level, W);
 }
 int cfs_hip_amg_create_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
                            const cfs_hip_amg_options *opt, cfs_hip_amg_t *out) {
@@ -2449,6 +2491,45 @@ int cfs_hip_debug_amg_coarsen_dominant(int n, const int *rowptr, const int *coli
                                        int *rounds) {
   return amg_coarsen_entry(n, rowptr, colind, values, passes, agg, w, nc, c_rowptr, c_colind, c_values, capacity, c_nnz,
                            CFS_HIP_AMG_MATCHING_DOMINANT, rounds);
+}
+int cfs_hip_debug_amg_coarsen_block(int n, const int *rowptr, const int *colind, const double *values, int block, int passes, int matching,
+                                    int *agg, double *W, int *nc, int *c_rowptr, int *c_colind, double *c_values, long long capacity,
+                                    long long *c_nnz, int *rounds) {
+  if (block != 1 && block != 2 && block != 3 && block != 4 && block != 6)
+    return set_err(CFS_HIP_ERR_ARG, "amg_coarsen_block: block must be 1, 2, 3, 4 or 6, got " + std::to_string(block));
+  if (matching != CFS_HIP_AMG_MATCHING_GREEDY && matching != CFS_HIP_AMG_MATCHING_DOMINANT)
+    return set_err(CFS_HIP_ERR_ARG, "amg_coarsen_block: matching must be CFS_HIP_AMG_MATCHING_GREEDY (0) or CFS_HIP_AMG_MATCHING_DOMINANT (1), got " +
+                                        std::to_string(matching));
+  int own_rounds[3] = {0, 0, 0};
+  if (!rounds) rounds = own_rounds;
+  if (block == 1)
+    return amg_coarsen_entry(n, rowptr, colind, values, passes, agg, W, nc, c_rowptr, c_colind, c_values, capacity, c_nnz, matching,
+                             matching == CFS_HIP_AMG_MATCHING_DOMINANT ? rounds : nullptr);
+  if (n < 0 || !rowptr || !agg || !W || !nc || !c_rowptr || !c_nnz || (n > 0 && rowptr[n] > 0 && (!colind || !values)))
+    return set_err(CFS_HIP_ERR_ARG, "amg_coarsen_block: null argument");
+  if (passes < 1 || passes > 3) return set_err(CFS_HIP_ERR_ARG, "amg_coarsen_block: passes must lie in [1, 3], got " + std::to_string(passes));
+  if (n % block != 0)
+    return set_err(CFS_HIP_ERR_ARG, "amg_coarsen_block: n = " + std::to_string(n) + " is not a multiple of block = " + std::to_string(block) +
+                                        " (a trailing partial node)");
+  cfs_solver::AmgCsr low, coarse;
+  cfs_solver::amg_lower(n, rowptr, colind, values, low);
+  std::vector<int> ag;
+  std::vector<double> wv;
+  long long bad = 0;
+  if (cfs_solver::amg_coarsen_block(low, block, passes, ag, wv, coarse, &bad, matching, rounds))
+    return set_err(CFS_HIP_ERR_ARG, "amg_coarsen_block: node-block multigrid needs positive definite node blocks, " + std::to_string(bad) +
+                                        " of " + std::to_string(n / block) + " blocks of " + std::to_string(block) +
+                                        " rows have an eigenvalue that is zero, negative or not finite (level 0)");
+  *nc = coarse.n;
+  *c_nnz = coarse.nnz();
+  for (int i = 0; i < n; ++i) agg[i] = ag[i];
+  for (size_t k = 0; k < wv.size(); ++k) W[k] = wv[k];
+  for (int i = 0; i <= coarse.n; ++i) c_rowptr[i] = (int)coarse.rp[i];
+  if (coarse.nnz() > capacity || (coarse.nnz() > 0 && (!c_colind || !c_values)))
+    return set_err(CFS_HIP_ERR_ARG, "amg_coarsen_block: the coarse matrix has " + std::to_string(coarse.nnz()) + " entries, room for " +
+                                        std::to_string(capacity));
+  for (long long k = 0; k < coarse.nnz(); ++k) c_colind[k] = coarse.ci[k], c_values[k] = coarse.va[k];
+  return 0;
 }
 
 // a vector argument of the eigensolver entry points: device memory on the handle's device

@@ -71,6 +71,29 @@
 // DEVICE (cfs_hip_amg_create_device_*, cfs_solver_amg_setup.hpp) and gives the host's hierarchy in every bit; build()
 // below is one loop over the levels for both, the host keeping what it kept: the level handles' create path, the dense
 // inverse and the power method's look.
+//
+// THE NODE-BLOCK FORM (cfs_hip_amg_create_block_*, Amg<V, BS> with BS = 2, 3, 4 or 6; amg_coarsen_block) treats the
+// m = n / BS mesh nodes as the units of a level, for multi-dof matrices whose couplings inside a node are as strong as
+// the diagonal.  Per level, with D_i the BS x BS diagonal block of A_l (both triangles):
+//   W_i = D_i^-1/2, the SYMMETRIC root: D_i = Q diag(ev) Q^T by symeig (cyclic Jacobi, fp64), W_i = Q diag(1/sqrt(ev)) Q^T,
+//         its lower triangle computed (the sum over the eigenpairs ascending) and mirrored; an eigenvalue that is not
+//         finite and > 0 refuses the block.  The symmetric root keeps the node's frame -- on H (L x I) H it returns L x I --
+//         where a Cholesky factor would leave a rotation in every off-diagonal block
+//   B = W A_l W, node block by node block: B_ij = (W_i A_ij) W_j for j <= i, every sum over the inner index ascending,
+//         a coupled pair of nodes stored as a full block (zeros included); the upper triangle is the mirror
+//   `passes` rounds of pairwise matching on the NODE graph with n_ij = ||B_ij||_F (the squares added row-major, j <= i,
+//         the other triangle mirrored): amg_match / amg_match_dominant unchanged, so s_ij = n_ij / sqrt(n_ii n_jj);
+//         then B <- Q^T B Q by amg_galerkin with q[i BS + c] = q_node[i] BS + c
+//   agg_l[i BS + c] = agg_node[i] BS + c;  P_l = W Q_1 .. Q_p;  A_{l+1} = the last B, again a node-block matrix
+// Everything else of a level is the scalar form's.  The hierarchy is host-built and not refreshable.  On the device W is
+// kept the way the block-Jacobi inverse is -- packed lower triangle, word t = i (i + 1) / 2 + j of node k at
+// w[t m + k], read by block_apply -- and the aggregate lists and agg hold NODES.  The cycle is the one above with
+//   the smoother in M^-1 A_l, M = blockdiag(A_l):  Precond<V, BS>, cheb_power<V, BS>, cheb_start_kernel<V, BS>, cheb_chain<V, BS>
+//   rc_I = (V)(sum_{i in I, ascending} W_i (r_i - t_i))                          amg_restrict_block_kernel
+//   z_i = (V)(z_i + W_i ec_I)                                                    amg_prolong_block_kernel
+//   d_i = (V)((1/theta) M_i^-1 (r_i - t_i));  z_i = (V)(z_i + d_i)               amg_restart_block_kernel
+// one thread per node, the same 8 + 6 (m - 1) launches; W_i is symmetric and restriction the transpose of prolongation,
+// so M^-1 stays symmetric, and nothing is atomic.
 #pragma once
 
 #include <algorithm>
@@ -94,6 +117,8 @@ struct cfs_hip_amg_s {
   virtual int update_values(const void *values_dev, long long nnz, hipStream_t st) = 0;
   virtual int refresh_info(long long *map_bytes, int *refreshes, double *last_seconds, double *split) = 0;
   virtual int setup_info(int *matching, int *on_device, int *rounds, double *seconds, long long *scratch_bytes) = 0;
+  virtual int block() const = 0; // rows per node: 1, or the BS of a node-block hierarchy
+  virtual int level_node_weights(int level, void *W) = 0;
 };
 
 namespace cfs_solver {
@@ -449,6 +474,162 @@ inline int amg_coarsen(const AmgCsr &low, int passes, std::vector<int> &agg, std
   return 0;
 }
 
+// ---- the node-block form of a level (see THE NODE-BLOCK FORM in the header comment) ------------------
+// the node blocks of row i of a lower triangle + diagonal whose n is a multiple of bs: cols <- the node columns j <= i,
+// ascending; blk <- per column the bs x bs block, row-major, zeros where nothing is stored, the diagonal block mirrored
+// into both triangles.  slot: m entries of -1, restored on return
+inline void amg_node_row(const AmgCsr &low, int bs, int i, std::vector<int> &slot, std::vector<int> &cols, std::vector<double> &blk) {
+  const size_t bb = (size_t)bs * bs;
+  std::vector<int> seen;
+  std::vector<double> raw;
+  for (int c = 0; c < bs; ++c) {
+    const int row = i * bs + c;
+    for (long long k = low.rp[row]; k < low.rp[(size_t)row + 1]; ++k) {
+      const int j = low.ci[k] / bs, d = low.ci[k] % bs;
+      if (slot[j] < 0) {
+        slot[j] = (int)seen.size();
+        seen.push_back(j);
+        raw.resize(raw.size() + bb, 0.0);
+      }
+      raw[(size_t)slot[j] * bb + (size_t)c * bs + d] = low.va[k];
+    }
+  }
+  cols = seen;
+  std::sort(cols.begin(), cols.end());
+  blk.resize(raw.size());
+  for (size_t s = 0; s < cols.size(); ++s) std::copy_n(&raw[(size_t)slot[cols[s]] * bb], bb, &blk[s * bb]);
+  if (!cols.empty() && cols.back() == i) {
+    double *dg = &blk[(cols.size() - 1) * bb];
+    for (int c = 0; c < bs; ++c)
+      for (int d = 0; d < c; ++d) dg[(size_t)d * bs + c] = dg[(size_t)c * bs + d];
+  }
+  for (int j : seen) slot[j] = -1;
+}
+
+// W_i = D_i^-1/2 of every node block, m x bs x bs row-major, exactly symmetric; returns the blocks with an eigenvalue
+// that is not finite and > 0 (their W_i is left zero)
+inline long long amg_node_weights(const AmgCsr &low, int bs, std::vector<double> &W) {
+  const int m = low.n / bs;
+  const size_t bb = (size_t)bs * bs;
+  W.assign((size_t)m * bb, 0.0);
+  std::vector<int> slot((size_t)m, -1), cols;
+  std::vector<double> blk, ev((size_t)bs), Q(bb), dz(bb, 0.0);
+  long long bad = 0;
+  for (int i = 0; i < m; ++i) {
+    amg_node_row(low, bs, i, slot, cols, blk);
+    const double *D = !cols.empty() && cols.back() == i ? &blk[(cols.size() - 1) * bb] : dz.data();
+    bool ok = true;
+    for (size_t k = 0; k < bb; ++k) ok = ok && D[k] * 0.0 == 0.0; // (symeig is given finite numbers only)
+    if (ok) ok = symeig(bs, D, ev.data(), Q.data()) >= 0;
+    for (int k = 0; ok && k < bs; ++k) ok = ev[k] > 0.0 && ev[k] * 0.0 == 0.0;
+    if (!ok) {
+      bad += 1;
+      continue;
+    }
+    double *Wi = &W[(size_t)i * bb];
+    for (int k = 0; k < bs; ++k) ev[k] = 1.0 / std::sqrt(ev[k]);
+    for (int c = 0; c < bs; ++c)
+      for (int d = 0; d <= c; ++d) {
+        double s = 0.0;
+        for (int k = 0; k < bs; ++k) s += (Q[(size_t)c * bs + k] * ev[k]) * Q[(size_t)d * bs + k];
+        Wi[(size_t)c * bs + d] = Wi[(size_t)d * bs + c] = s;
+      }
+  }
+  return bad;
+}
+
+// the lower triangle + diagonal of B = W A W: B_ij = (W_i A_ij) W_j for the node pairs j <= i of `low`, full blocks
+inline void amg_scale_block(const AmgCsr &low, int bs, const std::vector<double> &W, AmgCsr &out) {
+  const int m = low.n / bs;
+  const size_t bb = (size_t)bs * bs;
+  std::vector<int> slot((size_t)m, -1), cols;
+  std::vector<double> blk, T(bb), B;
+  out.n = low.n;
+  out.rp.assign((size_t)low.n + 1, 0);
+  out.ci.clear();
+  out.va.clear();
+  for (int i = 0; i < m; ++i) {
+    amg_node_row(low, bs, i, slot, cols, blk);
+    B.resize(blk.size());
+    const double *Wi = &W[(size_t)i * bb];
+    for (size_t s = 0; s < cols.size(); ++s) {
+      const double *A = &blk[s * bb], *Wj = &W[(size_t)cols[s] * bb];
+      for (int c = 0; c < bs; ++c)
+        for (int d = 0; d < bs; ++d) {
+          double v = 0.0;
+          for (int k = 0; k < bs; ++k) v += Wi[(size_t)c * bs + k] * A[(size_t)k * bs + d];
+          T[(size_t)c * bs + d] = v;
+        }
+      for (int c = 0; c < bs; ++c)
+        for (int d = 0; d < bs; ++d) {
+          double v = 0.0;
+          for (int k = 0; k < bs; ++k) v += T[(size_t)c * bs + k] * Wj[(size_t)k * bs + d];
+          B[s * bb + (size_t)c * bs + d] = v;
+        }
+    }
+    for (int c = 0; c < bs; ++c) {
+      for (size_t s = 0; s < cols.size(); ++s)
+        for (int d = 0; d < bs && cols[s] * bs + d <= i * bs + c; ++d) {
+          out.ci.push_back(cols[s] * bs + d);
+          out.va.push_back(B[s * bb + (size_t)c * bs + d]);
+        }
+      out.rp[(size_t)i * bs + c + 1] = (long long)out.ci.size();
+    }
+  }
+}
+
+// the node graph of a lower triangle + diagonal, both triangles: entry (i, j) = ||B_ij||_F, computed for j <= i (the
+// squares added row-major over the full block) and mirrored -- what amg_match and amg_match_dominant are given
+inline void amg_node_graph(const AmgCsr &low, int bs, AmgCsr &graph) {
+  const int m = low.n / bs;
+  const size_t bb = (size_t)bs * bs;
+  std::vector<int> slot((size_t)m, -1), cols;
+  std::vector<double> blk;
+  AmgCsr g;
+  g.n = m;
+  g.rp.assign((size_t)m + 1, 0);
+  for (int i = 0; i < m; ++i) {
+    amg_node_row(low, bs, i, slot, cols, blk);
+    for (size_t s = 0; s < cols.size(); ++s) {
+      double f = 0.0;
+      for (size_t k = 0; k < bb; ++k) f += blk[s * bb + k] * blk[s * bb + k];
+      g.ci.push_back(cols[s]);
+      g.va.push_back(std::sqrt(f));
+    }
+    g.rp[(size_t)i + 1] = (long long)g.ci.size();
+  }
+  amg_mirror(g, nullptr, graph);
+}
+
+// one level of the node-block form: agg (per unknown), W (m x bs x bs) and the lower triangle + diagonal of A_{l+1} from
+// that of A_l, low.n a multiple of bs.  *bad: node blocks that are not positive definite (then -1 is returned)
+inline int amg_coarsen_block(const AmgCsr &low, int bs, int passes, std::vector<int> &agg, std::vector<double> &W, AmgCsr &coarse,
+                             long long *bad, int matching = CFS_HIP_AMG_MATCHING_GREEDY, int *rounds = nullptr) {
+  const int n = low.n, m = n / bs;
+  *bad = amg_node_weights(low, bs, W);
+  if (*bad) return -1;
+  AmgCsr cur, B, graph, next;
+  amg_scale_block(low, bs, W, cur);
+  std::vector<int> nagg((size_t)m), qn, q;
+  for (int i = 0; i < m; ++i) nagg[i] = i;
+  for (int p = 0; p < passes; ++p) {
+    amg_node_graph(cur, bs, graph);
+    const int nc = matching == CFS_HIP_AMG_MATCHING_DOMINANT ? amg_match_dominant(graph, qn, rounds ? rounds + p : nullptr) : amg_match(graph, qn);
+    q.resize((size_t)cur.n);
+    for (int i = 0; i < cur.n / bs; ++i)
+      for (int c = 0; c < bs; ++c) q[(size_t)i * bs + c] = qn[i] * bs + c;
+    amg_mirror(cur, nullptr, B);
+    amg_galerkin(B, q, nc * bs, next);
+    for (int i = 0; i < m; ++i) nagg[i] = qn[nagg[i]];
+    cur = std::move(next);
+  }
+  agg.resize((size_t)n);
+  for (int i = 0; i < m; ++i)
+    for (int c = 0; c < bs; ++c) agg[(size_t)i * bs + c] = nagg[i] * bs + c;
+  coarse = std::move(cur);
+  return 0;
+}
+
 // the inverse of a dense level from its lower triangle + diagonal: A = L L^T in fp64, the columns by two triangular
 // solves each, then (X + X^T) / 2.  Returns the first pivot that is not finite and > 0, or -1
 inline int amg_dense_inverse(const AmgCsr &low, std::vector<double> &inv) {
@@ -544,6 +725,76 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// ---- the node-block transfers: one thread per node, W and M^-1 packed as cg_binv_kernel packs, read by block_apply ----
+// rc_I = (V)(sum over the member nodes i of aggregate I, ascending, of W_i (r_i - t_i)): one thread per coarse node;
+// m: the nodes of the fine level (the stride of the packed W)
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    amg_restrict_block_kernel(V *__restrict__ rc, const V *__restrict__ r, const V *__restrict__ t, const V *__restrict__ w, long long m,
+                              const int *__restrict__ aggptr, const int *__restrict__ aggidx, long long nc, const int *__restrict__ ic) {
+  if (ic[I_DONE]) return;
+  for (long long I = (long long)blockIdx.x * kThreads + threadIdx.x; I < nc; I += (long long)gridDim.x * kThreads) {
+    double s[BS];
+#pragma unroll
+    for (int c = 0; c < BS; ++c) s[c] = 0.0;
+    for (int k = aggptr[I]; k < aggptr[I + 1]; ++k) {
+      const long long i = aggidx[k];
+      double x[BS], y[BS];
+#pragma unroll
+      for (int c = 0; c < BS; ++c) x[c] = (double)r[i * BS + c] - (double)t[i * BS + c];
+      block_apply<V, BS>(w, m, i, x, y);
+#pragma unroll
+      for (int c = 0; c < BS; ++c) s[c] += y[c];
+    }
+#pragma unroll
+    for (int c = 0; c < BS; ++c) rc[I * BS + c] = (V)s[c];
+  }
+}
+
+// z_i = (V)(z_i + W_i ec_I), I = agg[i] the coarse NODE of node i: one thread per fine node
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    amg_prolong_block_kernel(V *__restrict__ z, const V *__restrict__ ec, const V *__restrict__ w, const int *__restrict__ agg, long long m,
+                             const int *__restrict__ ic) {
+  if (ic[I_DONE]) return;
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < m; i += (long long)gridDim.x * kThreads) {
+    const long long I = agg[i];
+    double e[BS], y[BS];
+#pragma unroll
+    for (int c = 0; c < BS; ++c) e[c] = (double)ec[I * BS + c];
+    block_apply<V, BS>(w, m, i, e, y);
+#pragma unroll
+    for (int c = 0; c < BS; ++c) z[i * BS + c] = (V)((double)z[i * BS + c] + y[c]);
+  }
+}
+
+// amg_restart_kernel with M = blockdiag(A_l):  d_k = (V)((1 / theta) Minv_k (r_k - t_k));  z_k = (V)(z_k + d_k), the
+// inverse applied as cheb_start_kernel<V, BS> applies it
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    amg_restart_block_kernel(V *__restrict__ z, V *__restrict__ d, const V *__restrict__ r, const V *__restrict__ t, long long n,
+                             double inv_theta, const V *__restrict__ minv, long long nb, const int *__restrict__ ic) {
+  if (ic[I_DONE]) return;
+  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+    double x[BS], zz[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      const long long g = k * BS + i;
+      x[i] = g < n ? (double)r[g] - (double)t[g] : 0.0;
+    }
+    block_apply<V, BS>(minv, nb, k, x, zz);
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      const long long g = k * BS + i;
+      if (g < n) {
+        const V di = (V)(inv_theta * zz[i]);
+        d[g] = di;
+        z[g] = (V)((double)z[g] + (double)di);
+      }
+    }
+  }
+}
+
 // z = (V)(inv r) on the dense level: one wave per row, the lanes stride over the columns, a fixed-order sum
 template <typename V>
 __global__ void __launch_bounds__(kThreads)
@@ -612,13 +863,14 @@ __global__ void __launch_bounds__(kThreads)
 enum AmgKind { AMG_MULTIGRID = 0, AMG_SMOOTHER = 1, AMG_DENSE = 2 };
 enum AmgPhase { AMG_T_GALERKIN = 0, AMG_T_POUR, AMG_T_POWER, AMG_T_DENSE, AMG_T_COUNT }; // the split of a refresh's time
 
-template <typename V> struct AmgLevel {
+template <typename V, int BS = 1> struct AmgLevel {
   int n = 0, nc = 0, kind = AMG_MULTIGRID;
   long long nnz = 0;
   double lmin = 0.0, lmax = 0.0, theta = 1.0, c1[kChebMaxDegree], c2[kChebMaxDegree];
   cfs_hip_sym_s *h = nullptr;
   bool owned = false;
-  Precond<V, 1> pre; // dinv of a level that smooths
+  Precond<V, BS> pre; // dinv (BS >= 2: the packed inverse node blocks) of a level that smooths
+  // (BS >= 2: aggptr, aggidx and agg hold NODES, w the packed W_i)
   cfs_rt::DevBuf aggptr, aggidx, agg, w, r, z, d, t, inv;
   // the CSR the level's handle was created from (levels >= 1): lower triangle + diagonal, values in V
   std::vector<int> rp, ci;
@@ -646,8 +898,8 @@ template <typename V> struct AmgLevel {
 #include "cfs_solver_amg_setup.hpp" // a level coarsened on the device: AmgDeviceSetup
 namespace cfs_solver {
 
-template <typename V> struct Amg : cfs_hip_amg_s {
-  using Level = AmgLevel<V>;
+template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
+  using Level = AmgLevel<V, BS>;
   std::vector<std::unique_ptr<Level>> lv;
   Slots part;         // the partial-sum slots the smoother's kernels are handed
   cfs_rt::DevBuf cnt; // a done flag that is never set
@@ -690,7 +942,7 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     // a device set-up holds the level on the device; `cur` is then the coarse CSR it brought down (levels >= 1), or
     // amg_lower's when level 0 is the last one
     std::unique_ptr<AmgDeviceSetup<V>> dev;
-    if (on_device && n > coarse_max) {
+    if (BS == 1 && on_device && n > coarse_max) {
       dev.reset(new AmgDeviceSetup<V>());
       if ((rc = dev->begin(n, rowptr, colind, values, st))) return rc;
       if (dev->host_lower) on_device = 2;
@@ -701,6 +953,12 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     auto bad_diagonal = [](long long bad, int rows, int l) {
       return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_create: Jacobi needs a positive diagonal, " + std::to_string(bad) + " of " +
                                                   std::to_string(rows) + " entries are zero, negative or not finite (level " +
+                                                  std::to_string(l) + ")");
+    };
+    auto bad_blocks = [](long long bad, int rows, int l) {
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_create: node-block multigrid needs positive definite node blocks, " + std::to_string(bad) +
+                                                  " of " + std::to_string(rows / BS) + " blocks of " + std::to_string(BS) +
+                                                  " rows have an eigenvalue that is zero, negative or not finite (level " +
                                                   std::to_string(l) + ")");
     };
     std::vector<int> agg;
@@ -742,7 +1000,9 @@ template <typename V> struct Amg : cfs_hip_amg_s {
       bool last = L.n <= coarse_max;
       L.kind = last ? AMG_DENSE : AMG_MULTIGRID;
       if (!last) {
-        if (dev) {
+        if constexpr (BS >= 2) {
+          if (amg_coarsen_block(cur, BS, passes, agg, w, next, &bad, matching, rounds[l])) return bad_blocks(bad, L.n, l);
+        } else if (dev) {
           if ((rc = dev->coarsen(L, passes, &bad, next, rounds[l]))) return rc == 1 ? bad_diagonal(bad, L.n, l) : rc;
         } else if (amg_coarsen(cur, passes, agg, w, next, &bad, refreshable ? &frozen : nullptr, matching, rounds[l])) {
           return cfs_rt::set_err(CFS_HIP_ERR_INTERNAL, "amg_create: the diagonal changed");
@@ -790,15 +1050,27 @@ template <typename V> struct Amg : cfs_hip_amg_s {
         cur = std::move(next);
         continue;
       }
-      std::vector<int> ptr((size_t)next.n + 1, 0), idx((size_t)cur.n);
-      for (int i = 0; i < cur.n; ++i) ptr[(size_t)agg[i] + 1] += 1;
-      for (int I = 0; I < next.n; ++I) ptr[(size_t)I + 1] += ptr[I];
+      std::vector<V> wv;
+      if constexpr (BS >= 2) { // the lists and agg over the nodes; W packed as cg_binv_kernel packs the inverse
+        const int m = cur.n / BS;
+        for (int i = 0; i < m; ++i) agg[i] = agg[(size_t)i * BS] / BS;
+        agg.resize((size_t)m);
+        wv.resize((size_t)m * tri_words(BS));
+        for (int i = 0; i < m; ++i)
+          for (int c = 0; c < BS; ++c)
+            for (int e = 0; e <= c; ++e) wv[(size_t)(c * (c + 1) / 2 + e) * m + i] = (V)w[((size_t)i * BS + c) * BS + e];
+      } else {
+        wv.resize((size_t)cur.n);
+        for (int i = 0; i < cur.n; ++i) wv[i] = (V)w[i];
+      }
+      const int units = cur.n / BS, cunits = next.n / BS; // rows, or nodes
+      std::vector<int> ptr((size_t)cunits + 1, 0), idx((size_t)units);
+      for (int i = 0; i < units; ++i) ptr[(size_t)agg[i] + 1] += 1;
+      for (int I = 0; I < cunits; ++I) ptr[(size_t)I + 1] += ptr[I];
       {
         std::vector<int> pos(ptr.begin(), ptr.end() - 1);
-        for (int i = 0; i < cur.n; ++i) idx[pos[agg[i]]++] = i; // (rows ascending: members ascending)
+        for (int i = 0; i < units; ++i) idx[pos[agg[i]]++] = i; // (rows ascending: members ascending)
       }
-      std::vector<V> wv((size_t)cur.n);
-      for (int i = 0; i < cur.n; ++i) wv[i] = (V)w[i];
       if ((rc = L.aggptr.upload(ptr.data(), ptr.size() * sizeof(int))) || (rc = L.aggidx.upload(idx.data(), idx.size() * sizeof(int))) ||
           (rc = L.agg.upload(agg.data(), agg.size() * sizeof(int))) || (rc = L.w.upload(wv.data(), wv.size() * sizeof(V))))
         return rc;
@@ -974,9 +1246,10 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     double est = 0.0;
     int rc;
     if ((rc = alloc_vectors<V>(n, {&L.d, &L.t})) || (rc = L.pre.setup(L.h, part.dev(), st)) || (rc = alloc_vectors<V>(n, {&vbuf})) ||
-        (rc = cheb_power<V, 1>(L.h, (V *)L.d.p, (V *)L.t.p, (V *)vbuf.p, (const V *)nullptr, n, 16, lpart, L.pre.minv(), 0LL, &est, st)) ||
+        (rc = cheb_power<V, BS>(L.h, (V *)L.d.p, (V *)L.t.p, (V *)vbuf.p, (const V *)nullptr, n, 16, lpart, L.pre.minv(), L.pre.nb, &est, st)) ||
         (rc = part.fetch()) || (rc = L.pre.check("amg_create", part, n)))
       return rc;
+    L.pre.blkbuf = cfs_rt::DevBuf(); // (the gathered blocks of BS >= 2 have been inverted: the stream is idle after the fetch)
     if (!(est > 0.0) || est * 0.0 != 0.0)
       return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_create: the power method gave no positive estimate of lambda_max(D^-1 A) on a level of " +
                                                   std::to_string(n) + " rows (" + std::to_string(est) + ")");
@@ -997,20 +1270,33 @@ template <typename V> struct Amg : cfs_hip_amg_s {
     }
     V *d = (V *)L.d.p, *t = (V *)L.t.p;
     const V *dinv = L.pre.minv();
+    const long long nb = L.pre.nb; // the nodes of the level (BS >= 2), else 0
     int rc;
-    hipLaunchKernelGGL((cheb_start_kernel<V, 1>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, n, 1.0 / L.theta, -1, pp, dinv, 0LL);
-    if ((rc = cheb_chain<V, 1>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, 0LL, st))) return rc;
+    hipLaunchKernelGGL((cheb_start_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, n, 1.0 / L.theta, -1, pp, dinv, nb);
+    if ((rc = cheb_chain<V, BS>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, nb, st))) return rc;
     if (L.kind == AMG_SMOOTHER) return 0;
     Level &C = *lv[l + 1];
     if ((rc = L.h->spmv_local(t, z, nullptr, st))) return rc;
-    hipLaunchKernelGGL((amg_restrict_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)C.r.p, r, (const V *)t, (const V *)L.w.p,
-                       (const int *)L.aggptr.p, (const int *)L.aggidx.p, (long long)L.nc, ic);
+    if constexpr (BS >= 2)
+      hipLaunchKernelGGL((amg_restrict_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)C.r.p, r, (const V *)t,
+                         (const V *)L.w.p, nb, (const int *)L.aggptr.p, (const int *)L.aggidx.p, (long long)(L.nc / BS), ic);
+    else
+      hipLaunchKernelGGL((amg_restrict_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)C.r.p, r, (const V *)t, (const V *)L.w.p,
+                         (const int *)L.aggptr.p, (const int *)L.aggidx.p, (long long)L.nc, ic);
     if ((rc = cycle(l + 1, (V *)C.z.p, (const V *)C.r.p, ic, st))) return rc;
-    hipLaunchKernelGGL((amg_prolong_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, (const V *)C.z.p, (const V *)L.w.p,
-                       (const int *)L.agg.p, n, ic);
-    if ((rc = L.h->spmv_local(t, z, nullptr, st))) return rc;
-    hipLaunchKernelGGL((amg_restart_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, (const V *)t, n, 1.0 / L.theta, dinv, ic);
-    return cheb_chain<V, 1>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, 0LL, st);
+    if constexpr (BS >= 2) {
+      hipLaunchKernelGGL((amg_prolong_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, z, (const V *)C.z.p, (const V *)L.w.p,
+                         (const int *)L.agg.p, nb, ic);
+      if ((rc = L.h->spmv_local(t, z, nullptr, st))) return rc;
+      hipLaunchKernelGGL((amg_restart_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, (const V *)t, n, 1.0 / L.theta,
+                         dinv, nb, ic);
+    } else {
+      hipLaunchKernelGGL((amg_prolong_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, (const V *)C.z.p, (const V *)L.w.p,
+                         (const int *)L.agg.p, n, ic);
+      if ((rc = L.h->spmv_local(t, z, nullptr, st))) return rc;
+      hipLaunchKernelGGL((amg_restart_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, (const V *)t, n, 1.0 / L.theta, dinv, ic);
+    }
+    return cheb_chain<V, BS>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, nb, st);
   }
 
   int apply(void *z_dev, const void *r_dev, hipStream_t st) override {
@@ -1058,8 +1344,43 @@ template <typename V> struct Amg : cfs_hip_amg_s {
                                                   std::to_string(lv.size()) + " levels)");
     const Level &L = *lv[level];
     cfs_rt::DeviceGuard g(device);
+    if constexpr (BS >= 2) { // the device holds the map of the nodes: agg[i BS + c] = agg_node[i] BS + c
+      if (w)
+        return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_level_aggregates: a node-block hierarchy has no scalar weights, w must be NULL "
+                                                "(cfs_hip_amg_level_node_weights returns its W)");
+      if (agg) {
+        const size_t m = (size_t)L.n / BS;
+        std::vector<int> nagg(m);
+        HIPCHK(hipMemcpy(nagg.data(), L.agg.p, m * sizeof(int), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < m; ++i)
+          for (int c = 0; c < BS; ++c) agg[i * BS + c] = nagg[i] * BS + c;
+      }
+      return 0;
+    }
     if (agg) HIPCHK(hipMemcpy(agg, L.agg.p, (size_t)L.n * sizeof(int), hipMemcpyDeviceToHost));
     if (w) HIPCHK(hipMemcpy(w, L.w.p, (size_t)L.n * sizeof(V), hipMemcpyDeviceToHost));
+    return 0;
+  }
+
+  int block() const override { return BS; }
+
+  // W of a level that has a coarser one as m full row-major blocks, unpacked from what the kernels read
+  int level_node_weights(int level, void *W) override {
+    if (BS == 1)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_level_node_weights: the hierarchy was not made by cfs_hip_amg_create_block_* with "
+                                              "block > 1 (cfs_hip_amg_level_aggregates returns its w)");
+    if (level < 0 || level + 1 >= (int)lv.size())
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_level_node_weights: level " + std::to_string(level) + " has no coarser level (" +
+                                                  std::to_string(lv.size()) + " levels)");
+    const Level &L = *lv[level];
+    const size_t m = (size_t)L.n / BS;
+    std::vector<V> packed(m * tri_words(BS));
+    cfs_rt::DeviceGuard g(device);
+    HIPCHK(hipMemcpy(packed.data(), L.w.p, packed.size() * sizeof(V), hipMemcpyDeviceToHost));
+    V *out = (V *)W;
+    for (size_t i = 0; i < m; ++i)
+      for (int c = 0; c < BS; ++c)
+        for (int e = 0; e <= c; ++e) out[(i * BS + c) * BS + e] = out[(i * BS + e) * BS + c] = packed[(size_t)(c * (c + 1) / 2 + e) * m + i];
     return 0;
   }
 

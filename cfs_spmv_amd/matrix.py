@@ -391,7 +391,7 @@ class SymMatrix:
         return est.value
 
     def amg(self, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512, refreshable=False, matching="greedy",
-            setup="host"):
+            setup="host", block=1):
         """the aggregation multigrid hierarchy of this matrix (cfs_hip_amg_create_*), an Amg: rowptr, colind, values
         are the CSR the handle was created from (only entries with col <= row are read; the caller vouches that it is
         this handle's matrix).  passes 1 .. 3 rounds of pairwise matching per level, degree 1 .. 4 of the Chebyshev
@@ -403,9 +403,13 @@ class SymMatrix:
         locally dominant matching of cfs_hip.h, parallel by definition: usually more iterations, and the only one with
         setup="device", where the hierarchy is built by kernels on the device -- the hierarchy of matching="dominant",
         setup="host" in every bit, in a fraction of the time).  setup="device" with matching="greedy" and a refreshable
-        hierarchy with matching="dominant" do not exist: ValueError."""
+        hierarchy with matching="dominant" do not exist: ValueError.
+        block = 2, 3, 4 or 6: the node-block form (cfs_hip_amg_create_block_*) for a multi-dof mesh matrix whose
+        `block` consecutive rows are one node -- the nodes are aggregated, the transfers carry W_i = D_i^-1/2 of the node
+        blocks and the smoother is block Jacobi; n must be a multiple of block.  Host-built and not refreshable:
+        refreshable=True or setup="device" with block > 1 is a ValueError.  pcg_amg() and Amg.apply() take it unchanged."""
         return Amg(self, rowptr, colind, values, passes=passes, degree=degree, ratio=ratio, coarse_max=coarse_max,
-                   refreshable=refreshable, matching=matching, setup=setup)
+                   refreshable=refreshable, matching=matching, setup=setup, block=block)
 
     def pcg_amg(self, u, b, amg, tol=1e-10, maxiter=1000, check_every=1, stream=None):
         """PCG with one V-cycle of `amg` (self.amg(...)) as the preconditioner (cfs_hip_sym_pcg_amg): like
@@ -602,9 +606,11 @@ class Amg:
     to its matrix, which must stay open for as long as the hierarchy is used."""
 
     def __init__(self, A, rowptr, colind, values, passes=2, degree=1, ratio=4.0, coarse_max=512, refreshable=False,
-                 matching="greedy", setup="host"):
+                 matching="greedy", setup="host", block=1):
         if matching not in ("greedy", "dominant") or setup not in ("host", "device"):
             raise ValueError(f'matching is "greedy" or "dominant" and setup "host" or "device", got {matching!r}, {setup!r}')
+        if block != 1 and (refreshable or setup == "device"):
+            raise ValueError(f"a node-block hierarchy (block={block}) is built on the host and is not refreshable")
         if setup == "device" and matching == "greedy":
             raise ValueError('setup="device" needs matching="dominant": the greedy matching has no parallel form')
         if refreshable and matching != "greedy":
@@ -618,16 +624,23 @@ class Amg:
         suf = "f64" if self.dtype == np.float64 else "f32"
         self.refreshable = bool(refreshable)
         kind = "refreshable_" if refreshable else "device_" if setup == "device" else "dominant_" if matching == "dominant" else ""
+        if block != 1:  # (block = 1 through this entry point is the scalar create itself; the scalar names stay in use)
+            create = getattr(lib, "cfs_hip_amg_create_block_" + suf)
+            _lib.check(create(A._h, A.n, rowptr.ctypes.data, colind.ctypes.data, values.ctypes.data, int(block),
+                              1 if matching == "dominant" else 0, C.byref(opt), C.byref(self._a)))
+            return
         create = getattr(lib, "cfs_hip_amg_create_" + kind + suf)
         _lib.check(create(A._h, A.n, rowptr.ctypes.data, colind.ctypes.data, values.ctypes.data, C.byref(opt), C.byref(self._a)))
 
     def info(self):
         """dict: levels, the options used, device_bytes, setup_seconds (of which handles_seconds for the create path
-        of the level handles), and per level n, nnz (stored), lmin, lmax, kind (0 multigrid, 1 smoother-only,
-        2 dense)"""
-        out = _lib.AmgInfo()
-        _lib.check(_lib.load().cfs_hip_amg_info(self._a, C.byref(out)))
-        return out.asdict()
+        of the level handles), per level n, nnz (stored), lmin, lmax, kind (0 multigrid, 1 smoother-only,
+        2 dense), and block, the rows per node (1: the scalar form)"""
+        out, blk = _lib.AmgInfo(), C.c_int()
+        lib = _lib.load()
+        _lib.check(lib.cfs_hip_amg_info(self._a, C.byref(out)))
+        _lib.check(lib.cfs_hip_amg_block(self._a, C.byref(blk)))
+        return dict(out.asdict(), block=blk.value)
 
     def setup_info(self):
         """dict (cfs_hip_amg_setup_info): matching ("greedy" / "dominant"), setup ("host" / "device"), lower_on_host (a
@@ -671,10 +684,24 @@ class Amg:
     def aggregates(self, level):
         """(agg, w) of a level that has a coarser one, as the device holds them: the aggregate of every row and the
         weights in the value type"""
-        n = self.info()["n"][level] if 0 <= level < self.info()["levels"] else 0
+        inf = self.info()
+        n = inf["n"][level] if 0 <= level < inf["levels"] else 0
         agg, w = np.zeros(n, np.int32), np.zeros(n, self.dtype)
+        if inf["block"] != 1:  # (agg is the map of the unknowns; the weights are node_weights())
+            _lib.check(_lib.load().cfs_hip_amg_level_aggregates(self._a, int(level), agg.ctypes.data, None))
+            return agg, None
         _lib.check(_lib.load().cfs_hip_amg_level_aggregates(self._a, int(level), agg.ctypes.data, w.ctypes.data))
         return agg, w
+
+    def node_weights(self, level):
+        """W of a level of a node-block hierarchy that has a coarser one (cfs_hip_amg_level_node_weights): an
+        (n_l / block, block, block) array of the symmetric W_i = D_i^-1/2 in the value type, as the device holds them"""
+        inf = self.info()
+        bs = inf["block"]
+        n = inf["n"][level] if 0 <= level < inf["levels"] else 0
+        W = np.zeros((n // bs, bs, bs), self.dtype)
+        _lib.check(_lib.load().cfs_hip_amg_level_node_weights(self._a, int(level), W.ctypes.data))
+        return W
 
     def level_matrix(self, level):
         """(n, rowptr, colind, values) of level >= 1: the lower triangle + diagonal its handle was created from"""
@@ -710,15 +737,33 @@ class Amg:
             pass
 
 
-def coarsen(n, rowptr, colind, values, passes=2, matching="greedy", rounds=None):
+def coarsen(n, rowptr, colind, values, passes=2, matching="greedy", rounds=None, block=1):
     """host only: one level of the multigrid set-up (cfs_hip_debug_amg_coarsen, or cfs_hip_debug_amg_coarsen_dominant
     with matching="dominant").  Returns (agg, w, (nc, rowptr, colind, values)): the aggregate of every row, the weights
     1 / sqrt(a_ii) and the lower triangle + diagonal of the coarse matrix, all in fp64.  rounds (a list, dominant only):
-    receives the rounds every pass ran"""
+    receives the rounds every pass ran.  block != 1: one level of the node-block form (cfs_hip_debug_amg_coarsen_block);
+    w is then W, an (n / block, block, block) array of the symmetric W_i = D_i^-1/2, and agg the map of the unknowns"""
     if matching not in ("greedy", "dominant"):
         raise ValueError(f'matching is "greedy" or "dominant", got {matching!r}')
     rowptr, colind = _np_i32(rowptr), _np_i32(colind)
     values = np.ascontiguousarray(values, dtype=np.float64)
+    if block != 1:
+        bs = int(block)
+        cap = 0
+        if bs > 1 and n > 0 and int(rowptr[n]) > 0:  # a coupled pair of nodes is a full block of the coarse matrix
+            rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rowptr[:n + 1]))
+            cols = colind[:int(rowptr[n])].astype(np.int64)
+            low = (cols >= 0) & (cols <= rows)
+            cap = bs * bs * int(np.unique((rows[low] // bs) * (n // bs + 1) + cols[low] // bs).size)
+        agg, W = np.zeros(max(n, 0), np.int32), np.zeros((max(n, 0) // max(bs, 1), max(bs, 1), max(bs, 1)), np.float64)
+        crp, cci, cva = np.zeros(max(n, 0) + 1, np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float64)
+        nc, nnz, rnd = C.c_int(), C.c_longlong(), (C.c_int * 3)()
+        _lib.check(_lib.load().cfs_hip_debug_amg_coarsen_block(
+            n, rowptr.ctypes.data, colind.ctypes.data, values.ctypes.data, bs, int(passes), 1 if matching == "dominant" else 0,
+            agg.ctypes.data, W.ctypes.data, C.byref(nc), crp.ctypes.data, cci.ctypes.data, cva.ctypes.data, cap, C.byref(nnz), rnd))
+        if rounds is not None and matching == "dominant":
+            rounds[:] = list(rnd)[:int(passes)]
+        return agg, W, (nc.value, crp[:nc.value + 1].copy(), cci[:nnz.value].copy(), cva[:nnz.value].copy())
     cap = int(rowptr[n]) if n > 0 else 0
     agg, w = np.zeros(n, np.int32), np.zeros(n, np.float64)
     crp, cci, cva = np.zeros(n + 1, np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float64)

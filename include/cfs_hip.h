@@ -473,9 +473,9 @@ int cfs_hip_sym_precond_lmax(cfs_hip_sym_t h, int block_rows, int steps, const v
 int cfs_hip_debug_cheb_coeffs(int degree, double lmin, double lmax, double *theta, double *c1, double *c2);
 /* ---- aggregation multigrid: a V-cycle as the preconditioner of the native PCG ------------------------------------
  * For scalar problems whose condition number, not their size, is the cost: the iteration count of every solver above
- * grows with its square root, a multilevel cycle removes the low end of the spectrum.  (Block / node smoothers are not
- * part of it: on a multi-dof matrix whose couplings inside a node are as strong as the diagonal, block Jacobi does
- * better.)  CFS_HIP_ABI_VERSION is unchanged; callers detect the symbols.
+ * grows with its square root, a multilevel cycle removes the low end of the spectrum.  (On a multi-dof matrix whose
+ * couplings inside a node are as strong as the diagonal use the node-block form, cfs_hip_amg_create_block_* below: this
+ * one does worse than block Jacobi there.)  CFS_HIP_ABI_VERSION is unchanged; callers detect the symbols.
  * THE HIERARCHY, built on the host in fp64 from the caller's CSR (as for cfs_hip_sym_create_*: only entries with
  * col <= row are read).  Per level l, A_0 = A:  w_i = 1 / sqrt(a_ii), B = W A_l W;  `passes` rounds of pairwise
  * matching on B -- the rows in ascending order, an unmatched row i takes the unmatched neighbour j != i with the largest
@@ -683,6 +683,54 @@ int cfs_hip_debug_amg_coarsen(int n, const int *rowptr, const int *colind, const
 int cfs_hip_debug_amg_coarsen_dominant(int n, const int *rowptr, const int *colind, const double *values, int passes,
                                        int *agg, double *w, int *nc, int *c_rowptr, int *c_colind, double *c_values,
                                        long long capacity, long long *c_nnz, int *rounds);
+/* ---- the NODE-BLOCK form: aggregate mesh nodes, smooth with block Jacobi ------------------------------------------
+ * For multi-dof mesh matrices (`block` consecutive rows are one node, as for cfs_hip_sym_pcg_block) whose couplings
+ * inside a node are as strong as the diagonal and whose node frames are not the coordinate axes: there the scalar
+ * hierarchy above -- scaled by 1 / sqrt(a_ii), matched row by row, smoothed by point Jacobi -- can be worse than none.
+ * n must be a multiple of block; m = n / block nodes.  Per level, D_i the block x block diagonal block of A_l:
+ *   W_i = D_i^-1/2, the SYMMETRIC inverse square root, from a cyclic Jacobi eigen-solve in fp64 (Q diag(1 / sqrt(ev)) Q^T,
+ *   exactly symmetric).  The symmetric root keeps the node's frame; a Cholesky factor would not.
+ *   B = W A_l W with W = blockdiag(W_i), a coupled pair of nodes stored as a full block.
+ *   `passes` rounds of pairwise matching on the NODE graph with s_ij = ||B_ij||_F / sqrt(||B_ii||_F ||B_jj||_F) > 0, by
+ *   the rule of `matching` (CFS_HIP_AMG_MATCHING_GREEDY or _DOMINANT) exactly as above, each followed by B <- Q^T B Q
+ *   with Q = Q_node (x) I, the sums in the order of the scalar form.
+ *   Coarse unknown I * block + c is component c of coarse node I: agg[i * block + c] = agg_node[i] * block + c,
+ *   P_l = W Q_1 .. Q_p, A_{l+1} = the last B rounded to the value type -- again a node-block matrix.
+ * The rules that end a hierarchy (coarse_max counts rows), the dense level and the level handles are those above.
+ * THE CYCLE is the one above with M = blockdiag(A_l) on the node blocks in the smoother (the inverse blocks and the
+ * power method of cfs_hip_sym_pcg_cheb with CFS_HIP_CHEB_BLOCK), rc_I = sum_{i in I} W_i (r_i - t_i) over the member
+ * nodes ascending, z_i += W_i ec_I and d_i = (1 / theta) M_i^-1 (r_i - t_i): one thread per node, the same launch counts,
+ * the same rounding rule, no atomics; M^-1 is symmetric because W_i is and restriction is the transpose of prolongation.
+ * cfs_hip_sym_pcg_amg and cfs_hip_amg_apply take the object unchanged.  MEMORY: per level block (block + 1) / 2 words of
+ * W and as many of M^-1 per node where the scalar form holds w and dinv; the aggregate lists hold nodes.
+ * cfs_hip_amg_create_block_*: block = 1 IS cfs_hip_amg_create_* (greedy) or cfs_hip_amg_create_dominant_* (dominant),
+ * bit for bit.  CFS_HIP_ERR_ARG, in this order and before anything else: a block outside 1, 2, 3, 4, 6; a matching that
+ * is neither constant; an n that is not a multiple of block (a trailing partial node is not supported); then every
+ * check of cfs_hip_amg_create_* in its words and order.  A node block of any level with an eigenvalue that is not
+ * finite and > 0: CFS_HIP_ERR_ARG, "... needs positive definite node blocks, <count> of <nodes> blocks of <block> rows
+ * ... (level <l>)".  The hierarchy is built on the host and is NOT refreshable: cfs_hip_amg_update_values_* returns
+ * CFS_HIP_ERR_ARG as for any object of cfs_hip_amg_create_*.  There is no device set-up of this form.
+ * cfs_hip_amg_block: *block = the rows per node of the hierarchy, 1 for every object of the entry points above.
+ * cfs_hip_amg_level_node_weights (level < levels - 1, block > 1; otherwise CFS_HIP_ERR_ARG): W[m_l * block * block] in
+ * the value type, node i's W_i row-major at W + i * block * block, as the device holds them (it keeps the lower
+ * triangles, packed like the block-Jacobi inverse).  On a node-block hierarchy cfs_hip_amg_level_aggregates returns the
+ * map of the unknowns in agg[n_l] and its w must be NULL (CFS_HIP_ERR_ARG otherwise).                              */
+int cfs_hip_amg_create_block_f64(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const double *values,
+                                 int block, int matching, const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_create_block_f32(cfs_hip_sym_t h, int n, const int *rowptr, const int *colind, const float *values,
+                                 int block, int matching, const cfs_hip_amg_options *opt, cfs_hip_amg_t *out);
+int cfs_hip_amg_block(cfs_hip_amg_t a, int *block);
+int cfs_hip_amg_level_node_weights(cfs_hip_amg_t a, int level, void *W);
+/* Host only, no device work: one level of the node-block set-up in fp64, the counterpart of cfs_hip_debug_amg_coarsen.
+ * block = 1: that function (or cfs_hip_debug_amg_coarsen_dominant) itself, W = w[n].  Otherwise agg[n] is the map of the
+ * unknowns, W[(n / block) * block * block] the full row-major W_i, and the coarse CSR is returned as there; a coupled
+ * pair of nodes is a full block, so size `capacity` for block * block entries per pair of coupled nodes (too little
+ * room: CFS_HIP_ERR_ARG with *c_nnz set).  rounds[passes] (may be NULL): the rounds of the dominant matching.
+ * CFS_HIP_ERR_ARG: block, matching, a null argument, passes, n not a multiple of block, a node block that is not
+ * positive definite (the message of create, level 0).                                                              */
+int cfs_hip_debug_amg_coarsen_block(int n, const int *rowptr, const int *colind, const double *values, int block,
+                                    int passes, int matching, int *agg, double *W, int *nc, int *c_rowptr, int *c_colind,
+                                    double *c_values, long long capacity, long long *c_nnz, int *rounds);
 /* Host only, no device work: one level of a REFRESH.  The lists are built from values_at_create by the code
  * cfs_hip_amg_create_refreshable_* uses (the matchings of that array, frozen), then evaluated for values_new -- the
  * same CSR pattern -- in a host loop that adds in the order the kernels add.  Out: w[n] (fp64) and the coarse values in

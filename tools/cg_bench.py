@@ -33,7 +33,15 @@ dominant / host and dominant / device (cfs_hip_amg_create_device_*), SETUP_CREAT
 median of setup_seconds, of handles_seconds and of their difference (the level handles' create path is the same code in
 all three); the split and the scratch of the device set-up (cfs_hip_amg_setup_info); the levels and device_bytes; then
 pcg_amg to TOL on the greedy and the dominant hierarchy, interleaved as above.
-usage: python tools/cg_bench.py [--only-cheb | --only-amg | --only-amg-refresh | --only-amg-setup] [matrix[:scale] | lap2dNXxNY ...]"""
+--only-amg-block: the NODE-BLOCK hierarchy (SymMatrix.amg(block=3)) beside the block-Jacobi PCG, the scalar hierarchy and the
+Chebyshev degree-4 PCG on block Jacobi of the same build: solves down to TOL, interleaved, AMG_ROUNDS rounds, the best wall time
+of each, both hierarchies built outside the timed solves; iterations, ms, ms per iteration of the two hierarchies (the block
+kernels move bs^2 weights per node where the scalar ones move bs), their levels, device bytes and set-up seconds.  A matrix
+whose n is not a multiple of 3 has no node-block hierarchy (a trailing partial node): the refusal is recorded.  Default
+matrices: pwtk, ldoor, Flan_1565 and rotnode3x400x330 -- rotnodeBSxNXxNY is the rotated node Laplacian of
+tests/test_amg_block_abi.py, A = H (L' (x) I) H with node frames rotated against the axes.
+usage: python tools/cg_bench.py [--only-cheb | --only-amg | --only-amg-refresh | --only-amg-setup | --only-amg-block]
+       [matrix[:scale] | lap2dNXxNY | rotnodeBSxNXxNY ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -55,6 +63,7 @@ ONLY_REFRESH = "--only-amg-refresh" in sys.argv
 ONLY_AMG = "--only-amg" in sys.argv or ONLY_REFRESH
 HAVE_REFRESH = hasattr(cfs.load(), "cfs_hip_amg_update_values_f64")
 ONLY_SETUP = "--only-amg-setup" in sys.argv
+ONLY_BLOCK = "--only-amg-block" in sys.argv
 SETUP_CREATES = 3
 REFRESH_TIMED = 5
 AMG_DEGREES, AMG_ROUNDS = (1, 2), 3
@@ -192,6 +201,73 @@ def setup_section(A, b, res, rp, ci, va):
         G.close()
 
 
+def rotated_node_laplacian(bs, nx, ny, seed=11):
+    """A = H (L' (x) I_bs) H, symmetrised: H_i = Q_i diag(sqrt(ev)) Q_i^T with seeded rotations Q_i, L' the anisotropic
+    Laplacian below with the two mirrors of every off-diagonal entry multiplied by 1 + 0.3 u and the row sums kept"""
+    import scipy.sparse as sp
+    T = lambda k: sp.diags([-np.ones(k - 1), 2 * np.ones(k), -np.ones(k - 1)], [-1, 0, 1])
+    L = (sp.kron(sp.identity(ny), T(nx)) + 0.37 * sp.kron(T(ny), sp.identity(nx))).tocoo()
+    m = L.shape[0]
+    low = L.row > L.col
+    i, j, v = L.row[low], L.col[low], L.data[low]
+    extra = 0.3 * np.random.default_rng(seed + 1).uniform(0, 1, len(v)) * v
+    diag = L.diagonal()
+    np.subtract.at(diag, i, extra)
+    np.subtract.at(diag, j, extra)
+    Lp = sp.csr_matrix((np.concatenate([v + extra, v + extra, diag]), (np.concatenate([i, j, np.arange(m)]), np.concatenate([j, i, np.arange(m)]))),
+                       shape=(m, m))
+    ev = np.array((1, 30, 900, 2700, 5000, 8100), np.float64)[:bs]
+    Q = np.linalg.qr(np.random.default_rng(seed).standard_normal((m, bs, bs)))[0]
+    H = sp.bsr_matrix((np.einsum("kia,a,kja->kij", Q, np.sqrt(ev), Q), np.arange(m), np.arange(m + 1)), shape=(m * bs, m * bs)).tocsr()
+    A = (H @ sp.kron(Lp, sp.identity(bs), format="csr") @ H).tocsr()
+    A = ((A + A.T) * 0.5).tocsr()
+    A.sort_indices()
+    return m * bs, A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float64)
+
+
+def block_section(A, b, res, rp, ci, va):
+    """solves down to TOL: block-Jacobi PCG, Chebyshev degree 4 on block Jacobi, the scalar and the node-block hierarchy"""
+    loops = {f"pcg_block{BLOCK}": lambda: pcg_native(A, b, precond="block_jacobi", block=BLOCK, tol=TOL, maxiter=MAXITER, check_every=16)[1:3],
+             f"cheb4_block{BLOCK}": lambda: pcg_cheb_native(A, b, base="block_jacobi", block=BLOCK, degree=4, tol=TOL, maxiter=MAXITER,
+                                                            check_every=16)[1:3]}
+    hierarchies = {}
+    for tag, kw in (("amg_scalar", dict()), (f"amg_block{BLOCK}", dict(block=BLOCK))):
+        try:
+            hierarchies[tag] = G = A.amg(rp, ci, va, **kw)
+        except cfs.CfsHipError as e:
+            res[tag + "_refused"] = str(e)
+            continue
+        inf = G.info()
+        res[tag + "_levels"], res[tag + "_kinds"], res[tag + "_device_bytes"] = inf["n"], inf["kind"], inf["device_bytes"]
+        res[tag + "_setup_seconds"] = round(inf["setup_seconds"], 4)
+        res[tag + "_setup_seconds_level_handles"] = round(inf["handles_seconds"], 4)
+        loops[tag] = (lambda G=G: pcg_amg_native(A, b, G, tol=TOL, maxiter=MAXITER)[1:3])
+    res["matrix_device_bytes"] = A.stats()["device_bytes"]
+    best = {}
+    for _ in range(AMG_ROUNDS):
+        for label, fn in loops.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            it, rel = fn()
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            if t < best.get(label, (float("inf"),))[0]:
+                best[label] = (t, it, rel)
+    res["amg_tolerance"], res["amg_rounds"], res["maxiter"] = TOL, AMG_ROUNDS, MAXITER
+    for label, (t, it, rel) in best.items():
+        res[label + "_ms_to_tolerance"] = round(t * 1e3, 3)
+        res[label + "_iterations"] = it
+        res[label + "_relres"] = rel
+        res[label + "_ms_per_iteration"] = round(t * 1e3 / max(it, 1), 4)
+    blk = f"amg_block{BLOCK}"
+    if blk in best:
+        res[blk + "_over_amg_scalar_ms_per_iteration"] = round(res[blk + "_ms_per_iteration"] / res["amg_scalar_ms_per_iteration"], 4)
+        for other in ("amg_scalar", f"pcg_block{BLOCK}", f"cheb4_block{BLOCK}"):
+            res[f"{blk}_over_{other}_time"] = round(best[blk][0] / best[other][0], 4)
+    for G in hierarchies.values():
+        G.close()
+
+
 def amg_section(A, b, res, rp, ci, va):
     """solves down to TOL: Jacobi PCG, Chebyshev degree 4 on Jacobi, and the V-cycle at AMG_DEGREES, interleaved"""
     if ONLY_REFRESH:
@@ -233,7 +309,7 @@ def amg_section(A, b, res, rp, ci, va):
 
 
 out = {}
-for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ldoor", "Flan_1565"]):
+for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ldoor", "Flan_1565"] + (["rotnode3x400x330"] if ONLY_BLOCK else [])):
     name, _, sc = spec.partition(":")
     if name.startswith("lap2d"):  # lap2dNXxNY: the anisotropic 5-point Laplacian of the tests, a matrix that needs many iterations
         import scipy.sparse as sp
@@ -242,6 +318,8 @@ for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ld
         L = (sp.kron(sp.identity(ny), T(nx)) + 0.37 * sp.kron(T(ny), sp.identity(nx))).tocsr()
         L.sort_indices()
         n, rp, ci, va = L.shape[0], L.indptr.astype(np.int32), L.indices.astype(np.int32), L.data
+    elif name.startswith("rotnode"):  # rotnodeBSxNXxNY: node frames rotated against the axes, what the node-block hierarchy is for
+        n, rp, ci, va = rotated_node_laplacian(*(int(v) for v in name[7:].split("x")))
     else:
         n, rp, ci, va, _ = synth.generate(name, float(sc or 1.0))
     # (--only-amg: the refresh part pours new values into the handle)
@@ -258,7 +336,9 @@ for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ld
     spmv_us = (time.perf_counter() - t0) / 200 * 1e6
     K = 200
     res = {"n": n, "spmv_us": round(spmv_us, 2)}
-    if ONLY_CHEB or ONLY_AMG or ONLY_SETUP:
+    if ONLY_CHEB or ONLY_AMG or ONLY_SETUP or ONLY_BLOCK:
+        if ONLY_BLOCK:
+            block_section(A, b, res, rp, ci, va)
         if ONLY_SETUP:
             setup_section(A, b, res, rp, ci, va)
         if ONLY_CHEB:
