@@ -2444,6 +2444,32 @@ int cfs_hip_amg_apply(cfs_hip_amg_t a, void *z_dev, const void *r_dev, void *str
   DeviceGuard g(h->device);
   return a->apply(z_dev, r_dev, (hipStream_t)stream);
 }
+int cfs_hip_amg_apply_cols(cfs_hip_amg_t a, void *z_dev, const void *r_dev, long long ld, int ncols, unsigned active, void *stream) {
+  const char *who = "amg_apply_cols";
+  if (!a || !z_dev || !r_dev) return set_err(CFS_HIP_ERR_ARG, "amg_apply_cols: null argument");
+  if (ncols < 1 || ncols > CFS_HIP_LOBPCG_MAX_K)
+    return set_err(CFS_HIP_ERR_ARG, "amg_apply_cols: 1 <= ncols <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + ", got " + std::to_string(ncols));
+  if (active >> ncols) return set_err(CFS_HIP_ERR_ARG, "amg_apply_cols: active names a column that is not in [0, ncols)");
+  if ((((uintptr_t)z_dev) | ((uintptr_t)r_dev)) & 15) return set_err(CFS_HIP_ERR_ARG, "amg_apply_cols: Z and R must be 16-byte aligned");
+  cfs_hip_sym_t h = a->fine;
+  const long long n = h->n(), vb = a->value_bytes;
+  if (ld < n || ld > (1LL << 56) || (ncols > 1 && (ld * vb) % 16 != 0))
+    return set_err(CFS_HIP_ERR_ARG, "amg_apply_cols: bad ld " + std::to_string(ld) + ": at least n = " + std::to_string(n) +
+                                        " and, for more than one column, a multiple of 16 bytes");
+  const uintptr_t span = (uintptr_t)(((long long)(ncols - 1) * ld + n) * vb), z0 = (uintptr_t)z_dev, r0 = (uintptr_t)r_dev;
+  if (z0 < r0 + span && r0 < z0 + span) return set_err(CFS_HIP_ERR_ARG, "amg_apply_cols: the blocks Z and R overlap");
+  if (a->is_stale()) return set_err(CFS_HIP_ERR_ARG, "amg_apply_cols: the last refresh failed");
+  int rc = check_solve_handle(h, z_dev, r_dev, not_a_shard(who), true, "");
+  if (rc) return rc;
+  if (active == 0) return 0;
+  DeviceGuard g(h->device);
+  return a->apply_cols(z_dev, r_dev, ld, ncols, active, (hipStream_t)stream);
+}
+int cfs_hip_amg_column_cycles(cfs_hip_amg_t a, long long *cycles) {
+  if (!a || !cycles) return set_err(CFS_HIP_ERR_ARG, "amg_column_cycles: null argument");
+  *cycles = a->column_cycles();
+  return 0;
+}
 int cfs_hip_sym_pcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const void *b_dev, double tol, int maxiter, int check_every,
                         int *iterations, double *relres, void *stream) {
   (void)check_every; // (the host looks after every iteration: cfs_hip.h)
@@ -2642,8 +2668,9 @@ int cfs_hip_debug_eigs_combine(void *out_dev, long long ldo, const void *basis_d
 
 // ---- LOBPCG ----
 // the checks that cfs_hip_sym_lobpcg and cfs_hip_sym_debug_lobpcg share, from "bad k" on, in the documented order
+// (a: the hierarchy of the multigrid form, whose value type must be the handle's -- asked when the handle is first read)
 static int check_lobpcg(cfs_hip_sym_t h, int k, int block_rows, bool tol_ok, const void *x0_dev, long long ld0, const void *vectors_dev,
-                        long long ld) {
+                        long long ld, cfs_hip_amg_t a = nullptr) {
   if (k < 1 || k > CFS_HIP_LOBPCG_MAX_K)
     return set_err(CFS_HIP_ERR_ARG, "lobpcg: bad k: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + " and 3 k <= n, got k = " + std::to_string(k));
   if (block_rows != 0 && !block_rows_ok(block_rows))
@@ -2651,6 +2678,7 @@ static int check_lobpcg(cfs_hip_sym_t h, int k, int block_rows, bool tol_ok, con
   if (!tol_ok) return set_err(CFS_HIP_ERR_ARG, "lobpcg: bad tolerance / scale / iteration limit");
   if ((((uintptr_t)x0_dev) | ((uintptr_t)vectors_dev)) & 15)
     return set_err(CFS_HIP_ERR_ARG, "lobpcg: x0 and the vectors must be 16-byte aligned");
+  if (a && a->value_bytes != h->value_bytes) return set_err(CFS_HIP_ERR_ARG, "lobpcg_amg: value type differs from the hierarchy's");
   if (!h->send_rows().empty() || h->rows() != h->n())
     return set_err(CFS_HIP_ERR_UNSUPPORTED, "lobpcg: a handle of the whole matrix, not a shard");
   const long long n = h->n();
@@ -2702,6 +2730,44 @@ int cfs_hip_sym_debug_lobpcg(cfs_hip_sym_t h, int k, int block_rows, const void 
     return cfs_solver::lobpcg<decltype(v), decltype(bs)::value>(h, k, 0.0, 1.0, 0, iters, x0_dev, ld0, theta, vectors_dev, ld, resnorms,
                                                                 nullptr, nullptr, nullptr, st);
   });
+}
+
+// the checks of the two multigrid forms behind their null checks: check_lobpcg (no stored M^-1: block_rows 0; the
+// hierarchy's value type), one device as cfs_hip_sym_pcg_amg asks, the hierarchy created on h and not stale
+static int check_lobpcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, int k, bool tol_ok, const void *x0_dev, long long ld0, const void *vectors_dev,
+                            long long ld) {
+  int rc = check_lobpcg(h, k, 0, tol_ok, x0_dev, ld0, vectors_dev, ld, a);
+  if (rc || (rc = check_whole_matrix(h, not_a_shard("lobpcg_amg"), true, "lobpcg_amg: the whole matrix on one device, not a multi-device handle")))
+    return rc;
+  if (a->fine != h) return set_err(CFS_HIP_ERR_ARG, "lobpcg_amg: the hierarchy was created on another handle");
+  if (a->is_stale()) return set_err(CFS_HIP_ERR_ARG, "lobpcg_amg: the last refresh failed");
+  return 0;
+}
+
+int cfs_hip_sym_lobpcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, int k, double tol, double scale, int maxiter, const void *x0_dev, long long ld0,
+                           double *eigenvalues, void *vectors_dev, long long ld, double *residuals, int *nconv, int *iterations,
+                           int *products, void *stream) {
+  if (!h || !a || !eigenvalues || !vectors_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (nconv) *nconv = 0;
+  if (iterations) *iterations = 0;
+  if (products) *products = 0;
+  const bool tol_ok = tol >= 0.0 && scale > 0.0 && std::isfinite(scale) && maxiter >= 0;
+  int rc = check_lobpcg_amg(h, a, k, tol_ok, x0_dev, ld0, vectors_dev, ld);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  return a->lobpcg(k, tol, scale, maxiter, -1, x0_dev, ld0, eigenvalues, vectors_dev, ld, residuals, nconv, iterations, products,
+                   (hipStream_t)stream);
+}
+
+int cfs_hip_sym_debug_lobpcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, int k, const void *x0_dev, long long ld0, int iters, double *theta,
+                                 void *vectors_dev, long long ld, double *resnorms, void *stream) {
+  if (!h || !a || !theta || !vectors_dev || !resnorms) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  int rc = check_lobpcg_amg(h, a, k, iters >= 0, x0_dev, ld0, vectors_dev, ld);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  return a->lobpcg(k, 0.0, 1.0, 0, iters, x0_dev, ld0, theta, vectors_dev, ld, resnorms, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int cfs_hip_debug_lobpcg_rr(int m, const double *g, const double *hh, int k, double drop, double *theta, double *c, int *rank) {

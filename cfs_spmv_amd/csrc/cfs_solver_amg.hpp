@@ -94,6 +94,26 @@
 //   d_i = (V)((1/theta) M_i^-1 (r_i - t_i));  z_i = (V)(z_i + d_i)               amg_restart_block_kernel
 // one thread per node, the same 8 + 6 (m - 1) launches; W_i is symmetric and restriction the transpose of prolongation,
 // so M^-1 stays symmetric, and nothing is atomic.
+//
+// THE COLUMN-BLOCKED CYCLE (cfs_hip_amg_apply_cols, cfs_hip_sym_lobpcg_amg; cycle_cols) is the cycle above on the columns
+// c < ncols <= 16 of a block whose bit is set in a mask, Z_c = M^-1 R_c, for the W block of LOBPCG.  Every vector kernel
+// has a _cols form that is launched ONCE for the block --
+//   cheb_start_cols_kernel, cheb_step_cols_kernel (cfs_solver_cheb.hpp), amg_restrict_cols_kernel, amg_prolong_cols_kernel,
+//   amg_restart_cols_kernel (BS = 1 and the node-block form in one template), amg_dense_cols_kernel
+// -- so a level costs 4 + 2 (m - 1) vector-kernel launches for any ncols, where ncols one-column cycles cost ncols times
+// that; the products stay one spmv_local per active column at each place where cycle() has one.  What a row, node or
+// aggregate reads of the level -- dinv or the packed inverse block, the packed W, agg, the aggregate list, a row of the
+// dense inverse -- is loaded once and used for all columns of a chunk: the whole block in the element-wise kernels (the
+// columns are the inner loop, the level's words stay in registers), chunks of 8 / 4 / 2 columns (BS = 1 / 2, 3, 4 / 6)
+// in the restriction, whose fp64 accumulators are per column, and of 8 in the dense kernel.  A column whose bit is clear
+// is neither read nor written.  Per column the expressions are those of the one-column kernels operand for operand, so
+// the compiler forms the same operations: on a deterministic handle column c has the bits of cycle() on R_c alone.
+// (Neither family of kernels switches contraction off: under the compiler's default both get the same fused
+// multiply-adds because the expression trees are the same.  The bit equality rests on that, and
+// tests/test_gpu_amg_apply_cols.py is what notices if a compiler ever chooses differently for the two loop nests.)
+// The levels' work vectors for a block (cd, ct on a level that smooths, cr, cz below level 0; columns of n_l rounded up
+// to 16 bytes) are allocated at the first blocked call of a width, kept, and made again only for a wider call
+// (reserve_cols); cycle() keeps its own vectors and is not touched.
 #pragma once
 
 #include <algorithm>
@@ -112,6 +132,11 @@ struct cfs_hip_amg_s {
   virtual int level_matrix(int level, int *rowptr, int *colind, void *values) = 0;
   virtual int coarse_inverse(void *inv) = 0;
   virtual int apply(void *z_dev, const void *r_dev, hipStream_t st) = 0;
+  virtual int apply_cols(void *z_dev, const void *r_dev, long long ld, int ncols, unsigned active, hipStream_t st) = 0;
+  virtual int lobpcg(int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0, double *eigenvalues,
+                     void *vectors_dev, long long ld, double *residuals, int *nconv, int *iterations, int *products, hipStream_t st) = 0;
+  virtual bool is_stale() const = 0;              // the last refresh failed
+  virtual long long column_cycles() const = 0;    // cycles applied to columns of blocks, since create
   virtual int pcg(void *u_dev, const void *b_dev, double tol, int maxiter, int *iterations, double *relres, hipStream_t st) = 0;
   virtual int update_check(long long nnz) = 0;
   virtual int update_values(const void *values_dev, long long nnz, hipStream_t st) = 0;
@@ -811,6 +836,203 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// ---- the kernels of the cycle on a BLOCK OF COLUMNS (see THE COLUMN-BLOCKED CYCLE in the header comment) ----
+// Column c of a block at base + c ld; the columns whose bit is set in `active` (c < ncols) are worked on in one launch,
+// the others neither read nor written.  BS = 1: the scalar form, BS >= 2: the node-block form (one thread per node, w
+// the packed W or M^-1, m the nodes of the level).  The columns go in chunks of CW: what a row, node or aggregate reads
+// of the level -- w_i or W_i, agg, the aggregate list, a row of the dense inverse -- is loaded once per chunk.
+template <int BS> constexpr int amg_restrict_chunk() { return BS == 1 ? 8 : BS == 6 ? 2 : 4; } // (CW BS fp64 accumulators)
+constexpr int kAmgDenseChunk = 8;
+
+// rc_{I,c} = (V)(sum over the members i of aggregate I, ascending, of W_i (r_{i,c} - t_{i,c}))
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    amg_restrict_cols_kernel(V *__restrict__ rc, long long ldc, const V *__restrict__ r, long long ldr, const V *__restrict__ t,
+                             long long ldt, const V *__restrict__ w, long long m, const int *__restrict__ aggptr,
+                             const int *__restrict__ aggidx, long long nc, const int *__restrict__ ic, int ncols, unsigned active) {
+  if (ic[I_DONE]) return;
+  constexpr int CW = amg_restrict_chunk<BS>();
+  for (int c0 = 0; c0 < ncols; c0 += CW) {
+    const unsigned bits = (active >> c0) & ((1u << CW) - 1u); // (uniform over the grid; no bit from ncols on is set)
+    if (!bits) continue;
+    for (long long I = (long long)blockIdx.x * kThreads + threadIdx.x; I < nc; I += (long long)gridDim.x * kThreads) {
+      if constexpr (BS >= 2) {
+        double s[CW][BS];
+#pragma unroll
+        for (int e = 0; e < CW; ++e)
+#pragma unroll
+          for (int c = 0; c < BS; ++c) s[e][c] = 0.0;
+        for (int k = aggptr[I]; k < aggptr[I + 1]; ++k) {
+          const long long i = aggidx[k];
+          double mm[BS][BS];
+          block_load<V, BS>(w, m, i, mm);
+#pragma unroll
+          for (int e = 0; e < CW; ++e) {
+            if (!((bits >> e) & 1u)) continue;
+            const V *re = r + (c0 + e) * ldr, *te = t + (c0 + e) * ldt;
+            double x[BS], y[BS];
+#pragma unroll
+            for (int c = 0; c < BS; ++c) x[c] = (double)re[i * BS + c] - (double)te[i * BS + c];
+            block_mul<BS>(mm, x, y);
+#pragma unroll
+            for (int c = 0; c < BS; ++c) s[e][c] += y[c];
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+#pragma unroll
+          for (int c = 0; c < BS; ++c) rc[(c0 + e) * ldc + I * BS + c] = (V)s[e][c];
+        }
+      } else {
+        double s[CW];
+#pragma unroll
+        for (int e = 0; e < CW; ++e) s[e] = 0.0;
+        for (int k = aggptr[I]; k < aggptr[I + 1]; ++k) {
+          const int i = aggidx[k];
+          const V wi = w[i];
+#pragma unroll
+          for (int e = 0; e < CW; ++e)
+            if ((bits >> e) & 1u) s[e] += (double)wi * ((double)r[(c0 + e) * ldr + i] - (double)t[(c0 + e) * ldt + i]);
+        }
+#pragma unroll
+        for (int e = 0; e < CW; ++e)
+          if ((bits >> e) & 1u) rc[(c0 + e) * ldc + I] = (V)s[e];
+      }
+    }
+  }
+}
+
+// z_{i,c} = (V)(z_{i,c} + W_i ec_{agg(i),c}): one thread per row (BS = 1, m = n) or per fine node
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    amg_prolong_cols_kernel(V *__restrict__ z, long long ldz, const V *__restrict__ ec, long long lde, const V *__restrict__ w,
+                            const int *__restrict__ agg, long long m, const int *__restrict__ ic, int ncols, unsigned active) {
+  if (ic[I_DONE]) return;
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < m; i += (long long)gridDim.x * kThreads) {
+    const long long I = agg[i];
+    if constexpr (BS >= 2) {
+      double mm[BS][BS];
+      block_load<V, BS>(w, m, i, mm);
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const V *ecc = ec + c * lde;
+        V *zc = z + c * ldz;
+        double e[BS], y[BS];
+#pragma unroll
+        for (int q = 0; q < BS; ++q) e[q] = (double)ecc[I * BS + q];
+        block_mul<BS>(mm, e, y);
+#pragma unroll
+        for (int q = 0; q < BS; ++q) zc[i * BS + q] = (V)((double)zc[i * BS + q] + y[q]);
+      }
+    } else {
+      const V wi = w[i];
+      for (int c = 0; c < ncols; ++c)
+        if ((active >> c) & 1u) z[c * ldz + i] = (V)((double)z[c * ldz + i] + (double)wi * (double)ec[c * lde + I]);
+    }
+  }
+}
+
+// amg_restart_kernel / amg_restart_block_kernel on the active columns:  d_c = (V)((1 / theta) M^-1 (r_c - t_c));
+// z_c = (V)(z_c + d_c)
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    amg_restart_cols_kernel(V *__restrict__ z, long long ldz, V *__restrict__ d, long long ldd, const V *__restrict__ r, long long ldr,
+                            const V *__restrict__ t, long long ldt, long long n, double inv_theta, const V *__restrict__ minv, long long nb,
+                            const int *__restrict__ ic, int ncols, unsigned active) {
+  if (ic[I_DONE]) return;
+  if constexpr (BS >= 2) {
+    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+      double mm[BS][BS];
+      block_load<V, BS>(minv, nb, k, mm);
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const V *rc = r + c * ldr, *tc = t + c * ldt;
+        V *zc = z + c * ldz, *dc = d + c * ldd;
+        double x[BS], zz[BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+          const long long g = k * BS + i;
+          x[i] = g < n ? (double)rc[g] - (double)tc[g] : 0.0;
+        }
+        block_mul<BS>(mm, x, zz);
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+          const long long g = k * BS + i;
+          if (g < n) {
+            const V di = (V)(inv_theta * zz[i]);
+            dc[g] = di;
+            zc[g] = (V)((double)zc[g] + (double)di);
+          }
+        }
+      }
+    }
+  } else {
+    constexpr int W = Vec16<V>::W;
+    typedef typename Vec16<V>::type VT;
+    const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+    for (long long i = t0; i < nv; i += stride) {
+      const VT mv = reinterpret_cast<const VT *>(minv)[i];
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const VT rv = reinterpret_cast<const VT *>(r + c * ldr)[i], tv = reinterpret_cast<const VT *>(t + c * ldt)[i];
+        VT zv = reinterpret_cast<VT *>(z + c * ldz)[i], dv;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          dv[k] = (V)(inv_theta * (((double)rv[k] - (double)tv[k]) * (double)mv[k]));
+          zv[k] = (V)((double)zv[k] + (double)dv[k]);
+        }
+        reinterpret_cast<VT *>(d + c * ldd)[i] = dv;
+        reinterpret_cast<VT *>(z + c * ldz)[i] = zv;
+      }
+    }
+    for (long long i = nv * W + t0; i < n; i += stride) {
+      const V mi = minv[i];
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const V di = (V)(inv_theta * (((double)r[c * ldr + i] - (double)t[c * ldt + i]) * (double)mi));
+        d[c * ldd + i] = di;
+        z[c * ldz + i] = (V)((double)z[c * ldz + i] + (double)di);
+      }
+    }
+  }
+}
+
+// z_c = (V)(inv r_c) on the dense level: one wave per row, which it reads ONCE per chunk of columns; per column the
+// lane-strided sum and the tree of amg_dense_kernel
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    amg_dense_cols_kernel(V *__restrict__ z, long long ldz, const V *__restrict__ inv, const V *__restrict__ r, long long ldr, int n,
+                          const int *__restrict__ ic, int ncols, unsigned active) {
+  if (ic[I_DONE]) return;
+  constexpr int CW = kAmgDenseChunk;
+  const int lane = threadIdx.x & 63, nwaves = gridDim.x * (kThreads / 64);
+  for (int c0 = 0; c0 < ncols; c0 += CW) {
+    const unsigned bits = (active >> c0) & ((1u << CW) - 1u); // (uniform over the grid)
+    if (!bits) continue;
+    for (int i = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); i < n; i += nwaves) { // (uniform over the wave)
+      const V *row = inv + (size_t)i * n;
+      double s[CW];
+#pragma unroll
+      for (int e = 0; e < CW; ++e) s[e] = 0.0;
+      for (int j = lane; j < n; j += 64) {
+        const V a = row[j];
+#pragma unroll
+        for (int e = 0; e < CW; ++e)
+          if ((bits >> e) & 1u) s[e] += (double)a * (double)r[(c0 + e) * ldr + j];
+      }
+#pragma unroll
+      for (int e = 0; e < CW; ++e) {
+        if (!((bits >> e) & 1u)) continue;
+        double v = s[e];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+        if (lane == 0) z[(c0 + e) * ldz + i] = (V)v;
+      }
+    }
+  }
+}
+
 // ---- the kernels of a refresh (see REFRESH at the end of the header comment) ------------------------
 // out[e] = src[idx[ptr[e]]] + src[idx[ptr[e] + 1]] + ... in fp64, in the order of the list: one thread per output entry.
 // LAST (the last round of a level): vout[e] = (V)s, what the next level's handle is poured, and out[e] = (double)(V)s,
@@ -872,6 +1094,10 @@ template <typename V, int BS = 1> struct AmgLevel {
   Precond<V, BS> pre; // dinv (BS >= 2: the packed inverse node blocks) of a level that smooths
   // (BS >= 2: aggptr, aggidx and agg hold NODES, w the packed W_i)
   cfs_rt::DevBuf aggptr, aggidx, agg, w, r, z, d, t, inv;
+  // the work vectors of the column-blocked cycle, column c at + c cld values (cld: n rounded up to 16 bytes): cd and ct
+  // on a level that smooths, cr and cz below level 0; made by Amg::reserve_cols at the first blocked call of a width
+  cfs_rt::DevBuf cr, cz, cd, ct;
+  long long cld = 0;
   // the CSR the level's handle was created from (levels >= 1): lower triangle + diagonal, values in V
   std::vector<int> rp, ci;
   std::vector<V> va;
@@ -885,7 +1111,8 @@ template <typename V, int BS = 1> struct AmgLevel {
     if (owned) delete h;
   }
   size_t bytes() const {
-    return pre.dbuf.bytes + aggptr.bytes + aggidx.bytes + agg.bytes + w.bytes + r.bytes + z.bytes + d.bytes + t.bytes + inv.bytes;
+    return pre.dbuf.bytes + aggptr.bytes + aggidx.bytes + agg.bytes + w.bytes + r.bytes + z.bytes + d.bytes + t.bytes + inv.bytes +
+           cr.bytes + cz.bytes + cd.bytes + ct.bytes;
   }
   size_t map_bytes() const {
     size_t b = lptr.bytes + lidx.bytes + fdiag.bytes + frow.bytes + fcol.bytes + vdev.bytes;
@@ -919,6 +1146,8 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
   int matching = CFS_HIP_AMG_MATCHING_GREEDY, on_device = 0, rounds[CFS_HIP_AMG_MAX_LEVELS][3] = {};
   double setup_split[4] = {0.0, 0.0, 0.0, 0.0};
   long long scratch_bytes = 0;
+  int col_cap = 0;           // the columns the levels' blocked work vectors hold (0: no blocked call yet)
+  long long col_cycles = 0;  // cycles applied through cycle_cols, one per active column (cfs_hip_amg_column_cycles)
 
   ~Amg() override {
     cfs_rt::DeviceGuard g(device);
@@ -1298,6 +1527,92 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
     }
     return cheb_chain<V, BS>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, nb, st);
   }
+
+  // the levels' work vectors for a block of `ncols` columns: allocated at the first blocked call, kept, and made again
+  // only for a wider one (hipFree waits for the device: nothing enqueued still uses the old ones)
+  int reserve_cols(int ncols) {
+    if (ncols <= col_cap) return 0;
+    col_cap = 0; // (an allocation that fails half-way leaves no width behind: the next call reserves again)
+    for (size_t l = 0; l < lv.size(); ++l) {
+      Level &L = *lv[l];
+      L.cld = ((long long)L.n + Vec16<V>::W - 1) / Vec16<V>::W * Vec16<V>::W;
+      const size_t bytes = (size_t)ncols * (size_t)L.cld * sizeof(V) + 64;
+      int rc;
+      if (L.kind != AMG_DENSE && ((rc = L.cd.alloc(bytes)) || (rc = L.ct.alloc(bytes)))) return rc;
+      if (l > 0 && ((rc = L.cr.alloc(bytes)) || (rc = L.cz.alloc(bytes)))) return rc;
+    }
+    col_cap = ncols;
+    return 0;
+  }
+
+  // Z_c = M^-1 R_c for the columns c < ncols whose bit is set in `active`, from level l down, on `st`: cycle() with
+  // every vector kernel launched ONCE for the block and one product per active column where cycle() has one.  Column c
+  // of Z at Z + c ld_z, of R at R + c ld_r; reserve_cols(ncols) has been called
+  int cycle_cols(int l, V *Z, const V *R, long long ld_z, long long ld_r, int ncols, unsigned active, const int *ic, hipStream_t st) {
+    Level &L = *lv[l];
+    const long long n = L.n;
+    if (L.kind == AMG_DENSE) {
+      hipLaunchKernelGGL((amg_dense_cols_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, (const V *)L.inv.p, R, ld_r, L.n, ic,
+                         ncols, active);
+      return 0;
+    }
+    V *d = (V *)L.cd.p, *t = (V *)L.ct.p;
+    const long long ldw = L.cld;
+    const V *dinv = L.pre.minv();
+    const long long nb = L.pre.nb; // the nodes of the level (BS >= 2), else 0
+    int rc;
+    auto products = [&]() -> int { // t_c = A_l z_c
+      for (int c = 0; c < ncols; ++c)
+        if ((active >> c) & 1u)
+          if (int r2 = L.h->spmv_local(t + c * ldw, Z + c * ld_z, nullptr, st)) return r2;
+      return 0;
+    };
+    hipLaunchKernelGGL((cheb_start_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, d, ldw, R, ld_r, n, 1.0 / L.theta,
+                       dinv, nb, ncols, active);
+    if ((rc = cheb_chain_cols<V, BS>(L.h, Z, ld_z, d, t, ldw, R, ld_r, n, degree, L.c1, L.c2, ic, dinv, nb, ncols, active, st))) return rc;
+    if (L.kind == AMG_SMOOTHER) return 0;
+    Level &C = *lv[l + 1];
+    const long long units = BS >= 2 ? nb : n; // nodes, or rows
+    if ((rc = products())) return rc;
+    hipLaunchKernelGGL((amg_restrict_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)C.cr.p, C.cld, R, ld_r, (const V *)t, ldw,
+                       (const V *)L.w.p, units, (const int *)L.aggptr.p, (const int *)L.aggidx.p, (long long)(L.nc / BS), ic, ncols, active);
+    if ((rc = cycle_cols(l + 1, (V *)C.cz.p, (const V *)C.cr.p, C.cld, C.cld, ncols, active, ic, st))) return rc;
+    hipLaunchKernelGGL((amg_prolong_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, (const V *)C.cz.p, C.cld,
+                       (const V *)L.w.p, (const int *)L.agg.p, units, ic, ncols, active);
+    if ((rc = products())) return rc;
+    hipLaunchKernelGGL((amg_restart_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, d, ldw, R, ld_r, (const V *)t, ldw, n,
+                       1.0 / L.theta, dinv, nb, ic, ncols, active);
+    return cheb_chain_cols<V, BS>(L.h, Z, ld_z, d, t, ldw, R, ld_r, n, degree, L.c1, L.c2, ic, dinv, nb, ncols, active, st);
+  }
+
+  // cfs_hip_amg_apply_cols (arguments checked by the caller; active != 0)
+  int apply_cols(void *z_dev, const void *r_dev, long long ld, int ncols, unsigned active, hipStream_t st) override {
+    if (stale) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_apply_cols: the last refresh failed");
+    int rc = follow_fine(st);
+    if (rc || (rc = reserve_cols(ncols))) return rc;
+    rc = cycle_cols(0, (V *)z_dev, (const V *)r_dev, ld, ld, ncols, active, (const int *)cnt.p, st);
+    if (rc) return rc;
+    col_cycles += __builtin_popcount(active);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // cfs_hip_sym_lobpcg_amg / cfs_hip_sym_debug_lobpcg_amg: the iteration of cfs_solver_lobpcg.hpp with W formed by the
+  // blocked cycle on the columns still active (arguments checked by the caller)
+  int lobpcg(int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0, double *eigenvalues,
+             void *vectors_dev, long long ld, double *residuals, int *nconv, int *iterations, int *products, hipStream_t st) override {
+    if (stale) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "lobpcg_amg: the last refresh failed");
+    int rc = follow_fine(st);
+    if (rc || (rc = reserve_cols(k))) return rc;
+    auto form_w = [&](V *W, const V *R, long long ldw, int kk, unsigned mask) -> int {
+      if (int r2 = cycle_cols(0, W, R, ldw, ldw, kk, mask, (const int *)cnt.p, st)) return r2;
+      col_cycles += __builtin_popcount(mask);
+      return 0;
+    };
+    return cfs_solver::lobpcg<V, 0>(fine, k, tol, scale, maxiter, debug_iters, x0_dev, ld0, eigenvalues, vectors_dev, ld, residuals, nconv,
+                                    iterations, products, st, form_w);
+  }
+  bool is_stale() const override { return stale; }
+  long long column_cycles() const override { return col_cycles; }
 
   int apply(void *z_dev, const void *r_dev, hipStream_t st) override {
     if (stale) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_apply: the last refresh failed");

@@ -261,6 +261,159 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// ---- the two smoother kernels on a BLOCK OF COLUMNS (the column-blocked V-cycle of cfs_solver_amg.hpp) ----
+// Column c of a block lives at base + c ld; the columns whose bit is set in `active` (c < ncols <= 16) are worked on
+// in ONE launch, the others neither read nor written.  The stored M^-1 of a row (its dinv word, or the packed inverse
+// block of its node: block_load) is loaded once and used for every column.  Per column the expressions are those of
+// cheb_start_kernel / cheb_step_kernel, operand for operand, so that the compiler forms the same operations and a
+// column of the block has the bits of the one-column kernel; no dot product (the cycle asks for none).  (Contraction
+// is left at the compiler's default in both families: the same trees get the same fused multiply-adds.)
+// block_apply() in two halves: the node's inverse block into registers, and its product with one column's values
+template <typename V, int BS>
+__device__ __forceinline__ void block_load(const V *__restrict__ minv, long long nb, long long k, double (&m)[BS][BS]) {
+#pragma unroll
+  for (int i = 0; i < BS; ++i)
+#pragma unroll
+    for (int j = 0; j <= i; ++j) m[i][j] = m[j][i] = (double)minv[(long long)(i * (i + 1) / 2 + j) * nb + k];
+}
+template <int BS> __device__ __forceinline__ void block_mul(const double (&m)[BS][BS], const double (&r)[BS], double (&z)[BS]) {
+#pragma unroll
+  for (int i = 0; i < BS; ++i) {
+    double v = 0.0;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) v += m[i][j] * r[j];
+    z[i] = v;
+  }
+}
+
+// z_c = d_c = (V)((1 / theta) M^-1 r_c) for the active columns c
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cheb_start_cols_kernel(V *__restrict__ z, long long ldz, V *__restrict__ d, long long ldd, const V *__restrict__ r, long long ldr,
+                           long long n, double inv_theta, const V *__restrict__ minv, long long nb, int ncols, unsigned active) {
+  if constexpr (BS >= 2) {
+    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+      double m[BS][BS];
+      block_load<V, BS>(minv, nb, k, m);
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const V *rc = r + c * ldr;
+        V *zc = z + c * ldz, *dc = d + c * ldd;
+        double rd[BS], zz[BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+          const long long g = k * BS + i;
+          rd[i] = g < n ? (double)rc[g] : 0.0;
+        }
+        block_mul<BS>(m, rd, zz);
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+          const long long g = k * BS + i;
+          if (g < n) {
+            const V zi = (V)(inv_theta * zz[i]);
+            zc[g] = zi;
+            dc[g] = zi;
+          }
+        }
+      }
+    }
+  } else {
+    constexpr int W = Vec16<V>::W;
+    typedef typename Vec16<V>::type VT;
+    const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+    for (long long i = t0; i < nv; i += stride) {
+      VT mv;
+      if (BS == 1) mv = reinterpret_cast<const VT *>(minv)[i];
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const VT rv = reinterpret_cast<const VT *>(r + c * ldr)[i];
+        VT zv;
+#pragma unroll
+        for (int k = 0; k < W; ++k) zv[k] = (V)(inv_theta * cheb_minv1<V, BS>((double)rv[k], BS == 1 ? mv[k] : (V)1));
+        reinterpret_cast<VT *>(z + c * ldz)[i] = zv;
+        reinterpret_cast<VT *>(d + c * ldd)[i] = zv;
+      }
+    }
+    for (long long i = nv * W + t0; i < n; i += stride) {
+      const V mi = BS == 1 ? minv[i] : (V)1;
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const V zi = (V)(inv_theta * cheb_minv1<V, BS>((double)r[c * ldr + i], mi));
+        z[c * ldz + i] = zi;
+        d[c * ldd + i] = zi;
+      }
+    }
+  }
+}
+
+// One inner step on the active columns c:  d_c = (V)(c1 d_c + c2 M^-1 (r_c - t_c));  z_c = (V)(z_c + d_c)
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cheb_step_cols_kernel(const V *__restrict__ r, long long ldr, const V *__restrict__ t, long long ldt, V *__restrict__ d, long long ldd,
+                          V *__restrict__ z, long long ldz, long long n, double c1, double c2, const int *__restrict__ ic,
+                          const V *__restrict__ minv, long long nb, int ncols, unsigned active) {
+  if (ic[I_DONE]) return;
+  if constexpr (BS >= 2) {
+    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+      double m[BS][BS];
+      block_load<V, BS>(minv, nb, k, m);
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const V *rc = r + c * ldr, *tc = t + c * ldt;
+        V *zc = z + c * ldz, *dc = d + c * ldd;
+        double rd[BS], w[BS], zz[BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+          const long long g = k * BS + i;
+          rd[i] = g < n ? (double)rc[g] : 0.0;
+          w[i] = g < n ? rd[i] - (double)tc[g] : 0.0;
+        }
+        block_mul<BS>(m, w, zz);
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+          const long long g = k * BS + i;
+          if (g < n) {
+            const V di = (V)(c1 * (double)dc[g] + c2 * zz[i]);
+            const V zi = (V)((double)zc[g] + (double)di);
+            dc[g] = di;
+            zc[g] = zi;
+          }
+        }
+      }
+    }
+  } else {
+    constexpr int W = Vec16<V>::W;
+    typedef typename Vec16<V>::type VT;
+    const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+    for (long long i = t0; i < nv; i += stride) {
+      VT mv;
+      if (BS == 1) mv = reinterpret_cast<const VT *>(minv)[i];
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const VT rv = reinterpret_cast<const VT *>(r + c * ldr)[i], tv = reinterpret_cast<const VT *>(t + c * ldt)[i];
+        VT dv = reinterpret_cast<VT *>(d + c * ldd)[i], zv = reinterpret_cast<VT *>(z + c * ldz)[i];
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          dv[k] = (V)(c1 * (double)dv[k] + c2 * cheb_minv1<V, BS>((double)rv[k] - (double)tv[k], BS == 1 ? mv[k] : (V)1));
+          zv[k] = (V)((double)zv[k] + (double)dv[k]);
+        }
+        reinterpret_cast<VT *>(d + c * ldd)[i] = dv;
+        reinterpret_cast<VT *>(z + c * ldz)[i] = zv;
+      }
+    }
+    for (long long i = nv * W + t0; i < n; i += stride) {
+      const V mi = BS == 1 ? minv[i] : (V)1;
+      for (int c = 0; c < ncols; ++c) {
+        if (!((active >> c) & 1u)) continue;
+        const V di = (V)(c1 * (double)d[c * ldd + i] + c2 * cheb_minv1<V, BS>((double)r[c * ldr + i] - (double)t[c * ldt + i], mi));
+        const V zi = (V)((double)z[c * ldz + i] + (double)di);
+        d[c * ldd + i] = di;
+        z[c * ldz + i] = zi;
+      }
+    }
+  }
+}
+
 // cg_direction_kernel<V, true> with z stored:  beta = rz' / rz;  p = z + beta p;  one thread: iteration count,
 // convergence flag from rr' (only workgroup 0 adds it up)
 template <typename V>
@@ -367,6 +520,21 @@ int cheb_chain(Handle *h, V *z, V *d, V *t, const V *r, long long n, int degree,
     if (rc) return rc;
     hipLaunchKernelGGL((cheb_step_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, (const V *)t, d, z, n, c1[j - 1], c2[j - 1],
                        j == degree - 1 ? rz_slot : -1, part, ic, minv, nb);
+  }
+  return 0;
+}
+
+// cheb_chain on the active columns of a block: per step one product per active column, then ONE step kernel
+template <typename V, int BS, class Handle>
+int cheb_chain_cols(Handle *h, V *z, long long ldz, V *d, V *t, long long ldw, const V *r, long long ldr, long long n, int degree,
+                    const double *c1, const double *c2, const int *ic, const V *minv, long long nb, int ncols, unsigned active,
+                    hipStream_t st) {
+  for (int j = 1; j < degree; ++j) {
+    for (int c = 0; c < ncols; ++c)
+      if ((active >> c) & 1u)
+        if (int rc = h->spmv_local(t + c * ldw, z + c * ldz, nullptr, st)) return rc;
+    hipLaunchKernelGGL((cheb_step_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, ldr, (const V *)t, ldw, d, ldw, z, ldz, n,
+                       c1[j - 1], c2[j - 1], ic, minv, nb, ncols, active);
   }
   return 0;
 }

@@ -14,6 +14,9 @@
 //   lobpcg_reduce_kernel        the 2 k sums                                            -> host look 2 (2 k doubles)
 //   tile kernel + fold          AW_i = A W_i for the active i
 // Two host looks per iteration are inherent: C depends on G and H, the active set on the norms.
+// cfs_hip_sym_lobpcg_amg is the same lobpcg() with W formed outside the residual kernel: that kernel runs in its BS = 0
+// form and writes the raw (V)R_i into the W-columns of AS, and the column-blocked multigrid cycle of cfs_solver_amg.hpp
+// (Amg::cycle_cols) reads them there and writes W_i = M^-1 R_i for the pairs still active.  Memory: no extra k n block.
 //
 // The Gram kernel is a small SYRK: m (m + 1) sums of n terms each, m <= 48.  One walk per chunk of 8 accumulators
 // (eigs_project_kernel) would read its rows 290 times at m = 48; instead a workgroup stages R rows of all 2 m columns
@@ -34,6 +37,7 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace cfs_solver {
@@ -467,12 +471,18 @@ int debug_residual(Handle *h, const void *x_dev, const void *ax_dev, void *w_dev
 }
 
 // cfs_hip_sym_lobpcg, and with debug_iters >= 0 cfs_hip_sym_debug_lobpcg: iteration 0 and debug_iters more, every
-// pair active, no convergence test, no confirm step (arguments checked by the caller)
-template <typename V, int BS, class Handle>
+// pair active, no convergence test, no confirm step (arguments checked by the caller).
+// HOW W IS FORMED is the one thing the iteration leaves open.  form_w = nullptr: by the residual kernel itself from the
+// stored M^-1 of BS.  Otherwise (cfs_hip_sym_lobpcg_amg, BS = 0): the residual kernel writes the raw (V)R_i into the
+// W-columns of AS -- free at that moment: the products of step 6 rewrite them before anything reads them, so no extra
+// block is held -- and form_w(W, R, ld, k, mask) enqueues W_i = M^-1 R_i for the bits of mask (column i at + i ld).
+template <typename V, int BS, class Handle, class FormW = std::nullptr_t>
 int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0,
            double *eigenvalues, void *vectors_dev, long long ldx, double *residuals, int *nconv_out, int *iterations_out,
-           int *products_out, hipStream_t st) {
+           int *products_out, hipStream_t st, FormW form_w = nullptr) {
   using cfs_rt::DevBuf;
+  constexpr bool external_w = !std::is_same<FormW, std::nullptr_t>::value;
+  static_assert(!external_w || BS == 0, "an external M^-1 reads the raw residuals");
   const bool debug = debug_iters >= 0;
   const long long n = h->n();
   const long long ld = (n + Vec16<V>::W - 1) / Vec16<V>::W * Vec16<V>::W; // columns 16-byte aligned
@@ -528,9 +538,11 @@ int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_it
   };
   // step 4 and the host's look at the norms: res[i] = ||R_i|| / ||X_i||
   auto norms = [&](unsigned wmask) -> int {
-    int r2 = lobpcg_residual<V, BS>((const V *)S, (const V *)AS, col(S, k), ld, n, k, theta.data(), wmask, minv, part, (double *)nout.p,
-                                    hn.data(), st);
+    int r2 = lobpcg_residual<V, BS>((const V *)S, (const V *)AS, col(external_w ? AS : S, k), ld, n, k, theta.data(), wmask, minv, part,
+                                    (double *)nout.p, hn.data(), st);
     if (r2) return r2;
+    if constexpr (external_w)
+      if (wmask && (r2 = form_w(col(S, k), (const V *)col(AS, k), ld, k, wmask))) return r2;
     for (int i = 0; i < k; ++i) res[i] = std::sqrt(hn[2 * i]) / std::sqrt(hn[2 * i + 1]);
     return 0;
   };

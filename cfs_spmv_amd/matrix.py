@@ -476,9 +476,21 @@ class SymMatrix:
         self.eigs(k=1, which="LM", tol=1e-3), whose products are not counted).  x0: a device tensor (n, k) whose
         columns are the start block (any strides; None: the library's fixed start block).  Returns (w, X, info): w a
         numpy float64 array (k,), ascending; X a device tensor (n, k) with strides (1, ld); info = dict(nconv,
-        iterations, products, residuals) -- residuals recomputed from the returned vectors."""
+        iterations, products, residuals) -- residuals recomputed from the returned vectors.
+        precond = G, an Amg of this matrix (self.amg(...)): one column-blocked multigrid cycle per iteration forms W on the
+        pairs still active (cfs_hip_sym_lobpcg_amg); info then also has "cycles", the cycles applied, one per column.
+        The name "amg" alone is a ValueError here -- this method has no argument for the hierarchy -- and
+        solver.lobpcg_native(A, k, precond="amg", amg=G) is the spelling by name."""
         import torch
-        if isinstance(precond, str):
+        amg = precond if isinstance(precond, Amg) else None
+        if amg is not None:
+            if amg.A is not self:
+                raise ValueError("the hierarchy was made for another matrix")
+            block_rows = 0
+        elif isinstance(precond, str):
+            if precond == "amg":
+                raise ValueError('precond="amg" needs the hierarchy: pass it as precond (precond=A.amg(...)), or call '
+                                 'solver.lobpcg_native(A, k, precond="amg", amg=G)')
             if precond not in LOBPCG_PRECOND:
                 raise ValueError(f"unknown preconditioner {precond!r}: one of {sorted(LOBPCG_PRECOND)}")
             block_rows = int(block) if precond == "block_jacobi" else LOBPCG_PRECOND[precond]
@@ -501,6 +513,15 @@ class SymMatrix:
             torch.as_strided(x0buf, (n, k), (1, ld)).copy_(x0)
         dp = C.POINTER(C.c_double)
         nconv, iterations, products = C.c_int(), C.c_int(), C.c_int()
+        if amg is not None:
+            before = amg.column_cycles()
+            _lib.check(_lib.load().cfs_hip_sym_lobpcg_amg(
+                self._h, amg._a, k, float(tol), float(scale), int(maxiter), _ptr(x0buf) if x0buf is not None else None, ld,
+                w.ctypes.data_as(dp), _ptr(X), ld, res.ctypes.data_as(dp), C.byref(nconv), C.byref(iterations),
+                C.byref(products), _stream_ptr(stream)))
+            X = torch.as_strided(X, (n, k), (1, ld))
+            return w, X, {"nconv": nconv.value, "iterations": iterations.value, "products": products.value, "residuals": res,
+                          "cycles": amg.column_cycles() - before}
         _lib.check(_lib.load().cfs_hip_sym_lobpcg(
             self._h, k, block_rows, float(tol), float(scale), int(maxiter), _ptr(x0buf) if x0buf is not None else None, ld,
             w.ctypes.data_as(dp), _ptr(X), ld, res.ctypes.data_as(dp), C.byref(nconv), C.byref(iterations),
@@ -525,6 +546,26 @@ class SymMatrix:
         dp = C.POINTER(C.c_double)
         _lib.check(_lib.load().cfs_hip_sym_debug_lobpcg(
             self._h, int(k), int(block_rows), _ptr(x0buf) if x0buf is not None else None, ld, int(iters),
+            theta.ctypes.data_as(dp), _ptr(X), ld, res.ctypes.data_as(dp), _stream_ptr(stream)))
+        return theta, torch.as_strided(X, (n, k), (1, ld)), res
+
+    def debug_lobpcg_amg(self, amg, k, iters, x0=None, stream=None):
+        """developer / test: debug_lobpcg() with W formed by the blocked cycle of `amg` (cfs_hip_sym_debug_lobpcg_amg).
+        Returns (theta, X, resnorms)."""
+        import torch
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        n = self.nrows()
+        per = 16 // self.dtype.itemsize
+        ld = -(-n // per) * per
+        theta, res = np.zeros(k), np.zeros(k)
+        X = torch.zeros(k * ld, dtype=tdt, device="cuda")
+        x0buf = None
+        if x0 is not None:
+            x0buf = torch.zeros(k * ld, dtype=tdt, device="cuda")
+            torch.as_strided(x0buf, (n, k), (1, ld)).copy_(x0)
+        dp = C.POINTER(C.c_double)
+        _lib.check(_lib.load().cfs_hip_sym_debug_lobpcg_amg(
+            self._h, amg._a, int(k), _ptr(x0buf) if x0buf is not None else None, ld, int(iters),
             theta.ctypes.data_as(dp), _ptr(X), ld, res.ctypes.data_as(dp), _stream_ptr(stream)))
         return theta, torch.as_strided(X, (n, k), (1, ld)), res
 
@@ -720,10 +761,35 @@ class Amg:
         _lib.check(_lib.load().cfs_hip_amg_coarse_inverse(self._a, inv.ctypes.data))
         return inv
 
-    def apply(self, z, r, stream=None):
-        """z <- M^-1 r, one cycle (cfs_hip_amg_apply): device tensors of n values.  Returns z."""
-        _lib.check(_lib.load().cfs_hip_amg_apply(self._a, _ptr(z), _ptr(r), _stream_ptr(stream)))
+    def apply(self, z, r, *, active=None, stream=None):
+        """z <- M^-1 r, one cycle.  1-D device tensors of n values: cfs_hip_amg_apply.  2-D blocks (n, ncols) in the
+        column layout SymMatrix.lobpcg uses -- strides (1, ld), ld >= n and, for more than one column, ld a multiple
+        of 16 bytes: the column-blocked cycle (cfs_hip_amg_apply_cols), every vector kernel once for the block.
+        active: a bit mask of the columns to work on (None: all); the others are neither read nor written.
+        Returns z."""
+        if z.dim() == 1 and r.dim() == 1:
+            if active is not None:
+                raise ValueError("active names columns of a 2-D block")
+            _lib.check(_lib.load().cfs_hip_amg_apply(self._a, _ptr(z), _ptr(r), _stream_ptr(stream)))
+            return z
+        if z.dim() != 2 or r.dim() != 2 or z.shape != r.shape or z.dtype != r.dtype:
+            raise ValueError("z and r are both 1-D vectors, or both 2-D blocks of the same shape and type")
+        ncols = int(z.shape[1])
+        ld = int(z.stride(1)) if ncols > 1 else max(int(z.shape[0]), 1)
+        for t in (z, r):
+            if (z.shape[0] > 1 and t.stride(0) != 1) or (ncols > 1 and t.stride(1) != ld):
+                raise ValueError("a block is stored by columns: strides (1, ld), the same ld for z and r")
+        mask = (1 << ncols) - 1 if active is None else int(active)
+        if mask < 0 or mask >> 32:
+            raise ValueError("active is a mask of at most 32 bits")
+        _lib.check(_lib.load().cfs_hip_amg_apply_cols(self._a, _ptr(z), _ptr(r), ld, ncols, mask, _stream_ptr(stream)))
         return z
+
+    def column_cycles(self):
+        """the cycles applied to columns of blocks since the hierarchy was made (cfs_hip_amg_column_cycles)"""
+        out = C.c_longlong()
+        _lib.check(_lib.load().cfs_hip_amg_column_cycles(self._a, C.byref(out)))
+        return out.value
 
     def close(self):
         if getattr(self, "_a", None) and self._a.value:

@@ -555,9 +555,34 @@ def default_x0(n, k, dtype):
     return np.ascontiguousarray(v.reshape(k, n).T.astype(dtype))
 
 
-def _lobpcg_minv(A, precond, block):
-    """apply(R) -> M^-1 R in fp64 for an (n, j) block, with the stored inverse diagonal / inverse blocks of the handle"""
+def _lobpcg_amg_args(precond, amg):
+    """the two ValueErrors of precond="amg" / amg=, before any device work"""
+    if precond == "amg" and amg is None:
+        raise ValueError('lobpcg: precond="amg" needs amg=, the hierarchy (A.amg(...))')
+    if amg is not None and precond != "amg":
+        raise ValueError(f'lobpcg: amg= goes with precond="amg", not with {precond!r}')
+
+
+def _lobpcg_minv(A, precond, block, amg=None):
+    """apply(R) -> M^-1 R in fp64 for an (n, j) block, with the stored inverse diagonal / inverse blocks of the handle.
+    precond="amg": apply(R, cols) -> an (n, j) block whose columns `cols` are one cycle of `amg` each, on the column
+    rounded to the value type as the native loop stores it, by the ONE-COLUMN amg.apply (the model does not depend on the
+    blocked kernels); the other columns are zero"""
+    import numpy as np
     import torch
+    if precond == "amg":
+        tdt = torch.float64 if A.dtype == np.float64 else torch.float32
+
+        def cycles(R, cols):
+            n, j = R.shape
+            out = torch.zeros((n, j), dtype=torch.float64, device=R.device)
+            r, z = torch.empty(n, dtype=tdt, device=R.device), torch.empty(n, dtype=tdt, device=R.device)
+            for c in cols:
+                r.copy_(R[:, c])
+                amg.apply(z, r)
+                out[:, c] = z.double()
+            return out
+        return cycles
     if precond == "none":
         return lambda R: R
     if precond == "jacobi":
@@ -582,15 +607,18 @@ def _lobpcg_minv(A, precond, block):
     raise ValueError(f"unknown preconditioner {precond!r}: 'none', 'jacobi' or 'block_jacobi'")
 
 
-def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, iters=None):
+def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, iters=None, amg=None):
     """the k smallest eigenpairs by LOBPCG, host-driven: the recurrence of cfs_hip_sym_lobpcg (Gram matrices of
     S = [X | W | P_act] in fp64, the Rayleigh-Ritz step with its drop rule, X, P, AX, AP updated implicitly and rounded
     to the value type when stored, W = M^-1 R in fp64, soft locking, the confirm step) with torch operations on A's
     product and numpy on the host -- the model and the baseline of the native loop.  iters: like
     cfs_hip_sym_debug_lobpcg, iteration 0 and `iters` more with every pair active, no convergence test.  Returns
-    (w, X, info) like SymMatrix.lobpcg; with iters, info["residuals"] are those of the implicit AX."""
+    (w, X, info) like SymMatrix.lobpcg; with iters, info["residuals"] are those of the implicit AX.
+    precond="amg", amg=G: the model of cfs_hip_sym_lobpcg_amg -- W_i one cycle of G on the stored R_i, for the pairs the
+    native loop forms it for (those active, as its wmask); info["cycles"] counts them."""
     import numpy as np
     import torch
+    _lobpcg_amg_args(precond, amg)
     n = A.nrows()
     tdt = torch.float64 if A.dtype == np.float64 else torch.float32
     unit = 2.0 ** -53 if A.dtype == np.float64 else 2.0 ** -24
@@ -600,7 +628,8 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
     if scale is None and not debug:
         scale = abs(float(A.eigs(k=1, which="LM", tol=1e-3, vectors=False)[0][0]))
     thr = 0.0 if debug else tol * scale
-    apply = _lobpcg_minv(A, precond, block)
+    apply = _lobpcg_minv(A, precond, block, amg)
+    cycles = 0
     dev = "cuda" if x0 is None else x0.device
     S = torch.zeros((3 * k, n), dtype=tdt, device=dev)   # row c = physical column c: X | W | P
     AS = torch.zeros((3 * k, n), dtype=tdt, device=dev)
@@ -633,10 +662,16 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
 
     res = np.zeros(k)
 
-    def norms():
+    def norms(wcols=None):
+        nonlocal cycles
         X, AX = S[:k].double(), AS[:k].double()
         R = AX - torch.from_numpy(theta).to(dev)[:, None] * X
-        S[k:2 * k] = apply(R.T).T.to(tdt)
+        if amg is None:
+            S[k:2 * k] = apply(R.T).T.to(tdt)
+        else:  # (the native loop's wmask: every pair, or those active)
+            wcols = list(range(k)) if wcols is None else wcols
+            cycles += len(wcols)
+            S[k:2 * k] = apply(R.T, wcols).T.to(tdt)
         res[:] = (torch.linalg.vector_norm(R, dim=1) / torch.linalg.vector_norm(X, dim=1)).cpu().numpy()
 
     for attempt in range(3):
@@ -651,6 +686,7 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
             product(c)
     norms()
     it, fresh, have_p = 0, False, False
+    wmask = list(range(k))
     while True:
         act = [i for i in range(k) if debug or not res[i] <= thr]
         if not debug and not act:
@@ -659,32 +695,43 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
             for c in range(k):
                 product(c)
             norms()
+            wmask = list(range(k))
             fresh = True
             continue
         if it >= (iters if debug else maxiter):
             break
+        if amg is not None and set(act) - set(wmask):  # a pair that had converged and no longer does: its W is formed now
+            norms(act)
+            wmask = act
         for i in act:
             product(k + i)
         cols = list(range(k)) + [k + i for i in act] + ([2 * k + i for i in act] if have_p else [])
         if rayleigh_ritz(cols) < k:
             raise RuntimeError("lobpcg: the basis lost rank")
         have_p, fresh = True, False
-        norms()
+        wmask = act
+        norms(act)
         it += 1
     if not debug and not fresh:
         for c in range(k):
             product(c)
-        norms()
+        norms([])
     nconv = 0
     while nconv < k and res[nconv] <= thr:
         nconv += 1
-    return theta.copy(), S[:k].T.clone(), {"nconv": nconv, "iterations": it, "products": products, "residuals": res.copy()}
+    info = {"nconv": nconv, "iterations": it, "products": products, "residuals": res.copy()}
+    if amg is not None:
+        info["cycles"] = cycles
+    return theta.copy(), S[:k].T.clone(), info
 
 
-def lobpcg_native(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None):
+def lobpcg_native(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, amg=None):
     """the same iteration inside the library (cfs_hip_sym_lobpcg): the Gram matrices by one small-SYRK kernel, the
     update in place, residual and preconditioner in one kernel; two host looks per iteration.  Returns (w, X, info),
-    like lobpcg()."""
+    like lobpcg().  precond="amg", amg=G: cfs_hip_sym_lobpcg_amg, W by one column-blocked cycle of G per iteration."""
+    _lobpcg_amg_args(precond, amg)
+    if amg is not None:
+        return A.lobpcg(k=k, precond=amg, block=block, tol=tol, scale=scale, maxiter=maxiter, x0=x0)
     return A.lobpcg(k=k, precond=precond, block=block, tol=tol, scale=scale, maxiter=maxiter, x0=x0)
 
 

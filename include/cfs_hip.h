@@ -658,6 +658,27 @@ int cfs_hip_amg_coarse_inverse(cfs_hip_amg_t a, void *inv);
  * vectors belong to the object: one cycle of an object at a time.  CFS_HIP_ERR_ARG: a null pointer, z == r, a pointer
  * that is not 16-byte aligned, a host pointer or one on another device.                                          */
 int cfs_hip_amg_apply(cfs_hip_amg_t a, void *z_dev, const void *r_dev, void *stream);
+/* One cycle on a BLOCK OF COLUMNS, enqueued on `stream`: Z_c = M^-1 R_c for every column c < ncols whose bit is set in
+ * `active`; a column whose bit is clear is neither read nor written.  Column c of Z at z_dev + c ld values, of R at
+ * r_dev + c ld values; rows [0, n) of the active columns of Z are fully overwritten, nothing else of the caller's is
+ * written, R is not modified.  Every vector kernel of the cycle runs ONCE for the block -- a level costs the launches
+ * of the one-column cycle, 4 at degree 1 and 2 more per further degree, whatever ncols -- and reads the level's data
+ * (the inverse diagonal or blocks, W, the aggregates, the dense inverse) once per chunk of columns; the products stay
+ * one per active column.  Per column the arithmetic is that of cfs_hip_amg_apply: on a CFS_HIP_FLAG_DETERMINISTIC
+ * handle column c has the bits of cfs_hip_amg_apply on R_c alone.  Serves every hierarchy cfs_hip_amg_apply serves
+ * (scalar, node-block, device-built, refreshable: the values poured into the fine handle since are followed).  The
+ * levels' work vectors for ncols columns are allocated at the first call of that width and kept (counted in
+ * cfs_hip_amg_info().device_bytes); only a wider call makes them again.  One cycle of an object at a time.
+ * CFS_HIP_ERR_ARG, before any device work, in this order: a null pointer; ncols outside 1 .. CFS_HIP_LOBPCG_MAX_K; a
+ * bit of `active` from ncols on; z_dev or r_dev not 16-byte aligned; ld < n, or ncols > 1 and ld sizeof(V) not a
+ * multiple of 16; the two blocks overlap; a hierarchy whose last refresh failed; then as cfs_hip_amg_apply for a host
+ * pointer or one on another device.  active == 0: returns 0 behind those checks and enqueues nothing.            */
+int cfs_hip_amg_apply_cols(cfs_hip_amg_t a, void *z_dev, const void *r_dev, long long ld, int ncols, unsigned active,
+                           void *stream);
+/* *cycles: the cycles the object has applied to columns of blocks since it was created -- one per active column of
+ * every cfs_hip_amg_apply_cols and of every W block formed by cfs_hip_sym_lobpcg_amg / _debug_lobpcg_amg (the
+ * difference across a solve is the number of cycles it cost).  cfs_hip_amg_apply and cfs_hip_sym_pcg_amg do not count. */
+int cfs_hip_amg_column_cycles(cfs_hip_amg_t a, long long *cycles);
 /* cfs_hip_sym_pcg_cheb with the polynomial replaced by the cycle of `a`, which must have been created on h (otherwise
  * CFS_HIP_ERR_ARG): the same residual kernel, the same stopping rule on the UNPRECONDITIONED residual, r.r <= tol^2 b.b;
  * a NaN ends the solve; *relres is RECOMPUTED from the returned u; r.z sums the stored r and the stored final z; all
@@ -905,6 +926,29 @@ int cfs_hip_debug_gram(const void *s_dev, const void *t_dev, long long ld, long 
  * after the last one (the sibling of cfs_hip_sym_debug_lanczos).  Arguments as for cfs_hip_sym_lobpcg.       */
 int cfs_hip_sym_debug_lobpcg(cfs_hip_sym_t h, int k, int block_rows, const void *x0_dev, long long ld0, int iters,
                              double *theta, void *vectors_dev, long long ld, double *resnorms, void *stream);
+/* cfs_hip_sym_lobpcg with W_i = M^-1 R_i formed by ONE column-blocked multigrid cycle of `a` per iteration
+ * (cfs_hip_amg_apply_cols on the pairs still active) instead of a stored inverse diagonal.  Everything else of the
+ * iteration is the same code: the Gram kernel, the Rayleigh-Ritz step, the update kernel, the stopping rule on
+ * tol scale, soft locking, the confirm step, the rank rule for x0; all arguments as there.  Step 4 writes the raw
+ * (V)R_i into the W-columns of AS, which are free until the products of step 6 rewrite them, and the cycle reads them
+ * from there: device memory held is that of cfs_hip_sym_lobpcg without the inverse diagonal, 6 k n values, plus the
+ * hierarchy's work vectors for k columns (cfs_hip_amg_apply_cols).  *products counts only the solver's own products,
+ * as cfs_hip_sym_lobpcg does.  A cycle costs 2 + 2 (degree - 1) smoothing products per multigrid level and column
+ * (one for the restriction and one for the restart, and degree - 1 in each Chebyshev chain), and degree - 1 on a
+ * smoother-only level; the number of cycles is the difference of cfs_hip_amg_column_cycles across the call.  On a
+ * CFS_HIP_FLAG_DETERMINISTIC handle the solve is bit-reproducible.
+ * Refusals, nothing written but the counters zeroed: CFS_HIP_ERR_ARG for a null h, a, eigenvalues or vectors_dev
+ * ("null"); then those of cfs_hip_sym_lobpcg from "bad k" on, in its order, with CFS_HIP_ERR_ARG for a value type of
+ * `a` other than h's where the handle is first read (before a shard: CFS_HIP_ERR_UNSUPPORTED); then
+ * CFS_HIP_ERR_UNSUPPORTED for a multi-device handle; then CFS_HIP_ERR_ARG for a hierarchy created on another handle,
+ * and for one whose last refresh failed.                                                                       */
+int cfs_hip_sym_lobpcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, int k, double tol, double scale, int maxiter,
+                           const void *x0_dev, long long ld0, double *eigenvalues, void *vectors_dev, long long ld,
+                           double *residuals, int *nconv, int *iterations, int *products, void *stream);
+/* the counterpart of cfs_hip_sym_debug_lobpcg: iteration 0 and `iters` more with the kernels of
+ * cfs_hip_sym_lobpcg_amg, every pair active, no convergence test, no confirm step.  Arguments and refusals as there. */
+int cfs_hip_sym_debug_lobpcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, int k, const void *x0_dev, long long ld0, int iters,
+                                 double *theta, void *vectors_dev, long long ld, double *resnorms, void *stream);
 /* step 3 alone, on one n x 3 k device block (X | W | P): with S its first m columns (1 <= m <= 3 k) and c m x 2 k
  * row-major on the host, X <- (V)(S c[:, :k]) and P <- (V)(S c[:, k:]), in place.  The call waits for the kernel. */
 int cfs_hip_debug_lobpcg_update(void *s_dev, long long ld, long long n, int k, int m, const double *c, int value_bytes,

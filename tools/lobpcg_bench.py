@@ -15,7 +15,17 @@ looks: synchronisation, the copies, the host's Rayleigh-Ritz step and launch gap
 Last, products and wall time to nconv = 4 at tol 1e-8 on Flan_1565 at scale 0.05 with block Jacobi, beside
 eigs(which="SA") given at least the same number of products.  Prints one JSON line and writes it to
 profiles/lobpcg_bench.json.
-usage: python tools/lobpcg_bench.py [matrix[:scale] ...]"""
+
+--amg: the multigrid form (cfs_hip_sym_lobpcg_amg) on its own, the columns above untouched.  Per matrix (default:
+lap2d400x330, lap2d800x660, pwtk, ldoor, Flan_1565; fp64, the default hierarchy options, tol AMG_TOL = 1e-8) and k = 4, 16:
+wall time to tolerance, iterations, products and cycles of Jacobi and block-Jacobi LOBPCG of the same build against the
+multigrid form, and the microseconds per iteration of each (the wall time over the iterations of that solve); the runs
+interleaved, AMG_ROUNDS = 3 rounds, the best of each, as tools/cg_bench.py does.  The hierarchy is built outside the timed
+region and its set-up seconds stand beside the numbers.  Separately, one blocked apply of k columns
+(cfs_hip_amg_apply_cols) against k one-column applies on the same hierarchy.  A solve stops at AMG_MAXITER = 2000
+iterations; nconv says whether it got there.  Prints one JSON line and writes it to profiles/lobpcg_amg_bench.json.
+usage: python tools/lobpcg_bench.py [matrix[:scale] ...]
+       python tools/lobpcg_bench.py --amg [--rounds R] [--k 4,16] [matrix[:scale] | lap2dNXxNY ...]"""
 import csv, ctypes as C, glob, json, os, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -148,8 +158,102 @@ def main(specs):
         f.write(line + "\n")
 
 
+AMG_TOL, AMG_ROUNDS, AMG_MAXITER = 1e-8, 3, 2000
+
+
+def amg_matrix(spec):
+    name, _, sc = spec.partition(":")
+    if name.startswith("lap2d"):  # lap2dNXxNY: the anisotropic 5-point Laplacian of the tests
+        import scipy.sparse as sp
+        nx, ny = (int(v) for v in name[5:].split("x"))
+        T = lambda k: sp.diags([-np.ones(k - 1), 2 * np.ones(k), -np.ones(k - 1)], [-1, 0, 1])
+        L = (sp.kron(sp.identity(ny), T(nx)) + 0.37 * sp.kron(T(ny), sp.identity(nx))).tocsr()
+        L.sort_indices()
+        return L.shape[0], L.indptr.astype(np.int32), L.indices.astype(np.int32), L.data
+    return synth.generate(name, float(sc or 1.0))[:4]
+
+
+def main_amg(specs, rounds, ks):
+    out = {"tolerance": AMG_TOL, "rounds": rounds, "maxiter": AMG_MAXITER, "dtype": "float64"}
+    for spec in specs:
+        n, rp, ci, va = amg_matrix(spec)
+        A = cfs.SymMatrix(n, rp, ci, va)
+        G = A.amg(rp, ci, va)
+        inf = G.info()
+        scale = abs(float(A.eigs(k=1, which="LM", tol=1e-3, vectors=False)[0][0]))
+        res = {"n": n, "scale": scale, "amg_levels": inf["n"], "amg_kinds": inf["kind"], "amg_setup_seconds": round(inf["setup_seconds"], 4),
+               "amg_device_bytes": inf["device_bytes"]}
+        for k in ks:
+            kw = dict(k=k, tol=AMG_TOL, scale=scale, maxiter=AMG_MAXITER)
+            loops = {"jacobi": lambda: A.lobpcg(precond="jacobi", **kw)[2], "block3": lambda: A.lobpcg(precond="block_jacobi", block=3, **kw)[2],
+                     "amg": lambda: A.lobpcg(precond=G, **kw)[2]}
+            if n % 3:  # (no node blocks of 3 rows)
+                del loops["block3"]
+            best_of = {}
+            for _ in range(rounds):  # interleaved
+                for label, fn in loops.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    info = fn()
+                    torch.cuda.synchronize()
+                    t = time.perf_counter() - t0
+                    if t < best_of.get(label, (float("inf"),))[0]:
+                        best_of[label] = (t, info)
+            for label, (t, info) in best_of.items():
+                res[f"k{k}_{label}"] = {"ms_to_tolerance": round(t * 1e3, 3), "nconv": info["nconv"], "iterations": info["iterations"],
+                                        "products": info["products"], "cycles": info.get("cycles", 0),
+                                        "us_per_iteration": round(t * 1e6 / max(1, info["iterations"]), 2),
+                                        "max_residual_over_scale": float(np.max(info["residuals"]) / scale)}
+            for label in ("jacobi", "block3"):
+                if label in best_of:
+                    res[f"k{k}_amg_over_{label}_time"] = round(best_of["amg"][0] / best_of[label][0], 4)
+            # one blocked cycle of k columns against k one-column cycles
+            per = 2
+            ld = -(-n // per) * per
+            Rb = torch.zeros(k * ld, dtype=torch.float64, device="cuda")
+            R = torch.as_strided(Rb, (n, k), (1, ld))
+            R.copy_(torch.from_numpy(np.random.default_rng(k).uniform(-1, 1, (n, k))))
+            Z = torch.as_strided(torch.zeros(k * ld, dtype=torch.float64, device="cuda"), (n, k), (1, ld))
+            reps = 20
+            blocked = lambda: [G.apply(Z, R) for _ in range(reps)]
+            single = lambda: [G.apply(Z[:, c], R[:, c]) for _ in range(reps) for c in range(k)]
+            tb = ts = float("inf")
+            blocked(), single()
+            for _ in range(rounds):  # interleaved
+                for which, fn in (("b", blocked), ("s", single)):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    t = (time.perf_counter() - t0) / reps
+                    if which == "b":
+                        tb = min(tb, t)
+                    else:
+                        ts = min(ts, t)
+            res[f"k{k}_apply"] = {"blocked_us": round(tb * 1e6, 2), "k_one_column_us": round(ts * 1e6, 2), "blocked_over_one_column": round(tb / ts, 4)}
+        G.close()
+        A.close()
+        out[spec] = res
+        print(json.dumps({spec: res}), flush=True)
+    line = json.dumps(out)
+    print(line)
+    with open(os.path.join(ROOT, "profiles", "lobpcg_amg_bench.json"), "w") as f:
+        f.write(line + "\n")
+
+
 if __name__ == "__main__":
     if sys.argv[1:2] == ["--child"]:
         child(sys.argv[2], int(sys.argv[3]))
+    elif "--amg" in sys.argv[1:]:
+        args, rounds, ks = [a for a in sys.argv[1:] if a != "--amg"], AMG_ROUNDS, (4, 16)
+        if "--rounds" in args:
+            i = args.index("--rounds")
+            rounds = int(args[i + 1])
+            del args[i:i + 2]
+        if "--k" in args:
+            i = args.index("--k")
+            ks = tuple(int(v) for v in args[i + 1].split(","))
+            del args[i:i + 2]
+        main_amg(args or ["lap2d400x330", "lap2d800x660", "pwtk", "ldoor", "Flan_1565"], rounds, ks)
     else:
         main(sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"])
