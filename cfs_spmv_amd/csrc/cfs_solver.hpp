@@ -87,6 +87,34 @@ template <typename V> struct Vec16 {
   typedef V type __attribute__((ext_vector_type(16 / sizeof(V))));
 };
 
+// The columns a kernel of the multigrid cycle works on (cfs_solver_cheb.hpp, cfs_solver_amg.hpp), as a type.  Column c of
+// a vector lives at base + c ld.  each(f) calls f(c) for every column of the set, ascending; where a kernel's accumulators
+// are per column it takes the columns in chunks of chunk(cw): chunks<CW>(f) calls f(c0, bits) per chunk that has a
+// column, bit e of bits saying whether column c0 + e is one.
+// OneColumn: column 0, known at compile time: no loop, no mask test, and the c ld offsets fold away.
+struct OneColumn {
+  static constexpr bool one = true;
+  static constexpr int chunk(int) { return 1; }
+  template <class F> __host__ __device__ __forceinline__ void each(F &&f) const { f(0); }
+  template <int CW, class F> __device__ __forceinline__ void chunks(F &&f) const { f(0, 1u); }
+};
+// ColumnMask: the columns c < ncols <= 16 whose bit is set in `active` (no bit from ncols on is set), known at run time
+// and uniform over the grid; a column whose bit is clear is neither read nor written
+struct ColumnMask {
+  static constexpr bool one = false;
+  static constexpr int chunk(int cw) { return cw; }
+  int ncols;
+  unsigned active;
+  template <class F> __host__ __device__ __forceinline__ void each(F &&f) const {
+    for (int c = 0; c < ncols; ++c)
+      if ((active >> c) & 1u) f(c);
+  }
+  template <int CW, class F> __device__ __forceinline__ void chunks(F &&f) const {
+    for (int c0 = 0; c0 < ncols; c0 += CW)
+      if (const unsigned bits = (active >> c0) & ((1u << CW) - 1u)) f(c0, bits);
+  }
+};
+
 // dinv = (V)(1 / d) in place over the gathered diagonal;  part[P_BAD] <- entries that are not finite and > 0
 template <typename V>
 __global__ void __launch_bounds__(kThreads) cg_dinv_kernel(V *__restrict__ d, long long n, double *__restrict__ part) {
@@ -338,15 +366,17 @@ __global__ void __launch_bounds__(kThreads)
       }
 }
 
-// z = Minv_k r over node block k, in fp64 (r: the block's rounded residual, 0 outside the matrix)
+// z = Minv_k r over node block k, in fp64 (r: the block's rounded residual, 0 outside the matrix), in two halves: the
+// packed inverse block of node k into registers (the one place that reads the packed layout), and its product with
+// one vector's values -- a kernel that works on several columns loads once and multiplies per column
 template <typename V, int BS>
-__device__ __forceinline__ void block_apply(const V *__restrict__ minv, long long nb, long long k, const double (&r)[BS],
-                                            double (&z)[BS]) {
-  double m[BS][BS];
+__device__ __forceinline__ void block_load(const V *__restrict__ minv, long long nb, long long k, double (&m)[BS][BS]) {
 #pragma unroll
   for (int i = 0; i < BS; ++i)
 #pragma unroll
     for (int j = 0; j <= i; ++j) m[i][j] = m[j][i] = (double)minv[(long long)(i * (i + 1) / 2 + j) * nb + k];
+}
+template <int BS> __device__ __forceinline__ void block_mul(const double (&m)[BS][BS], const double (&r)[BS], double (&z)[BS]) {
 #pragma unroll
   for (int i = 0; i < BS; ++i) {
     double v = 0.0;
@@ -354,6 +384,13 @@ __device__ __forceinline__ void block_apply(const V *__restrict__ minv, long lon
     for (int j = 0; j < BS; ++j) v += m[i][j] * r[j];
     z[i] = v;
   }
+}
+template <typename V, int BS>
+__device__ __forceinline__ void block_apply(const V *__restrict__ minv, long long nb, long long k, const double (&r)[BS],
+                                            double (&z)[BS]) {
+  double m[BS][BS];
+  block_load<V, BS>(minv, nb, k, m);
+  block_mul<BS>(m, r, z);
 }
 
 // cg_residual_kernel<V, true> with M = blockdiag(A):  r = b - q;  p = z = Minv r;  part <- r . r, b . b, r . z

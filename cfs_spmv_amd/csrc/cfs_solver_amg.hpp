@@ -18,7 +18,9 @@
 // handle is); level 0 is the caller's handle.  Per non-dense level: dinv as cg_dinv_kernel stores it, the bound
 // lmax = 1.1 x cheb_power (Jacobi, 16 steps, the fixed start vector), lmin = lmax / ratio, the coefficient pairs.
 //
-// ONE CYCLE z = M^-1 r, S_l the level's Chebyshev polynomial of degree m in D^-1 A_l (cfs_solver_cheb.hpp):
+// ONE CYCLE z = M^-1 r, S_l the level's Chebyshev polynomial of degree m in D^-1 A_l (cfs_solver_cheb.hpp).  Amg::cycle
+// and every vector kernel of it are templates over the set of columns they work on (OneColumn or ColumnMask,
+// cfs_solver.hpp): written once, for one column here and for a block of columns under THE COLUMNS OF A CYCLE below.
 //   dense level:          z = (V)(A_L^-1 r)                                   amg_dense_kernel               1 launch
 //   smoother-only level:  z = S_l r                                           cheb_start_kernel + cheb_chain 1 + 3 (m - 1)
 //   otherwise:            z = S_l r                                                                          1 + 3 (m - 1)
@@ -87,33 +89,32 @@
 //   agg_l[i BS + c] = agg_node[i] BS + c;  P_l = W Q_1 .. Q_p;  A_{l+1} = the last B, again a node-block matrix
 // Everything else of a level is the scalar form's.  The hierarchy is host-built and not refreshable.  On the device W is
 // kept the way the block-Jacobi inverse is -- packed lower triangle, word t = i (i + 1) / 2 + j of node k at
-// w[t m + k], read by block_apply -- and the aggregate lists and agg hold NODES.  The cycle is the one above with
+// w[t m + k], read by block_load -- and the aggregate lists and agg hold NODES.  The cycle is the one above, the BS >= 2
+// branch of the same kernels, with
 //   the smoother in M^-1 A_l, M = blockdiag(A_l):  Precond<V, BS>, cheb_power<V, BS>, cheb_start_kernel<V, BS>, cheb_chain<V, BS>
-//   rc_I = (V)(sum_{i in I, ascending} W_i (r_i - t_i))                          amg_restrict_block_kernel
-//   z_i = (V)(z_i + W_i ec_I)                                                    amg_prolong_block_kernel
-//   d_i = (V)((1/theta) M_i^-1 (r_i - t_i));  z_i = (V)(z_i + d_i)               amg_restart_block_kernel
+//   rc_I = (V)(sum_{i in I, ascending} W_i (r_i - t_i))                          amg_restrict_kernel<V, BS>
+//   z_i = (V)(z_i + W_i ec_I)                                                    amg_prolong_kernel<V, BS>
+//   d_i = (V)((1/theta) M_i^-1 (r_i - t_i));  z_i = (V)(z_i + d_i)               amg_restart_kernel<V, BS>
 // one thread per node, the same 8 + 6 (m - 1) launches; W_i is symmetric and restriction the transpose of prolongation,
 // so M^-1 stays symmetric, and nothing is atomic.
 //
-// THE COLUMN-BLOCKED CYCLE (cfs_hip_amg_apply_cols, cfs_hip_sym_lobpcg_amg; cycle_cols) is the cycle above on the columns
-// c < ncols <= 16 of a block whose bit is set in a mask, Z_c = M^-1 R_c, for the W block of LOBPCG.  Every vector kernel
-// has a _cols form that is launched ONCE for the block --
-//   cheb_start_cols_kernel, cheb_step_cols_kernel (cfs_solver_cheb.hpp), amg_restrict_cols_kernel, amg_prolong_cols_kernel,
-//   amg_restart_cols_kernel (BS = 1 and the node-block form in one template), amg_dense_cols_kernel
-// -- so a level costs 4 + 2 (m - 1) vector-kernel launches for any ncols, where ncols one-column cycles cost ncols times
-// that; the products stay one spmv_local per active column at each place where cycle() has one.  What a row, node or
-// aggregate reads of the level -- dinv or the packed inverse block, the packed W, agg, the aggregate list, a row of the
-// dense inverse -- is loaded once and used for all columns of a chunk: the whole block in the element-wise kernels (the
-// columns are the inner loop, the level's words stay in registers), chunks of 8 / 4 / 2 columns (BS = 1 / 2, 3, 4 / 6)
-// in the restriction, whose fp64 accumulators are per column, and of 8 in the dense kernel.  A column whose bit is clear
-// is neither read nor written.  Per column the expressions are those of the one-column kernels operand for operand, so
-// the compiler forms the same operations: on a deterministic handle column c has the bits of cycle() on R_c alone.
-// (Neither family of kernels switches contraction off: under the compiler's default both get the same fused
-// multiply-adds because the expression trees are the same.  The bit equality rests on that, and
-// tests/test_gpu_amg_apply_cols.py is what notices if a compiler ever chooses differently for the two loop nests.)
-// The levels' work vectors for a block (cd, ct on a level that smooths, cr, cz below level 0; columns of n_l rounded up
-// to 16 bytes) are allocated at the first blocked call of a width, kept, and made again only for a wider call
-// (reserve_cols); cycle() keeps its own vectors and is not touched.
+// THE COLUMNS OF A CYCLE.  cfs_hip_amg_apply_cols and cfs_hip_sym_lobpcg_amg run the cycle above on the columns
+// c < ncols <= 16 of a block whose bit is set in a mask, Z_c = M^-1 R_c, for the W block of LOBPCG: cycle() with a
+// ColumnMask where cfs_hip_amg_apply and cfs_hip_sym_pcg_amg pass OneColumn.  Every vector kernel is launched ONCE for
+// the columns, so a level costs 4 + 2 (m - 1) vector-kernel launches for any ncols, where ncols one-column cycles cost
+// ncols times that; the products stay one spmv_local per column at each place.  What a row, node or aggregate reads of
+// the level -- dinv or the packed inverse block, the packed W, agg, the aggregate list, a row of the dense inverse -- is
+// loaded once and used for all columns of a chunk: the whole block in the element-wise kernels (the columns are the
+// inner loop, the level's words stay in registers), chunks of 8 / 4 / 2 columns (BS = 1 / 2, 3, 4 / 6) in the
+// restriction, whose fp64 accumulators are per column, and of 8 in the dense kernel.  A column whose bit is clear is
+// neither read nor written.  For OneColumn the loops, the mask tests and the c ld offsets fold away at compile time.
+// There is one body per kernel, but its OneColumn and ColumnMask instantiations are compiled separately, and neither
+// switches contraction off: that column c of a block has the bits of the one-column cycle on R_c alone (on a
+// deterministic handle) still rests on the compiler contracting both alike -- now from literally the same source text,
+// the same casts, parentheses and order of sums -- and test B1 of tests/test_gpu_amg_apply_cols.py remains the judge.
+// The work vectors differ (Amg::work): one column uses the level's d, t, r, z that build() allocates; a block uses cd, ct
+// on a level that smooths and cr, cz below level 0, columns of n_l rounded up to 16 bytes, allocated at the first blocked
+// call of a width, kept, and made again only for a wider call (reserve_cols).  Nothing is allocated for blocks before.
 #pragma once
 
 #include <algorithm>
@@ -696,165 +697,25 @@ inline int amg_dense_inverse(const AmgCsr &low, std::vector<double> &inv) {
   return -1;
 }
 
-// ---- the kernels of the cycle ----------------------------------------------------------------------
-// rc_I = (V)(sum over the members i of aggregate I, ascending, of w_i (r_i - t_i)): one thread per aggregate
-template <typename V>
-__global__ void __launch_bounds__(kThreads)
-    amg_restrict_kernel(V *__restrict__ rc, const V *__restrict__ r, const V *__restrict__ t, const V *__restrict__ w,
-                        const int *__restrict__ aggptr, const int *__restrict__ aggidx, long long nc, const int *__restrict__ ic) {
-  if (ic[I_DONE]) return;
-  for (long long I = (long long)blockIdx.x * kThreads + threadIdx.x; I < nc; I += (long long)gridDim.x * kThreads) {
-    double s = 0.0;
-    for (int k = aggptr[I]; k < aggptr[I + 1]; ++k) {
-      const int i = aggidx[k];
-      s += (double)w[i] * ((double)r[i] - (double)t[i]);
-    }
-    rc[I] = (V)s;
-  }
-}
-
-// z_i = (V)(z_i + w_i ec_agg(i))
-template <typename V>
-__global__ void __launch_bounds__(kThreads)
-    amg_prolong_kernel(V *__restrict__ z, const V *__restrict__ ec, const V *__restrict__ w, const int *__restrict__ agg, long long n,
-                       const int *__restrict__ ic) {
-  if (ic[I_DONE]) return;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads)
-    z[i] = (V)((double)z[i] + (double)w[i] * (double)ec[agg[i]]);
-}
-
-// cheb_start_kernel from a nonzero z, t = A z given:  d = (V)((1 / theta) dinv (r - t));  z = (V)(z + d)
-template <typename V>
-__global__ void __launch_bounds__(kThreads)
-    amg_restart_kernel(V *__restrict__ z, V *__restrict__ d, const V *__restrict__ r, const V *__restrict__ t, long long n,
-                       double inv_theta, const V *__restrict__ dinv, const int *__restrict__ ic) {
-  if (ic[I_DONE]) return;
-  constexpr int W = Vec16<V>::W;
-  typedef typename Vec16<V>::type VT;
-  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  for (long long i = t0; i < nv; i += stride) {
-    const VT rv = reinterpret_cast<const VT *>(r)[i], tv = reinterpret_cast<const VT *>(t)[i], mv = reinterpret_cast<const VT *>(dinv)[i];
-    VT zv = reinterpret_cast<VT *>(z)[i], dv;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      dv[k] = (V)(inv_theta * (((double)rv[k] - (double)tv[k]) * (double)mv[k]));
-      zv[k] = (V)((double)zv[k] + (double)dv[k]);
-    }
-    reinterpret_cast<VT *>(d)[i] = dv;
-    reinterpret_cast<VT *>(z)[i] = zv;
-  }
-  for (long long i = nv * W + t0; i < n; i += stride) {
-    const V di = (V)(inv_theta * (((double)r[i] - (double)t[i]) * (double)dinv[i]));
-    d[i] = di;
-    z[i] = (V)((double)z[i] + (double)di);
-  }
-}
-
-// ---- the node-block transfers: one thread per node, W and M^-1 packed as cg_binv_kernel packs, read by block_apply ----
-// rc_I = (V)(sum over the member nodes i of aggregate I, ascending, of W_i (r_i - t_i)): one thread per coarse node;
-// m: the nodes of the fine level (the stride of the packed W)
-template <typename V, int BS>
-__global__ void __launch_bounds__(kThreads)
-    amg_restrict_block_kernel(V *__restrict__ rc, const V *__restrict__ r, const V *__restrict__ t, const V *__restrict__ w, long long m,
-                              const int *__restrict__ aggptr, const int *__restrict__ aggidx, long long nc, const int *__restrict__ ic) {
-  if (ic[I_DONE]) return;
-  for (long long I = (long long)blockIdx.x * kThreads + threadIdx.x; I < nc; I += (long long)gridDim.x * kThreads) {
-    double s[BS];
-#pragma unroll
-    for (int c = 0; c < BS; ++c) s[c] = 0.0;
-    for (int k = aggptr[I]; k < aggptr[I + 1]; ++k) {
-      const long long i = aggidx[k];
-      double x[BS], y[BS];
-#pragma unroll
-      for (int c = 0; c < BS; ++c) x[c] = (double)r[i * BS + c] - (double)t[i * BS + c];
-      block_apply<V, BS>(w, m, i, x, y);
-#pragma unroll
-      for (int c = 0; c < BS; ++c) s[c] += y[c];
-    }
-#pragma unroll
-    for (int c = 0; c < BS; ++c) rc[I * BS + c] = (V)s[c];
-  }
-}
-
-// z_i = (V)(z_i + W_i ec_I), I = agg[i] the coarse NODE of node i: one thread per fine node
-template <typename V, int BS>
-__global__ void __launch_bounds__(kThreads)
-    amg_prolong_block_kernel(V *__restrict__ z, const V *__restrict__ ec, const V *__restrict__ w, const int *__restrict__ agg, long long m,
-                             const int *__restrict__ ic) {
-  if (ic[I_DONE]) return;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < m; i += (long long)gridDim.x * kThreads) {
-    const long long I = agg[i];
-    double e[BS], y[BS];
-#pragma unroll
-    for (int c = 0; c < BS; ++c) e[c] = (double)ec[I * BS + c];
-    block_apply<V, BS>(w, m, i, e, y);
-#pragma unroll
-    for (int c = 0; c < BS; ++c) z[i * BS + c] = (V)((double)z[i * BS + c] + y[c]);
-  }
-}
-
-// amg_restart_kernel with M = blockdiag(A_l):  d_k = (V)((1 / theta) Minv_k (r_k - t_k));  z_k = (V)(z_k + d_k), the
-// inverse applied as cheb_start_kernel<V, BS> applies it
-template <typename V, int BS>
-__global__ void __launch_bounds__(kThreads)
-    amg_restart_block_kernel(V *__restrict__ z, V *__restrict__ d, const V *__restrict__ r, const V *__restrict__ t, long long n,
-                             double inv_theta, const V *__restrict__ minv, long long nb, const int *__restrict__ ic) {
-  if (ic[I_DONE]) return;
-  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
-    double x[BS], zz[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      const long long g = k * BS + i;
-      x[i] = g < n ? (double)r[g] - (double)t[g] : 0.0;
-    }
-    block_apply<V, BS>(minv, nb, k, x, zz);
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      const long long g = k * BS + i;
-      if (g < n) {
-        const V di = (V)(inv_theta * zz[i]);
-        d[g] = di;
-        z[g] = (V)((double)z[g] + (double)di);
-      }
-    }
-  }
-}
-
-// z = (V)(inv r) on the dense level: one wave per row, the lanes stride over the columns, a fixed-order sum
-template <typename V>
-__global__ void __launch_bounds__(kThreads)
-    amg_dense_kernel(V *__restrict__ z, const V *__restrict__ inv, const V *__restrict__ r, int n, const int *__restrict__ ic) {
-  if (ic[I_DONE]) return;
-  const int lane = threadIdx.x & 63, nwaves = gridDim.x * (kThreads / 64);
-  for (int i = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); i < n; i += nwaves) { // (uniform over the wave)
-    const V *row = inv + (size_t)i * n;
-    double s = 0.0;
-    for (int j = lane; j < n; j += 64) s += (double)row[j] * (double)r[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    if (lane == 0) z[i] = (V)s;
-  }
-}
-
-// ---- the kernels of the cycle on a BLOCK OF COLUMNS (see THE COLUMN-BLOCKED CYCLE in the header comment) ----
-// Column c of a block at base + c ld; the columns whose bit is set in `active` (c < ncols) are worked on in one launch,
-// the others neither read nor written.  BS = 1: the scalar form, BS >= 2: the node-block form (one thread per node, w
-// the packed W or M^-1, m the nodes of the level).  The columns go in chunks of CW: what a row, node or aggregate reads
-// of the level -- w_i or W_i, agg, the aggregate list, a row of the dense inverse -- is loaded once per chunk.
+// ---- the kernels of the cycle, on a set of columns CS (see ONE CYCLE and THE COLUMNS OF A CYCLE in the header comment) ----
+// Column c of a vector at base + c ld; the columns of cs are worked on in one launch, the others neither read nor
+// written.  BS = 1: the scalar form, BS >= 2: the node-block form (one thread per node, w the packed W or M^-1 read by
+// block_load, m the nodes of the level).  Where the accumulators are per column the columns go in chunks of CW: what a
+// row, node or aggregate reads of the level -- w_i or W_i, agg, the aggregate list, a row of the dense inverse -- is
+// loaded once per chunk.  One column is one chunk of one.
 template <int BS> constexpr int amg_restrict_chunk() { return BS == 1 ? 8 : BS == 6 ? 2 : 4; } // (CW BS fp64 accumulators)
 constexpr int kAmgDenseChunk = 8;
 
-// rc_{I,c} = (V)(sum over the members i of aggregate I, ascending, of W_i (r_{i,c} - t_{i,c}))
-template <typename V, int BS>
+// rc_{I,c} = (V)(sum over the members i of aggregate I, ascending, of W_i (r_{i,c} - t_{i,c})): one thread per aggregate
+// (BS >= 2: per coarse node, the members fine nodes)
+template <typename V, int BS, class CS>
 __global__ void __launch_bounds__(kThreads)
-    amg_restrict_cols_kernel(V *__restrict__ rc, long long ldc, const V *__restrict__ r, long long ldr, const V *__restrict__ t,
-                             long long ldt, const V *__restrict__ w, long long m, const int *__restrict__ aggptr,
-                             const int *__restrict__ aggidx, long long nc, const int *__restrict__ ic, int ncols, unsigned active) {
+    amg_restrict_kernel(V *__restrict__ rc, long long ldc, const V *__restrict__ r, long long ldr, const V *__restrict__ t, long long ldt,
+                        const V *__restrict__ w, long long m, const int *__restrict__ aggptr, const int *__restrict__ aggidx,
+                        long long nc, const int *__restrict__ ic, CS cs) {
   if (ic[I_DONE]) return;
-  constexpr int CW = amg_restrict_chunk<BS>();
-  for (int c0 = 0; c0 < ncols; c0 += CW) {
-    const unsigned bits = (active >> c0) & ((1u << CW) - 1u); // (uniform over the grid; no bit from ncols on is set)
-    if (!bits) continue;
+  constexpr int CW = CS::chunk(amg_restrict_chunk<BS>());
+  cs.template chunks<CW>([&](int c0, unsigned bits) { // (uniform over the grid)
     for (long long I = (long long)blockIdx.x * kThreads + threadIdx.x; I < nc; I += (long long)gridDim.x * kThreads) {
       if constexpr (BS >= 2) {
         double s[CW][BS];
@@ -900,22 +761,21 @@ __global__ void __launch_bounds__(kThreads)
           if ((bits >> e) & 1u) rc[(c0 + e) * ldc + I] = (V)s[e];
       }
     }
-  }
+  });
 }
 
 // z_{i,c} = (V)(z_{i,c} + W_i ec_{agg(i),c}): one thread per row (BS = 1, m = n) or per fine node
-template <typename V, int BS>
+template <typename V, int BS, class CS>
 __global__ void __launch_bounds__(kThreads)
-    amg_prolong_cols_kernel(V *__restrict__ z, long long ldz, const V *__restrict__ ec, long long lde, const V *__restrict__ w,
-                            const int *__restrict__ agg, long long m, const int *__restrict__ ic, int ncols, unsigned active) {
+    amg_prolong_kernel(V *__restrict__ z, long long ldz, const V *__restrict__ ec, long long lde, const V *__restrict__ w,
+                       const int *__restrict__ agg, long long m, const int *__restrict__ ic, CS cs) {
   if (ic[I_DONE]) return;
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < m; i += (long long)gridDim.x * kThreads) {
     const long long I = agg[i];
     if constexpr (BS >= 2) {
       double mm[BS][BS];
       block_load<V, BS>(w, m, i, mm);
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
+      cs.each([&](int c) {
         const V *ecc = ec + c * lde;
         V *zc = z + c * ldz;
         double e[BS], y[BS];
@@ -924,29 +784,27 @@ __global__ void __launch_bounds__(kThreads)
         block_mul<BS>(mm, e, y);
 #pragma unroll
         for (int q = 0; q < BS; ++q) zc[i * BS + q] = (V)((double)zc[i * BS + q] + y[q]);
-      }
+      });
     } else {
       const V wi = w[i];
-      for (int c = 0; c < ncols; ++c)
-        if ((active >> c) & 1u) z[c * ldz + i] = (V)((double)z[c * ldz + i] + (double)wi * (double)ec[c * lde + I]);
+      cs.each([&](int c) { z[c * ldz + i] = (V)((double)z[c * ldz + i] + (double)wi * (double)ec[c * lde + I]); });
     }
   }
 }
 
-// amg_restart_kernel / amg_restart_block_kernel on the active columns:  d_c = (V)((1 / theta) M^-1 (r_c - t_c));
-// z_c = (V)(z_c + d_c)
-template <typename V, int BS>
+// cheb_start_kernel from a nonzero z, t = A z given:  d_c = (V)((1 / theta) M^-1 (r_c - t_c));  z_c = (V)(z_c + d_c), M^-1
+// applied as cheb_start_kernel<V, BS> applies it
+template <typename V, int BS, class CS>
 __global__ void __launch_bounds__(kThreads)
-    amg_restart_cols_kernel(V *__restrict__ z, long long ldz, V *__restrict__ d, long long ldd, const V *__restrict__ r, long long ldr,
-                            const V *__restrict__ t, long long ldt, long long n, double inv_theta, const V *__restrict__ minv, long long nb,
-                            const int *__restrict__ ic, int ncols, unsigned active) {
+    amg_restart_kernel(V *__restrict__ z, long long ldz, V *__restrict__ d, long long ldd, const V *__restrict__ r, long long ldr,
+                       const V *__restrict__ t, long long ldt, long long n, double inv_theta, const V *__restrict__ minv, long long nb,
+                       const int *__restrict__ ic, CS cs) {
   if (ic[I_DONE]) return;
   if constexpr (BS >= 2) {
     for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
       double mm[BS][BS];
       block_load<V, BS>(minv, nb, k, mm);
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
+      cs.each([&](int c) {
         const V *rc = r + c * ldr, *tc = t + c * ldt;
         V *zc = z + c * ldz, *dc = d + c * ldd;
         double x[BS], zz[BS];
@@ -965,7 +823,7 @@ __global__ void __launch_bounds__(kThreads)
             zc[g] = (V)((double)zc[g] + (double)di);
           }
         }
-      }
+      });
     }
   } else {
     constexpr int W = Vec16<V>::W;
@@ -973,8 +831,7 @@ __global__ void __launch_bounds__(kThreads)
     const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
     for (long long i = t0; i < nv; i += stride) {
       const VT mv = reinterpret_cast<const VT *>(minv)[i];
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
+      cs.each([&](int c) {
         const VT rv = reinterpret_cast<const VT *>(r + c * ldr)[i], tv = reinterpret_cast<const VT *>(t + c * ldt)[i];
         VT zv = reinterpret_cast<VT *>(z + c * ldz)[i], dv;
 #pragma unroll
@@ -984,32 +841,29 @@ __global__ void __launch_bounds__(kThreads)
         }
         reinterpret_cast<VT *>(d + c * ldd)[i] = dv;
         reinterpret_cast<VT *>(z + c * ldz)[i] = zv;
-      }
+      });
     }
     for (long long i = nv * W + t0; i < n; i += stride) {
       const V mi = minv[i];
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
+      cs.each([&](int c) {
         const V di = (V)(inv_theta * (((double)r[c * ldr + i] - (double)t[c * ldt + i]) * (double)mi));
         d[c * ldd + i] = di;
         z[c * ldz + i] = (V)((double)z[c * ldz + i] + (double)di);
-      }
+      });
     }
   }
 }
 
-// z_c = (V)(inv r_c) on the dense level: one wave per row, which it reads ONCE per chunk of columns; per column the
-// lane-strided sum and the tree of amg_dense_kernel
-template <typename V>
+// z_c = (V)(inv r_c) on the dense level: one wave per row, which it reads ONCE per chunk of columns; per column the lanes
+// stride over the row, a fixed-order sum
+template <typename V, class CS>
 __global__ void __launch_bounds__(kThreads)
-    amg_dense_cols_kernel(V *__restrict__ z, long long ldz, const V *__restrict__ inv, const V *__restrict__ r, long long ldr, int n,
-                          const int *__restrict__ ic, int ncols, unsigned active) {
+    amg_dense_kernel(V *__restrict__ z, long long ldz, const V *__restrict__ inv, const V *__restrict__ r, long long ldr, int n,
+                     const int *__restrict__ ic, CS cs) {
   if (ic[I_DONE]) return;
-  constexpr int CW = kAmgDenseChunk;
+  constexpr int CW = CS::chunk(kAmgDenseChunk);
   const int lane = threadIdx.x & 63, nwaves = gridDim.x * (kThreads / 64);
-  for (int c0 = 0; c0 < ncols; c0 += CW) {
-    const unsigned bits = (active >> c0) & ((1u << CW) - 1u); // (uniform over the grid)
-    if (!bits) continue;
+  cs.template chunks<CW>([&](int c0, unsigned bits) { // (uniform over the grid)
     for (int i = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); i < n; i += nwaves) { // (uniform over the wave)
       const V *row = inv + (size_t)i * n;
       double s[CW];
@@ -1030,7 +884,7 @@ __global__ void __launch_bounds__(kThreads)
         if (lane == 0) z[(c0 + e) * ldz + i] = (V)v;
       }
     }
-  }
+  });
 }
 
 // ---- the kernels of a refresh (see REFRESH at the end of the header comment) ------------------------
@@ -1147,7 +1001,7 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
   double setup_split[4] = {0.0, 0.0, 0.0, 0.0};
   long long scratch_bytes = 0;
   int col_cap = 0;           // the columns the levels' blocked work vectors hold (0: no blocked call yet)
-  long long col_cycles = 0;  // cycles applied through cycle_cols, one per active column (cfs_hip_amg_column_cycles)
+  long long col_cycles = 0;  // cycles applied to the columns of a ColumnMask, one per active column (cfs_hip_amg_column_cycles)
 
   ~Amg() override {
     cfs_rt::DeviceGuard g(device);
@@ -1488,44 +1342,55 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
     return 0;
   }
 
-  // z = M^-1 r from level l down, on `st`; ic: the done flag the kernels look at
-  int cycle(int l, V *z, const V *r, const int *ic, hipStream_t st) {
+  // the work vectors of a level for a column set and their leading dimension: those build() allocates for one column,
+  // those of reserve_cols for a block
+  struct Work {
+    V *d, *t, *r, *z;
+    long long ld;
+  };
+  static Work work(Level &L, OneColumn) { return {(V *)L.d.p, (V *)L.t.p, (V *)L.r.p, (V *)L.z.p, L.n}; }
+  static Work work(Level &L, ColumnMask) { return {(V *)L.cd.p, (V *)L.ct.p, (V *)L.cr.p, (V *)L.cz.p, L.cld}; }
+
+  // Z_c = M^-1 R_c for the columns c of cs, from level l down, on `st`; ic: the done flag the kernels look at.  Every
+  // vector kernel is launched ONCE for the columns, the products are one per column.  Column c of Z at Z + c ld_z, of R
+  // at R + c ld_r; for a ColumnMask reserve_cols(cs.ncols) has been called
+  template <class CS> int cycle(int l, CS cs, V *Z, long long ld_z, const V *R, long long ld_r, const int *ic, hipStream_t st) {
     Level &L = *lv[l];
     const long long n = L.n;
     double *pp = part.dev();
     if (L.kind == AMG_DENSE) {
-      hipLaunchKernelGGL((amg_dense_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, (const V *)L.inv.p, r, L.n, ic);
+      hipLaunchKernelGGL((amg_dense_kernel<V, CS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, (const V *)L.inv.p, R, ld_r, L.n, ic, cs);
       return 0;
     }
-    V *d = (V *)L.d.p, *t = (V *)L.t.p;
+    const Work wk = work(L, cs);
+    V *d = wk.d, *t = wk.t;
+    const long long ldw = wk.ld;
     const V *dinv = L.pre.minv();
     const long long nb = L.pre.nb; // the nodes of the level (BS >= 2), else 0
     int rc;
-    hipLaunchKernelGGL((cheb_start_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, n, 1.0 / L.theta, -1, pp, dinv, nb);
-    if ((rc = cheb_chain<V, BS>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, nb, st))) return rc;
+    auto products = [&]() -> int { // t_c = A_l z_c
+      int r2 = 0;
+      cs.each([&](int c) {
+        if (!r2) r2 = L.h->spmv_local(t + c * ldw, Z + c * ld_z, nullptr, st);
+      });
+      return r2;
+    };
+    hipLaunchKernelGGL((cheb_start_kernel<V, BS, CS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, d, ldw, R, ld_r, n, 1.0 / L.theta, -1,
+                       pp, dinv, nb, cs);
+    if ((rc = cheb_chain<V, BS>(L.h, cs, Z, ld_z, d, t, ldw, R, ld_r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, nb, st))) return rc;
     if (L.kind == AMG_SMOOTHER) return 0;
-    Level &C = *lv[l + 1];
-    if ((rc = L.h->spmv_local(t, z, nullptr, st))) return rc;
-    if constexpr (BS >= 2)
-      hipLaunchKernelGGL((amg_restrict_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)C.r.p, r, (const V *)t,
-                         (const V *)L.w.p, nb, (const int *)L.aggptr.p, (const int *)L.aggidx.p, (long long)(L.nc / BS), ic);
-    else
-      hipLaunchKernelGGL((amg_restrict_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (V *)C.r.p, r, (const V *)t, (const V *)L.w.p,
-                         (const int *)L.aggptr.p, (const int *)L.aggidx.p, (long long)L.nc, ic);
-    if ((rc = cycle(l + 1, (V *)C.z.p, (const V *)C.r.p, ic, st))) return rc;
-    if constexpr (BS >= 2) {
-      hipLaunchKernelGGL((amg_prolong_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, z, (const V *)C.z.p, (const V *)L.w.p,
-                         (const int *)L.agg.p, nb, ic);
-      if ((rc = L.h->spmv_local(t, z, nullptr, st))) return rc;
-      hipLaunchKernelGGL((amg_restart_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, (const V *)t, n, 1.0 / L.theta,
-                         dinv, nb, ic);
-    } else {
-      hipLaunchKernelGGL((amg_prolong_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, (const V *)C.z.p, (const V *)L.w.p,
-                         (const int *)L.agg.p, n, ic);
-      if ((rc = L.h->spmv_local(t, z, nullptr, st))) return rc;
-      hipLaunchKernelGGL((amg_restart_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, z, d, r, (const V *)t, n, 1.0 / L.theta, dinv, ic);
-    }
-    return cheb_chain<V, BS>(L.h, z, d, t, r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, nb, st);
+    const Work cw = work(*lv[l + 1], cs);
+    const long long units = BS >= 2 ? nb : n; // nodes, or rows
+    if ((rc = products())) return rc;
+    hipLaunchKernelGGL((amg_restrict_kernel<V, BS, CS>), dim3(kGrid), dim3(kThreads), 0, st, cw.r, cw.ld, R, ld_r, (const V *)t, ldw,
+                       (const V *)L.w.p, units, (const int *)L.aggptr.p, (const int *)L.aggidx.p, (long long)(L.nc / BS), ic, cs);
+    if ((rc = cycle(l + 1, cs, cw.z, cw.ld, (const V *)cw.r, cw.ld, ic, st))) return rc;
+    hipLaunchKernelGGL((amg_prolong_kernel<V, BS, CS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, (const V *)cw.z, cw.ld,
+                       (const V *)L.w.p, (const int *)L.agg.p, units, ic, cs);
+    if ((rc = products())) return rc;
+    hipLaunchKernelGGL((amg_restart_kernel<V, BS, CS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, d, ldw, R, ld_r, (const V *)t, ldw, n,
+                       1.0 / L.theta, dinv, nb, ic, cs);
+    return cheb_chain<V, BS>(L.h, cs, Z, ld_z, d, t, ldw, R, ld_r, n, degree, L.c1, L.c2, -1, pp, ic, dinv, nb, st);
   }
 
   // the levels' work vectors for a block of `ncols` columns: allocated at the first blocked call, kept, and made again
@@ -1545,52 +1410,12 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
     return 0;
   }
 
-  // Z_c = M^-1 R_c for the columns c < ncols whose bit is set in `active`, from level l down, on `st`: cycle() with
-  // every vector kernel launched ONCE for the block and one product per active column where cycle() has one.  Column c
-  // of Z at Z + c ld_z, of R at R + c ld_r; reserve_cols(ncols) has been called
-  int cycle_cols(int l, V *Z, const V *R, long long ld_z, long long ld_r, int ncols, unsigned active, const int *ic, hipStream_t st) {
-    Level &L = *lv[l];
-    const long long n = L.n;
-    if (L.kind == AMG_DENSE) {
-      hipLaunchKernelGGL((amg_dense_cols_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, (const V *)L.inv.p, R, ld_r, L.n, ic,
-                         ncols, active);
-      return 0;
-    }
-    V *d = (V *)L.cd.p, *t = (V *)L.ct.p;
-    const long long ldw = L.cld;
-    const V *dinv = L.pre.minv();
-    const long long nb = L.pre.nb; // the nodes of the level (BS >= 2), else 0
-    int rc;
-    auto products = [&]() -> int { // t_c = A_l z_c
-      for (int c = 0; c < ncols; ++c)
-        if ((active >> c) & 1u)
-          if (int r2 = L.h->spmv_local(t + c * ldw, Z + c * ld_z, nullptr, st)) return r2;
-      return 0;
-    };
-    hipLaunchKernelGGL((cheb_start_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, d, ldw, R, ld_r, n, 1.0 / L.theta,
-                       dinv, nb, ncols, active);
-    if ((rc = cheb_chain_cols<V, BS>(L.h, Z, ld_z, d, t, ldw, R, ld_r, n, degree, L.c1, L.c2, ic, dinv, nb, ncols, active, st))) return rc;
-    if (L.kind == AMG_SMOOTHER) return 0;
-    Level &C = *lv[l + 1];
-    const long long units = BS >= 2 ? nb : n; // nodes, or rows
-    if ((rc = products())) return rc;
-    hipLaunchKernelGGL((amg_restrict_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)C.cr.p, C.cld, R, ld_r, (const V *)t, ldw,
-                       (const V *)L.w.p, units, (const int *)L.aggptr.p, (const int *)L.aggidx.p, (long long)(L.nc / BS), ic, ncols, active);
-    if ((rc = cycle_cols(l + 1, (V *)C.cz.p, (const V *)C.cr.p, C.cld, C.cld, ncols, active, ic, st))) return rc;
-    hipLaunchKernelGGL((amg_prolong_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, (const V *)C.cz.p, C.cld,
-                       (const V *)L.w.p, (const int *)L.agg.p, units, ic, ncols, active);
-    if ((rc = products())) return rc;
-    hipLaunchKernelGGL((amg_restart_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, Z, ld_z, d, ldw, R, ld_r, (const V *)t, ldw, n,
-                       1.0 / L.theta, dinv, nb, ic, ncols, active);
-    return cheb_chain_cols<V, BS>(L.h, Z, ld_z, d, t, ldw, R, ld_r, n, degree, L.c1, L.c2, ic, dinv, nb, ncols, active, st);
-  }
-
   // cfs_hip_amg_apply_cols (arguments checked by the caller; active != 0)
   int apply_cols(void *z_dev, const void *r_dev, long long ld, int ncols, unsigned active, hipStream_t st) override {
     if (stale) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_apply_cols: the last refresh failed");
     int rc = follow_fine(st);
     if (rc || (rc = reserve_cols(ncols))) return rc;
-    rc = cycle_cols(0, (V *)z_dev, (const V *)r_dev, ld, ld, ncols, active, (const int *)cnt.p, st);
+    rc = cycle(0, ColumnMask{ncols, active}, (V *)z_dev, ld, (const V *)r_dev, ld, (const int *)cnt.p, st);
     if (rc) return rc;
     col_cycles += __builtin_popcount(active);
     HIPCHK(hipGetLastError());
@@ -1604,7 +1429,7 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
     int rc = follow_fine(st);
     if (rc || (rc = reserve_cols(k))) return rc;
     auto form_w = [&](V *W, const V *R, long long ldw, int kk, unsigned mask) -> int {
-      if (int r2 = cycle_cols(0, W, R, ldw, ldw, kk, mask, (const int *)cnt.p, st)) return r2;
+      if (int r2 = cycle(0, ColumnMask{kk, mask}, W, ldw, R, ldw, (const int *)cnt.p, st)) return r2;
       col_cycles += __builtin_popcount(mask);
       return 0;
     };
@@ -1618,7 +1443,7 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
     if (stale) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "amg_apply: the last refresh failed");
     int rc = follow_fine(st);
     if (rc) return rc;
-    rc = cycle(0, (V *)z_dev, (const V *)r_dev, (const int *)cnt.p, st);
+    rc = cycle(0, OneColumn{}, (V *)z_dev, lv[0]->n, (const V *)r_dev, lv[0]->n, (const int *)cnt.p, st);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;
@@ -1761,7 +1586,7 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
     int *ic = s.ic;
     // z = M^-1 r;  part[slot] <- r . z of the stored r and the stored final z
     auto cycle_and_dot = [&](int slot) -> int {
-      if (int r2 = cycle(0, z, (const V *)r, (const int *)ic, st)) return r2;
+      if (int r2 = cycle(0, OneColumn{}, z, n, (const V *)r, n, (const int *)ic, st)) return r2;
       hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, n, pp, slot, (const int *)ic);
       return 0;
     };

@@ -60,60 +60,85 @@ template <typename V, int BS> __device__ __forceinline__ double cheb_minv1(doubl
   return BS == 1 ? x * (double)dinv : x;
 }
 
-// z = d = (V)((1 / theta) M^-1 r);  rz_slot >= 0: part[rz_slot] <- r . z of the stored values
-template <typename V, int BS>
+// ---- the two smoother kernels, on a set of columns CS (OneColumn or ColumnMask, cfs_solver.hpp) ----
+// Column c of a vector lives at base + c ld; the columns of cs are worked on in ONE launch, the others neither read nor
+// written.  The stored M^-1 of a row (its dinv word, or the packed inverse block of its node: block_load) is loaded once
+// and used for every column.  There is one body: PCG and the one-column V-cycle run its OneColumn instantiation, where
+// the column loop and the offsets fold away, the column-blocked V-cycle of cfs_solver_amg.hpp its ColumnMask one.  The
+// two are compiled separately, so that column c of a block has the bits of the one-column kernel still rests on the
+// compiler contracting both alike -- now from literally the same source text (contraction is left at the compiler's
+// default) -- and test B1 of tests/test_gpu_amg_apply_cols.py remains the judge.  The r . z partial sum exists in the
+// OneColumn instantiation only; a blocked launch has no dot product (the cycle asks for none).  BS = 0 (M = I) is
+// instantiated for one column only.
+
+// z_c = d_c = (V)((1 / theta) M^-1 r_c);  one column and rz_slot >= 0: part[rz_slot] <- r . z of the stored values
+template <typename V, int BS, class CS>
 __global__ void __launch_bounds__(kThreads)
-    cheb_start_kernel(V *__restrict__ z, V *__restrict__ d, const V *__restrict__ r, long long n, double inv_theta, int rz_slot,
-                      double *__restrict__ part, const V *__restrict__ minv, long long nb) {
+    cheb_start_kernel(V *__restrict__ z, long long ldz, V *__restrict__ d, long long ldd, const V *__restrict__ r, long long ldr,
+                      long long n, double inv_theta, int rz_slot, double *__restrict__ part, const V *__restrict__ minv, long long nb,
+                      CS cs) {
   double sz = 0.0;
   if constexpr (BS >= 2) {
     for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
-      double rd[BS], zz[BS];
+      double m[BS][BS];
+      block_load<V, BS>(minv, nb, k, m);
+      cs.each([&](int c) {
+        const V *rc = r + c * ldr;
+        V *zc = z + c * ldz, *dc = d + c * ldd;
+        double rd[BS], zz[BS];
 #pragma unroll
-      for (int i = 0; i < BS; ++i) {
-        const long long g = k * BS + i;
-        rd[i] = g < n ? (double)r[g] : 0.0;
-      }
-      block_apply<V, BS>(minv, nb, k, rd, zz);
-#pragma unroll
-      for (int i = 0; i < BS; ++i) {
-        const long long g = k * BS + i;
-        if (g < n) {
-          const V zi = (V)(inv_theta * zz[i]);
-          z[g] = zi;
-          d[g] = zi;
-          sz += rd[i] * (double)zi;
+        for (int i = 0; i < BS; ++i) {
+          const long long g = k * BS + i;
+          rd[i] = g < n ? (double)rc[g] : 0.0;
         }
-      }
+        block_mul<BS>(m, rd, zz);
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+          const long long g = k * BS + i;
+          if (g < n) {
+            const V zi = (V)(inv_theta * zz[i]);
+            zc[g] = zi;
+            dc[g] = zi;
+            if constexpr (CS::one) sz += rd[i] * (double)zi;
+          }
+        }
+      });
     }
   } else {
     constexpr int W = Vec16<V>::W;
     typedef typename Vec16<V>::type VT;
     const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
     for (long long i = t0; i < nv; i += stride) {
-      const VT rv = reinterpret_cast<const VT *>(r)[i];
-      VT mv, zv;
+      VT mv;
       if (BS == 1) mv = reinterpret_cast<const VT *>(minv)[i];
+      cs.each([&](int c) {
+        const VT rv = reinterpret_cast<const VT *>(r + c * ldr)[i];
+        VT zv;
 #pragma unroll
-      for (int k = 0; k < W; ++k) {
-        zv[k] = (V)(inv_theta * cheb_minv1<V, BS>((double)rv[k], BS == 1 ? mv[k] : (V)1));
-        sz += (double)rv[k] * (double)zv[k];
-      }
-      reinterpret_cast<VT *>(z)[i] = zv;
-      reinterpret_cast<VT *>(d)[i] = zv;
+        for (int k = 0; k < W; ++k) {
+          zv[k] = (V)(inv_theta * cheb_minv1<V, BS>((double)rv[k], BS == 1 ? mv[k] : (V)1));
+          if constexpr (CS::one) sz += (double)rv[k] * (double)zv[k];
+        }
+        reinterpret_cast<VT *>(z + c * ldz)[i] = zv;
+        reinterpret_cast<VT *>(d + c * ldd)[i] = zv;
+      });
     }
     for (long long i = nv * W + t0; i < n; i += stride) {
-      const V ri = r[i];
-      const V zi = (V)(inv_theta * cheb_minv1<V, BS>((double)ri, BS == 1 ? minv[i] : (V)1));
-      z[i] = zi;
-      d[i] = zi;
-      sz += (double)ri * (double)zi;
+      const V mi = BS == 1 ? minv[i] : (V)1;
+      cs.each([&](int c) {
+        const V ri = r[c * ldr + i];
+        const V zi = (V)(inv_theta * cheb_minv1<V, BS>((double)ri, mi));
+        z[c * ldz + i] = zi;
+        d[c * ldd + i] = zi;
+        if constexpr (CS::one) sz += (double)ri * (double)zi;
+      });
     }
   }
-  if (rz_slot >= 0) { // (uniform over the grid)
-    sz = block_sum(sz);
-    if (threadIdx.x == 0) part[rz_slot * kGrid + blockIdx.x] = sz;
-  }
+  if constexpr (CS::one)
+    if (rz_slot >= 0) { // (uniform over the grid)
+      sz = block_sum(sz);
+      if (threadIdx.x == 0) part[rz_slot * kGrid + blockIdx.x] = sz;
+    }
 }
 
 // cg_update_kernel<V, true> with z stored:  alpha = rz / pq;  u += alpha p;  r -= alpha q;  part[rr'] <- r . r;
@@ -198,167 +223,20 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-// One inner step:  d = (V)(c1 d + c2 M^-1 (r - t));  z = (V)(z + d);  rz_slot >= 0 (the last step): part[rz_slot] <- r . z
-template <typename V, int BS>
+// One inner step:  d_c = (V)(c1 d_c + c2 M^-1 (r_c - t_c));  z_c = (V)(z_c + d_c);  one column and rz_slot >= 0 (the last
+// step): part[rz_slot] <- r . z
+template <typename V, int BS, class CS>
 __global__ void __launch_bounds__(kThreads)
-    cheb_step_kernel(const V *__restrict__ r, const V *__restrict__ t, V *__restrict__ d, V *__restrict__ z, long long n, double c1,
-                     double c2, int rz_slot, double *__restrict__ part, const int *__restrict__ ic, const V *__restrict__ minv,
-                     long long nb) {
+    cheb_step_kernel(const V *__restrict__ r, long long ldr, const V *__restrict__ t, long long ldt, V *__restrict__ d, long long ldd,
+                     V *__restrict__ z, long long ldz, long long n, double c1, double c2, int rz_slot, double *__restrict__ part,
+                     const int *__restrict__ ic, const V *__restrict__ minv, long long nb, CS cs) {
   if (ic[I_DONE]) return;
   double sz = 0.0;
   if constexpr (BS >= 2) {
     for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
-      double rd[BS], w[BS], zz[BS];
-#pragma unroll
-      for (int i = 0; i < BS; ++i) {
-        const long long g = k * BS + i;
-        rd[i] = g < n ? (double)r[g] : 0.0;
-        w[i] = g < n ? rd[i] - (double)t[g] : 0.0;
-      }
-      block_apply<V, BS>(minv, nb, k, w, zz);
-#pragma unroll
-      for (int i = 0; i < BS; ++i) {
-        const long long g = k * BS + i;
-        if (g < n) {
-          const V di = (V)(c1 * (double)d[g] + c2 * zz[i]);
-          const V zi = (V)((double)z[g] + (double)di);
-          d[g] = di;
-          z[g] = zi;
-          sz += rd[i] * (double)zi;
-        }
-      }
-    }
-  } else {
-    constexpr int W = Vec16<V>::W;
-    typedef typename Vec16<V>::type VT;
-    const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-    for (long long i = t0; i < nv; i += stride) {
-      const VT rv = reinterpret_cast<const VT *>(r)[i], tv = reinterpret_cast<const VT *>(t)[i];
-      VT dv = reinterpret_cast<VT *>(d)[i], zv = reinterpret_cast<VT *>(z)[i];
-      VT mv;
-      if (BS == 1) mv = reinterpret_cast<const VT *>(minv)[i];
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        dv[k] = (V)(c1 * (double)dv[k] + c2 * cheb_minv1<V, BS>((double)rv[k] - (double)tv[k], BS == 1 ? mv[k] : (V)1));
-        zv[k] = (V)((double)zv[k] + (double)dv[k]);
-        sz += (double)rv[k] * (double)zv[k];
-      }
-      reinterpret_cast<VT *>(d)[i] = dv;
-      reinterpret_cast<VT *>(z)[i] = zv;
-    }
-    for (long long i = nv * W + t0; i < n; i += stride) {
-      const V ri = r[i];
-      const V di = (V)(c1 * (double)d[i] + c2 * cheb_minv1<V, BS>((double)ri - (double)t[i], BS == 1 ? minv[i] : (V)1));
-      const V zi = (V)((double)z[i] + (double)di);
-      d[i] = di;
-      z[i] = zi;
-      sz += (double)ri * (double)zi;
-    }
-  }
-  if (rz_slot >= 0) { // (uniform over the grid)
-    sz = block_sum(sz);
-    if (threadIdx.x == 0) part[rz_slot * kGrid + blockIdx.x] = sz;
-  }
-}
-
-// ---- the two smoother kernels on a BLOCK OF COLUMNS (the column-blocked V-cycle of cfs_solver_amg.hpp) ----
-// Column c of a block lives at base + c ld; the columns whose bit is set in `active` (c < ncols <= 16) are worked on
-// in ONE launch, the others neither read nor written.  The stored M^-1 of a row (its dinv word, or the packed inverse
-// block of its node: block_load) is loaded once and used for every column.  Per column the expressions are those of
-// cheb_start_kernel / cheb_step_kernel, operand for operand, so that the compiler forms the same operations and a
-// column of the block has the bits of the one-column kernel; no dot product (the cycle asks for none).  (Contraction
-// is left at the compiler's default in both families: the same trees get the same fused multiply-adds.)
-// block_apply() in two halves: the node's inverse block into registers, and its product with one column's values
-template <typename V, int BS>
-__device__ __forceinline__ void block_load(const V *__restrict__ minv, long long nb, long long k, double (&m)[BS][BS]) {
-#pragma unroll
-  for (int i = 0; i < BS; ++i)
-#pragma unroll
-    for (int j = 0; j <= i; ++j) m[i][j] = m[j][i] = (double)minv[(long long)(i * (i + 1) / 2 + j) * nb + k];
-}
-template <int BS> __device__ __forceinline__ void block_mul(const double (&m)[BS][BS], const double (&r)[BS], double (&z)[BS]) {
-#pragma unroll
-  for (int i = 0; i < BS; ++i) {
-    double v = 0.0;
-#pragma unroll
-    for (int j = 0; j < BS; ++j) v += m[i][j] * r[j];
-    z[i] = v;
-  }
-}
-
-// z_c = d_c = (V)((1 / theta) M^-1 r_c) for the active columns c
-template <typename V, int BS>
-__global__ void __launch_bounds__(kThreads)
-    cheb_start_cols_kernel(V *__restrict__ z, long long ldz, V *__restrict__ d, long long ldd, const V *__restrict__ r, long long ldr,
-                           long long n, double inv_theta, const V *__restrict__ minv, long long nb, int ncols, unsigned active) {
-  if constexpr (BS >= 2) {
-    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
       double m[BS][BS];
       block_load<V, BS>(minv, nb, k, m);
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
-        const V *rc = r + c * ldr;
-        V *zc = z + c * ldz, *dc = d + c * ldd;
-        double rd[BS], zz[BS];
-#pragma unroll
-        for (int i = 0; i < BS; ++i) {
-          const long long g = k * BS + i;
-          rd[i] = g < n ? (double)rc[g] : 0.0;
-        }
-        block_mul<BS>(m, rd, zz);
-#pragma unroll
-        for (int i = 0; i < BS; ++i) {
-          const long long g = k * BS + i;
-          if (g < n) {
-            const V zi = (V)(inv_theta * zz[i]);
-            zc[g] = zi;
-            dc[g] = zi;
-          }
-        }
-      }
-    }
-  } else {
-    constexpr int W = Vec16<V>::W;
-    typedef typename Vec16<V>::type VT;
-    const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-    for (long long i = t0; i < nv; i += stride) {
-      VT mv;
-      if (BS == 1) mv = reinterpret_cast<const VT *>(minv)[i];
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
-        const VT rv = reinterpret_cast<const VT *>(r + c * ldr)[i];
-        VT zv;
-#pragma unroll
-        for (int k = 0; k < W; ++k) zv[k] = (V)(inv_theta * cheb_minv1<V, BS>((double)rv[k], BS == 1 ? mv[k] : (V)1));
-        reinterpret_cast<VT *>(z + c * ldz)[i] = zv;
-        reinterpret_cast<VT *>(d + c * ldd)[i] = zv;
-      }
-    }
-    for (long long i = nv * W + t0; i < n; i += stride) {
-      const V mi = BS == 1 ? minv[i] : (V)1;
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
-        const V zi = (V)(inv_theta * cheb_minv1<V, BS>((double)r[c * ldr + i], mi));
-        z[c * ldz + i] = zi;
-        d[c * ldd + i] = zi;
-      }
-    }
-  }
-}
-
-// One inner step on the active columns c:  d_c = (V)(c1 d_c + c2 M^-1 (r_c - t_c));  z_c = (V)(z_c + d_c)
-template <typename V, int BS>
-__global__ void __launch_bounds__(kThreads)
-    cheb_step_cols_kernel(const V *__restrict__ r, long long ldr, const V *__restrict__ t, long long ldt, V *__restrict__ d, long long ldd,
-                          V *__restrict__ z, long long ldz, long long n, double c1, double c2, const int *__restrict__ ic,
-                          const V *__restrict__ minv, long long nb, int ncols, unsigned active) {
-  if (ic[I_DONE]) return;
-  if constexpr (BS >= 2) {
-    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
-      double m[BS][BS];
-      block_load<V, BS>(minv, nb, k, m);
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
+      cs.each([&](int c) {
         const V *rc = r + c * ldr, *tc = t + c * ldt;
         V *zc = z + c * ldz, *dc = d + c * ldd;
         double rd[BS], w[BS], zz[BS];
@@ -377,9 +255,10 @@ __global__ void __launch_bounds__(kThreads)
             const V zi = (V)((double)zc[g] + (double)di);
             dc[g] = di;
             zc[g] = zi;
+            if constexpr (CS::one) sz += rd[i] * (double)zi;
           }
         }
-      }
+      });
     }
   } else {
     constexpr int W = Vec16<V>::W;
@@ -388,30 +267,36 @@ __global__ void __launch_bounds__(kThreads)
     for (long long i = t0; i < nv; i += stride) {
       VT mv;
       if (BS == 1) mv = reinterpret_cast<const VT *>(minv)[i];
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
+      cs.each([&](int c) {
         const VT rv = reinterpret_cast<const VT *>(r + c * ldr)[i], tv = reinterpret_cast<const VT *>(t + c * ldt)[i];
         VT dv = reinterpret_cast<VT *>(d + c * ldd)[i], zv = reinterpret_cast<VT *>(z + c * ldz)[i];
 #pragma unroll
         for (int k = 0; k < W; ++k) {
           dv[k] = (V)(c1 * (double)dv[k] + c2 * cheb_minv1<V, BS>((double)rv[k] - (double)tv[k], BS == 1 ? mv[k] : (V)1));
           zv[k] = (V)((double)zv[k] + (double)dv[k]);
+          if constexpr (CS::one) sz += (double)rv[k] * (double)zv[k];
         }
         reinterpret_cast<VT *>(d + c * ldd)[i] = dv;
         reinterpret_cast<VT *>(z + c * ldz)[i] = zv;
-      }
+      });
     }
     for (long long i = nv * W + t0; i < n; i += stride) {
       const V mi = BS == 1 ? minv[i] : (V)1;
-      for (int c = 0; c < ncols; ++c) {
-        if (!((active >> c) & 1u)) continue;
-        const V di = (V)(c1 * (double)d[c * ldd + i] + c2 * cheb_minv1<V, BS>((double)r[c * ldr + i] - (double)t[c * ldt + i], mi));
+      cs.each([&](int c) {
+        const V ri = r[c * ldr + i];
+        const V di = (V)(c1 * (double)d[c * ldd + i] + c2 * cheb_minv1<V, BS>((double)ri - (double)t[c * ldt + i], mi));
         const V zi = (V)((double)z[c * ldz + i] + (double)di);
         d[c * ldd + i] = di;
         z[c * ldz + i] = zi;
-      }
+        if constexpr (CS::one) sz += (double)ri * (double)zi;
+      });
     }
   }
+  if constexpr (CS::one)
+    if (rz_slot >= 0) { // (uniform over the grid)
+      sz = block_sum(sz);
+      if (threadIdx.x == 0) part[rz_slot * kGrid + blockIdx.x] = sz;
+    }
 }
 
 // cg_direction_kernel<V, true> with z stored:  beta = rz' / rz;  p = z + beta p;  one thread: iteration count,
@@ -511,30 +396,20 @@ __global__ void __launch_bounds__(kThreads)
 // ---- host ----------------------------------------------------------------------------------------
 // (the stored M^-1 of a call is Precond<V, BS> of cfs_solver.hpp)
 
-// the m - 1 inner steps behind a z = d = z_1 that is already enqueued; t: n values of scratch
-template <typename V, int BS, class Handle>
-int cheb_chain(Handle *h, V *z, V *d, V *t, const V *r, long long n, int degree, const double *c1, const double *c2, int rz_slot,
-               double *part, const int *ic, const V *minv, long long nb, hipStream_t st) {
+// the m - 1 inner steps behind a z = d = z_1 that is already enqueued, on the columns of cs: per step one product per
+// column, then ONE step kernel.  Column c of z at z + c ldz, of r at r + c ldr, of d and of t (n values of scratch per
+// column) at + c ldw
+template <typename V, int BS, class CS, class Handle>
+int cheb_chain(Handle *h, CS cs, V *z, long long ldz, V *d, V *t, long long ldw, const V *r, long long ldr, long long n, int degree,
+               const double *c1, const double *c2, int rz_slot, double *part, const int *ic, const V *minv, long long nb, hipStream_t st) {
   for (int j = 1; j < degree; ++j) {
-    int rc = h->spmv_local(t, z, nullptr, st);
+    int rc = 0;
+    cs.each([&](int c) {
+      if (!rc) rc = h->spmv_local(t + c * ldw, z + c * ldz, nullptr, st);
+    });
     if (rc) return rc;
-    hipLaunchKernelGGL((cheb_step_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, (const V *)t, d, z, n, c1[j - 1], c2[j - 1],
-                       j == degree - 1 ? rz_slot : -1, part, ic, minv, nb);
-  }
-  return 0;
-}
-
-// cheb_chain on the active columns of a block: per step one product per active column, then ONE step kernel
-template <typename V, int BS, class Handle>
-int cheb_chain_cols(Handle *h, V *z, long long ldz, V *d, V *t, long long ldw, const V *r, long long ldr, long long n, int degree,
-                    const double *c1, const double *c2, const int *ic, const V *minv, long long nb, int ncols, unsigned active,
-                    hipStream_t st) {
-  for (int j = 1; j < degree; ++j) {
-    for (int c = 0; c < ncols; ++c)
-      if ((active >> c) & 1u)
-        if (int rc = h->spmv_local(t + c * ldw, z + c * ldz, nullptr, st)) return rc;
-    hipLaunchKernelGGL((cheb_step_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, ldr, (const V *)t, ldw, d, ldw, z, ldz, n,
-                       c1[j - 1], c2[j - 1], ic, minv, nb, ncols, active);
+    hipLaunchKernelGGL((cheb_step_kernel<V, BS, CS>), dim3(kGrid), dim3(kThreads), 0, st, r, ldr, (const V *)t, ldw, d, ldw, z, ldz, n,
+                       c1[j - 1], c2[j - 1], j == degree - 1 ? rz_slot : -1, part, ic, minv, nb, cs);
   }
   return 0;
 }
@@ -602,10 +477,10 @@ int cheb_apply(Handle *h, int degree, double lmin, double lmax, void *z_dev, con
   if ((rc = pre.setup(h, part.dev(), st))) return rc;
   double theta, c1[kChebMaxDegree], c2[kChebMaxDegree];
   cheb_coeffs(degree, lmin, lmax, &theta, c1, c2);
-  hipLaunchKernelGGL((cheb_start_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, (V *)z_dev, (V *)dvec.p, (const V *)r_dev, n,
-                     1.0 / theta, -1, part.dev(), pre.minv(), pre.nb);
-  if ((rc = cheb_chain<V, BS>(h, (V *)z_dev, (V *)dvec.p, (V *)tvec.p, (const V *)r_dev, n, degree, c1, c2, -1, part.dev(),
-                              (const int *)cnt.p, pre.minv(), pre.nb, st)))
+  hipLaunchKernelGGL((cheb_start_kernel<V, BS, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, (V *)z_dev, n, (V *)dvec.p, n,
+                     (const V *)r_dev, n, n, 1.0 / theta, -1, part.dev(), pre.minv(), pre.nb, OneColumn{});
+  if ((rc = cheb_chain<V, BS>(h, OneColumn{}, (V *)z_dev, n, (V *)dvec.p, (V *)tvec.p, n, (const V *)r_dev, n, n, degree, c1, c2, -1,
+                              part.dev(), (const int *)cnt.p, pre.minv(), pre.nb, st)))
     return rc;
   HIPCHK(hipGetLastError());
   if ((rc = part.fetch())) return rc;
@@ -648,9 +523,10 @@ int cg_cheb(Handle *h, void *u_dev, const void *b_dev, int degree, double lmin, 
   cheb_coeffs(degree, lmin, lmax, &theta, c1, c2);
   const double inv_theta = 1.0 / theta, stop = s.stop;
   if (s.live()) { // z = P_m r, rz[0] = r . z, p = z
-    hipLaunchKernelGGL((cheb_start_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, z, d, (const V *)r, n, inv_theta,
-                       degree == 1 ? (int)P_RZ0 : -1, part, minv, nb);
-    if ((rc = cheb_chain<V, BS>(h, z, d, q, (const V *)r, n, degree, c1, c2, (int)P_RZ0, part, (const int *)ic, minv, nb, st)))
+    hipLaunchKernelGGL((cheb_start_kernel<V, BS, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, z, n, d, n, (const V *)r, n, n,
+                       inv_theta, degree == 1 ? (int)P_RZ0 : -1, part, minv, nb, OneColumn{});
+    if ((rc = cheb_chain<V, BS>(h, OneColumn{}, z, n, d, q, n, (const V *)r, n, n, degree, c1, c2, (int)P_RZ0, part, (const int *)ic, minv,
+                                nb, st)))
       return rc;
     HIPCHK(hipMemcpyAsync(p, z, (size_t)n * sizeof(V), hipMemcpyDeviceToDevice, st));
   }
@@ -661,8 +537,8 @@ int cg_cheb(Handle *h, void *u_dev, const void *b_dev, int degree, double lmin, 
                        (const int *)ic);
     hipLaunchKernelGGL((cheb_update_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, z, d, n, part,
                        (const int *)ic, k, inv_theta, degree == 1 ? 1 : 0, minv, nb);
-    if ((r2 = cheb_chain<V, BS>(h, z, d, q, (const V *)r, n, degree, c1, c2, (int)P_RZ0 + ((k + 1) & 1), part, (const int *)ic, minv,
-                                nb, st)))
+    if ((r2 = cheb_chain<V, BS>(h, OneColumn{}, z, n, d, q, n, (const V *)r, n, n, degree, c1, c2, (int)P_RZ0 + ((k + 1) & 1), part,
+                                (const int *)ic, minv, nb, st)))
       return r2;
     hipLaunchKernelGGL((cheb_direction_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, n, (const double *)part, ic, k,
                        stop);

@@ -16,7 +16,7 @@
 // Two host looks per iteration are inherent: C depends on G and H, the active set on the norms.
 // cfs_hip_sym_lobpcg_amg is the same lobpcg() with W formed outside the residual kernel: that kernel runs in its BS = 0
 // form and writes the raw (V)R_i into the W-columns of AS, and the column-blocked multigrid cycle of cfs_solver_amg.hpp
-// (Amg::cycle_cols) reads them there and writes W_i = M^-1 R_i for the pairs still active.  Memory: no extra k n block.
+// (Amg::cycle on a ColumnMask) reads them there and writes W_i = M^-1 R_i for the pairs still active.  Memory: no extra k n block.
 //
 // The Gram kernel is a small SYRK: m (m + 1) sums of n terms each, m <= 48.  One walk per chunk of 8 accumulators
 // (eigs_project_kernel) would read its rows 290 times at m = 48; instead a workgroup stages R rows of all 2 m columns

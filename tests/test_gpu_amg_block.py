@@ -18,8 +18,8 @@ Cases of the cycle: rotated_node_laplacian(bs, 24, 20) with coarse_max 128 (ends
 coupled nodes, the block form of pairs2300 -- the level of 600 nodes is block diagonal, stalls and, with more than 1024
 rows, is smoother-only.
 
-The loop edges.  Every new kernel gives one thread a node: amg_restrict_block_kernel a COARSE node of the level,
-amg_prolong_block_kernel and amg_restart_block_kernel a fine one; one trip of the grid is 512 x 256 = 131 072 nodes.
+The loop edges.  Every transfer kernel gives one thread a node in its BS >= 2 form: amg_restrict_kernel a COARSE node of
+the level, amg_prolong_kernel and amg_restart_kernel a fine one; one trip of the grid is 512 x 256 = 131 072 nodes.
 node_band(bs, 524 292): a chain of nodes, 2 passes pair it perfectly twice, so level 0 has 524 292 = 4 x 131 072 + 4 fine
 nodes -- prolong and restart take four full trips and a fifth of 4 threads -- and 131 073 = 131 072 + 1 coarse ones:
 restrict takes a second trip of one thread.  524 289 nodes is the least number with more than 131 072 coarse nodes; 524 292
@@ -390,8 +390,8 @@ def test_a_deterministic_handle_repeats_its_bits(dtype):
 @pytest.mark.parametrize("bs", (2, 3))
 def test_beyond_one_trip_of_the_grid(bs, dtype):
     """node_band(bs): 524 292 = 4 x 131 072 + 4 fine nodes and 131 073 = 131 072 + 1 coarse nodes at level 0 (the module
-    docstring has the arithmetic): amg_prolong_block_kernel and amg_restart_block_kernel run five trips, the last of 4
-    threads, amg_restrict_block_kernel a second trip of one thread.  The cycle against the long-double model."""
+    docstring has the arithmetic): amg_prolong_kernel and amg_restart_kernel run five trips, the last of 4
+    threads, amg_restrict_kernel a second trip of one thread.  The cycle against the long-double model."""
     A, G, H = _setup("band", bs, dtype, 1, coarse_max=512)
     inf = H.info
     print(f"amg-block edges {_f(dtype)} bs={bs}: levels {_shape(H)}, set-up {inf['setup_seconds']:.2f} s of which the level handles "
