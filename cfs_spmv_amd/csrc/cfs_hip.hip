@@ -2483,6 +2483,65 @@ int cfs_hip_sym_pcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const voi
   DeviceGuard g(h->device);
   return a->pcg(u_dev, b_dev, tol, maxiter, iterations, relres, (hipStream_t)stream);
 }
+// ---- PCG on a block of right-hand sides -------------------------------------------------------------
+// What cfs_hip_sym_pcg_cols and cfs_hip_sym_pcg_amg_cols check of their blocks before they look at the handle's
+// placement, in the order cfs_hip.h documents: null, ncols, alignment, ld, overlap, tol / maxiter.  The outputs are
+// zeroed as soon as their length is known to be sane.
+static int check_cols_args(const char *who, bool any_null, cfs_hip_sym_t h, const void *u, const void *b, long long ld, int ncols,
+                           double tol, int maxiter, int *iterations, double *relres) {
+  const std::string w(who);
+  if (any_null) return set_err(CFS_HIP_ERR_ARG, w + ": null argument");
+  if (iterations) iterations[0] = 0;
+  if (relres) relres[0] = 0.0;
+  if (ncols < 1 || ncols > CFS_HIP_LOBPCG_MAX_K)
+    return set_err(CFS_HIP_ERR_ARG, w + ": 1 <= ncols <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + ", got " + std::to_string(ncols));
+  for (int c = 0; c < ncols; ++c) {
+    if (iterations) iterations[c] = 0;
+    if (relres) relres[c] = 0.0;
+  }
+  if ((((uintptr_t)u) | ((uintptr_t)b)) & 15) return set_err(CFS_HIP_ERR_ARG, w + ": U and B must be 16-byte aligned");
+  const long long n = h->n(), vb = h->value_bytes;
+  if (ld < n || ld > (1LL << 56) || (ncols > 1 && (ld * vb) % 16 != 0))
+    return set_err(CFS_HIP_ERR_ARG, w + ": bad ld " + std::to_string(ld) + ": at least n = " + std::to_string(n) +
+                                        " and, for more than one column, a multiple of 16 bytes");
+  const uintptr_t span = (uintptr_t)(((long long)(ncols - 1) * ld + n) * vb), u0 = (uintptr_t)u, b0 = (uintptr_t)b;
+  if (u0 < b0 + span && b0 < u0 + span) return set_err(CFS_HIP_ERR_ARG, w + ": the blocks U and B overlap");
+  if (maxiter < 0 || !(tol >= 0.0)) return set_err(CFS_HIP_ERR_ARG, w + ": bad tolerance / iteration limit");
+  return 0;
+}
+
+int cfs_hip_sym_pcg_cols(cfs_hip_sym_t h, void *u_dev, const void *b_dev, long long ld, int ncols, int block_rows, double tol,
+                         int maxiter, int check_every, int *iterations, double *relres, void *stream) {
+  const char *who = "pcg_cols";
+  int rc = check_cols_args(who, !h || !u_dev || !b_dev, h, u_dev, b_dev, ld, ncols, tol, maxiter, iterations, relres);
+  if (rc) return rc;
+  if (block_rows != 0 && !block_rows_ok(block_rows))
+    return set_err(CFS_HIP_ERR_ARG, "pcg_cols: block_rows " + std::to_string(block_rows) + " is not one of 0, 1, 2, 3, 4, 6");
+  if ((rc = check_whole_matrix(h, not_a_shard(who), true, "pcg_cols: the whole matrix on one device, not a multi-device handle")) ||
+      (rc = check_placement(h, u_dev, b_dev)))
+    return rc;
+  h->ok_x = h->ok_y = nullptr; // (as check_solve_handle)
+  DeviceGuard g(h->device);
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::cg_cols<decltype(v), decltype(bs)::value>(h, u_dev, b_dev, ld, ncols, tol, maxiter, check_every, iterations, relres,
+                                                                 (hipStream_t)stream);
+  });
+}
+
+int cfs_hip_sym_pcg_amg_cols(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const void *b_dev, long long ld, int ncols, double tol,
+                             int maxiter, int check_every, int *iterations, double *relres, void *stream) {
+  (void)check_every; // (the host looks after every iteration, as in cfs_hip_sym_pcg_amg)
+  const char *who = "pcg_amg_cols";
+  int rc = check_cols_args(who, !h || !a || !u_dev || !b_dev, h, u_dev, b_dev, ld, ncols, tol, maxiter, iterations, relres);
+  if (rc || (rc = check_whole_matrix(h, not_a_shard(who), true, "pcg_amg_cols: the whole matrix on one device, not a multi-device handle")))
+    return rc;
+  if (a->fine != h) return set_err(CFS_HIP_ERR_ARG, "pcg_amg_cols: the hierarchy was created on another handle");
+  if (a->is_stale()) return set_err(CFS_HIP_ERR_ARG, "pcg_amg_cols: the last refresh failed");
+  if ((rc = check_placement(h, u_dev, b_dev))) return rc;
+  h->ok_x = h->ok_y = nullptr; // (as check_solve_handle)
+  DeviceGuard g(h->device);
+  return a->pcg_cols(u_dev, b_dev, ld, ncols, tol, maxiter, iterations, relres, (hipStream_t)stream);
+}
 static int amg_coarsen_entry(int n, const int *rowptr, const int *colind, const double *values, int passes, int *agg, double *w, int *nc,
                              int *c_rowptr, int *c_colind, double *c_values, long long capacity, long long *c_nnz, int matching, int *rounds) {
   if (n < 0 || !rowptr || !agg || !w || !nc || !c_rowptr || !c_nnz || (n > 0 && rowptr[n] > 0 && (!colind || !values)) ||

@@ -500,6 +500,417 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// ---- the recurrence on a block of columns (cfs_hip_sym_pcg_cols, cfs_hip_sym_pcg_amg_cols) --------
+// The four kernels above for the columns of a ColumnMask, launched ONCE for the block.  Column c of every vector at
+// base + c ld; its scalars in slots of its own, part[c][slot][kGrid], its counters at ic[c][I_ITER], ic[c][I_DONE], its
+// stop in stop.v[c].  BS = 0: no stored M^-1 (PRE = false), 1: dinv (PRE = true), 2, 3, 4, 6: the packed inverse blocks.
+// Per column the arithmetic is that of the one-column kernel: the same grid and grid-stride walk, the same casts and
+// parentheses, the same order of sums -- block_sum_cols and slot_sums add what block_sum and slot_sum add, in their
+// order, for the columns of a chunk at once, so a chunk costs the barriers of one column.  The columns are taken in
+// chunks of CW (chunks<CW>): the accumulators and the scalars are per column of a chunk, and dinv or the inverse block
+// is read once per chunk.  A kernel that the one-column solver guards with ic[I_DONE] skips every column whose flag is
+// up (live_columns): nothing of such a column is read or written, not its vectors, its slots or its counters, so a
+// column stops at the iteration at which its one-column solve stops while the host's mask may be a window old.  A
+// column whose bit is clear in the mask is neither read nor written.
+constexpr int kColSlots = P_COUNT * kGrid; // doubles between the slots of two columns
+struct ColumnStops {
+  double v[16];
+};
+// the columns per chunk for a stored M^-1 of BS: the widest that keeps every instantiation free of spills, scalar
+// registers included.  four: the residual and update kernels, which hold four vectors' addresses per column
+constexpr int cols_chunk(int bs, bool four = false) { return bs >= 6 || (four && bs <= 1) ? 2 : 4; }
+
+// block_sum for N values at once, each summed in block_sum's order
+template <int N> __device__ __forceinline__ void block_sum_cols(double (&v)[N]) {
+  __shared__ double part[N][kThreads / 64];
+  __shared__ double total[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[e] += __shfl_down(v[e], o);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0)
+#pragma unroll
+    for (int e = 0; e < N; ++e) part[e][wave] = v[e];
+  __syncthreads();
+  if (threadIdx.x < N) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) s += part[threadIdx.x][w];
+    total[threadIdx.x] = s;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < N; ++e) v[e] = total[e];
+}
+// out[e] = slot_sum of column c0 + e for the columns of `bits` (0 for the others, whose slots are not read)
+template <int CW> __device__ __forceinline__ void slot_sums(const double *part, int slot, int c0, unsigned bits, double (&out)[CW]) {
+#pragma unroll
+  for (int e = 0; e < CW; ++e) {
+    double v = 0.0;
+    if ((bits >> e) & 1u)
+      for (int g = threadIdx.x; g < kGrid; g += kThreads) v += part[(size_t)(c0 + e) * kColSlots + slot * kGrid + g];
+    out[e] = v;
+  }
+  block_sum_cols<CW>(out);
+}
+// the columns of cs whose flag is down, the same answer in every thread of the workgroup (one thread reads the flags:
+// workgroup 0 of a direction kernel raises them while other workgroups may still be starting)
+__device__ __forceinline__ ColumnMask live_columns(const int *ic, ColumnMask cs) {
+  __shared__ unsigned live;
+  if (threadIdx.x == 0) {
+    unsigned m = 0;
+    cs.each([&](int c) {
+      if (!ic[c * I_COUNT + I_DONE]) m |= 1u << c;
+    });
+    live = m;
+  }
+  __syncthreads();
+  return ColumnMask{cs.ncols, live};
+}
+
+// cg_residual_kernel<V, BS == 1> / cg_residual_block_kernel<V, BS> on the columns of cs (r, p may be null for BS = 0)
+template <typename V, int BS>
+__global__ void __launch_bounds__(kThreads)
+    cg_residual_cols_kernel(V *__restrict__ r, V *__restrict__ p, const V *__restrict__ b, const V *__restrict__ q, long long ld,
+                            long long n, double *__restrict__ part, int slot_rr, int with_bb, const V *__restrict__ minv, long long nb,
+                            ColumnMask cs) {
+  constexpr int CW = cols_chunk(BS, true);
+  constexpr bool PRE = BS == 1;
+  cs.chunks<CW>([&](int c0, unsigned bits) {
+    double rr[CW], bb[CW], rz[CW];
+#pragma unroll
+    for (int e = 0; e < CW; ++e) rr[e] = bb[e] = rz[e] = 0.0;
+    if constexpr (BS >= 2) {
+      for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+        double m[BS][BS];
+        block_load<V, BS>(minv, nb, k, m);
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+          const long long off = (long long)(c0 + e) * ld;
+          double rd[BS], z[BS];
+#pragma unroll
+          for (int i = 0; i < BS; ++i) {
+            const long long g = k * BS + i;
+            rd[i] = 0.0;
+            if (g < n) {
+              const V bi = b[off + g], ri = bi - q[off + g];
+              r[off + g] = ri;
+              rd[i] = (double)ri;
+              rr[e] += (double)ri * (double)ri;
+              bb[e] += (double)bi * (double)bi;
+            }
+          }
+          block_mul<BS>(m, rd, z);
+#pragma unroll
+          for (int i = 0; i < BS; ++i) {
+            const long long g = k * BS + i;
+            if (g < n) {
+              rz[e] += rd[i] * z[i];
+              p[off + g] = (V)z[i];
+            }
+          }
+        }
+      }
+    } else {
+      constexpr int W = Vec16<V>::W;
+      typedef typename Vec16<V>::type VT;
+      const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+      for (long long i = t0; i < nv; i += stride) {
+        VT dv;
+        if (PRE) dv = reinterpret_cast<const VT *>(minv)[i];
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+          const long long off = (long long)(c0 + e) * ld;
+          const VT bv = reinterpret_cast<const VT *>(b + off)[i], qv = reinterpret_cast<const VT *>(q + off)[i];
+          VT rv, zv;
+#pragma unroll
+          for (int k = 0; k < W; ++k) {
+            rv[k] = bv[k] - qv[k];
+            rr[e] += (double)rv[k] * (double)rv[k];
+            bb[e] += (double)bv[k] * (double)bv[k];
+            if (PRE) {
+              const double z = (double)rv[k] * (double)dv[k];
+              rz[e] += (double)rv[k] * z;
+              zv[k] = (V)z;
+            }
+          }
+          if (r) reinterpret_cast<VT *>(r + off)[i] = rv;
+          if (p) reinterpret_cast<VT *>(p + off)[i] = PRE ? zv : rv;
+        }
+      }
+      for (long long i = nv * W + t0; i < n; i += stride) {
+        const V di = PRE ? minv[i] : (V)0;
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+          const long long off = (long long)(c0 + e) * ld;
+          const V bi = b[off + i], ri = bi - q[off + i];
+          if (r) r[off + i] = ri;
+          if (PRE) {
+            const double z = (double)ri * (double)di;
+            rz[e] += (double)ri * z;
+            if (p) p[off + i] = (V)z;
+          } else if (p) {
+            p[off + i] = ri;
+          }
+          rr[e] += (double)ri * (double)ri;
+          bb[e] += (double)bi * (double)bi;
+        }
+      }
+    }
+    block_sum_cols<CW>(rr);
+    block_sum_cols<CW>(bb);
+    if (BS >= 1) block_sum_cols<CW>(rz);
+    if (threadIdx.x == 0)
+#pragma unroll
+      for (int e = 0; e < CW; ++e)
+        if ((bits >> e) & 1u) {
+          double *pc = part + (size_t)(c0 + e) * kColSlots;
+          pc[slot_rr * kGrid + blockIdx.x] = rr[e];
+          if (with_bb) pc[P_BB * kGrid + blockIdx.x] = bb[e];
+          if (BS >= 1) pc[P_RZ0 * kGrid + blockIdx.x] = rz[e];
+        }
+  });
+}
+
+// cg_dot_kernel on the columns of cs that are not done
+template <typename V>
+__global__ void __launch_bounds__(kThreads)
+    cg_dot_cols_kernel(const V *__restrict__ a, const V *__restrict__ b, long long ld, long long n, double *__restrict__ part, int slot,
+                       const int *__restrict__ ic, ColumnMask cs) {
+  constexpr int CW = cols_chunk(0);
+  live_columns(ic, cs).chunks<CW>([&](int c0, unsigned bits) {
+    constexpr int W = Vec16<V>::W;
+    typedef typename Vec16<V>::type VT;
+    const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+    double s[CW];
+#pragma unroll
+    for (int e = 0; e < CW; ++e) s[e] = 0.0;
+    for (long long i = t0; i < nv; i += stride)
+#pragma unroll
+      for (int e = 0; e < CW; ++e) {
+        if (!((bits >> e) & 1u)) continue;
+        const long long off = (long long)(c0 + e) * ld;
+        const VT av = reinterpret_cast<const VT *>(a + off)[i], bv = reinterpret_cast<const VT *>(b + off)[i];
+#pragma unroll
+        for (int k = 0; k < W; ++k) s[e] += (double)av[k] * (double)bv[k];
+      }
+    for (long long i = nv * W + t0; i < n; i += stride)
+#pragma unroll
+      for (int e = 0; e < CW; ++e) {
+        if (!((bits >> e) & 1u)) continue;
+        const long long off = (long long)(c0 + e) * ld;
+        s[e] += (double)a[off + i] * (double)b[off + i];
+      }
+    block_sum_cols<CW>(s);
+    if (threadIdx.x == 0)
+#pragma unroll
+      for (int e = 0; e < CW; ++e)
+        if ((bits >> e) & 1u) part[(size_t)(c0 + e) * kColSlots + slot * kGrid + blockIdx.x] = s[e];
+  });
+}
+
+// cg_update_kernel<V, BS == 1, ALPHA> / cg_update_block_kernel<V, BS> on the columns of cs that are not done
+// (BS = 0 with ALPHA = P_RZ0: z is stored elsewhere, cfs_solver_amg.hpp)
+template <typename V, int BS, int ALPHA = BS >= 1 ? P_RZ0 : P_RR0>
+__global__ void __launch_bounds__(kThreads)
+    cg_update_cols_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q, long long ld,
+                          long long n, double *__restrict__ part, const int *__restrict__ ic, int it, const V *__restrict__ minv,
+                          long long nb, ColumnMask cs) {
+  constexpr int CW = cols_chunk(BS, true);
+  constexpr bool PRE = BS == 1;
+  live_columns(ic, cs).chunks<CW>([&](int c0, unsigned bits) {
+    double alpha[CW], s[CW], sz[CW];
+    {
+      double pq[CW], rr_old[CW];
+      slot_sums<CW>(part, P_PQ, c0, bits, pq);
+      slot_sums<CW>(part, ALPHA + (it & 1), c0, bits, rr_old);
+#pragma unroll
+      for (int e = 0; e < CW; ++e) {
+        alpha[e] = pq[e] != 0.0 ? rr_old[e] / pq[e] : 0.0;
+        s[e] = sz[e] = 0.0;
+      }
+    }
+    if constexpr (BS >= 2) {
+      for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+        double m[BS][BS];
+        block_load<V, BS>(minv, nb, k, m);
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+          const long long off = (long long)(c0 + e) * ld;
+          double rd[BS], z[BS];
+#pragma unroll
+          for (int i = 0; i < BS; ++i) {
+            const long long g = k * BS + i;
+            rd[i] = 0.0;
+            if (g < n) {
+              u[off + g] = (V)((double)u[off + g] + alpha[e] * (double)p[off + g]);
+              const double ri = (double)r[off + g] - alpha[e] * (double)q[off + g];
+              const V rn = (V)ri;
+              r[off + g] = rn;
+              s[e] += ri * ri;
+              rd[i] = (double)rn;
+            }
+          }
+          block_mul<BS>(m, rd, z);
+#pragma unroll
+          for (int i = 0; i < BS; ++i) sz[e] += rd[i] * z[i]; // (rd = 0 outside the matrix)
+        }
+      }
+    } else {
+      constexpr int W = Vec16<V>::W;
+      typedef typename Vec16<V>::type VT;
+      const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+      for (long long i = t0; i < nv; i += stride) {
+        VT dv;
+        if (PRE) dv = reinterpret_cast<const VT *>(minv)[i];
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+          const long long off = (long long)(c0 + e) * ld;
+          VT uv = reinterpret_cast<VT *>(u + off)[i], rv = reinterpret_cast<VT *>(r + off)[i];
+          const VT pv = reinterpret_cast<const VT *>(p + off)[i], qv = reinterpret_cast<const VT *>(q + off)[i];
+#pragma unroll
+          for (int k = 0; k < W; ++k) {
+            uv[k] = (V)((double)uv[k] + alpha[e] * (double)pv[k]);
+            const double ri = (double)rv[k] - alpha[e] * (double)qv[k];
+            rv[k] = (V)ri;
+            s[e] += ri * ri;
+            if (PRE) sz[e] += (double)rv[k] * ((double)rv[k] * (double)dv[k]);
+          }
+          reinterpret_cast<VT *>(u + off)[i] = uv;
+          reinterpret_cast<VT *>(r + off)[i] = rv;
+        }
+      }
+      for (long long i = nv * W + t0; i < n; i += stride) {
+        const V di = PRE ? minv[i] : (V)0;
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+          const long long off = (long long)(c0 + e) * ld;
+          u[off + i] = (V)((double)u[off + i] + alpha[e] * (double)p[off + i]);
+          const double ri = (double)r[off + i] - alpha[e] * (double)q[off + i];
+          const V rn = (V)ri;
+          r[off + i] = rn;
+          s[e] += ri * ri;
+          if (PRE) sz[e] += (double)rn * ((double)rn * (double)di);
+        }
+      }
+    }
+    block_sum_cols<CW>(s);
+    if (BS >= 1) block_sum_cols<CW>(sz);
+    if (threadIdx.x == 0)
+#pragma unroll
+      for (int e = 0; e < CW; ++e)
+        if ((bits >> e) & 1u) {
+          double *pc = part + (size_t)(c0 + e) * kColSlots;
+          pc[(P_RR0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = s[e];
+          if (BS >= 1) pc[(P_RZ0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = sz[e];
+        }
+  });
+}
+
+// r d + beta p (PRE) or r + beta p of cg_direction_kernel.  With PRE the sum of two products can be contracted two
+// ways, and which one the compiler takes depends on the code around it: cg_direction_kernel<V, true> is compiled to
+// fma(r, d, beta p) in both value types, in its vector loop and in its tail, while the same expression inside the
+// column loop became fma(beta, p, r d), whose iterates differ in the last bit.  So the form of the one-column kernel
+// is spelled out here; test C1 of tests/test_gpu_pcg_cols.py fails if the two ever part again.
+template <bool PRE> __device__ __forceinline__ double direction_sum(double r, double d, double beta, double p) {
+  if constexpr (PRE) {
+    const double bp = beta * p;
+    return __builtin_fma(r, d, bp);
+  } else {
+    return r + beta * p;
+  }
+}
+
+// cg_direction_kernel<V, BS == 1> / cg_direction_block_kernel<V, BS> on the columns of cs that are not done; one
+// thread: the iteration count and the flag of each of them.  BS = 0 with S0 = P_RZ0 and z for r: cheb_direction_kernel
+template <typename V, int BS, int S0 = BS >= 1 ? P_RZ0 : P_RR0>
+__global__ void __launch_bounds__(kThreads)
+    cg_direction_cols_kernel(V *__restrict__ p, const V *__restrict__ r, long long ld, long long n, const double *__restrict__ part,
+                             int *__restrict__ ic, int it, ColumnStops stop, const V *__restrict__ minv, long long nb, ColumnMask cs) {
+  constexpr int CW = cols_chunk(BS);
+  constexpr bool PRE = BS == 1;
+  live_columns(ic, cs).chunks<CW>([&](int c0, unsigned bits) {
+    double beta[CW], res[CW];
+    {
+      double rr[CW];
+      slot_sums<CW>(part, S0 + (it & 1), c0, bits, rr);
+      slot_sums<CW>(part, S0 + ((it + 1) & 1), c0, bits, res);
+#pragma unroll
+      for (int e = 0; e < CW; ++e) beta[e] = rr[e] != 0.0 ? res[e] / rr[e] : 0.0;
+      // what the stopping rule looks at: r . r (only workgroup 0 adds it up)
+      if (S0 != P_RR0 && blockIdx.x == 0) slot_sums<CW>(part, P_RR0 + ((it + 1) & 1), c0, bits, res);
+    }
+    if constexpr (BS >= 2) {
+      for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+        double m[BS][BS];
+        block_load<V, BS>(minv, nb, k, m);
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+          const long long off = (long long)(c0 + e) * ld;
+          double rd[BS], z[BS];
+#pragma unroll
+          for (int i = 0; i < BS; ++i) {
+            const long long g = k * BS + i;
+            rd[i] = g < n ? (double)r[off + g] : 0.0;
+          }
+          block_mul<BS>(m, rd, z);
+#pragma unroll
+          for (int i = 0; i < BS; ++i) {
+            const long long g = k * BS + i;
+            if (g < n) p[off + g] = (V)(z[i] + beta[e] * (double)p[off + g]);
+          }
+        }
+      }
+    } else {
+      constexpr int W = Vec16<V>::W;
+      typedef typename Vec16<V>::type VT;
+      const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+      for (long long i = t0; i < nv; i += stride) {
+        VT dv;
+        if (PRE) dv = reinterpret_cast<const VT *>(minv)[i];
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+          const long long off = (long long)(c0 + e) * ld;
+          VT pv = reinterpret_cast<VT *>(p + off)[i];
+          const VT rv = reinterpret_cast<const VT *>(r + off)[i];
+#pragma unroll
+          for (int k = 0; k < W; ++k)
+            pv[k] = (V)direction_sum<PRE>((double)rv[k], PRE ? (double)dv[k] : 0.0, beta[e], (double)pv[k]);
+          reinterpret_cast<VT *>(p + off)[i] = pv;
+        }
+      }
+      for (long long i = nv * W + t0; i < n; i += stride) {
+        const V di = PRE ? minv[i] : (V)0;
+#pragma unroll
+        for (int e = 0; e < CW; ++e) {
+          if (!((bits >> e) & 1u)) continue;
+          const long long off = (long long)(c0 + e) * ld;
+          p[off + i] = (V)direction_sum<PRE>((double)r[off + i], (double)di, beta[e], (double)p[off + i]);
+        }
+      }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+#pragma unroll
+      for (int e = 0; e < CW; ++e)
+        if ((bits >> e) & 1u) {
+          int *icc = ic + (c0 + e) * I_COUNT;
+          icc[I_ITER] += 1;
+          // (!(x > y): a NaN residual also ends the iteration)
+          if (!(res[e] > stop.v[c0 + e])) icc[I_DONE] = 1;
+        }
+  });
+}
+
 // ---- host: what every solver behind the C ABI shares ---------------------------------------------
 // n values of V (+ 64 bytes) in each of the buffers
 template <typename V> inline int alloc_vectors(long long n, std::initializer_list<cfs_rt::DevBuf *> bufs) {
@@ -760,6 +1171,162 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
         if ((rc = iteration(s.it))) return rc;
         ++s.it;
       }
+    }
+    if ((rc = s.look())) return rc;
+  }
+  return s.finish(iterations, relres);
+}
+
+// ---- preconditioned CG on a block of right-hand sides ---------------------------------------------
+// The iterations a block solve may enqueue between two host looks.  The limit of look_window() is on LAUNCHES: its cap
+// of 16 iterations of 5 launches keeps at most 80 of them ahead of the GPU, under the ~100 beyond which the runtime
+// stalls.  An iteration of a block with k columns the host believes active is 2 k + 3 launches -- a product is two,
+// the tile kernel and the fold, and there is one per column; then the dot, update and direction kernels, once for
+// the block -- so the window is the largest w with w (2 k + 3) <= 80, at least 1 (k = 16: 35 launches, w = 2; k = 1:
+// 5 launches, w = 16), and never more than check_every asks for.  The window only decides when the host looks: a
+// column is frozen by the device at its own iteration, so the bits do not depend on it.
+inline int look_window_cols(int check_every, int active_cols) {
+  return look_window(check_every, std::max(1, 80 / (2 * active_cols + 3)));
+}
+
+// Pcg<V, Handle> for the columns c < ncols of blocks U and B with leading dimension ld: R, P, Q are blocks with the
+// caller's ld, there is one slot array part[c][slot][kGrid] and one counter array ic[c][I_COUNT].  `active`: the columns
+// the host believes are not done; after first_look() those with r_c . r_c > stop_c (a column with b_c = 0, one whose
+// first guess solves it or one with a NaN never is), after look() those whose flag the device has not raised.
+//   begin;  [set-up of M^-1];  product_u(all());  a residual kernel;  first_look;  [refusals: U has not been written];
+//   while (live()) { until = window_end();  [iterations it .. until - 1 on the columns of active, ++it each];  look(); }
+//   finish
+template <typename V, class Handle> struct PcgCols {
+  Handle *h = nullptr;
+  V *u = nullptr;
+  const V *b = nullptr;
+  long long n = 0, ld = 0;
+  int ncols = 0;
+  hipStream_t st = nullptr;
+  int maxiter = 0, check_every = 0;
+  double tol = 0.0;
+  std::vector<double> bb;
+  ColumnStops stop;
+  cfs_rt::DevBuf rbuf, pbuf, qbuf, cnt;
+  Slots part;
+  V *r = nullptr, *p = nullptr, *q = nullptr;
+  int *ic = nullptr;
+  std::vector<int> host_ic;
+  int it = 0;          // iterations enqueued
+  unsigned active = 0; // the columns the host believes are not done
+  unsigned ever = 0;   // the columns that were active after the first look
+
+  unsigned all() const { return ncols >= 32 ? ~0u : (1u << ncols) - 1u; }
+  ColumnMask mask(unsigned bits) const { return ColumnMask{ncols, bits}; }
+  size_t block_values() const { return (size_t)(ncols - 1) * (size_t)ld + (size_t)n; }
+
+  int begin(const char *who, Handle *handle, void *u_dev, const void *b_dev, long long lead, int columns, double tolerance,
+            int max_iterations, int look_every, hipStream_t stream) {
+    h = handle, u = (V *)u_dev, b = (const V *)b_dev, n = h->n(), ld = lead, ncols = columns, st = stream, tol = tolerance;
+    maxiter = max_iterations, check_every = look_every;
+    if (h->rows() != h->n())
+      return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, std::string(who) + ": the handle holds a row block, not the whole matrix");
+    int rc;
+    if ((rc = alloc_vectors<V>((long long)block_values(), {&rbuf, &pbuf, &qbuf})) || (rc = part.alloc(ncols * P_COUNT, st)) ||
+        (rc = cnt.alloc((size_t)ncols * I_COUNT * sizeof(int))))
+      return rc;
+    r = (V *)rbuf.p, p = (V *)pbuf.p, q = (V *)qbuf.p, ic = (int *)cnt.p;
+    bb.assign(ncols, 0.0);
+    host_ic.assign((size_t)ncols * I_COUNT, 0);
+    for (double &s : stop.v) s = 0.0;
+    if ((rc = part.zero())) return rc;
+    HIPCHK(hipMemsetAsync(ic, 0, (size_t)ncols * I_COUNT * sizeof(int), st));
+    return 0;
+  }
+  // dst_c = A src_c for the columns of bits: one product per column
+  int products(V *dst, const V *src, unsigned bits) {
+    int rc = 0;
+    mask(bits).each([&](int c) {
+      if (!rc) rc = h->spmv_local(dst + (long long)c * ld, src + (long long)c * ld, nullptr, st);
+    });
+    return rc;
+  }
+  int product_u(unsigned bits) { return products(q, u, bits); } // Q_c = A U_c
+  // behind a residual kernel that left r_c . r_c in P_RR0 and b_c . b_c in P_BB of every column
+  int first_look() {
+    HIPCHK(hipGetLastError());
+    if (int rc = part.fetch()) return rc;
+    active = 0;
+    for (int c = 0; c < ncols; ++c) {
+      bb[c] = part.sum(c * P_COUNT + P_BB);
+      stop.v[c] = tol * tol * bb[c];
+      if (part.sum(c * P_COUNT + P_RR0) > stop.v[c]) active |= 1u << c;
+    }
+    if (maxiter <= 0) active = 0; // (maxiter = 0 behaves like done)
+    ever = active;
+    return 0;
+  }
+  // R = B - A U, rr[0], bb per column by the residual kernel of the plain iteration, and the look
+  int first_residual() {
+    if (int rc = product_u(all())) return rc;
+    hipLaunchKernelGGL((cg_residual_cols_kernel<V, 0>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, ld, n,
+                       part.dev(), (int)P_RR0, 1, (const V *)nullptr, 0LL, mask(all()));
+    return first_look();
+  }
+  bool live() const { return active != 0 && it < maxiter; }
+  int window_end() const { return std::min(maxiter, it + look_window_cols(check_every, __builtin_popcount(active))); }
+  int look() { // one copy of the counters + synchronisation
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host_ic.data(), ic, host_ic.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int c = 0; c < ncols; ++c)
+      if (host_ic[(size_t)c * I_COUNT + I_DONE]) active &= ~(1u << c);
+    return 0;
+  }
+  // the true residual of every column of what is returned: one product per column and one residual kernel
+  int finish(int *iterations, double *relres) {
+    int rc;
+    if ((rc = product_u(all()))) return rc;
+    hipLaunchKernelGGL((cg_residual_cols_kernel<V, 0>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b, (const V *)q,
+                       ld, n, part.dev(), (int)P_RES, 0, (const V *)nullptr, 0LL, mask(all()));
+    HIPCHK(hipGetLastError());
+    if ((rc = part.fetch())) return rc;
+    HIPCHK(hipMemcpy(host_ic.data(), ic, host_ic.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int c = 0; c < ncols; ++c) {
+      const double res2 = part.sum(c * P_COUNT + P_RES);
+      if (iterations) iterations[c] = host_ic[(size_t)c * I_COUNT + I_ITER];
+      if (relres) relres[c] = bb[c] > 0.0 ? std::sqrt(res2 / bb[c]) : std::sqrt(res2);
+    }
+    return 0;
+  }
+};
+
+// cfs_hip_sym_pcg_cols: cg<V, BS> on the columns of U and B.  Set-up of M^-1 once; per iteration one product per
+// column the host believes active, then the dot, update and direction kernels once for the block.  iterations, relres:
+// ncols entries each (or null).  CFS_HIP_CG_GRAPH is not looked at.
+template <typename V, int BS = 0, class Handle>
+int cg_cols(Handle *h, void *u_dev, const void *b_dev, long long ld, int ncols, double tol, int maxiter, int check_every,
+            int *iterations, double *relres, hipStream_t st) {
+  PcgCols<V, Handle> s;
+  Precond<V, BS> pre;
+  int rc;
+  if ((rc = s.begin("pcg_cols", h, u_dev, b_dev, ld, ncols, tol, maxiter, check_every, st)) || (rc = pre.setup(h, s.part.dev(), st)))
+    return rc;
+  V *u = s.u, *r = s.r, *p = s.p, *q = s.q;
+  const long long n = s.n, nb = pre.nb;
+  double *part = s.part.dev();
+  int *ic = s.ic;
+  const V *minv = pre.minv();
+  if ((rc = s.product_u(s.all()))) return rc;
+  hipLaunchKernelGGL((cg_residual_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, p, s.b, (const V *)q, ld, n, part,
+                     (int)P_RR0, 1, minv, nb, s.mask(s.all()));
+  if ((rc = s.first_look()) || (rc = pre.check("pcg_cols", s.part, n))) return rc; // (U has not been touched yet)
+  while (s.live()) {
+    const int until = s.window_end();
+    const ColumnMask cs = s.mask(s.active);
+    for (; s.it < until; ++s.it) {
+      if ((rc = s.products(q, p, s.active))) return rc;
+      hipLaunchKernelGGL((cg_dot_cols_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, ld, n, part, (int)P_PQ,
+                         (const int *)ic, cs);
+      hipLaunchKernelGGL((cg_update_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, ld, n, part,
+                         (const int *)ic, s.it, minv, nb, cs);
+      hipLaunchKernelGGL((cg_direction_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, ld, n,
+                         (const double *)part, ic, s.it, s.stop, minv, nb, cs);
     }
     if ((rc = s.look())) return rc;
   }

@@ -139,6 +139,8 @@ struct cfs_hip_amg_s {
   virtual bool is_stale() const = 0;              // the last refresh failed
   virtual long long column_cycles() const = 0;    // cycles applied to columns of blocks, since create
   virtual int pcg(void *u_dev, const void *b_dev, double tol, int maxiter, int *iterations, double *relres, hipStream_t st) = 0;
+  virtual int pcg_cols(void *u_dev, const void *b_dev, long long ld, int ncols, double tol, int maxiter, int *iterations, double *relres,
+                       hipStream_t st) = 0;
   virtual int update_check(long long nnz) = 0;
   virtual int update_values(const void *values_dev, long long nnz, hipStream_t st) = 0;
   virtual int refresh_info(long long *map_bytes, int *refreshes, double *last_seconds, double *split) = 0;
@@ -1603,6 +1605,60 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
       if ((rc = cycle_and_dot((int)P_RZ0 + ((it + 1) & 1)))) return rc;
       hipLaunchKernelGGL((cheb_direction_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, n, (const double *)pp, ic, it,
                          s.stop);
+      ++s.it;
+      if ((rc = s.look())) return rc;
+    }
+    return s.finish(iterations, relres);
+  }
+
+  // cfs_hip_sym_pcg_amg_cols: pcg() on the columns of blocks U and B (arguments checked by the caller).  One Z block;
+  // the cycle runs on the columns still active, every vector kernel of it once for the block, and so do the four
+  // kernels of the recurrence; the products stay one per active column.  The host looks after every iteration, as
+  // pcg() does, so its mask is exact: the cycle's kernels, which know one flag only, are given the object's own counters
+  // (never raised) and the mask alone says which columns they work on.
+  int pcg_cols(void *u_dev, const void *b_dev, long long ld, int ncols, double tol, int maxiter, int *iterations, double *relres,
+               hipStream_t st) override {
+    if (stale) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "pcg_amg_cols: the last refresh failed");
+    PcgCols<V, cfs_hip_sym_s> s;
+    cfs_rt::DevBuf zbuf;
+    int rc;
+    if ((rc = follow_fine(st)) || (rc = reserve_cols(ncols))) return rc;
+    if ((rc = s.begin("pcg_amg_cols", fine, u_dev, b_dev, ld, ncols, tol, maxiter, 1, st)) ||
+        (rc = alloc_vectors<V>((long long)s.block_values(), {&zbuf})) || (rc = s.first_residual()))
+      return rc;
+    V *u = s.u, *r = s.r, *p = s.p, *q = s.q, *z = (V *)zbuf.p;
+    const long long n = s.n;
+    double *pp = s.part.dev();
+    int *ic = s.ic;
+    // Z_c = M^-1 R_c;  part[c][slot] <- r_c . z_c of the stored r and the stored final z, for the active columns
+    auto cycle_and_dot = [&](int slot) -> int {
+      const ColumnMask cs = s.mask(s.active);
+      if (int r2 = cycle(0, cs, z, ld, (const V *)r, ld, (const int *)cnt.p, st)) return r2;
+      col_cycles += __builtin_popcount(s.active);
+      hipLaunchKernelGGL((cg_dot_cols_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, ld, n, pp, slot,
+                         (const int *)ic, cs);
+      return 0;
+    };
+    if (s.live()) { // Z = M^-1 R, rz[0] = r . z, P = Z
+      if ((rc = cycle_and_dot((int)P_RZ0))) return rc;
+      int r2 = 0;
+      s.mask(s.active).each([&](int c) {
+        if (!r2 && hipMemcpyAsync(p + (long long)c * ld, z + (long long)c * ld, (size_t)n * sizeof(V), hipMemcpyDeviceToDevice, st) != hipSuccess)
+          r2 = cfs_rt::set_err(CFS_HIP_ERR_DEVICE, "pcg_amg_cols: copying Z to P failed");
+      });
+      if (r2) return r2;
+    }
+    while (s.live()) { // (a window of one: a cycle is more than may be enqueued ahead of the GPU)
+      const int it = s.it;
+      const ColumnMask cs = s.mask(s.active);
+      if ((rc = s.products(q, p, s.active))) return rc;
+      hipLaunchKernelGGL((cg_dot_cols_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, ld, n, pp, (int)P_PQ,
+                         (const int *)ic, cs);
+      hipLaunchKernelGGL((cg_update_cols_kernel<V, 0, P_RZ0>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, ld, n,
+                         pp, (const int *)ic, it, (const V *)nullptr, 0LL, cs);
+      if ((rc = cycle_and_dot((int)P_RZ0 + ((it + 1) & 1)))) return rc;
+      hipLaunchKernelGGL((cg_direction_cols_kernel<V, 0, P_RZ0>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, ld, n,
+                         (const double *)pp, ic, it, s.stop, (const V *)nullptr, 0LL, cs);
       ++s.it;
       if ((rc = s.look())) return rc;
     }

@@ -420,6 +420,53 @@ class SymMatrix:
                                                    int(check_every), C.byref(it), C.byref(res), _stream_ptr(stream)))
         return it.value, res.value
 
+    @staticmethod
+    def _block_layout(U, B):
+        """(ld, ncols) of two 2-D blocks stored by columns, strides (1, ld), as Amg.apply takes them; ValueError otherwise"""
+        if U.dim() != 2 or B.dim() != 2 or U.shape != B.shape or U.dtype != B.dtype:
+            raise ValueError("U and B are both 2-D blocks of the same shape and type")
+        ncols = int(U.shape[1])
+        ld = int(U.stride(1)) if ncols > 1 else max(int(U.shape[0]), 1)
+        for t in (U, B):
+            if (U.shape[0] > 1 and t.stride(0) != 1) or (ncols > 1 and t.stride(1) != ld):
+                raise ValueError("a block is stored by columns: strides (1, ld), the same ld for U and B")
+        return ld, ncols
+
+    def pcg_cols(self, U, B, precond="jacobi", block=3, tol=1e-10, maxiter=1000, check_every=8, stream=None):
+        """preconditioned CG on a block of right-hand sides inside the library (cfs_hip_sym_pcg_cols): A U_c = B_c for
+        the columns of the 2-D device blocks U (in: the first guesses, out: the solutions) and B, shape (n, ncols),
+        strides (1, ld) as Amg.apply() takes them, ncols <= 16.  precond = "none", "jacobi" or "block_jacobi" (block one
+        of 1, 2, 3, 4, 6), or G, an Amg of this matrix (cfs_hip_sym_pcg_amg_cols: one column-blocked cycle per
+        iteration).  Every column runs the recurrence of pcg() / pcg_amg() and stops by its rule on its own; the set-up
+        runs once, the products stay one per active column and every vector kernel runs once for the block.  Returns
+        (iterations, relres): numpy arrays of ncols entries, what pcg() returns per column.  ValueError, before any
+        device work, for blocks that are not 2-D, differ in shape or type, or are not stored by columns with one ld."""
+        ld, ncols = SymMatrix._block_layout(U, B)
+        amg = precond if isinstance(precond, Amg) else None
+        if amg is not None:
+            if amg.A is not self:
+                raise ValueError("the hierarchy was made for another matrix")
+        elif isinstance(precond, str):
+            if precond == "amg":
+                raise ValueError('precond="amg" needs the hierarchy: pass it as precond (precond=A.amg(...)), or call '
+                                 'solver.pcg_cols_native(A, B, precond="amg", amg=G)')
+            if precond not in LOBPCG_PRECOND:
+                raise ValueError(f"unknown preconditioner {precond!r}: one of {sorted(LOBPCG_PRECOND)}")
+            block_rows = int(block) if precond == "block_jacobi" else LOBPCG_PRECOND[precond]
+        else:
+            block_rows = int(precond)
+        it, res = np.zeros(max(ncols, 1), np.int32), np.zeros(max(ncols, 1), np.float64)
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        if amg is not None:
+            _lib.check(_lib.load().cfs_hip_sym_pcg_amg_cols(
+                self._h, amg._a, _ptr(U), _ptr(B), ld, ncols, float(tol), int(maxiter), int(check_every), it.ctypes.data_as(ip),
+                res.ctypes.data_as(dp), _stream_ptr(stream)))
+        else:
+            _lib.check(_lib.load().cfs_hip_sym_pcg_cols(
+                self._h, _ptr(U), _ptr(B), ld, ncols, block_rows, float(tol), int(maxiter), int(check_every),
+                it.ctypes.data_as(ip), res.ctypes.data_as(dp), _stream_ptr(stream)))
+        return it[:ncols], res[:ncols]
+
     def minres(self, u, b, precond="none", shift=0.0, tol=1e-10, maxiter=1000, check_every=8, stream=None):
         """MINRES inside the library (cfs_hip_sym_minres): u (device tensor) holds the first guess and
         receives the solution of (A - shift I) u = b, A symmetric and possibly indefinite; five launches per

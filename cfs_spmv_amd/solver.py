@@ -263,6 +263,62 @@ def pcg_amg_native(A, b, amg, tol=1e-10, maxiter=1000, x0=None, check_every=1):
     return u, it, res
 
 
+def _pcg_cols_amg_args(precond, amg):
+    """the two ValueErrors of precond="amg" / amg=, before any device work"""
+    if precond == "amg" and amg is None:
+        raise ValueError('pcg_cols: precond="amg" needs amg=, the hierarchy (A.amg(...))')
+    if amg is not None and precond != "amg":
+        raise ValueError(f'pcg_cols: amg= goes with precond="amg", not with {precond!r}')
+
+
+def column_block(n, ncols, dtype, device="cuda"):
+    """a zeroed (n, ncols) device block in the layout the column entry points take: strides (1, ld), ld = n rounded up
+    to 16 bytes"""
+    import torch
+    per = 16 // torch.empty(0, dtype=dtype).element_size()
+    ld = -(-n // per) * per
+    return torch.as_strided(torch.zeros(max(ncols, 1) * max(ld, 1), dtype=dtype, device=device), (n, ncols), (1, ld))
+
+
+def pcg_cols(A, B, precond="jacobi", block=3, amg=None, tol=1e-10, maxiter=1000, X0=None):
+    """PCG on the columns of the (n, ncols) device block B, host-driven: one pcg() (precond = "jacobi", "block_jacobi"),
+    cg() ("none") or pcg_amg() (precond="amg", amg=G) per column -- the model of cfs_hip_sym_pcg_cols /
+    cfs_hip_sym_pcg_amg_cols, in which every column is the one-column solve on (u_c, b_c) alone.  X0: the first guesses,
+    (n, ncols).  Returns (U, iterations, relres): U (n, ncols) with strides (1, ld), numpy arrays of ncols entries."""
+    import numpy as np
+    import torch
+    _pcg_cols_amg_args(precond, amg)
+    n, ncols = int(B.shape[0]), int(B.shape[1])
+    U = column_block(n, ncols, B.dtype, B.device)
+    its, res = np.zeros(ncols, np.int32), np.zeros(ncols, np.float64)
+    for c in range(ncols):
+        b = B[:, c].contiguous()
+        x0 = None if X0 is None else X0[:, c].contiguous()
+        if precond == "amg":
+            u, its[c], res[c] = pcg_amg(A, b, amg, tol=tol, maxiter=maxiter, x0=x0)
+        elif precond == "none":
+            u, its[c], res[c] = cg(A, b, tol=tol, maxiter=maxiter, x0=x0)
+        else:
+            u, its[c], res[c] = pcg(A, b, tol=tol, maxiter=maxiter, x0=x0, precond=precond, block=block)
+        U[:, c] = u
+    return U, its, res
+
+
+def pcg_cols_native(A, B, precond="jacobi", block=3, amg=None, tol=1e-10, maxiter=1000, X0=None, check_every=8):
+    """the same solves inside the library as ONE call (cfs_hip_sym_pcg_cols, or cfs_hip_sym_pcg_amg_cols with
+    precond="amg", amg=G): the set-up once, one product per active column, every vector kernel once for the block.
+    B (n, ncols), any strides: it is copied into the column layout.  Returns (U, iterations, relres), like pcg_cols()."""
+    _pcg_cols_amg_args(precond, amg)
+    n, ncols = int(B.shape[0]), int(B.shape[1])
+    U, Bc = column_block(n, ncols, B.dtype, B.device), column_block(n, ncols, B.dtype, B.device)
+    Bc.copy_(B)
+    if X0 is not None:
+        U.copy_(X0)
+    its, res = A.pcg_cols(U, Bc, precond=amg if precond == "amg" else precond, block=block, tol=tol, maxiter=maxiter,
+                          check_every=check_every)
+    return U, its, res
+
+
 def pcg_mixed(M, b, tol=1e-10, delta=0.1, maxiter=1000, x0=None, precond="jacobi", block=3, check_every=8):
     """mixed-precision PCG, host-driven: the recurrence of cfs_hip_sym_pcg_mixed on a MixedSym.  One CG
     recurrence in float32 (r, p, q and the correction xlo; the products on M.A32; dots and z = M^-1 r in

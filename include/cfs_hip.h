@@ -691,6 +691,40 @@ int cfs_hip_amg_column_cycles(cfs_hip_amg_t a, long long *cycles);
  * *iterations = 0.                                                                                                */
 int cfs_hip_sym_pcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const void *b_dev, double tol, int maxiter,
                         int check_every, int *iterations, double *relres, void *stream);
+/* PRECONDITIONED CG ON A BLOCK OF RIGHT-HAND SIDES: A U_c = B_c for the columns c < ncols <= CFS_HIP_LOBPCG_MAX_K, column c
+ * of U at u_dev + c ld values and of B at b_dev + c ld values.  On entry U holds the first guesses, on return the
+ * solutions; B, the rows from n on of every column and everything else of the caller's are not written.  block_rows: the
+ * stored M^-1, as in the Chebyshev entry points -- 0 none (cfs_hip_sym_cg), 1 Jacobi (cfs_hip_sym_pcg), 2, 3, 4 or 6
+ * block Jacobi (cfs_hip_sym_pcg_block).  Every column runs the recurrence of its one-column entry point and stops by
+ * its rule, r_c.r_c <= tol^2 b_c.b_c, on its own: the set-up of M^-1 runs once per call, the products stay one per
+ * column that is still active, and the dot, update and direction kernels run ONCE for the block, 2 k + 3 launches per
+ * iteration with k active columns where k one-column solves enqueue 5 k.  The scalars, the iteration counter and the
+ * convergence flag are per column and live on the device; a column whose flag is up is frozen by the kernels
+ * themselves, so the host's looks (every check_every iterations, < 1 means 8, and never more iterations than keep
+ * about 80 launches ahead of the GPU) decide nothing but when the loop ends.  A column with b_c = 0, one whose first
+ * guess already solves it and one that holds a NaN never become active.  iterations[ncols], relres[ncols] (either may
+ * be NULL): per column what the one-column entry point returns, relres RECOMPUTED from the returned U.  Returns 0 also
+ * when some column reaches maxiter.  MEMORY: 3 blocks of (ncols - 1) ld + n values (R, P, Q) besides M^-1.  On a
+ * CFS_HIP_FLAG_DETERMINISTIC handle column c of U, iterations[c] and relres[c] have the bits of the one-column entry
+ * point on (u_c, b_c) alone.  CFS_HIP_CG_GRAPH has no effect here.  Refusals, all before U is touched and with every
+ * iterations[c] = 0, in this order: CFS_HIP_ERR_ARG for a null pointer; ncols outside 1 .. CFS_HIP_LOBPCG_MAX_K; u_dev or
+ * b_dev not 16-byte aligned; ld < n, or ncols > 1 and ld sizeof(V) not a multiple of 16; the two blocks overlap;
+ * tol < 0, maxiter < 0 or a block_rows that is not one of 0, 1, 2, 3, 4, 6; CFS_HIP_ERR_UNSUPPORTED for a shard or a
+ * multi-device handle; then CFS_HIP_ERR_ARG for a host pointer or one on another device, and for a diagonal entry or
+ * block that is not positive (definite), which refuses the whole call.  Out of scope: Chebyshev, mixed-precision and
+ * MINRES block forms, and a product that serves several columns in one pass over the matrix.                      */
+int cfs_hip_sym_pcg_cols(cfs_hip_sym_t h, void *u_dev, const void *b_dev, long long ld, int ncols, int block_rows,
+                         double tol, int maxiter, int check_every, int *iterations, double *relres, void *stream);
+/* cfs_hip_sym_pcg_amg on a block of right-hand sides, the blocks, outputs and guarantee as for cfs_hip_sym_pcg_cols:
+ * the cycle of `a` runs column-blocked on the columns still active (cfs_hip_amg_apply_cols: every vector kernel once
+ * for the block) and so do the four kernels of the recurrence; every hierarchy cfs_hip_sym_pcg_amg serves is served.
+ * The host looks after every iteration, check_every is accepted and not used.  cfs_hip_amg_column_cycles grows by
+ * iterations[c] + 1 for every column that was ever active.  MEMORY: 4 blocks of (ncols - 1) ld + n values (R, P, Q,
+ * Z) and the hierarchy's work vectors for ncols columns (kept, as by cfs_hip_amg_apply_cols).  Refusals as for
+ * cfs_hip_sym_pcg_cols (no block_rows), with, behind CFS_HIP_ERR_UNSUPPORTED and in this order, CFS_HIP_ERR_ARG for a
+ * hierarchy created on another handle, one whose last refresh failed, a host pointer or one on another device.    */
+int cfs_hip_sym_pcg_amg_cols(cfs_hip_sym_t h, cfs_hip_amg_t a, void *u_dev, const void *b_dev, long long ld, int ncols,
+                             double tol, int maxiter, int check_every, int *iterations, double *relres, void *stream);
 /* Host only, no device work: one level of the set-up above.  In: the CSR of A_l (entries with col <= row are read),
  * passes (1 .. 3).  Out: agg[n], w[n] (fp64), *nc, and the lower triangle + diagonal CSR of A_{l+1} in fp64,
  * c_rowptr[*nc + 1] (at least n + 1 ints: *nc is not known before), c_colind / c_values with room for `capacity`

@@ -40,7 +40,13 @@ kernels move bs^2 weights per node where the scalar ones move bs), their levels,
 whose n is not a multiple of 3 has no node-block hierarchy (a trailing partial node): the refusal is recorded.  Default
 matrices: pwtk, ldoor, Flan_1565 and rotnode3x400x330 -- rotnodeBSxNXxNY is the rotated node Laplacian of
 tests/test_amg_block_abi.py, A = H (L' (x) I) H with node frames rotated against the axes.
-usage: python tools/cg_bench.py [--only-cheb | --only-amg | --only-amg-refresh | --only-amg-setup | --only-amg-block]
+--only-cols: PCG on a BLOCK OF RIGHT-HAND SIDES (cfs_hip_sym_pcg_cols, cfs_hip_sym_pcg_amg_cols) beside k one-column solves of
+the same build in the same process: for k = 1, 4, 16 one blocked solve down to TOL against cfs_hip_sym_pcg / _pcg_block /
+_pcg_amg called once per column, with Jacobi, block Jacobi on 3 x 3 node blocks and the multigrid hierarchy at degree 1 (built
+once, outside the timed part), interleaved, COLS_ROUNDS rounds, the best wall time of each; the iterations of every column, and
+the launches per iteration of both forms while all k columns are active.  Default matrices: lap2d400x330, pwtk, ldoor,
+Flan_1565.
+usage: python tools/cg_bench.py [--only-cheb | --only-amg | --only-amg-refresh | --only-amg-setup | --only-amg-block | --only-cols]
        [matrix[:scale] | lap2dNXxNY | rotnodeBSxNXxNY ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -64,6 +70,8 @@ ONLY_AMG = "--only-amg" in sys.argv or ONLY_REFRESH
 HAVE_REFRESH = hasattr(cfs.load(), "cfs_hip_amg_update_values_f64")
 ONLY_SETUP = "--only-amg-setup" in sys.argv
 ONLY_BLOCK = "--only-amg-block" in sys.argv
+ONLY_COLS = "--only-cols" in sys.argv
+COLS_K, COLS_ROUNDS = (1, 4, 16), 3
 SETUP_CREATES = 3
 REFRESH_TIMED = 5
 AMG_DEGREES, AMG_ROUNDS = (1, 2), 3
@@ -268,6 +276,67 @@ def block_section(A, b, res, rp, ci, va):
         G.close()
 
 
+def cols_section(A, res, rp, ci, va):
+    """one blocked solve of k right-hand sides down to TOL against k one-column solves, for Jacobi, block Jacobi and multigrid"""
+    from cfs_spmv_amd.solver import column_block
+    n = A.n
+    G = A.amg(rp, ci, va, degree=1)  # (outside the timed part: both forms use it)
+    levels = G.info()["levels"]
+    forms = {"jacobi": dict(precond="jacobi"), f"block{BLOCK}": dict(precond="block_jacobi", block=BLOCK), "amg1": dict(precond=G)}
+    res["cols_tolerance"], res["cols_rounds"], res["maxiter"], res["amg1_levels"] = TOL, COLS_ROUNDS, MAXITER, G.info()["n"]
+    tdt = torch.float64 if A.dtype == np.float64 else torch.float32
+    for k in COLS_K:
+        B, U = column_block(n, k, tdt), column_block(n, k, tdt)
+        for c in range(k):
+            B[:, c] = torch.from_numpy(synth.make_x(n, 11 + c).astype(A.dtype)).cuda()
+        u = torch.zeros(n, dtype=tdt, device="cuda")
+
+        def blocked(kw):
+            U.zero_()
+            return A.pcg_cols(U, B, tol=TOL, maxiter=MAXITER, check_every=16, **kw)
+
+        def one_by_one(kw):
+            its, rel = [], []
+            for c in range(k):
+                u.zero_()
+                if kw["precond"] is G:
+                    it, r = A.pcg_amg(u, B[:, c], G, tol=TOL, maxiter=MAXITER)
+                else:
+                    it, r = A.pcg(u, B[:, c], tol=TOL, maxiter=MAXITER, check_every=16, **kw)
+                its.append(it), rel.append(r)
+            return np.array(its), np.array(rel)
+        loops = {}
+        for tag, kw in forms.items():
+            loops[f"{tag}_k{k}_blocked"] = lambda kw=kw: blocked(kw)
+            loops[f"{tag}_k{k}_one_by_one"] = lambda kw=kw: one_by_one(kw)
+        best = {}
+        for _ in range(COLS_ROUNDS):
+            for label, fn in loops.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                it, rel = fn()
+                torch.cuda.synchronize()
+                t = time.perf_counter() - t0
+                if t < best.get(label, (float("inf"),))[0]:
+                    best[label] = (t, it, rel)
+        for label, (t, it, rel) in best.items():
+            res[label + "_ms"] = round(t * 1e3, 3)
+            res[label + "_iterations"] = [int(v) for v in it]
+            res[label + "_max_relres"] = float(np.max(rel))
+        for tag in forms:
+            res[f"{tag}_k{k}_blocked_over_one_by_one_time"] = round(best[f"{tag}_k{k}_blocked"][0] / best[f"{tag}_k{k}_one_by_one"][0], 4)
+            # launches per iteration while all k columns are active (a product is two launches; a level that has a coarser one
+            # costs 4 vector kernels and 2 products at degree 1, the last level one kernel)
+            if tag == "amg1":
+                one, blk = k * (8 * levels - 1), 2 * k + 4 + 4 * (levels - 1) + 1 + 4 * k * (levels - 1)
+            else:
+                one, blk = 5 * k, 2 * k + 3
+            res[f"{tag}_k{k}_launches_per_iteration_one_by_one"], res[f"{tag}_k{k}_launches_per_iteration_blocked"] = one, blk
+            print(f"# {tag} k={k}: launches per iteration {one} one by one, {blk} blocked; "
+                  f"{res[f'{tag}_k{k}_one_by_one_ms']} ms one by one, {res[f'{tag}_k{k}_blocked_ms']} ms blocked", file=sys.stderr, flush=True)
+    G.close()
+
+
 def amg_section(A, b, res, rp, ci, va):
     """solves down to TOL: Jacobi PCG, Chebyshev degree 4 on Jacobi, and the V-cycle at AMG_DEGREES, interleaved"""
     if ONLY_REFRESH:
@@ -309,7 +378,7 @@ def amg_section(A, b, res, rp, ci, va):
 
 
 out = {}
-for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ldoor", "Flan_1565"] + (["rotnode3x400x330"] if ONLY_BLOCK else [])):
+for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or (["lap2d400x330"] if ONLY_COLS else []) + ["pwtk", "ldoor", "Flan_1565"] + (["rotnode3x400x330"] if ONLY_BLOCK else [])):
     name, _, sc = spec.partition(":")
     if name.startswith("lap2d"):  # lap2dNXxNY: the anisotropic 5-point Laplacian of the tests, a matrix that needs many iterations
         import scipy.sparse as sp
@@ -336,7 +405,9 @@ for spec in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["pwtk", "ld
     spmv_us = (time.perf_counter() - t0) / 200 * 1e6
     K = 200
     res = {"n": n, "spmv_us": round(spmv_us, 2)}
-    if ONLY_CHEB or ONLY_AMG or ONLY_SETUP or ONLY_BLOCK:
+    if ONLY_CHEB or ONLY_AMG or ONLY_SETUP or ONLY_BLOCK or ONLY_COLS:
+        if ONLY_COLS:
+            cols_section(A, res, rp, ci, va)
         if ONLY_BLOCK:
             block_section(A, b, res, rp, ci, va)
         if ONLY_SETUP:
