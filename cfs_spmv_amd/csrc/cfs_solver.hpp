@@ -20,26 +20,30 @@
 // kernels enqueued behind a converged iteration return at once.  cfs_hip_sym_cg recomputes the
 // true residual ||b - A u|| / ||b|| at the end.
 //
-// Jacobi (cfs_hip_sym_pcg; BS = 1 on the host, PRE = true in the kernels below): the same five launches.  dinv_i = (V)(1 / a_ii) is
+// Jacobi (cfs_hip_sym_pcg; BS = 1): the same five launches.  dinv_i = (V)(1 / a_ii) is
 // built once from the handle's own diagonal (cfs_diag_gather_kernel, then cg_dinv_kernel);
 // z = D^-1 r is never stored: z_i = (double)r_i * (double)dinv_i, with r_i the rounded value in
 // memory, is formed in fp64 where it is needed --
-//   cg_update_kernel<V, true>     u += (rz/pq) p;  r -= (rz/pq) q;  rz' = r . z;  rr' = r . r
-//   cg_direction_kernel<V, true>  p = dinv r + (rz'/rz) p;  converged?  (rr' <= stop: the
+//   cg_update_kernel<V, 1>        u += (rz/pq) p;  r -= (rz/pq) q;  rz' = r . z;  rr' = r . r
+//   cg_direction_kernel<V, 1>     p = dinv r + (rz'/rz) p;  converged?  (rr' <= stop: the
 //                                 unpreconditioned residual, the same rule as without)
-// r . z has two slots alternating with the parity of the iteration, like r . r.  The PRE = false
+// r . z has two slots alternating with the parity of the iteration, like r . r.  The BS = 0
 // instantiations are the kernels of the plain iteration, operation for operation.
 //
-// Block Jacobi (cfs_hip_sym_pcg_block, BS = 2, 3, 4, 6 below): M = blockdiag(A) on the BS x BS node blocks
+// Block Jacobi (cfs_hip_sym_pcg_block, BS = 2, 3, 4, 6): M = blockdiag(A) on the BS x BS node blocks
 // of a multi-dof mesh matrix, whose couplings inside a node are as strong as the diagonal.  Set-up, once
 // per call: the blocks are gathered from the handle (cfs_block_gather_kernel) and cg_binv_kernel inverts
 // them, one thread per block, in fp64 registers (Cholesky, then the inverse); the inverse is stored rounded
 // to the value type as its packed lower triangle, structure of arrays (word t of block k at minv[t nb + k]:
 // consecutive lanes read consecutive words).  The same five launches per iteration: z_i = sum_j
 // (double)Minv_ij (double)r_j over the block, r_j the rounded value in memory, is formed in fp64 inside
-// cg_update_block_kernel (for r . z) and again in cg_direction_block_kernel, and never stored.  These walk
-// the vectors one node block per thread, grid-stride; the scalars are the same partial-sum slots, so a solve
-// on a deterministic handle stays bit-reproducible.  The kernels above are not touched by it.
+// cg_update_kernel<V, BS> (for r . z) and again in cg_direction_kernel<V, BS>, and never stored.  These
+// instantiations walk the vectors one node block per thread, grid-stride; the scalars are the same
+// partial-sum slots, so a solve on a deterministic handle stays bit-reproducible.
+//
+// Each of the four kernels is ONE source, templated on BS and on the set of columns it works on: OneColumn for
+// the solvers above, ColumnMask for the same recurrence on a block of right-hand sides (cfs_hip_sym_pcg_cols),
+// launched once for the block.  See "the recurrence" below.
 #pragma once
 
 namespace cfs_solver {
@@ -127,160 +131,6 @@ __global__ void __launch_bounds__(kThreads) cg_dinv_kernel(V *__restrict__ d, lo
   }
   bad = block_sum(bad);
   if (threadIdx.x == 0) part[P_BAD * kGrid + blockIdx.x] = bad;
-}
-
-// r = b - q;  p = r (when given);  part[slot_rr] <- r . r;  part[P_BB] <- b . b (when with_bb)
-// PRE: p = z = dinv r instead, and part[P_RZ0] <- r . z
-template <typename V, bool PRE = false>
-__global__ void __launch_bounds__(kThreads)
-    cg_residual_kernel(V *__restrict__ r, V *__restrict__ p, const V *__restrict__ b, const V *__restrict__ q,
-                       long long n, double *__restrict__ part, int slot_rr, int with_bb,
-                       const V *__restrict__ dinv = nullptr) {
-  constexpr int W = Vec16<V>::W;
-  typedef typename Vec16<V>::type VT;
-  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  double rr = 0.0, bb = 0.0, rz = 0.0;
-  for (long long i = t0; i < nv; i += stride) {
-    const VT bv = reinterpret_cast<const VT *>(b)[i], qv = reinterpret_cast<const VT *>(q)[i];
-    VT rv, zv;
-    if (PRE) zv = reinterpret_cast<const VT *>(dinv)[i];
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      rv[k] = bv[k] - qv[k];
-      rr += (double)rv[k] * (double)rv[k];
-      bb += (double)bv[k] * (double)bv[k];
-      if (PRE) {
-        const double z = (double)rv[k] * (double)zv[k];
-        rz += (double)rv[k] * z;
-        zv[k] = (V)z;
-      }
-    }
-    if (r) reinterpret_cast<VT *>(r)[i] = rv;
-    if (p) reinterpret_cast<VT *>(p)[i] = PRE ? zv : rv;
-  }
-  for (long long i = nv * W + t0; i < n; i += stride) {
-    const V bi = b[i], ri = bi - q[i];
-    if (r) r[i] = ri;
-    if (PRE) {
-      const double z = (double)ri * (double)dinv[i];
-      rz += (double)ri * z;
-      if (p) p[i] = (V)z;
-    } else if (p) {
-      p[i] = ri;
-    }
-    rr += (double)ri * (double)ri;
-    bb += (double)bi * (double)bi;
-  }
-  rr = block_sum(rr);
-  bb = block_sum(bb);
-  if (PRE) rz = block_sum(rz);
-  if (threadIdx.x == 0) {
-    part[slot_rr * kGrid + blockIdx.x] = rr;
-    if (with_bb) part[P_BB * kGrid + blockIdx.x] = bb;
-    if (PRE) part[P_RZ0 * kGrid + blockIdx.x] = rz;
-  }
-}
-
-// part[slot] <- a . b of the stored values (p . q into P_PQ; r . z where z is stored: cfs_solver_amg.hpp)
-template <typename V>
-__global__ void __launch_bounds__(kThreads)
-    cg_dot_kernel(const V *__restrict__ a, const V *__restrict__ b, long long n, double *__restrict__ part, int slot,
-                  const int *__restrict__ ic) {
-  if (ic[I_DONE]) return;
-  constexpr int W = Vec16<V>::W;
-  typedef typename Vec16<V>::type VT;
-  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  double s = 0.0;
-  for (long long i = t0; i < nv; i += stride) {
-    const VT av = reinterpret_cast<const VT *>(a)[i], bv = reinterpret_cast<const VT *>(b)[i];
-#pragma unroll
-    for (int k = 0; k < W; ++k) s += (double)av[k] * (double)bv[k];
-  }
-  for (long long i = nv * W + t0; i < n; i += stride) s += (double)a[i] * (double)b[i];
-  s = block_sum(s);
-  if (threadIdx.x == 0) part[slot * kGrid + blockIdx.x] = s;
-}
-
-// alpha = rr / pq;  u += alpha p;  r -= alpha q;  part[rr of the next iteration] <- r . r
-// PRE: alpha = rz / pq, and part[rz of the next iteration] <- r . z with z = dinv r of the ROUNDED r
-// ALPHA: the first of the two slots alpha's numerator alternates between (PRE = false with P_RZ0: z is stored
-// elsewhere and r . z comes from cg_dot_kernel, cfs_solver_amg.hpp)
-template <typename V, bool PRE = false, int ALPHA = PRE ? P_RZ0 : P_RR0>
-__global__ void __launch_bounds__(kThreads)
-    cg_update_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q,
-                     long long n, double *__restrict__ part, const int *__restrict__ ic, int it,
-                     const V *__restrict__ dinv = nullptr) {
-  if (ic[I_DONE]) return;
-  const double pq = slot_sum(part, P_PQ), rr_old = slot_sum(part, ALPHA + (it & 1));
-  const double alpha = pq != 0.0 ? rr_old / pq : 0.0;
-  constexpr int W = Vec16<V>::W;
-  typedef typename Vec16<V>::type VT;
-  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  double s = 0.0, sz = 0.0;
-  for (long long i = t0; i < nv; i += stride) {
-    VT uv = reinterpret_cast<VT *>(u)[i], rv = reinterpret_cast<VT *>(r)[i];
-    const VT pv = reinterpret_cast<const VT *>(p)[i], qv = reinterpret_cast<const VT *>(q)[i];
-    VT dv;
-    if (PRE) dv = reinterpret_cast<const VT *>(dinv)[i];
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      uv[k] = (V)((double)uv[k] + alpha * (double)pv[k]);
-      const double ri = (double)rv[k] - alpha * (double)qv[k];
-      rv[k] = (V)ri;
-      s += ri * ri;
-      if (PRE) sz += (double)rv[k] * ((double)rv[k] * (double)dv[k]);
-    }
-    reinterpret_cast<VT *>(u)[i] = uv;
-    reinterpret_cast<VT *>(r)[i] = rv;
-  }
-  for (long long i = nv * W + t0; i < n; i += stride) {
-    u[i] = (V)((double)u[i] + alpha * (double)p[i]);
-    const double ri = (double)r[i] - alpha * (double)q[i];
-    const V rn = (V)ri;
-    r[i] = rn;
-    s += ri * ri;
-    if (PRE) sz += (double)rn * ((double)rn * (double)dinv[i]);
-  }
-  s = block_sum(s);
-  if (PRE) sz = block_sum(sz);
-  if (threadIdx.x == 0) {
-    part[(P_RR0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = s;
-    if (PRE) part[(P_RZ0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = sz;
-  }
-}
-
-// beta = rr' / rr;  p = r + beta p;  one thread: iteration count, convergence flag (rr' <= stop)
-// PRE: beta = rz' / rz;  p = dinv r + beta p;  the flag still from rr' (only workgroup 0 adds it up)
-template <typename V, bool PRE = false>
-__global__ void __launch_bounds__(kThreads)
-    cg_direction_kernel(V *__restrict__ p, const V *__restrict__ r, long long n, const double *__restrict__ part,
-                        int *__restrict__ ic, int it, double stop, const V *__restrict__ dinv = nullptr) {
-  if (ic[I_DONE]) return;
-  const int s0 = PRE ? P_RZ0 : P_RR0;
-  const double rr = slot_sum(part, s0 + (it & 1)), rrn = slot_sum(part, s0 + ((it + 1) & 1));
-  const double beta = rr != 0.0 ? rrn / rr : 0.0;
-  double res = rrn; // what the stopping rule looks at: r . r
-  if (PRE && blockIdx.x == 0) res = slot_sum(part, P_RR0 + ((it + 1) & 1));
-  constexpr int W = Vec16<V>::W;
-  typedef typename Vec16<V>::type VT;
-  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  for (long long i = t0; i < nv; i += stride) {
-    VT pv = reinterpret_cast<VT *>(p)[i];
-    const VT rv = reinterpret_cast<const VT *>(r)[i];
-    VT dv;
-    if (PRE) dv = reinterpret_cast<const VT *>(dinv)[i];
-#pragma unroll
-    for (int k = 0; k < W; ++k)
-      pv[k] = (V)((PRE ? (double)rv[k] * (double)dv[k] : (double)rv[k]) + beta * (double)pv[k]);
-    reinterpret_cast<VT *>(p)[i] = pv;
-  }
-  for (long long i = nv * W + t0; i < n; i += stride)
-    p[i] = (V)((PRE ? (double)r[i] * (double)dinv[i] : (double)r[i]) + beta * (double)p[i]);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    ic[I_ITER] += 1; // (counted on the device: a replayed graph passes the same `it` again, only its parity matters)
-    // (!(x > y): a NaN residual also ends the iteration)
-    if (!(res > stop)) ic[I_DONE] = 1;
-  }
 }
 
 // ---- block Jacobi --------------------------------------------------------------------------------
@@ -393,126 +243,25 @@ __device__ __forceinline__ void block_apply(const V *__restrict__ minv, long lon
   block_mul<BS>(m, r, z);
 }
 
-// cg_residual_kernel<V, true> with M = blockdiag(A):  r = b - q;  p = z = Minv r;  part <- r . r, b . b, r . z
-template <typename V, int BS>
-__global__ void __launch_bounds__(kThreads)
-    cg_residual_block_kernel(V *__restrict__ r, V *__restrict__ p, const V *__restrict__ b, const V *__restrict__ q,
-                             long long n, double *__restrict__ part, const V *__restrict__ minv, long long nb) {
-  double rr = 0.0, bb = 0.0, rz = 0.0;
-  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
-    double rd[BS], z[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      const long long g = k * BS + i;
-      rd[i] = 0.0;
-      if (g < n) {
-        const V bi = b[g], ri = bi - q[g];
-        r[g] = ri;
-        rd[i] = (double)ri;
-        rr += (double)ri * (double)ri;
-        bb += (double)bi * (double)bi;
-      }
-    }
-    block_apply<V, BS>(minv, nb, k, rd, z);
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      const long long g = k * BS + i;
-      if (g < n) {
-        rz += rd[i] * z[i];
-        p[g] = (V)z[i];
-      }
-    }
-  }
-  rr = block_sum(rr);
-  bb = block_sum(bb);
-  rz = block_sum(rz);
-  if (threadIdx.x == 0) {
-    part[P_RR0 * kGrid + blockIdx.x] = rr;
-    part[P_BB * kGrid + blockIdx.x] = bb;
-    part[P_RZ0 * kGrid + blockIdx.x] = rz;
-  }
-}
-
-// cg_update_kernel<V, true> with M = blockdiag(A): z = Minv r of the ROUNDED r
-template <typename V, int BS>
-__global__ void __launch_bounds__(kThreads)
-    cg_update_block_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q,
-                           long long n, double *__restrict__ part, const int *__restrict__ ic, int it,
-                           const V *__restrict__ minv, long long nb) {
-  if (ic[I_DONE]) return;
-  const double pq = slot_sum(part, P_PQ), rz_old = slot_sum(part, P_RZ0 + (it & 1));
-  const double alpha = pq != 0.0 ? rz_old / pq : 0.0;
-  double s = 0.0, sz = 0.0;
-  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
-    double rd[BS], z[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      const long long g = k * BS + i;
-      rd[i] = 0.0;
-      if (g < n) {
-        u[g] = (V)((double)u[g] + alpha * (double)p[g]);
-        const double ri = (double)r[g] - alpha * (double)q[g];
-        const V rn = (V)ri;
-        r[g] = rn;
-        s += ri * ri;
-        rd[i] = (double)rn;
-      }
-    }
-    block_apply<V, BS>(minv, nb, k, rd, z);
-#pragma unroll
-    for (int i = 0; i < BS; ++i) sz += rd[i] * z[i]; // (rd = 0 outside the matrix)
-  }
-  s = block_sum(s);
-  sz = block_sum(sz);
-  if (threadIdx.x == 0) {
-    part[(P_RR0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = s;
-    part[(P_RZ0 + ((it + 1) & 1)) * kGrid + blockIdx.x] = sz;
-  }
-}
-
-// cg_direction_kernel<V, true> with M = blockdiag(A):  p = Minv r + beta p
-template <typename V, int BS>
-__global__ void __launch_bounds__(kThreads)
-    cg_direction_block_kernel(V *__restrict__ p, const V *__restrict__ r, long long n, const double *__restrict__ part,
-                              int *__restrict__ ic, int it, double stop, const V *__restrict__ minv, long long nb) {
-  if (ic[I_DONE]) return;
-  const double rz = slot_sum(part, P_RZ0 + (it & 1)), rzn = slot_sum(part, P_RZ0 + ((it + 1) & 1));
-  const double beta = rz != 0.0 ? rzn / rz : 0.0;
-  double res = rzn;
-  if (blockIdx.x == 0) res = slot_sum(part, P_RR0 + ((it + 1) & 1)); // what the stopping rule looks at: r . r
-  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
-    double rd[BS], z[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      const long long g = k * BS + i;
-      rd[i] = g < n ? (double)r[g] : 0.0;
-    }
-    block_apply<V, BS>(minv, nb, k, rd, z);
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      const long long g = k * BS + i;
-      if (g < n) p[g] = (V)(z[i] + beta * (double)p[g]);
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    ic[I_ITER] += 1;
-    if (!(res > stop)) ic[I_DONE] = 1;
-  }
-}
-
-// ---- the recurrence on a block of columns (cfs_hip_sym_pcg_cols, cfs_hip_sym_pcg_amg_cols) --------
-// The four kernels above for the columns of a ColumnMask, launched ONCE for the block.  Column c of every vector at
-// base + c ld; its scalars in slots of its own, part[c][slot][kGrid], its counters at ic[c][I_ITER], ic[c][I_DONE], its
-// stop in stop.v[c].  BS = 0: no stored M^-1 (PRE = false), 1: dinv (PRE = true), 2, 3, 4, 6: the packed inverse blocks.
-// Per column the arithmetic is that of the one-column kernel: the same grid and grid-stride walk, the same casts and
-// parentheses, the same order of sums -- block_sum_cols and slot_sums add what block_sum and slot_sum add, in their
-// order, for the columns of a chunk at once, so a chunk costs the barriers of one column.  The columns are taken in
-// chunks of CW (chunks<CW>): the accumulators and the scalars are per column of a chunk, and dinv or the inverse block
-// is read once per chunk.  A kernel that the one-column solver guards with ic[I_DONE] skips every column whose flag is
-// up (live_columns): nothing of such a column is read or written, not its vectors, its slots or its counters, so a
-// column stops at the iteration at which its one-column solve stops while the host's mask may be a window old.  A
-// column whose bit is clear in the mask is neither read nor written.
+// ---- the recurrence: four kernels, each written once over the columns of a set CS ------------------
+// OneColumn: the one-column solvers (cg, cg_cheb, cg_mixed, Amg::pcg).  ColumnMask: the solvers on a block of
+// right-hand sides (cg_cols, Amg::pcg_cols), ONE launch for the block.  Column c of every vector at base + c ld; its
+// scalars in slots of its own, part[c][slot][kGrid], its counters at ic[c][I_ITER], ic[c][I_DONE], its stop in
+// stop.v[c] -- for one column that is part[slot][kGrid], ic[I_ITER], ic[I_DONE] and stop.v[0], and c ld folds away.
+// BS = 0: no stored M^-1, 1: dinv (PRE below), 2, 3, 4, 6: the packed inverse blocks.  BS <= 1 walks 16-byte vectors
+// and single values over the rest, BS >= 2 one node block per thread; both grid-stride.  Per column the arithmetic does
+// not depend on CS: the same walk, casts, parentheses and order of sums from the same text -- block_sum_cols and
+// slot_sums add in the order of block_sum and slot_sum, for the columns of a chunk at once, so a chunk costs the
+// barriers of one column.  The columns are taken in chunks of CW (chunks<CW>; one column is one chunk of one, no loop
+// and no mask test): the accumulators and the scalars are per column of a chunk, and dinv or the inverse block is
+// read once per chunk.  The dot, update and direction kernels do nothing behind a raised ic[I_DONE]: one column
+// returns at once; of a block every column whose flag is up is skipped (live_columns) -- nothing of it is read or
+// written, not its vectors, its slots or its counters, so a column stops at the iteration at which its one-column
+// solve stops while the host's mask may be a window old.  A column whose bit is clear in the mask is neither read nor
+// written.
 constexpr int kColSlots = P_COUNT * kGrid; // doubles between the slots of two columns
+// the first of the two slots the numerator of alpha and beta alternates between: r . z with a stored M^-1, else r . r
+constexpr int num_slot(int bs) { return bs >= 1 ? P_RZ0 : P_RR0; }
 struct ColumnStops {
   double v[16];
 };
@@ -522,6 +271,10 @@ constexpr int cols_chunk(int bs, bool four = false) { return bs >= 6 || (four &&
 
 // block_sum for N values at once, each summed in block_sum's order
 template <int N> __device__ __forceinline__ void block_sum_cols(double (&v)[N]) {
+  if constexpr (N == 1) { // (one column: block_sum itself -- the same sum; cg_update_kernel keeps its registers with it)
+    v[0] = block_sum(v[0]);
+    return;
+  }
   __shared__ double part[N][kThreads / 64];
   __shared__ double total[N];
 #pragma unroll
@@ -569,23 +322,29 @@ __device__ __forceinline__ ColumnMask live_columns(const int *ic, ColumnMask cs)
   __syncthreads();
   return ColumnMask{cs.ncols, live};
 }
+// (one column: the kernel has returned if its flag is up)
+__device__ __forceinline__ OneColumn live_columns(const int *, OneColumn cs) { return cs; }
 
-// cg_residual_kernel<V, BS == 1> / cg_residual_block_kernel<V, BS> on the columns of cs (r, p may be null for BS = 0)
-template <typename V, int BS>
+// r = b - q;  p = r (when given);  part[slot_rr] <- r . r;  part[P_BB] <- b . b (when with_bb)
+// BS >= 1: p = z = M^-1 r instead, and part[P_RZ0] <- r . z.  r, p may be null for BS = 0
+// (BS >= 2, here and in the direction kernel: one column reads the inverse block BEHIND its vector loads, by block_apply,
+// so that the block's words are consumed row by row as they arrive, between the loads and stores of p; a block of columns
+// reads it once, ahead of its column loop)
+template <typename V, int BS, class CS>
 __global__ void __launch_bounds__(kThreads)
-    cg_residual_cols_kernel(V *__restrict__ r, V *__restrict__ p, const V *__restrict__ b, const V *__restrict__ q, long long ld,
-                            long long n, double *__restrict__ part, int slot_rr, int with_bb, const V *__restrict__ minv, long long nb,
-                            ColumnMask cs) {
-  constexpr int CW = cols_chunk(BS, true);
+    cg_residual_kernel(V *__restrict__ r, V *__restrict__ p, const V *__restrict__ b, const V *__restrict__ q, long long ld,
+                       long long n, double *__restrict__ part, int slot_rr, int with_bb, const V *__restrict__ minv, long long nb,
+                       CS cs) {
+  constexpr int CW = CS::chunk(cols_chunk(BS, true));
   constexpr bool PRE = BS == 1;
-  cs.chunks<CW>([&](int c0, unsigned bits) {
+  cs.template chunks<CW>([&](int c0, unsigned bits) {
     double rr[CW], bb[CW], rz[CW];
 #pragma unroll
     for (int e = 0; e < CW; ++e) rr[e] = bb[e] = rz[e] = 0.0;
     if constexpr (BS >= 2) {
       for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
         double m[BS][BS];
-        block_load<V, BS>(minv, nb, k, m);
+        if constexpr (!CS::one) block_load<V, BS>(minv, nb, k, m);
 #pragma unroll
         for (int e = 0; e < CW; ++e) {
           if (!((bits >> e) & 1u)) continue;
@@ -603,7 +362,8 @@ __global__ void __launch_bounds__(kThreads)
               bb[e] += (double)bi * (double)bi;
             }
           }
-          block_mul<BS>(m, rd, z);
+          if constexpr (CS::one) block_apply<V, BS>(minv, nb, k, rd, z);
+          else block_mul<BS>(m, rd, z);
 #pragma unroll
           for (int i = 0; i < BS; ++i) {
             const long long g = k * BS + i;
@@ -677,13 +437,15 @@ __global__ void __launch_bounds__(kThreads)
   });
 }
 
-// cg_dot_kernel on the columns of cs that are not done
-template <typename V>
+// part[slot] <- a . b of the stored values (p . q into P_PQ; r . z where z is stored: cfs_solver_amg.hpp)
+template <typename V, class CS>
 __global__ void __launch_bounds__(kThreads)
-    cg_dot_cols_kernel(const V *__restrict__ a, const V *__restrict__ b, long long ld, long long n, double *__restrict__ part, int slot,
-                       const int *__restrict__ ic, ColumnMask cs) {
-  constexpr int CW = cols_chunk(0);
-  live_columns(ic, cs).chunks<CW>([&](int c0, unsigned bits) {
+    cg_dot_kernel(const V *__restrict__ a, const V *__restrict__ b, long long ld, long long n, double *__restrict__ part, int slot,
+                  const int *__restrict__ ic, CS cs) {
+  constexpr int CW = CS::chunk(cols_chunk(0));
+  if constexpr (CS::one)
+    if (ic[I_DONE]) return;
+  live_columns(ic, cs).template chunks<CW>([&](int c0, unsigned bits) {
     constexpr int W = Vec16<V>::W;
     typedef typename Vec16<V>::type VT;
     const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
@@ -714,16 +476,25 @@ __global__ void __launch_bounds__(kThreads)
   });
 }
 
-// cg_update_kernel<V, BS == 1, ALPHA> / cg_update_block_kernel<V, BS> on the columns of cs that are not done
-// (BS = 0 with ALPHA = P_RZ0: z is stored elsewhere, cfs_solver_amg.hpp)
-template <typename V, int BS, int ALPHA = BS >= 1 ? P_RZ0 : P_RR0>
+// alpha = rr / pq;  u += alpha p;  r -= alpha q;  part[rr of the next iteration] <- r . r
+// BS >= 1: alpha = rz / pq, and part[rz of the next iteration] <- r . z with z = M^-1 r of the ROUNDED r
+// ALPHA: the first of the two slots alpha's numerator alternates between (BS = 0 with P_RZ0: z is stored elsewhere and
+// r . z comes from cg_dot_kernel, cfs_solver_amg.hpp).  Registers: a block reads M^-1 ahead of its columns, one column
+// behind its vectors (block_apply) -- read ahead, it holds dinv or the inverse block across the loads; and the body is
+// inlined before it is optimised (always_inline), or the 21 words of a 6 x 6 fp64 block are all loaded before the first
+// product: 76 VGPRs and 6 waves per SIMD where these lines keep the 62 and 8 of a kernel without a lambda.  They steer
+// THIS compiler's scheduler and nothing committed guards them: after a compiler change, re-check the one-column side of
+// the resource table in DESIGN.md ("PCG on a block of right-hand sides")
+template <typename V, int BS, int ALPHA, class CS>
 __global__ void __launch_bounds__(kThreads)
-    cg_update_cols_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q, long long ld,
-                          long long n, double *__restrict__ part, const int *__restrict__ ic, int it, const V *__restrict__ minv,
-                          long long nb, ColumnMask cs) {
-  constexpr int CW = cols_chunk(BS, true);
+    cg_update_kernel(V *__restrict__ u, V *__restrict__ r, const V *__restrict__ p, const V *__restrict__ q, long long ld,
+                     long long n, double *__restrict__ part, const int *__restrict__ ic, int it, const V *__restrict__ minv,
+                     long long nb, CS cs) {
+  constexpr int CW = CS::chunk(cols_chunk(BS, true));
   constexpr bool PRE = BS == 1;
-  live_columns(ic, cs).chunks<CW>([&](int c0, unsigned bits) {
+  if constexpr (CS::one)
+    if (ic[I_DONE]) return;
+  live_columns(ic, cs).template chunks<CW>([&](int c0, unsigned bits) __attribute__((always_inline)) {
     double alpha[CW], s[CW], sz[CW];
     {
       double pq[CW], rr_old[CW];
@@ -738,7 +509,7 @@ __global__ void __launch_bounds__(kThreads)
     if constexpr (BS >= 2) {
       for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
         double m[BS][BS];
-        block_load<V, BS>(minv, nb, k, m);
+        if constexpr (!CS::one) block_load<V, BS>(minv, nb, k, m);
 #pragma unroll
         for (int e = 0; e < CW; ++e) {
           if (!((bits >> e) & 1u)) continue;
@@ -757,7 +528,8 @@ __global__ void __launch_bounds__(kThreads)
               rd[i] = (double)rn;
             }
           }
-          block_mul<BS>(m, rd, z);
+          if constexpr (CS::one) block_apply<V, BS>(minv, nb, k, rd, z);
+          else block_mul<BS>(m, rd, z);
 #pragma unroll
           for (int i = 0; i < BS; ++i) sz[e] += rd[i] * z[i]; // (rd = 0 outside the matrix)
         }
@@ -768,13 +540,14 @@ __global__ void __launch_bounds__(kThreads)
       const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
       for (long long i = t0; i < nv; i += stride) {
         VT dv;
-        if (PRE) dv = reinterpret_cast<const VT *>(minv)[i];
+        if (PRE && !CS::one) dv = reinterpret_cast<const VT *>(minv)[i];
 #pragma unroll
         for (int e = 0; e < CW; ++e) {
           if (!((bits >> e) & 1u)) continue;
           const long long off = (long long)(c0 + e) * ld;
           VT uv = reinterpret_cast<VT *>(u + off)[i], rv = reinterpret_cast<VT *>(r + off)[i];
           const VT pv = reinterpret_cast<const VT *>(p + off)[i], qv = reinterpret_cast<const VT *>(q + off)[i];
+          if (PRE && CS::one) dv = reinterpret_cast<const VT *>(minv)[i];
 #pragma unroll
           for (int k = 0; k < W; ++k) {
             uv[k] = (V)((double)uv[k] + alpha[e] * (double)pv[k]);
@@ -816,10 +589,10 @@ __global__ void __launch_bounds__(kThreads)
 }
 
 // r d + beta p (PRE) or r + beta p of cg_direction_kernel.  With PRE the sum of two products can be contracted two
-// ways, and which one the compiler takes depends on the code around it: cg_direction_kernel<V, true> is compiled to
-// fma(r, d, beta p) in both value types, in its vector loop and in its tail, while the same expression inside the
-// column loop became fma(beta, p, r d), whose iterates differ in the last bit.  So the form of the one-column kernel
-// is spelled out here; test C1 of tests/test_gpu_pcg_cols.py fails if the two ever part again.
+// ways, and which one the compiler takes depends on the code around it: written as r * d + beta * p, the one-column
+// form was compiled to fma(r, d, beta p) in both value types, in its vector loop and in its tail, while the same
+// expression inside a column loop became fma(beta, p, r d), whose iterates differ in the last bit.  So the contraction
+// is spelled out here, for both instantiations; test C1 of tests/test_gpu_pcg_cols.py fails if the two ever part.
 template <bool PRE> __device__ __forceinline__ double direction_sum(double r, double d, double beta, double p) {
   if constexpr (PRE) {
     const double bp = beta * p;
@@ -829,15 +602,19 @@ template <bool PRE> __device__ __forceinline__ double direction_sum(double r, do
   }
 }
 
-// cg_direction_kernel<V, BS == 1> / cg_direction_block_kernel<V, BS> on the columns of cs that are not done; one
-// thread: the iteration count and the flag of each of them.  BS = 0 with S0 = P_RZ0 and z for r: cheb_direction_kernel
-template <typename V, int BS, int S0 = BS >= 1 ? P_RZ0 : P_RR0>
+// beta = rr' / rr;  p = r + beta p;  one thread: iteration count, convergence flag (rr' <= stop), per column
+// BS >= 1: beta = rz' / rz;  p = M^-1 r + beta p;  the flag still from rr', the unpreconditioned residual
+// S0: the first of the two slots beta alternates between (BS = 0 with P_RZ0 and the stored z for r: p = z + beta p,
+// cfs_solver_cheb.hpp, cfs_solver_amg.hpp)
+template <typename V, int BS, int S0, class CS>
 __global__ void __launch_bounds__(kThreads)
-    cg_direction_cols_kernel(V *__restrict__ p, const V *__restrict__ r, long long ld, long long n, const double *__restrict__ part,
-                             int *__restrict__ ic, int it, ColumnStops stop, const V *__restrict__ minv, long long nb, ColumnMask cs) {
-  constexpr int CW = cols_chunk(BS);
+    cg_direction_kernel(V *__restrict__ p, const V *__restrict__ r, long long ld, long long n, const double *__restrict__ part,
+                        int *__restrict__ ic, int it, ColumnStops stop, const V *__restrict__ minv, long long nb, CS cs) {
+  constexpr int CW = CS::chunk(cols_chunk(BS));
   constexpr bool PRE = BS == 1;
-  live_columns(ic, cs).chunks<CW>([&](int c0, unsigned bits) {
+  if constexpr (CS::one)
+    if (ic[I_DONE]) return;
+  live_columns(ic, cs).template chunks<CW>([&](int c0, unsigned bits) {
     double beta[CW], res[CW];
     {
       double rr[CW];
@@ -851,7 +628,7 @@ __global__ void __launch_bounds__(kThreads)
     if constexpr (BS >= 2) {
       for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
         double m[BS][BS];
-        block_load<V, BS>(minv, nb, k, m);
+        if constexpr (!CS::one) block_load<V, BS>(minv, nb, k, m);
 #pragma unroll
         for (int e = 0; e < CW; ++e) {
           if (!((bits >> e) & 1u)) continue;
@@ -862,7 +639,8 @@ __global__ void __launch_bounds__(kThreads)
             const long long g = k * BS + i;
             rd[i] = g < n ? (double)r[off + g] : 0.0;
           }
-          block_mul<BS>(m, rd, z);
+          if constexpr (CS::one) block_apply<V, BS>(minv, nb, k, rd, z);
+          else block_mul<BS>(m, rd, z);
 #pragma unroll
           for (int i = 0; i < BS; ++i) {
             const long long g = k * BS + i;
@@ -904,7 +682,7 @@ __global__ void __launch_bounds__(kThreads)
       for (int e = 0; e < CW; ++e)
         if ((bits >> e) & 1u) {
           int *icc = ic + (c0 + e) * I_COUNT;
-          icc[I_ITER] += 1;
+          icc[I_ITER] += 1; // (counted on the device: a replayed graph passes the same `it` again, only its parity matters)
           // (!(x > y): a NaN residual also ends the iteration)
           if (!(res[e] > stop.v[c0 + e])) icc[I_DONE] = 1;
         }
@@ -1060,8 +838,8 @@ template <typename V, class Handle> struct Pcg {
   // r = b - A u, rr[0] = r . r, bb = b . b by the residual kernel of the plain iteration (the same bits), and the look
   int first_residual() {
     if (int rc = product_u()) return rc;
-    hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, n,
-                       part.dev(), (int)P_RR0, 1, (const V *)nullptr);
+    hipLaunchKernelGGL((cg_residual_kernel<V, 0, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, n, n,
+                       part.dev(), (int)P_RR0, 1, (const V *)nullptr, 0LL, OneColumn{});
     return first_look();
   }
   bool live() const { return !done && it < maxiter; } // (maxiter = 0 behaves like done)
@@ -1077,8 +855,8 @@ template <typename V, class Handle> struct Pcg {
   int finish(int *iterations, double *relres) {
     int rc;
     if ((rc = product_u())) return rc;
-    hipLaunchKernelGGL((cg_residual_kernel<V, false>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b,
-                       (const V *)q, n, part.dev(), (int)P_RES, 0, (const V *)nullptr);
+    hipLaunchKernelGGL((cg_residual_kernel<V, 0, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b,
+                       (const V *)q, n, n, part.dev(), (int)P_RES, 0, (const V *)nullptr, 0LL, OneColumn{});
     HIPCHK(hipGetLastError());
     if ((rc = part.fetch())) return rc;
     const double res2 = part.sum(P_RES);
@@ -1094,7 +872,6 @@ template <typename V, class Handle> struct Pcg {
 template <typename V, int BS = 0, class Handle>
 int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int check_every, int *iterations,
        double *relres, hipStream_t st) {
-  constexpr bool PRE = BS == 1, BLK = BS >= 2;
   check_every = look_window(check_every);
   const char *eg = getenv("CFS_HIP_CG_GRAPH");
   const bool use_graph = eg && atoi(eg) != 0;
@@ -1106,33 +883,23 @@ int cg(Handle *h, void *u_dev, const void *b_dev, double tol, int maxiter, int c
   const long long n = s.n, nb = pre.nb;
   double *part = s.part.dev();
   int *ic = s.ic;
-  const V *dinv = pre.minv();
-  // r = b - A u, p = r, rr[0] = r . r, bb = b . b  (PRE: p = dinv r, rz[0] = r . p), in one pass
+  const V *minv = pre.minv();
+  constexpr OneColumn one{};
+  // r = b - A u, p = r, rr[0] = r . r, bb = b . b  (BS >= 1: p = M^-1 r, rz[0] = r . p), in one pass
   if ((rc = s.product_u())) return rc;
-  if constexpr (BLK)
-    hipLaunchKernelGGL((cg_residual_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, p, s.b, (const V *)q, n, part,
-                       dinv, nb);
-  else
-    hipLaunchKernelGGL((cg_residual_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, r, p, s.b, (const V *)q, n, part,
-                       (int)P_RR0, 1, dinv);
+  hipLaunchKernelGGL((cg_residual_kernel<V, BS, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, r, p, s.b, (const V *)q, n, n, part,
+                     (int)P_RR0, 1, minv, nb, one);
   if ((rc = s.first_look()) || (rc = pre.check("pcg", s.part, n))) return rc; // (u has not been touched yet)
-  const double stop = s.stop;
+  const ColumnStops stop{{s.stop}};
   auto iteration = [&](int k) -> int {
     int r2 = h->spmv_local(q, p, nullptr, st);
     if (r2) return r2;
-    hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part, (int)P_PQ,
-                       (const int *)ic);
-    if constexpr (BLK) {
-      hipLaunchKernelGGL((cg_update_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q,
-                         n, part, (const int *)ic, k, dinv, nb);
-      hipLaunchKernelGGL((cg_direction_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
-                         (const double *)part, ic, k, stop, dinv, nb);
-    } else {
-      hipLaunchKernelGGL((cg_update_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n,
-                         part, (const int *)ic, k, dinv);
-      hipLaunchKernelGGL((cg_direction_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
-                         (const double *)part, ic, k, stop, dinv);
-    }
+    hipLaunchKernelGGL((cg_dot_kernel<V, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, n, part,
+                       (int)P_PQ, (const int *)ic, one);
+    hipLaunchKernelGGL((cg_update_kernel<V, BS, num_slot(BS), OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p,
+                       (const V *)q, n, n, part, (const int *)ic, k, minv, nb, one);
+    hipLaunchKernelGGL((cg_direction_kernel<V, BS, num_slot(BS), OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
+                       n, (const double *)part, ic, k, stop, minv, nb, one);
     return 0;
   };
   // CFS_HIP_CG_GRAPH=1: two iterations (both parities) captured once and replayed as one graph launch.
@@ -1264,7 +1031,7 @@ template <typename V, class Handle> struct PcgCols {
   // R = B - A U, rr[0], bb per column by the residual kernel of the plain iteration, and the look
   int first_residual() {
     if (int rc = product_u(all())) return rc;
-    hipLaunchKernelGGL((cg_residual_cols_kernel<V, 0>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, ld, n,
+    hipLaunchKernelGGL((cg_residual_kernel<V, 0, ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, r, (V *)nullptr, b, (const V *)q, ld, n,
                        part.dev(), (int)P_RR0, 1, (const V *)nullptr, 0LL, mask(all()));
     return first_look();
   }
@@ -1282,7 +1049,7 @@ template <typename V, class Handle> struct PcgCols {
   int finish(int *iterations, double *relres) {
     int rc;
     if ((rc = product_u(all()))) return rc;
-    hipLaunchKernelGGL((cg_residual_cols_kernel<V, 0>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b, (const V *)q,
+    hipLaunchKernelGGL((cg_residual_kernel<V, 0, ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, (V *)nullptr, (V *)nullptr, b, (const V *)q,
                        ld, n, part.dev(), (int)P_RES, 0, (const V *)nullptr, 0LL, mask(all()));
     HIPCHK(hipGetLastError());
     if ((rc = part.fetch())) return rc;
@@ -1313,7 +1080,7 @@ int cg_cols(Handle *h, void *u_dev, const void *b_dev, long long ld, int ncols, 
   int *ic = s.ic;
   const V *minv = pre.minv();
   if ((rc = s.product_u(s.all()))) return rc;
-  hipLaunchKernelGGL((cg_residual_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, r, p, s.b, (const V *)q, ld, n, part,
+  hipLaunchKernelGGL((cg_residual_kernel<V, BS, ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, r, p, s.b, (const V *)q, ld, n, part,
                      (int)P_RR0, 1, minv, nb, s.mask(s.all()));
   if ((rc = s.first_look()) || (rc = pre.check("pcg_cols", s.part, n))) return rc; // (U has not been touched yet)
   while (s.live()) {
@@ -1321,11 +1088,11 @@ int cg_cols(Handle *h, void *u_dev, const void *b_dev, long long ld, int ncols, 
     const ColumnMask cs = s.mask(s.active);
     for (; s.it < until; ++s.it) {
       if ((rc = s.products(q, p, s.active))) return rc;
-      hipLaunchKernelGGL((cg_dot_cols_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, ld, n, part, (int)P_PQ,
+      hipLaunchKernelGGL((cg_dot_kernel<V, ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, ld, n, part, (int)P_PQ,
                          (const int *)ic, cs);
-      hipLaunchKernelGGL((cg_update_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, ld, n, part,
+      hipLaunchKernelGGL((cg_update_kernel<V, BS, num_slot(BS), ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, ld, n, part,
                          (const int *)ic, s.it, minv, nb, cs);
-      hipLaunchKernelGGL((cg_direction_cols_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, ld, n,
+      hipLaunchKernelGGL((cg_direction_kernel<V, BS, num_slot(BS), ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, ld, n,
                          (const double *)part, ic, s.it, s.stop, minv, nb, cs);
     }
     if ((rc = s.look())) return rc;

@@ -39,10 +39,12 @@
 // The outer PCG (cg_amg) is cg_cheb with the chain replaced by the cycle:
 //   tile kernel + fold   q = A p
 //   cg_dot_kernel        pq = p . q
-//   cg_update_kernel<V, false, P_RZ0>   u += (rz/pq) p;  r -= (rz/pq) q;  rr' = r . r
+//   cg_update_kernel<V, 0, P_RZ0>      u += (rz/pq) p;  r -= (rz/pq) q;  rr' = r . r
 //   the cycle            z = M^-1 r
 //   cg_dot_kernel        rz' = r . z of the stored r and the stored final z
-//   cheb_direction_kernel  p = z + (rz'/rz) p;  iteration count;  converged?  (rr' <= tol^2 b.b)
+//   cg_direction_kernel<V, 0, P_RZ0>   p = z + (rz'/rz) p, z in the place of r;  iteration count;  converged?
+//                                      (rr' <= tol^2 b.b)
+// (the kernels of cfs_solver.hpp in their OneColumn instantiations; pcg_cols launches the ColumnMask ones)
 // 6 launches and the cycle; a cycle exceeds what may be enqueued between two host looks, so the host looks at the
 // convergence flag after every iteration.
 //
@@ -1589,7 +1591,8 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
     // z = M^-1 r;  part[slot] <- r . z of the stored r and the stored final z
     auto cycle_and_dot = [&](int slot) -> int {
       if (int r2 = cycle(0, OneColumn{}, z, n, (const V *)r, n, (const int *)ic, st)) return r2;
-      hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, n, pp, slot, (const int *)ic);
+      hipLaunchKernelGGL((cg_dot_kernel<V, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, n, n, pp, slot,
+                         (const int *)ic, OneColumn{});
       return 0;
     };
     if (s.live()) { // z = M^-1 r, rz[0] = r . z, p = z
@@ -1599,12 +1602,13 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
     while (s.live()) { // (a window of one: a cycle is more than may be enqueued ahead of the GPU)
       const int it = s.it;
       if ((rc = fine->spmv_local(q, p, nullptr, st))) return rc;
-      hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, pp, (int)P_PQ, (const int *)ic);
-      hipLaunchKernelGGL((cg_update_kernel<V, false, P_RZ0>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n, pp,
-                         (const int *)ic, it, (const V *)nullptr);
+      hipLaunchKernelGGL((cg_dot_kernel<V, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, n, pp, (int)P_PQ,
+                         (const int *)ic, OneColumn{});
+      hipLaunchKernelGGL((cg_update_kernel<V, 0, P_RZ0, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, n,
+                         n, pp, (const int *)ic, it, (const V *)nullptr, 0LL, OneColumn{});
       if ((rc = cycle_and_dot((int)P_RZ0 + ((it + 1) & 1)))) return rc;
-      hipLaunchKernelGGL((cheb_direction_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, n, (const double *)pp, ic, it,
-                         s.stop);
+      hipLaunchKernelGGL((cg_direction_kernel<V, 0, P_RZ0, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, n, n,
+                         (const double *)pp, ic, it, ColumnStops{{s.stop}}, (const V *)nullptr, 0LL, OneColumn{});
       ++s.it;
       if ((rc = s.look())) return rc;
     }
@@ -1635,7 +1639,7 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
       const ColumnMask cs = s.mask(s.active);
       if (int r2 = cycle(0, cs, z, ld, (const V *)r, ld, (const int *)cnt.p, st)) return r2;
       col_cycles += __builtin_popcount(s.active);
-      hipLaunchKernelGGL((cg_dot_cols_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, ld, n, pp, slot,
+      hipLaunchKernelGGL((cg_dot_kernel<V, ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)r, (const V *)z, ld, n, pp, slot,
                          (const int *)ic, cs);
       return 0;
     };
@@ -1652,12 +1656,12 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
       const int it = s.it;
       const ColumnMask cs = s.mask(s.active);
       if ((rc = s.products(q, p, s.active))) return rc;
-      hipLaunchKernelGGL((cg_dot_cols_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, ld, n, pp, (int)P_PQ,
+      hipLaunchKernelGGL((cg_dot_kernel<V, ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, ld, n, pp, (int)P_PQ,
                          (const int *)ic, cs);
-      hipLaunchKernelGGL((cg_update_cols_kernel<V, 0, P_RZ0>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, ld, n,
+      hipLaunchKernelGGL((cg_update_kernel<V, 0, P_RZ0, ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, ld, n,
                          pp, (const int *)ic, it, (const V *)nullptr, 0LL, cs);
       if ((rc = cycle_and_dot((int)P_RZ0 + ((it + 1) & 1)))) return rc;
-      hipLaunchKernelGGL((cg_direction_cols_kernel<V, 0, P_RZ0>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, ld, n,
+      hipLaunchKernelGGL((cg_direction_kernel<V, 0, P_RZ0, ColumnMask>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, ld, n,
                          (const double *)pp, ic, it, s.stop, (const V *)nullptr, 0LL, cs);
       ++s.it;
       if ((rc = s.look())) return rc;

@@ -20,13 +20,15 @@
 // The pairs (rho_j rho_{j-1}, 2 rho_j / delta) are computed on the host in fp64 (cheb_coeffs) and passed as
 // kernel arguments: an inner step has no dot product and reads no device scalar.  An outer iteration:
 //   tile kernel + fold            q = A p
-//   cg_dot_kernel                 pq = p . q                                      (cfs_solver.hpp, unchanged)
+//   cg_dot_kernel                 pq = p . q                                      (cfs_solver.hpp)
 //   cheb_update_kernel            u += (rz/pq) p;  r -= (rz/pq) q;  rr' = r . r;  z = d = (1/theta) M^-1 r
 //                                 (degree 1: also rz' = r . z)
 //   m - 1 times:  tile kernel + fold   t = A z        (t lives in the q buffer: q = A p has been consumed)
 //                 cheb_step_kernel     one pass over r, t, d, z and M^-1: d, z written; the last one: rz' = r . z
-//   cheb_direction_kernel         p = z + (rz'/rz) p;  iteration count;  converged?  (rr' <= tol^2 b.b: the
-//                                 unpreconditioned residual, the rule of cfs_hip_sym_pcg)
+//   cg_direction_kernel<V, 0, P_RZ0>  p = z + (rz'/rz) p: the direction kernel of cfs_solver.hpp with no stored M^-1,
+//                                 beta from the r . z slots and the stored z in the place of r;  iteration count;
+//                                 converged?  (rr' <= tol^2 b.b: the unpreconditioned residual, the rule of
+//                                 cfs_hip_sym_pcg)
 // 5 + 3 (m - 1) launches; an inner step moves 7 n words (r, t, d, z read, d, z written, M^-1 read) against
 // the 13 n of a CG iteration's vector kernels.  Memory held during a solve: r, p, q, z, d and the stored M^-1.
 //
@@ -141,7 +143,7 @@ __global__ void __launch_bounds__(kThreads)
     }
 }
 
-// cg_update_kernel<V, true> with z stored:  alpha = rz / pq;  u += alpha p;  r -= alpha q;  part[rr'] <- r . r;
+// cg_update_kernel<V, 1> with z stored:  alpha = rz / pq;  u += alpha p;  r -= alpha q;  part[rr'] <- r . r;
 // z = d = (V)((1 / theta) M^-1 r) of the ROUNDED r;  with_rz (degree 1): part[rz'] <- r . z
 template <typename V, int BS>
 __global__ void __launch_bounds__(kThreads)
@@ -297,35 +299,6 @@ __global__ void __launch_bounds__(kThreads)
       sz = block_sum(sz);
       if (threadIdx.x == 0) part[rz_slot * kGrid + blockIdx.x] = sz;
     }
-}
-
-// cg_direction_kernel<V, true> with z stored:  beta = rz' / rz;  p = z + beta p;  one thread: iteration count,
-// convergence flag from rr' (only workgroup 0 adds it up)
-template <typename V>
-__global__ void __launch_bounds__(kThreads)
-    cheb_direction_kernel(V *__restrict__ p, const V *__restrict__ z, long long n, const double *__restrict__ part,
-                          int *__restrict__ ic, int it, double stop) {
-  if (ic[I_DONE]) return;
-  const double rz = slot_sum(part, P_RZ0 + (it & 1)), rzn = slot_sum(part, P_RZ0 + ((it + 1) & 1));
-  const double beta = rz != 0.0 ? rzn / rz : 0.0;
-  double res = rzn;
-  if (blockIdx.x == 0) res = slot_sum(part, P_RR0 + ((it + 1) & 1)); // what the stopping rule looks at: r . r
-  constexpr int W = Vec16<V>::W;
-  typedef typename Vec16<V>::type VT;
-  const long long nv = n / W, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
-  for (long long i = t0; i < nv; i += stride) {
-    VT pv = reinterpret_cast<VT *>(p)[i];
-    const VT zv = reinterpret_cast<const VT *>(z)[i];
-#pragma unroll
-    for (int k = 0; k < W; ++k) pv[k] = (V)((double)zv[k] + beta * (double)pv[k]);
-    reinterpret_cast<VT *>(p)[i] = pv;
-  }
-  for (long long i = nv * W + t0; i < n; i += stride) p[i] = (V)((double)z[i] + beta * (double)p[i]);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    ic[I_ITER] += 1;
-    // (!(x > y): a NaN residual also ends the iteration)
-    if (!(res > stop)) ic[I_DONE] = 1;
-  }
 }
 
 // ---- the power method on M^-1 A ------------------------------------------------------------------
@@ -521,7 +494,8 @@ int cg_cheb(Handle *h, void *u_dev, const void *b_dev, int degree, double lmin, 
   if (bounds_used) bounds_used[0] = lmin, bounds_used[1] = lmax;
   double theta, c1[kChebMaxDegree], c2[kChebMaxDegree];
   cheb_coeffs(degree, lmin, lmax, &theta, c1, c2);
-  const double inv_theta = 1.0 / theta, stop = s.stop;
+  const double inv_theta = 1.0 / theta;
+  const ColumnStops stop{{s.stop}};
   if (s.live()) { // z = P_m r, rz[0] = r . z, p = z
     hipLaunchKernelGGL((cheb_start_kernel<V, BS, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, z, n, d, n, (const V *)r, n, n,
                        inv_theta, degree == 1 ? (int)P_RZ0 : -1, part, minv, nb, OneColumn{});
@@ -533,15 +507,15 @@ int cg_cheb(Handle *h, void *u_dev, const void *b_dev, int degree, double lmin, 
   auto iteration = [&](int k) -> int {
     int r2 = h->spmv_local(q, p, nullptr, st);
     if (r2) return r2;
-    hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part, (int)P_PQ,
-                       (const int *)ic);
+    hipLaunchKernelGGL((cg_dot_kernel<V, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, n, part,
+                       (int)P_PQ, (const int *)ic, OneColumn{});
     hipLaunchKernelGGL((cheb_update_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, u, r, (const V *)p, (const V *)q, z, d, n, part,
                        (const int *)ic, k, inv_theta, degree == 1 ? 1 : 0, minv, nb);
     if ((r2 = cheb_chain<V, BS>(h, OneColumn{}, z, n, d, q, n, (const V *)r, n, n, degree, c1, c2, (int)P_RZ0 + ((k + 1) & 1), part,
                                 (const int *)ic, minv, nb, st)))
       return r2;
-    hipLaunchKernelGGL((cheb_direction_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, n, (const double *)part, ic, k,
-                       stop);
+    hipLaunchKernelGGL((cg_direction_kernel<V, 0, P_RZ0, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)z, n, n,
+                       (const double *)part, ic, k, stop, (const V *)nullptr, 0LL, OneColumn{});
     return 0;
   };
   while (s.live()) {

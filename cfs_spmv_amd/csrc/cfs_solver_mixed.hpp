@@ -20,7 +20,7 @@
 //
 // The scalars are the partial-sum slots of cfs_solver.hpp (no atomics, fixed order): on two deterministic
 // handles the whole solve is bit-reproducible.  z = M^-1 r is formed in fp64 from the ROUNDED r and the fp32
-// preconditioner, exactly as cg_update_kernel<float, true> / cg_update_block_kernel<float, BS> form it.
+// preconditioner, exactly as cg_update_kernel<float, BS, P_RZ0, OneColumn> forms it.
 #pragma once
 
 namespace cfs_solver {
@@ -48,101 +48,89 @@ __global__ void __launch_bounds__(kThreads) cg_fold_kernel(double *__restrict__ 
 }
 
 // d = b - q64 in fp64, never stored;  r = (float)d;  p = (float)z (when given);  part[slot_rr] <- d . d;
-// part[P_BB] <- b . b (when with_bb);  PRE: part[slot_rz] <- r . z with z = dinv r of the ROUNDED r.
-// PRE = false: p = r (when given), no r . z (the plain iteration takes alpha from the r . r slot).
-template <bool PRE>
+// part[P_BB] <- b . b (when with_bb);  BS >= 1: part[slot_rz] <- r . z with z = M^-1 r of the ROUNDED r (BS = 1: dinv;
+// BS >= 2: the inverse node blocks, one node block per thread, as cg_residual_kernel<float, BS> walks).
+// BS = 0: p = r (when given), no r . z (the plain iteration takes alpha from the r . r slot).
+template <int BS>
 __global__ void __launch_bounds__(kThreads)
     cg_replace_kernel(float *__restrict__ r, float *__restrict__ p, const double *__restrict__ b, const double *__restrict__ q64,
                       long long n, double *__restrict__ part, int slot_rr, int slot_rz, int with_bb,
-                      const float *__restrict__ dinv) {
-  typedef Vec16<float>::type FT;
-  typedef Vec16<double>::type DT;
-  const long long nv = n / 4, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+                      const float *__restrict__ minv, long long nb) {
+  constexpr bool PRE = BS == 1;
   double rr = 0.0, bb = 0.0, rz = 0.0;
-  for (long long i = t0; i < nv; i += stride) {
-    const DT b0 = reinterpret_cast<const DT *>(b)[2 * i], b1 = reinterpret_cast<const DT *>(b)[2 * i + 1];
-    const DT q0 = reinterpret_cast<const DT *>(q64)[2 * i], q1 = reinterpret_cast<const DT *>(q64)[2 * i + 1];
-    const double bv[4] = {b0[0], b0[1], b1[0], b1[1]}, qv[4] = {q0[0], q0[1], q1[0], q1[1]};
-    FT rv, zv;
-    if (PRE) zv = reinterpret_cast<const FT *>(dinv)[i];
+  if constexpr (BS >= 2) {
+    for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
+      double rd[BS], z[BS];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const double d = bv[k] - qv[k];
-      rv[k] = (float)d;
-      rr += d * d;
-      bb += bv[k] * bv[k];
-      if (PRE) {
-        const double z = (double)rv[k] * (double)zv[k];
-        rz += (double)rv[k] * z;
-        zv[k] = (float)z;
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        rd[i] = 0.0;
+        if (g < n) {
+          const double bi = b[g], d = bi - q64[g];
+          const float ri = (float)d;
+          r[g] = ri;
+          rd[i] = (double)ri;
+          rr += d * d;
+          bb += bi * bi;
+        }
+      }
+      block_apply<float, BS>(minv, nb, k, rd, z);
+#pragma unroll
+      for (int i = 0; i < BS; ++i) {
+        const long long g = k * BS + i;
+        if (g < n) {
+          rz += rd[i] * z[i];
+          if (p) p[g] = (float)z[i];
+        }
       }
     }
-    reinterpret_cast<FT *>(r)[i] = rv;
-    if (p) reinterpret_cast<FT *>(p)[i] = PRE ? zv : rv;
-  }
-  for (long long i = nv * 4 + t0; i < n; i += stride) {
-    const double bi = b[i], d = bi - q64[i];
-    const float ri = (float)d;
-    r[i] = ri;
-    if (PRE) {
-      const double z = (double)ri * (double)dinv[i];
-      rz += (double)ri * z;
-      if (p) p[i] = (float)z;
-    } else if (p) {
-      p[i] = ri;
-    }
-    rr += d * d;
-    bb += bi * bi;
-  }
-  rr = block_sum(rr);
-  bb = block_sum(bb);
-  if (PRE) rz = block_sum(rz);
-  if (threadIdx.x == 0) {
-    part[slot_rr * kGrid + blockIdx.x] = rr;
-    if (with_bb) part[P_BB * kGrid + blockIdx.x] = bb;
-    if (PRE) part[slot_rz * kGrid + blockIdx.x] = rz;
-  }
-}
-
-// cg_replace_kernel<true> with M = blockdiag(A): one node block per thread, as cg_residual_block_kernel walks
-template <int BS>
-__global__ void __launch_bounds__(kThreads)
-    cg_replace_block_kernel(float *__restrict__ r, float *__restrict__ p, const double *__restrict__ b,
-                            const double *__restrict__ q64, long long n, double *__restrict__ part, int slot_rr, int slot_rz,
-                            int with_bb, const float *__restrict__ minv, long long nb) {
-  double rr = 0.0, bb = 0.0, rz = 0.0;
-  for (long long k = (long long)blockIdx.x * kThreads + threadIdx.x; k < nb; k += (long long)gridDim.x * kThreads) {
-    double rd[BS], z[BS];
+  } else {
+    typedef Vec16<float>::type FT;
+    typedef Vec16<double>::type DT;
+    const long long nv = n / 4, t0 = (long long)blockIdx.x * kThreads + threadIdx.x, stride = (long long)gridDim.x * kThreads;
+    for (long long i = t0; i < nv; i += stride) {
+      const DT b0 = reinterpret_cast<const DT *>(b)[2 * i], b1 = reinterpret_cast<const DT *>(b)[2 * i + 1];
+      const DT q0 = reinterpret_cast<const DT *>(q64)[2 * i], q1 = reinterpret_cast<const DT *>(q64)[2 * i + 1];
+      const double bv[4] = {b0[0], b0[1], b1[0], b1[1]}, qv[4] = {q0[0], q0[1], q1[0], q1[1]};
+      FT rv, zv;
+      if (PRE) zv = reinterpret_cast<const FT *>(minv)[i];
 #pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      const long long g = k * BS + i;
-      rd[i] = 0.0;
-      if (g < n) {
-        const double bi = b[g], d = bi - q64[g];
-        const float ri = (float)d;
-        r[g] = ri;
-        rd[i] = (double)ri;
+      for (int k = 0; k < 4; ++k) {
+        const double d = bv[k] - qv[k];
+        rv[k] = (float)d;
         rr += d * d;
-        bb += bi * bi;
+        bb += bv[k] * bv[k];
+        if (PRE) {
+          const double z = (double)rv[k] * (double)zv[k];
+          rz += (double)rv[k] * z;
+          zv[k] = (float)z;
+        }
       }
+      reinterpret_cast<FT *>(r)[i] = rv;
+      if (p) reinterpret_cast<FT *>(p)[i] = PRE ? zv : rv;
     }
-    block_apply<float, BS>(minv, nb, k, rd, z);
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-      const long long g = k * BS + i;
-      if (g < n) {
-        rz += rd[i] * z[i];
-        if (p) p[g] = (float)z[i];
+    for (long long i = nv * 4 + t0; i < n; i += stride) {
+      const double bi = b[i], d = bi - q64[i];
+      const float ri = (float)d;
+      r[i] = ri;
+      if (PRE) {
+        const double z = (double)ri * (double)minv[i];
+        rz += (double)ri * z;
+        if (p) p[i] = (float)z;
+      } else if (p) {
+        p[i] = ri;
       }
+      rr += d * d;
+      bb += bi * bi;
     }
   }
   rr = block_sum(rr);
   bb = block_sum(bb);
-  rz = block_sum(rz);
+  if (BS >= 1) rz = block_sum(rz);
   if (threadIdx.x == 0) {
     part[slot_rr * kGrid + blockIdx.x] = rr;
     if (with_bb) part[P_BB * kGrid + blockIdx.x] = bb;
-    part[slot_rz * kGrid + blockIdx.x] = rz;
+    if (BS >= 1) part[slot_rz * kGrid + blockIdx.x] = rz;
   }
 }
 
@@ -164,7 +152,6 @@ int cg_mixed(Handle *h64, Handle *h32, void *u_dev, const void *b_dev, double to
              int *iterations, int *replacements, double *relres, hipStream_t st) {
   using cfs_rt::DevBuf;
   typedef float V;
-  constexpr bool PRE = BS == 1, BLK = BS >= 2;
   const long long n = h64->n();
   if (h64->rows() != h64->n() || h32->rows() != h32->n())
     return cfs_rt::set_err(CFS_HIP_ERR_UNSUPPORTED, "pcg_mixed: the handles hold a row block, not the whole matrix");
@@ -193,12 +180,8 @@ int cg_mixed(Handle *h64, Handle *h32, void *u_dev, const void *b_dev, double to
     int r2 = h64->spmv_local(q64, u, nullptr, st);
     if (r2) return r2;
     const int slot_rr = P_RR0 + (k & 1), slot_rz = P_RZ0 + (k & 1);
-    if constexpr (BLK)
-      hipLaunchKernelGGL((cg_replace_block_kernel<BS>), dim3(kGrid), dim3(kThreads), 0, st, r, first ? p : (V *)nullptr, b,
-                         (const double *)q64, n, part, slot_rr, slot_rz, first ? 1 : 0, dinv, nb);
-    else
-      hipLaunchKernelGGL((cg_replace_kernel<PRE>), dim3(kGrid), dim3(kThreads), 0, st, r, first ? p : (V *)nullptr, b,
-                         (const double *)q64, n, part, slot_rr, slot_rz, first ? 1 : 0, dinv);
+    hipLaunchKernelGGL((cg_replace_kernel<BS>), dim3(kGrid), dim3(kThreads), 0, st, r, first ? p : (V *)nullptr, b,
+                       (const double *)q64, n, part, slot_rr, slot_rz, first ? 1 : 0, dinv, nb);
     HIPCHK(hipGetLastError());
     if ((r2 = slots.fetch())) return r2;
     *rr_true = slots.sum(slot_rr);
@@ -225,19 +208,12 @@ int cg_mixed(Handle *h64, Handle *h32, void *u_dev, const void *b_dev, double to
   auto iteration = [&](int k, double thr) -> int {
     int r2 = h32->spmv_local(q, p, nullptr, st);
     if (r2) return r2;
-    hipLaunchKernelGGL((cg_dot_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, part, (int)P_PQ,
-                       (const int *)ic);
-    if constexpr (BLK) {
-      hipLaunchKernelGGL((cg_update_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, xlo, r, (const V *)p, (const V *)q,
-                         n, part, (const int *)ic, k, dinv, nb);
-      hipLaunchKernelGGL((cg_direction_block_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
-                         (const double *)part, ic, k, -1.0, dinv, nb);
-    } else {
-      hipLaunchKernelGGL((cg_update_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, xlo, r, (const V *)p, (const V *)q, n,
-                         part, (const int *)ic, k, dinv);
-      hipLaunchKernelGGL((cg_direction_kernel<V, PRE>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
-                         (const double *)part, ic, k, -1.0, dinv);
-    }
+    hipLaunchKernelGGL((cg_dot_kernel<V, OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, (const V *)p, (const V *)q, n, n, part,
+                       (int)P_PQ, (const int *)ic, OneColumn{});
+    hipLaunchKernelGGL((cg_update_kernel<V, BS, num_slot(BS), OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, xlo, r, (const V *)p,
+                       (const V *)q, n, n, part, (const int *)ic, k, dinv, nb, OneColumn{});
+    hipLaunchKernelGGL((cg_direction_kernel<V, BS, num_slot(BS), OneColumn>), dim3(kGrid), dim3(kThreads), 0, st, p, (const V *)r, n,
+                       n, (const double *)part, ic, k, ColumnStops{{-1.0}}, dinv, nb, OneColumn{});
     hipLaunchKernelGGL(cg_pause_kernel, dim3(1), dim3(kThreads), 0, st, (const double *)part, ic, k, thr);
     return 0;
   };

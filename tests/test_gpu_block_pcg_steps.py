@@ -1,6 +1,6 @@
 """cfs_hip_sym_pcg_block step by step, by the method of test_gpu_pcg_steps.py: block Jacobi on the bs x bs
-node blocks, M = blockdiag(A) -- cfs_block_gather_kernel and cg_binv_kernel once, then
-cg_residual_block_kernel, cg_dot_kernel, cg_update_block_kernel, cg_direction_block_kernel behind the SpMV.
+node blocks, M = blockdiag(A) -- cfs_block_gather_kernel and cg_binv_kernel once, then cg_residual_kernel,
+cg_dot_kernel, cg_update_kernel, cg_direction_kernel<V, bs, ..., OneColumn> behind the SpMV.
 
 1. The inverse.  Minv = A.block_inverse(bs) (the solver's two set-up kernels plus an unpack) against the
    inverse of the blocks in np.longdouble.  The yardstick e_ref is the distance from that of the same

@@ -1,6 +1,6 @@
 """cfs_hip_sym_cg step by step: the ITERATES u_k of the native conjugate gradients (cg_residual_kernel,
-cg_dot_kernel, cg_update_kernel, cg_direction_kernel behind the SpMV) against the same recurrence in
-np.longdouble on the CPU,
+cg_dot_kernel, cg_update_kernel, cg_direction_kernel behind the SpMV, in their BS = 0, OneColumn
+instantiations) against the same recurrence in np.longdouble on the CPU,
 
     r = b - A u, p = r;   alpha = r.r / p.q;  u += alpha p;  r -= alpha q;  beta = r'.r' / r.r;  p = r + beta p
 

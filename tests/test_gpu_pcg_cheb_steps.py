@@ -1,6 +1,8 @@
 """cfs_hip_sym_pcg_cheb, cfs_hip_sym_cheb_apply and cfs_hip_sym_precond_lmax step by step, by the method of
-test_gpu_pcg_steps.py: what the kernels of csrc/cfs_solver_cheb.hpp compute against the same recurrences in
-np.longdouble on the CPU, the product as long-double row sums of the CSR (oracle.csr_spmv_ldx).
+test_gpu_pcg_steps.py: what the kernels of csrc/cfs_solver_cheb.hpp (and, for p . q and the direction step of
+the outer iteration, cg_dot_kernel and cg_direction_kernel<V, 0, P_RZ0, OneColumn> of csrc/cfs_solver.hpp)
+compute against the same recurrences in np.longdouble on the CPU, the product as long-double row sums of the
+CSR (oracle.csr_spmv_ldx).
 
     z = P_m r:   z_1 = d_1 = (1/theta) M^-1 r;   t = A z_j;  d_{j+1} = c1_j d_j + c2_j M^-1 (r - t);  z_{j+1} = z_j + d_{j+1}
     PCG:         r = b - A u;  z = P_m r;  p = z;  rz = r.z

@@ -9,7 +9,9 @@ column and guard words before and behind both blocks: B, the padding and the gua
 chosen to stop at different iterations (COLUMNS below; some stop at MAXITER): two ordinary ones, a zero column, one whose first guess already
 solves it, one that holds a NaN, and the rest started from first guesses at different distances from the solution.  The
 test asserts that the counts do differ, that the zero, solved and NaN columns never iterate in their one-column solves
-(so the block may not either), and the equality covers the columns beside them.
+(so the block may not either), and the equality covers the columns beside them.  Both sides run the same four kernel
+sources of csrc/cfs_solver.hpp, the one-column solves their OneColumn instantiation and the block its ColumnMask one: C1
+and C2 are the judge that the two are compiled to the same arithmetic.
 
 C2.  The same solve with check_every = 1, with the largest window, and with maxiter cutting some columns short gives
 the bytes of the one-column solves: a column is frozen by the device inside a window of enqueued iterations.

@@ -1,7 +1,7 @@
 """cfs_hip_sym_pcg step by step, by the method of test_gpu_cg_steps.py: the ITERATES u_k of the native
 Jacobi-preconditioned conjugate gradients (cfs_diag_gather_kernel and cg_dinv_kernel once, then
-cg_residual_kernel<PRE>, cg_dot_kernel, cg_update_kernel<PRE>, cg_direction_kernel<PRE> behind the SpMV)
-against the same recurrence in np.longdouble on the CPU,
+cg_residual_kernel, cg_dot_kernel, cg_update_kernel, cg_direction_kernel<V, 1, ..., OneColumn> behind the
+SpMV) against the same recurrence in np.longdouble on the CPU,
 
     r = b - A u;  z = D^-1 r;  p = z;  rz = r.z
     q = A p;  alpha = rz / p.q;  u += alpha p;  r -= alpha q;  z = D^-1 r;  rz' = r.z;  rr' = r.r
