@@ -103,7 +103,9 @@ SYMBOLS = [
     "cfs_hip_amg_setup_info", "cfs_hip_debug_amg_coarsen_dominant",
     "cfs_hip_amg_create_block_f64", "cfs_hip_amg_create_block_f32", "cfs_hip_amg_block", "cfs_hip_amg_level_node_weights", "cfs_hip_debug_amg_coarsen_block",
     "cfs_hip_sym_eigs", "cfs_hip_sym_debug_lanczos", "cfs_hip_debug_symeig", "cfs_hip_debug_eigs_combine", "cfs_hip_sym_lobpcg", "cfs_hip_debug_lobpcg_rr", "cfs_hip_debug_gram", "cfs_hip_sym_debug_lobpcg", "cfs_hip_debug_lobpcg_update", "cfs_hip_debug_gram_cols", "cfs_hip_debug_lobpcg_update_cols", "cfs_hip_sym_debug_lobpcg_residual",
-    "cfs_hip_amg_apply_cols", "cfs_hip_amg_column_cycles", "cfs_hip_sym_lobpcg_amg", "cfs_hip_sym_debug_lobpcg_amg", "cfs_hip_sym_pcg_cols", "cfs_hip_sym_pcg_amg_cols", "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
+    "cfs_hip_amg_apply_cols", "cfs_hip_amg_column_cycles", "cfs_hip_sym_lobpcg_amg", "cfs_hip_sym_debug_lobpcg_amg", "cfs_hip_sym_pcg_cols", "cfs_hip_sym_pcg_amg_cols",
+    "cfs_hip_sym_lobpcg_gen", "cfs_hip_sym_lobpcg_gen_amg", "cfs_hip_sym_debug_lobpcg_gen", "cfs_hip_debug_gram3_cols", "cfs_hip_debug_lobpcg_update3_cols", "cfs_hip_sym_debug_lobpcg_residual_gen",
+    "cfs_hip_sym_shard_send_counts", "cfs_hip_sym_shard_send_rows",
     "cfs_hip_sym_shard_set_recv", "cfs_hip_sym_spmv_local_async",
     "cfs_hip_sym_recv_fold_async", "cfs_hip_sym_spmv_phases_async", "cfs_hip_sym_get_stats", "cfs_hip_sym_debug_digest", "cfs_hip_sym_debug_kernel", "cfs_hip_sym_debug_fold_lists", "cfs_hip_sym_debug_plan_note", "cfs_hip_sym_debug_timeline", "cfs_hip_sym_debug_group_features", "cfs_hip_sym_plan_check_f64",
     "cfs_hip_sym_plan_check_f32", "cfs_hip_sym_plan_send_info_f64",
@@ -297,6 +299,17 @@ def load():
         lib.cfs_hip_sym_lobpcg_amg.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_longlong, dp, vp,
                                                C.c_longlong, dp, ip, ip, ip, vp]
         lib.cfs_hip_sym_debug_lobpcg_amg.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, C.c_int, dp, vp, C.c_longlong, dp, vp]
+    if hasattr(lib, "cfs_hip_sym_lobpcg_gen"):  # (absent from older builds loaded through CFS_HIP_LIB)
+        dp = C.POINTER(C.c_double)
+        lib.cfs_hip_sym_lobpcg_gen.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_longlong, dp, vp,
+                                               C.c_longlong, dp, ip, ip, ip, ip, vp]
+        lib.cfs_hip_sym_lobpcg_gen_amg.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_longlong, dp, vp,
+                                                   C.c_longlong, dp, ip, ip, ip, ip, vp]
+        lib.cfs_hip_sym_debug_lobpcg_gen.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_longlong, C.c_int, dp, vp, C.c_longlong, dp, vp]
+        lib.cfs_hip_debug_gram3_cols.argtypes = [vp, vp, vp, C.c_longlong, C.c_longlong, C.c_int, ip, C.c_int, dp, dp, vp]
+        lib.cfs_hip_debug_lobpcg_update3_cols.argtypes = [vp, vp, vp, C.c_longlong, C.c_longlong, C.c_int, C.c_int, ip, C.c_int, dp,
+                                                          C.c_int, vp]
+        lib.cfs_hip_sym_debug_lobpcg_residual_gen.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_longlong, C.c_int, dp, C.c_uint, dp, vp]
     if hasattr(lib, "cfs_hip_sym_pcg_cols"):  # (absent from older builds loaded through CFS_HIP_LIB)
         dp = C.POINTER(C.c_double)
         lib.cfs_hip_sym_pcg_cols.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, ip, dp, vp]

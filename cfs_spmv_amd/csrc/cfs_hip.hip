@@ -2729,7 +2729,7 @@ int cfs_hip_debug_eigs_combine(void *out_dev, long long ldo, const void *basis_d
 // the checks that cfs_hip_sym_lobpcg and cfs_hip_sym_debug_lobpcg share, from "bad k" on, in the documented order
 // (a: the hierarchy of the multigrid form, whose value type must be the handle's -- asked when the handle is first read)
 static int check_lobpcg(cfs_hip_sym_t h, int k, int block_rows, bool tol_ok, const void *x0_dev, long long ld0, const void *vectors_dev,
-                        long long ld, cfs_hip_amg_t a = nullptr) {
+                        long long ld, cfs_hip_amg_t a = nullptr, cfs_hip_sym_t hb = nullptr) {
   if (k < 1 || k > CFS_HIP_LOBPCG_MAX_K)
     return set_err(CFS_HIP_ERR_ARG, "lobpcg: bad k: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + " and 3 k <= n, got k = " + std::to_string(k));
   if (block_rows != 0 && !block_rows_ok(block_rows))
@@ -2738,8 +2738,21 @@ static int check_lobpcg(cfs_hip_sym_t h, int k, int block_rows, bool tol_ok, con
   if ((((uintptr_t)x0_dev) | ((uintptr_t)vectors_dev)) & 15)
     return set_err(CFS_HIP_ERR_ARG, "lobpcg: x0 and the vectors must be 16-byte aligned");
   if (a && a->value_bytes != h->value_bytes) return set_err(CFS_HIP_ERR_ARG, "lobpcg_amg: value type differs from the hierarchy's");
+  // (hb: the B of the pencil forms -- h's n, value type and device; then no shard and one device on either side)
+  if (hb && (hb->n() != h->n() || hb->value_bytes != h->value_bytes || hb->device != h->device))
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg_gen: B must have the n, the value type and the device of A: n " + std::to_string(hb->n()) +
+                                        " / " + std::to_string(h->n()) + ", value bytes " + std::to_string(hb->value_bytes) + " / " +
+                                        std::to_string(h->value_bytes) + ", device " + std::to_string(hb->device) + " / " +
+                                        std::to_string(h->device));
   if (!h->send_rows().empty() || h->rows() != h->n())
     return set_err(CFS_HIP_ERR_UNSUPPORTED, "lobpcg: a handle of the whole matrix, not a shard");
+  if (hb) {
+    int rc2;
+    const std::string one = "lobpcg_gen: the whole matrix on one device, not a multi-device handle";
+    if ((rc2 = check_whole_matrix(hb, not_a_shard("lobpcg_gen: B"), true, "")) || (rc2 = check_whole_matrix(h, not_a_shard("lobpcg_gen"), true, one)) ||
+        (rc2 = check_whole_matrix(hb, not_a_shard("lobpcg_gen: B"), true, one)))
+      return rc2;
+  }
   const long long n = h->n();
   if (3LL * k > n)
     return set_err(CFS_HIP_ERR_ARG, "lobpcg: bad k: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + " and 3 k <= n, got k = " + std::to_string(k) +
@@ -2772,8 +2785,9 @@ int cfs_hip_sym_lobpcg(cfs_hip_sym_t h, int k, int block_rows, double tol, doubl
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)stream;
   return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
-    return cfs_solver::lobpcg<decltype(v), decltype(bs)::value>(h, k, tol, scale, maxiter, -1, x0_dev, ld0, eigenvalues, vectors_dev, ld,
-                                                                residuals, nconv, iterations, products, st);
+    return cfs_solver::lobpcg<decltype(v), decltype(bs)::value, false>(h, (cfs_hip_sym_t) nullptr, k, tol, scale, maxiter, -1, x0_dev, ld0,
+                                                                       eigenvalues, vectors_dev, ld, residuals, nconv, iterations, products,
+                                                                       nullptr, st);
   });
 }
 
@@ -2786,16 +2800,16 @@ int cfs_hip_sym_debug_lobpcg(cfs_hip_sym_t h, int k, int block_rows, const void 
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)stream;
   return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
-    return cfs_solver::lobpcg<decltype(v), decltype(bs)::value>(h, k, 0.0, 1.0, 0, iters, x0_dev, ld0, theta, vectors_dev, ld, resnorms,
-                                                                nullptr, nullptr, nullptr, st);
+    return cfs_solver::lobpcg<decltype(v), decltype(bs)::value, false>(h, (cfs_hip_sym_t) nullptr, k, 0.0, 1.0, 0, iters, x0_dev, ld0, theta,
+                                                                       vectors_dev, ld, resnorms, nullptr, nullptr, nullptr, nullptr, st);
   });
 }
 
 // the checks of the two multigrid forms behind their null checks: check_lobpcg (no stored M^-1: block_rows 0; the
 // hierarchy's value type), one device as cfs_hip_sym_pcg_amg asks, the hierarchy created on h and not stale
 static int check_lobpcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, int k, bool tol_ok, const void *x0_dev, long long ld0, const void *vectors_dev,
-                            long long ld) {
-  int rc = check_lobpcg(h, k, 0, tol_ok, x0_dev, ld0, vectors_dev, ld, a);
+                            long long ld, cfs_hip_sym_t hb = nullptr) {
+  int rc = check_lobpcg(h, k, 0, tol_ok, x0_dev, ld0, vectors_dev, ld, a, hb);
   if (rc || (rc = check_whole_matrix(h, not_a_shard("lobpcg_amg"), true, "lobpcg_amg: the whole matrix on one device, not a multi-device handle")))
     return rc;
   if (a->fine != h) return set_err(CFS_HIP_ERR_ARG, "lobpcg_amg: the hierarchy was created on another handle");
@@ -2815,8 +2829,8 @@ int cfs_hip_sym_lobpcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, int k, double tol, 
   if (rc) return rc;
   h->ok_x = h->ok_y = nullptr;
   DeviceGuard g(h->device);
-  return a->lobpcg(k, tol, scale, maxiter, -1, x0_dev, ld0, eigenvalues, vectors_dev, ld, residuals, nconv, iterations, products,
-                   (hipStream_t)stream);
+  return a->lobpcg(nullptr, k, tol, scale, maxiter, -1, x0_dev, ld0, eigenvalues, vectors_dev, ld, residuals, nconv, iterations, products,
+                   nullptr, (hipStream_t)stream);
 }
 
 int cfs_hip_sym_debug_lobpcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, int k, const void *x0_dev, long long ld0, int iters, double *theta,
@@ -2826,7 +2840,60 @@ int cfs_hip_sym_debug_lobpcg_amg(cfs_hip_sym_t h, cfs_hip_amg_t a, int k, const 
   if (rc) return rc;
   h->ok_x = h->ok_y = nullptr;
   DeviceGuard g(h->device);
-  return a->lobpcg(k, 0.0, 1.0, 0, iters, x0_dev, ld0, theta, vectors_dev, ld, resnorms, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  return a->lobpcg(nullptr, k, 0.0, 1.0, 0, iters, x0_dev, ld0, theta, vectors_dev, ld, resnorms, nullptr, nullptr, nullptr, nullptr,
+                   (hipStream_t)stream);
+}
+
+// ---- LOBPCG for the pencil A x = lambda B x: the same templates with the third block B S ----
+int cfs_hip_sym_lobpcg_gen(cfs_hip_sym_t h, cfs_hip_sym_t hb, int k, int block_rows, double tol, double scale, int maxiter,
+                           const void *x0_dev, long long ld0, double *eigenvalues, void *vectors_dev, long long ld, double *residuals,
+                           int *nconv, int *iterations, int *products, int *b_products, void *stream) {
+  if (!h || !hb || !eigenvalues || !vectors_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (nconv) *nconv = 0;
+  if (iterations) *iterations = 0;
+  if (products) *products = 0;
+  if (b_products) *b_products = 0;
+  const bool tol_ok = tol >= 0.0 && scale > 0.0 && std::isfinite(scale) && maxiter >= 0;
+  int rc = check_lobpcg(h, k, block_rows, tol_ok, x0_dev, ld0, vectors_dev, ld, nullptr, hb);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = hb->ok_x = hb->ok_y = nullptr; // (the iteration's own vectors are library memory on the handles' device)
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::lobpcg<decltype(v), decltype(bs)::value, true>(h, hb, k, tol, scale, maxiter, -1, x0_dev, ld0, eigenvalues, vectors_dev,
+                                                                      ld, residuals, nconv, iterations, products, b_products, st);
+  });
+}
+
+int cfs_hip_sym_debug_lobpcg_gen(cfs_hip_sym_t h, cfs_hip_sym_t hb, int k, int block_rows, const void *x0_dev, long long ld0, int iters,
+                                 double *theta, void *vectors_dev, long long ld, double *resnorms, void *stream) {
+  if (!h || !hb || !theta || !vectors_dev || !resnorms) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  int rc = check_lobpcg(h, k, block_rows, iters >= 0, x0_dev, ld0, vectors_dev, ld, nullptr, hb);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = hb->ok_x = hb->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
+    return cfs_solver::lobpcg<decltype(v), decltype(bs)::value, true>(h, hb, k, 0.0, 1.0, 0, iters, x0_dev, ld0, theta, vectors_dev, ld,
+                                                                      resnorms, nullptr, nullptr, nullptr, nullptr, st);
+  });
+}
+
+int cfs_hip_sym_lobpcg_gen_amg(cfs_hip_sym_t h, cfs_hip_sym_t hb, cfs_hip_amg_t a, int k, double tol, double scale, int maxiter,
+                               const void *x0_dev, long long ld0, double *eigenvalues, void *vectors_dev, long long ld, double *residuals,
+                               int *nconv, int *iterations, int *products, int *b_products, void *stream) {
+  if (!h || !hb || !a || !eigenvalues || !vectors_dev) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (nconv) *nconv = 0;
+  if (iterations) *iterations = 0;
+  if (products) *products = 0;
+  if (b_products) *b_products = 0;
+  const bool tol_ok = tol >= 0.0 && scale > 0.0 && std::isfinite(scale) && maxiter >= 0;
+  int rc = check_lobpcg_amg(h, a, k, tol_ok, x0_dev, ld0, vectors_dev, ld, hb);
+  if (rc) return rc;
+  h->ok_x = h->ok_y = hb->ok_x = hb->ok_y = nullptr;
+  DeviceGuard g(h->device);
+  return a->lobpcg(hb, k, tol, scale, maxiter, -1, x0_dev, ld0, eigenvalues, vectors_dev, ld, residuals, nconv, iterations, products,
+                   b_products, (hipStream_t)stream);
 }
 
 int cfs_hip_debug_lobpcg_rr(int m, const double *g, const double *hh, int k, double drop, double *theta, double *c, int *rank) {
@@ -2879,7 +2946,7 @@ int cfs_hip_debug_gram_cols(const void *s_dev, const void *t_dev, long long ld, 
     return rc;
   DeviceGuard dg(dev);
   return cfs_rt::with_value_type(value_bytes, [&](auto v) {
-    return cfs_solver::debug_gram<decltype(v)>(s_dev, t_dev, ld, n, m, idx, full_h, g, hh, (hipStream_t)stream);
+    return cfs_solver::debug_gram<decltype(v)>(s_dev, t_dev, nullptr, ld, n, m, idx, full_h, g, hh, (hipStream_t)stream);
   });
 }
 
@@ -2909,7 +2976,7 @@ int cfs_hip_debug_lobpcg_update_cols(void *s_dev, void *as_dev, long long ld, lo
   if ((rc = check_lobpcg_dev(s_dev, "lobpcg_update", &dev)) || (as_dev && (rc = check_lobpcg_dev(as_dev, "lobpcg_update", &dev)))) return rc;
   DeviceGuard dg(dev);
   return cfs_rt::with_value_type(value_bytes, [&](auto v) {
-    return cfs_solver::debug_update<decltype(v)>(s_dev, as_dev, ld, n, k, m, idx, with_p, c, (hipStream_t)stream);
+    return cfs_solver::debug_update<decltype(v)>(s_dev, as_dev, nullptr, ld, n, k, m, idx, with_p, c, (hipStream_t)stream);
   });
 }
 
@@ -2919,15 +2986,56 @@ int cfs_hip_debug_lobpcg_update(void *s_dev, long long ld, long long n, int k, i
   return cfs_hip_debug_lobpcg_update_cols(s_dev, nullptr, ld, n, k, m, idx, 1, c, value_bytes, stream);
 }
 
-int cfs_hip_sym_debug_lobpcg_residual(cfs_hip_sym_t h, int block_rows, const void *x_dev, const void *ax_dev, void *w_dev, long long ld,
-                                      int k, const double *theta, unsigned active, double *sums, void *stream) {
-  if (!h || !x_dev || !ax_dev || !w_dev || !theta || !sums) return set_err(CFS_HIP_ERR_ARG, "null argument");
+// the three-block forms of the pencil solver: the checks of the two-block forms, with the third block among them
+int cfs_hip_debug_gram3_cols(const void *s_dev, const void *as_dev, const void *bs_dev, long long ld, long long n, int m, const int *idx,
+                             int value_bytes, double *g, double *hh, void *stream) {
+  if (!s_dev || !as_dev || !bs_dev || !idx || !g || !hh) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (m < 1 || m > 3 * CFS_HIP_LOBPCG_MAX_K)
+    return set_err(CFS_HIP_ERR_ARG, "gram3: m must lie in [1, " + std::to_string(3 * CFS_HIP_LOBPCG_MAX_K) + "]");
+  int dev = -1, rc;
+  if ((rc = check_lobpcg_idx(idx, m, 3 * CFS_HIP_LOBPCG_MAX_K, "gram3"))) return rc;
+  for (const void *p : {s_dev, as_dev, bs_dev})
+    if ((rc = check_lobpcg_geom(p, ld, n, value_bytes, "gram3"))) return rc;
+  for (const void *p : {s_dev, as_dev, bs_dev})
+    if ((rc = check_lobpcg_dev(p, "gram3", &dev))) return rc;
+  DeviceGuard dg(dev);
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    return cfs_solver::debug_gram<decltype(v)>(s_dev, as_dev, bs_dev, ld, n, m, idx, 0, g, hh, (hipStream_t)stream);
+  });
+}
+
+int cfs_hip_debug_lobpcg_update3_cols(void *s_dev, void *as_dev, void *bs_dev, long long ld, long long n, int k, int m, const int *idx,
+                                      int with_p, const double *c, int value_bytes, void *stream) {
+  if (!s_dev || !as_dev || !bs_dev || !idx || !c) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  if (k < 1 || k > CFS_HIP_LOBPCG_MAX_K || m < 1 || m > 3 * k)
+    return set_err(CFS_HIP_ERR_ARG, "lobpcg_update3: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + " and 1 <= m <= 3 k");
+  int dev = -1, rc;
+  if ((rc = check_lobpcg_idx(idx, m, 3 * k, "lobpcg_update3"))) return rc;
+  if (with_p != 0 && with_p != 1) return set_err(CFS_HIP_ERR_ARG, "lobpcg_update3: with_p must be 0 or 1");
+  for (const void *p : {(const void *)s_dev, (const void *)as_dev, (const void *)bs_dev})
+    if ((rc = check_lobpcg_geom(p, ld, n, value_bytes, "lobpcg_update3"))) return rc;
+  // the three blocks, first byte to the last row of the last column, must not overlap
+  const uintptr_t span = (uintptr_t)(((long long)(3 * k - 1) * ld + n) * value_bytes), b[3] = {(uintptr_t)s_dev, (uintptr_t)as_dev, (uintptr_t)bs_dev};
+  for (int i = 0; i < 3; ++i)
+    for (int j = i + 1; j < 3; ++j)
+      if (b[i] < b[j] + span && b[j] < b[i] + span) return set_err(CFS_HIP_ERR_ARG, "lobpcg_update3: two of the blocks overlap");
+  for (const void *p : {(const void *)s_dev, (const void *)as_dev, (const void *)bs_dev})
+    if ((rc = check_lobpcg_dev(p, "lobpcg_update3", &dev))) return rc;
+  DeviceGuard dg(dev);
+  return cfs_rt::with_value_type(value_bytes, [&](auto v) {
+    return cfs_solver::debug_update<decltype(v)>(s_dev, as_dev, bs_dev, ld, n, k, m, idx, with_p, c, (hipStream_t)stream);
+  });
+}
+
+// cfs_hip_sym_debug_lobpcg_residual (bx_dev = NULL) and _residual_gen behind their null checks
+static int run_lobpcg_residual(cfs_hip_sym_t h, int block_rows, const void *x_dev, const void *ax_dev, const void *bx_dev, void *w_dev,
+                               long long ld, int k, const double *theta, unsigned active, double *sums, void *stream) {
   if (k < 1 || k > CFS_HIP_LOBPCG_MAX_K)
     return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: bad k: 1 <= k <= " + std::to_string(CFS_HIP_LOBPCG_MAX_K) + ", got k = " + std::to_string(k));
   if (block_rows != 0 && !block_rows_ok(block_rows))
     return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: block_rows " + std::to_string(block_rows) + " is not one of 0, 1, 2, 3, 4, 6");
   if (active >> k) return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: active names a pair that is not in [0, k)");
-  if ((((uintptr_t)x_dev) | ((uintptr_t)ax_dev) | ((uintptr_t)w_dev)) & 15)
+  if ((((uintptr_t)x_dev) | ((uintptr_t)ax_dev) | ((uintptr_t)bx_dev) | ((uintptr_t)w_dev)) & 15)
     return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: X, AX and W must be 16-byte aligned");
   if (!h->send_rows().empty() || h->rows() != h->n())
     return set_err(CFS_HIP_ERR_UNSUPPORTED, "lobpcg_residual: a handle of the whole matrix, not a shard");
@@ -2938,8 +3046,8 @@ int cfs_hip_sym_debug_lobpcg_residual(cfs_hip_sym_t h, int block_rows, const voi
                                         " and a multiple of 16 bytes");
   // W is written while X and AX are read: the k columns of W may not overlap those of X or AX
   const uintptr_t span = (uintptr_t)(((long long)(k - 1) * ld + n) * h->value_bytes), w0 = (uintptr_t)w_dev;
-  for (const void *p : {x_dev, ax_dev})
-    if ((uintptr_t)p < w0 + span && w0 < (uintptr_t)p + span)
+  for (const void *p : {x_dev, ax_dev, bx_dev})
+    if (p && (uintptr_t)p < w0 + span && w0 < (uintptr_t)p + span)
       return set_err(CFS_HIP_ERR_ARG, "lobpcg_residual: W overlaps X or AX");
   if (block_rows >= 2) {
     int ngpus = 1;
@@ -2949,14 +3057,27 @@ int cfs_hip_sym_debug_lobpcg_residual(cfs_hip_sym_t h, int block_rows, const voi
   }
   int rc;
   if ((rc = check_eigs_ptr(h, x_dev, "lobpcg_residual", "X")) || (rc = check_eigs_ptr(h, ax_dev, "lobpcg_residual", "AX")) ||
-      (rc = check_eigs_ptr(h, w_dev, "lobpcg_residual", "W")))
+      (bx_dev && (rc = check_eigs_ptr(h, bx_dev, "lobpcg_residual", "BX"))) || (rc = check_eigs_ptr(h, w_dev, "lobpcg_residual", "W")))
     return rc;
   h->ok_x = h->ok_y = nullptr;
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)stream;
   return with_precond(h->value_bytes, block_rows, [&](auto v, auto bs) {
-    return cfs_solver::debug_residual<decltype(v), decltype(bs)::value>(h, x_dev, ax_dev, w_dev, ld, k, theta, active, sums, st);
+    return cfs_solver::debug_residual<decltype(v), decltype(bs)::value>(h, x_dev, ax_dev, bx_dev, w_dev, ld, k, theta, active, sums, st);
   });
+}
+
+int cfs_hip_sym_debug_lobpcg_residual(cfs_hip_sym_t h, int block_rows, const void *x_dev, const void *ax_dev, void *w_dev, long long ld,
+                                      int k, const double *theta, unsigned active, double *sums, void *stream) {
+  if (!h || !x_dev || !ax_dev || !w_dev || !theta || !sums) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  return run_lobpcg_residual(h, block_rows, x_dev, ax_dev, nullptr, w_dev, ld, k, theta, active, sums, stream);
+}
+
+int cfs_hip_sym_debug_lobpcg_residual_gen(cfs_hip_sym_t h, int block_rows, const void *x_dev, const void *ax_dev, const void *bx_dev,
+                                          void *w_dev, long long ld, int k, const double *theta, unsigned active, double *sums,
+                                          void *stream) {
+  if (!h || !x_dev || !ax_dev || !bx_dev || !w_dev || !theta || !sums) return set_err(CFS_HIP_ERR_ARG, "null argument");
+  return run_lobpcg_residual(h, block_rows, x_dev, ax_dev, bx_dev, w_dev, ld, k, theta, active, sums, stream);
 }
 
 int cfs_hip_sym_spmv(cfs_hip_sym_t h, void *y, const void *x) {

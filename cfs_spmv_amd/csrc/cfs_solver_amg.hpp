@@ -136,8 +136,10 @@ struct cfs_hip_amg_s {
   virtual int coarse_inverse(void *inv) = 0;
   virtual int apply(void *z_dev, const void *r_dev, hipStream_t st) = 0;
   virtual int apply_cols(void *z_dev, const void *r_dev, long long ld, int ncols, unsigned active, hipStream_t st) = 0;
-  virtual int lobpcg(int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0, double *eigenvalues,
-                     void *vectors_dev, long long ld, double *residuals, int *nconv, int *iterations, int *products, hipStream_t st) = 0;
+  // (hb: the B of the pencil form cfs_hip_sym_lobpcg_gen_amg, with its counter b_products; nullptr: A x = lambda x)
+  virtual int lobpcg(cfs_hip_sym_s *hb, int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0,
+                     double *eigenvalues, void *vectors_dev, long long ld, double *residuals, int *nconv, int *iterations, int *products,
+                     int *b_products, hipStream_t st) = 0;
   virtual bool is_stale() const = 0;              // the last refresh failed
   virtual long long column_cycles() const = 0;    // cycles applied to columns of blocks, since create
   virtual int pcg(void *u_dev, const void *b_dev, double tol, int maxiter, int *iterations, double *relres, hipStream_t st) = 0;
@@ -1427,8 +1429,9 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
   }
   // cfs_hip_sym_lobpcg_amg / cfs_hip_sym_debug_lobpcg_amg: the iteration of cfs_solver_lobpcg.hpp with W formed by the
   // blocked cycle on the columns still active (arguments checked by the caller)
-  int lobpcg(int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0, double *eigenvalues,
-             void *vectors_dev, long long ld, double *residuals, int *nconv, int *iterations, int *products, hipStream_t st) override {
+  int lobpcg(cfs_hip_sym_s *hb, int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0,
+             double *eigenvalues, void *vectors_dev, long long ld, double *residuals, int *nconv, int *iterations, int *products,
+             int *b_products, hipStream_t st) override {
     if (stale) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "lobpcg_amg: the last refresh failed");
     int rc = follow_fine(st);
     if (rc || (rc = reserve_cols(k))) return rc;
@@ -1437,8 +1440,11 @@ template <typename V, int BS = 1> struct Amg : cfs_hip_amg_s {
       col_cycles += __builtin_popcount(mask);
       return 0;
     };
-    return cfs_solver::lobpcg<V, 0>(fine, k, tol, scale, maxiter, debug_iters, x0_dev, ld0, eigenvalues, vectors_dev, ld, residuals, nconv,
-                                    iterations, products, st, form_w);
+    if (hb)
+      return cfs_solver::lobpcg<V, 0, true>(fine, hb, k, tol, scale, maxiter, debug_iters, x0_dev, ld0, eigenvalues, vectors_dev, ld,
+                                            residuals, nconv, iterations, products, b_products, st, form_w);
+    return cfs_solver::lobpcg<V, 0, false>(fine, hb, k, tol, scale, maxiter, debug_iters, x0_dev, ld0, eigenvalues, vectors_dev, ld, residuals,
+                                           nconv, iterations, products, nullptr, st, form_w);
   }
   bool is_stale() const override { return stale; }
   long long column_cycles() const override { return col_cycles; }

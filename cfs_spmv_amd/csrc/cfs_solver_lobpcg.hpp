@@ -32,6 +32,20 @@
 // four waves per CU, five waves per SIMD -- set the occupancy, not the registers.
 // The accumulators live across all row tiles of the workgroup; at the end the slices are added in ascending order
 // through LDS and the workgroup writes ONE partial sum per entry.  Fixed grid, fixed order: bit-reproducible.
+//
+// THE PENCIL A x = lambda B x (cfs_hip_sym_lobpcg_gen, _gen_amg; B a second handle, SPD) is the same templates with a
+// compile-time switch GEN and a nullable third block BS = B S, carried along like AS:
+//   lobpcg_gram_kernel<V, true>      G = S^T BS and H = S^T AS in ONE pass over the three blocks: a row of the tile is
+//                                    [s | t | u | 2 pad], 3 mp + 2 doubles (1168 bytes at m = 48, 96 j + 16 bytes in general:
+//                                    never a multiple of 256), and a G task takes its b operand from the u part
+//   lobpcg_update_kernel             gridDim.y = 3: BX <- (V)(BS C), BP <- (V)(BS C'), order and rounding of the other two
+//   lobpcg_residual_kernel<.., true> R_i = AX_i - theta_i BX_i; the sums stay R_i . R_i and X_i . X_i
+//   tile kernel + fold               AW_i = A W_i and BW_i = B W_i; the confirm step recomputes AX and BX
+// With the rows per tile of the standard form (lobpcg_gram_rows) the three-block tile takes up to 39936 bytes (mp = 8; 37376
+// at mp = 48): kLobTileBytes3 = 40 KiB, FOUR workgroups per CU instead of five.  Fewer rows (24 at m = 48) would have kept
+// 32 KiB, at the price of 96-byte runs per fp32 column in the staging loads; the fp64 pipe bounds the kernel at m = 48 and
+// four waves per SIMD feed it.  The GEN = false instantiations are the kernels as they were: same stride, same task table,
+// same order of summation.  Memory held: (9 k + 1) n values.
 #pragma once
 
 #include <algorithm>
@@ -50,6 +64,15 @@ constexpr int kLobTileBytes = 32768;             // LDS of the Gram kernel: a ro
 static_assert(kLobM % 4 == 0 && (kLobM / 4) * (kLobM / 4 + 1) / 2 + (kLobM / 4) * (kLobM / 4) <= kThreads,
               "one 4 x 4 register block of G or H per thread");
 static_assert(kThreads * 16 * sizeof(double) <= kLobTileBytes, "the slices' accumulators fit the tile");
+// the pencil form stages three blocks: a row is 3 mp + 2 doubles, and with the SAME rows per tile (lobpcg_gram_rows) the
+// tile is at most 39936 bytes (mp = 8: 192 rows of 208 bytes; 37376 at mp = 48): 40 KiB, four workgroups per CU
+constexpr int kLobTileBytes3 = 40960;
+constexpr int lobpcg_tile3_bytes(int mp) { return 32 * (8 < kLobM / mp ? 8 : kLobM / mp) * (3 * mp + 2) * (int)sizeof(double); }
+static_assert(lobpcg_tile3_bytes(4) <= kLobTileBytes3 && lobpcg_tile3_bytes(8) <= kLobTileBytes3 && lobpcg_tile3_bytes(12) <= kLobTileBytes3 &&
+                  lobpcg_tile3_bytes(16) <= kLobTileBytes3 && lobpcg_tile3_bytes(20) <= kLobTileBytes3 && lobpcg_tile3_bytes(24) <= kLobTileBytes3 &&
+                  lobpcg_tile3_bytes(28) <= kLobTileBytes3 && lobpcg_tile3_bytes(32) <= kLobTileBytes3 && lobpcg_tile3_bytes(36) <= kLobTileBytes3 &&
+                  lobpcg_tile3_bytes(40) <= kLobTileBytes3 && lobpcg_tile3_bytes(44) <= kLobTileBytes3 && lobpcg_tile3_bytes(48) <= kLobTileBytes3,
+              "the three-block row tile fits at every width");
 
 struct LobpcgCols { // the active columns of S (and of AS): physical column idx[j] is column j of this iteration
   int m;
@@ -92,22 +115,25 @@ __global__ void __launch_bounds__(kThreads) lobpcg_fill_kernel(V *__restrict__ x
 
 // part[(w m m + i m + j) kGrid + workgroup] <- this workgroup's share of column i of s . column j of s (w = 0) or of
 // t (w = 1), for i <= j (full_h: every (i, j) of w = 1).  Launched with kGrid workgroups and kLobTileBytes of LDS.
-template <typename V>
+// GEN, the pencil form (kLobTileBytes3 of LDS): a third block u = B S is staged behind t, a row is [s | t | u | 2 pad],
+// and a task of w = 0 takes its b operand from u: part of w = 0 is column i of s . column j of u, G = S^T (B S).
+template <typename V, bool GEN>
 __global__ void __launch_bounds__(kThreads)
-    lobpcg_gram_kernel(const V *__restrict__ s, const V *__restrict__ t, long long ld, long long n, LobpcgCols cols, int R,
-                       int full_h, double *__restrict__ part) {
+    lobpcg_gram_kernel(const V *__restrict__ s, const V *__restrict__ t, const V *__restrict__ u, long long ld, long long n,
+                       LobpcgCols cols, int R, int full_h, double *__restrict__ part) {
   CFS_LOBPCG_ROUNDING
   extern __shared__ __align__(16) unsigned char lobpcg_lds[];
   __shared__ int sidx[kLobM];
-  double *tile = reinterpret_cast<double *>(lobpcg_lds); // tile[r stride + c], c < mp: s, mp <= c < 2 mp: t
-  const int m = cols.m, mp = (m + 3) & ~3, nb = mp / 4, stride = 2 * mp + 2;
+  double *tile = reinterpret_cast<double *>(lobpcg_lds); // tile[r stride + c], c < mp: s, mp <= c < 2 mp: t, then u
+  constexpr int NBLK = GEN ? 3 : 2;
+  const int m = cols.m, mp = (m + 3) & ~3, nb = mp / 4, stride = NBLK * mp + 2;
   const int ntri = nb * (nb + 1) / 2, nt = ntri + (full_h ? nb * nb : ntri);
   const int nsl = min(kThreads / nt, R);
   const int task = threadIdx.x % nt, slice = threadIdx.x / nt;
   for (int j = threadIdx.x; j < m; j += kThreads) sidx[j] = cols.idx[j];
   int which, bi, bj;
   lobpcg_task(task, nb, full_h, which, bi, bj);
-  const int ao = 4 * bi, bo = (which ? mp : 0) + 4 * bj;
+  const int ao = 4 * bi, bo = (which ? mp : GEN ? 2 * mp : 0) + 4 * bj;
   double acc[4][4];
 #pragma unroll
   for (int e = 0; e < 4; ++e)
@@ -118,10 +144,10 @@ __global__ void __launch_bounds__(kThreads)
   for (long long tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
     const long long row0 = tl * R;
     // (consecutive threads read consecutive rows of one column: coalesced; rows and columns outside count as 0)
-    for (int e = threadIdx.x; e < 2 * mp * R; e += kThreads) {
-      const int c = e / R, r = e - c * R, cc = c < mp ? c : c - mp;
+    for (int e = threadIdx.x; e < NBLK * mp * R; e += kThreads) {
+      const int c = e / R, r = e - c * R, cc = c < mp ? c : c < 2 * mp ? c - mp : c - 2 * mp;
       double v = 0.0;
-      if (cc < m && row0 + r < n) v = (double)(c < mp ? s : t)[(long long)sidx[cc] * ld + row0 + r];
+      if (cc < m && row0 + r < n) v = (double)(c < mp ? s : (!GEN || c < 2 * mp) ? t : u)[(long long)sidx[cc] * ld + row0 + r];
       tile[r * stride + c] = v;
     }
     __syncthreads();
@@ -174,7 +200,7 @@ __global__ void __launch_bounds__(kThreads) lobpcg_reduce_kernel(const double *_
   if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
-// Step 3.  buf = sbuf (blockIdx.y = 0) or asbuf (1), 3 k physical columns each.  With the m active columns S of buf:
+// Step 3.  buf = sbuf (blockIdx.y = 0), asbuf (1) or bsbuf (2: the pencil form's B S), 3 k physical columns each.  With the m active columns S of buf:
 // column o <- (V)(S c[:, o]) for o < k (X / AX) and, with_p, column 2 k + o <- (V)(S c[:, k + o]) (P / AP); c is m x nout
 // row-major, nout = k or 2 k.  fp64, columns ascending, rounded once when stored.  Row-safe IN PLACE: a workgroup
 // stages all m columns of its R = 256 / sizeof(V) rows in LDS before it writes any of them -- X and P both come from
@@ -182,7 +208,7 @@ __global__ void __launch_bounds__(kThreads) lobpcg_reduce_kernel(const double *_
 // and the outputs g, g + G, ... in chunks of 8.  LDS: m nout doubles, then m R values.
 template <typename V>
 __global__ void __launch_bounds__(kThreads)
-    lobpcg_update_kernel(V *sbuf, V *asbuf, long long ld, long long n, LobpcgCols cols, int k, int with_p,
+    lobpcg_update_kernel(V *sbuf, V *asbuf, V *bsbuf, long long ld, long long n, LobpcgCols cols, int k, int with_p,
                          const double *__restrict__ c) {
   CFS_LOBPCG_ROUNDING
   extern __shared__ __align__(16) unsigned char lobpcg_lds[];
@@ -190,7 +216,7 @@ __global__ void __launch_bounds__(kThreads)
   const int m = cols.m, nout = with_p ? 2 * k : k;
   double *cs = reinterpret_cast<double *>(lobpcg_lds);
   V *tile = reinterpret_cast<V *>(cs + m * nout); // tile[j R + r]
-  V *buf = blockIdx.y ? asbuf : sbuf;
+  V *buf = blockIdx.y == 0 ? sbuf : blockIdx.y == 1 ? asbuf : bsbuf;
   constexpr int R = 256 / (int)sizeof(V), G = kThreads / R;
   const int r = threadIdx.x % R, g = threadIdx.x / R;
   for (int j = threadIdx.x; j < m; j += kThreads) sidx[j] = cols.idx[j];
@@ -234,10 +260,11 @@ __global__ void __launch_bounds__(kThreads)
 // cg_binv_kernel through block_apply(), as the PCG kernels form z; the rows of a trailing partial block that lie
 // outside the matrix count as 0 and are not written);  BS = 0: W_i = (V)R_i.  x, ax, w: column 0 of X, AX and W.
 // One node block per thread, grid-stride; the pairs in chunks of 8 (16 accumulators).
-template <typename V, int BS>
+// GEN, the pencil form: R_i = AX_i - theta_i BX_i with bx column 0 of BX; part[2 i + 1] stays X_i . X_i.
+template <typename V, int BS, bool GEN>
 __global__ void __launch_bounds__(kThreads)
-    lobpcg_residual_kernel(const V *__restrict__ x, const V *__restrict__ ax, V *__restrict__ w, long long ld, long long n, int k,
-                           LobpcgTheta th, const V *__restrict__ minv, long long nb, double *__restrict__ part) {
+    lobpcg_residual_kernel(const V *__restrict__ x, const V *__restrict__ ax, const V *__restrict__ bx, V *__restrict__ w, long long ld,
+                           long long n, int k, LobpcgTheta th, const V *__restrict__ minv, long long nb, double *__restrict__ part) {
   CFS_LOBPCG_ROUNDING
   constexpr int B = BS < 1 ? 1 : BS;
   __shared__ double stheta[kLobK];
@@ -260,7 +287,12 @@ __global__ void __launch_bounds__(kThreads)
           const long long gi = kb * B + i;
           rd[i] = 0.0;
           if (gi < n) {
-            const double xk = (double)x[base + gi], d = (double)ax[base + gi] - theta * xk;
+            const double xk = (double)x[base + gi];
+            double d;
+            if constexpr (GEN)
+              d = (double)ax[base + gi] - theta * (double)bx[base + gi];
+            else
+              d = (double)ax[base + gi] - theta * xk;
             rd[i] = d;
             acc[2 * e] = acc[2 * e] + d * d;
             acc[2 * e + 1] = acc[2 * e + 1] + xk * xk;
@@ -356,12 +388,17 @@ inline int lobpcg_rr(int m, const double *g, const double *hh, int k, double dro
 }
 
 // ---- launches shared by the solver and the developer entry points ----
+// (u: the third block B S of the pencil form, G = S^T u; nullptr: the standard form, G = S^T S)
 template <typename V>
-int lobpcg_gram(const V *s, const V *t, long long ld, long long n, const LobpcgCols &cols, int full_h, double *part, double *out,
-                double *g, double *hh, hipStream_t st) {
+int lobpcg_gram(const V *s, const V *t, const V *u, long long ld, long long n, const LobpcgCols &cols, int full_h, double *part,
+                double *out, double *g, double *hh, hipStream_t st) {
   const int m = cols.m;
-  hipLaunchKernelGGL((lobpcg_gram_kernel<V>), dim3(kGrid), dim3(kThreads), kLobTileBytes, st, s, t, ld, n, cols, lobpcg_gram_rows(m),
-                     full_h, part);
+  if (u)
+    hipLaunchKernelGGL((lobpcg_gram_kernel<V, true>), dim3(kGrid), dim3(kThreads), kLobTileBytes3, st, s, t, u, ld, n, cols,
+                       lobpcg_gram_rows(m), full_h, part);
+  else
+    hipLaunchKernelGGL((lobpcg_gram_kernel<V, false>), dim3(kGrid), dim3(kThreads), kLobTileBytes, st, s, t, u, ld, n, cols,
+                       lobpcg_gram_rows(m), full_h, part);
   hipLaunchKernelGGL(lobpcg_gram_reduce_kernel, dim3(2 * m * m), dim3(kThreads), 0, st, (const double *)part, out, m, full_h);
   HIPCHK(hipGetLastError());
   std::vector<double> host((size_t)2 * m * m);
@@ -377,16 +414,17 @@ int lobpcg_gram(const V *s, const V *t, long long ld, long long n, const LobpcgC
 inline size_t lobpcg_gram_part_bytes(int m) { return (size_t)2 * m * m * kGrid * sizeof(double); }
 
 template <typename V>
-int lobpcg_update(V *sbuf, V *asbuf, long long ld, long long n, const LobpcgCols &cols, int k, int with_p, const double *c_host,
-                  double *c_dev, hipStream_t st) {
+int lobpcg_update(V *sbuf, V *asbuf, V *bsbuf, long long ld, long long n, const LobpcgCols &cols, int k, int with_p,
+                  const double *c_host, double *c_dev, hipStream_t st) {
   const int nout = with_p ? 2 * k : k;
   // (c_host stays as it is until the stream has been synchronised again: the callers see to that)
   HIPCHK(hipMemcpyAsync(c_dev, c_host, (size_t)cols.m * nout * sizeof(double), hipMemcpyHostToDevice, st));
   constexpr int R = 256 / (int)sizeof(V);
   const long long ntiles = (n + R - 1) / R;
-  hipLaunchKernelGGL((lobpcg_update_kernel<V>), dim3((unsigned)std::min<long long>(ntiles, 2 * kGrid), asbuf ? 2 : 1), dim3(kThreads),
-                     (size_t)cols.m * nout * sizeof(double) + (size_t)cols.m * R * sizeof(V), st, sbuf, asbuf, ld, n, cols, k, with_p,
-                     (const double *)c_dev);
+  // (bsbuf goes with asbuf: the callers see to that)
+  hipLaunchKernelGGL((lobpcg_update_kernel<V>), dim3((unsigned)std::min<long long>(ntiles, 2 * kGrid), bsbuf ? 3 : asbuf ? 2 : 1),
+                     dim3(kThreads), (size_t)cols.m * nout * sizeof(double) + (size_t)cols.m * R * sizeof(V), st, sbuf, asbuf, bsbuf, ld, n,
+                     cols, k, with_p, (const double *)c_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -406,15 +444,16 @@ template <typename V, int BS, class Handle> int lobpcg_precond(Handle *h, Precon
 
 // step 4 and the host's look: sums[2 i] = R_i . R_i, sums[2 i + 1] = X_i . X_i (host, 2 k doubles); W_i written for the
 // bits set in `active`.  x, ax, w: column 0 of X, AX and W;  out_dev: 2 k doubles.  Waits for the stream.
-template <typename V, int BS>
-int lobpcg_residual(const V *x, const V *ax, V *w, long long ld, long long n, int k, const double *theta, unsigned active,
+// GEN: R_i = AX_i - theta_i BX_i, bx column 0 of BX (otherwise bx is not read).
+template <typename V, int BS, bool GEN = false>
+int lobpcg_residual(const V *x, const V *ax, const V *bx, V *w, long long ld, long long n, int k, const double *theta, unsigned active,
                     const V *minv, double *part, double *out_dev, double *sums, hipStream_t st) {
   constexpr int B = BS < 1 ? 1 : BS;
   const long long nb = (n + B - 1) / B;
   LobpcgTheta th;
   for (int i = 0; i < kLobK; ++i) th.theta[i] = i < k ? theta[i] : 0.0;
   th.active = active;
-  hipLaunchKernelGGL((lobpcg_residual_kernel<V, BS>), dim3(kGrid), dim3(kThreads), 0, st, x, ax, w, ld, n, k, th, minv, nb, part);
+  hipLaunchKernelGGL((lobpcg_residual_kernel<V, BS, GEN>), dim3(kGrid), dim3(kThreads), 0, st, x, ax, bx, w, ld, n, k, th, minv, nb, part);
   hipLaunchKernelGGL(lobpcg_reduce_kernel, dim3(2 * k), dim3(kThreads), 0, st, (const double *)part, out_dev);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(sums, out_dev, (size_t)2 * k * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -423,38 +462,41 @@ int lobpcg_residual(const V *x, const V *ax, V *w, long long ld, long long n, in
 }
 
 
-// cfs_hip_debug_gram_cols (cfs_hip_debug_gram: the identity list and full_h = 1)
+// cfs_hip_debug_gram_cols (cfs_hip_debug_gram: the identity list and full_h = 1); cfs_hip_debug_gram3_cols: u_dev, the
+// third block, and full_h = 0
 template <typename V>
-int debug_gram(const void *s_dev, const void *t_dev, long long ld, long long n, int m, const int *idx, int full_h, double *g,
-               double *hh, hipStream_t st) {
+int debug_gram(const void *s_dev, const void *t_dev, const void *u_dev, long long ld, long long n, int m, const int *idx, int full_h,
+               double *g, double *hh, hipStream_t st) {
   cfs_rt::DevBuf pbuf, obuf;
   int rc;
   if ((rc = pbuf.alloc(lobpcg_gram_part_bytes(m))) || (rc = obuf.alloc((size_t)2 * m * m * sizeof(double)))) return rc;
   LobpcgCols cols;
   cols.m = m;
   for (int j = 0; j < kLobM; ++j) cols.idx[j] = j < m ? idx[j] : 0;
-  return lobpcg_gram<V>((const V *)s_dev, (const V *)t_dev, ld, n, cols, full_h, (double *)pbuf.p, (double *)obuf.p, g, hh, st);
+  return lobpcg_gram<V>((const V *)s_dev, (const V *)t_dev, (const V *)u_dev, ld, n, cols, full_h, (double *)pbuf.p, (double *)obuf.p, g,
+                        hh, st);
 }
 
-// cfs_hip_debug_lobpcg_update_cols (cfs_hip_debug_lobpcg_update: the identity list, with_p = 1, no second block)
+// cfs_hip_debug_lobpcg_update_cols (cfs_hip_debug_lobpcg_update: the identity list, with_p = 1, no second block);
+// cfs_hip_debug_lobpcg_update3_cols: bs_dev, the third block
 template <typename V>
-int debug_update(void *s_dev, void *as_dev, long long ld, long long n, int k, int m, const int *idx, int with_p, const double *c,
-                 hipStream_t st) {
+int debug_update(void *s_dev, void *as_dev, void *bs_dev, long long ld, long long n, int k, int m, const int *idx, int with_p,
+                 const double *c, hipStream_t st) {
   cfs_rt::DevBuf cbuf;
   int rc;
   if ((rc = cbuf.alloc((size_t)m * 2 * k * sizeof(double)))) return rc;
   LobpcgCols cols;
   cols.m = m;
   for (int j = 0; j < kLobM; ++j) cols.idx[j] = j < m ? idx[j] : 0;
-  if ((rc = lobpcg_update<V>((V *)s_dev, (V *)as_dev, ld, n, cols, k, with_p, c, (double *)cbuf.p, st))) return rc;
+  if ((rc = lobpcg_update<V>((V *)s_dev, (V *)as_dev, (V *)bs_dev, ld, n, cols, k, with_p, c, (double *)cbuf.p, st))) return rc;
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }
 
-// cfs_hip_sym_debug_lobpcg_residual: the solver's preconditioner set-up, then step 4 alone
+// cfs_hip_sym_debug_lobpcg_residual: the solver's preconditioner set-up, then step 4 alone (bx_dev: _residual_gen)
 template <typename V, int BS, class Handle>
-int debug_residual(Handle *h, const void *x_dev, const void *ax_dev, void *w_dev, long long ld, int k, const double *theta,
-                   unsigned active, double *sums, hipStream_t st) {
+int debug_residual(Handle *h, const void *x_dev, const void *ax_dev, const void *bx_dev, void *w_dev, long long ld, int k,
+                   const double *theta, unsigned active, double *sums, hipStream_t st) {
   cfs_rt::DevBuf nout;
   Slots part;
   Precond<V, BS> pre;
@@ -463,9 +505,13 @@ int debug_residual(Handle *h, const void *x_dev, const void *ax_dev, void *w_dev
       (rc = lobpcg_precond<V, BS>(h, pre, part)))
     return rc;
   std::vector<double> hn(2 * kLobK);
-  if ((rc = lobpcg_residual<V, BS>((const V *)x_dev, (const V *)ax_dev, (V *)w_dev, ld, h->n(), k, theta, active, pre.minv(),
-                                   part.dev(), (double *)nout.p, hn.data(), st)))
-    return rc;
+  if (bx_dev)
+    rc = lobpcg_residual<V, BS, true>((const V *)x_dev, (const V *)ax_dev, (const V *)bx_dev, (V *)w_dev, ld, h->n(), k, theta, active,
+                                      pre.minv(), part.dev(), (double *)nout.p, hn.data(), st);
+  else
+    rc = lobpcg_residual<V, BS, false>((const V *)x_dev, (const V *)ax_dev, nullptr, (V *)w_dev, ld, h->n(), k, theta, active, pre.minv(),
+                                       part.dev(), (double *)nout.p, hn.data(), st);
+  if (rc) return rc;
   std::copy(hn.begin(), hn.begin() + 2 * k, sums);
   return 0;
 }
@@ -476,10 +522,14 @@ int debug_residual(Handle *h, const void *x_dev, const void *ax_dev, void *w_dev
 // stored M^-1 of BS.  Otherwise (cfs_hip_sym_lobpcg_amg, BS = 0): the residual kernel writes the raw (V)R_i into the
 // W-columns of AS -- free at that moment: the products of step 6 rewrite them before anything reads them, so no extra
 // block is held -- and form_w(W, R, ld, k, mask) enqueues W_i = M^-1 R_i for the bits of mask (column i at + i ld).
-template <typename V, int BS, class Handle, class FormW = std::nullptr_t>
-int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0,
+// GEN (cfs_hip_sym_lobpcg_gen, _gen_amg, _debug_lobpcg_gen): the pencil A x = lambda B x, B the handle hb (hb == h is
+// allowed).  A third resident block BS = B S is carried along like AS -- by products where AS is (the start block, the
+// W columns of step 6, the confirm step) and by the update kernel where AS is -- G = S^T BS, R_i = AX_i - theta_i BX_i;
+// the W-columns of BS are as free after step 4 as those of AS.  Without GEN hb and b_products_out are not looked at.
+template <typename V, int BS, bool GEN, class Handle, class FormW = std::nullptr_t>
+int lobpcg(Handle *h, Handle *hb, int k, double tol, double scale, int maxiter, int debug_iters, const void *x0_dev, long long ld0,
            double *eigenvalues, void *vectors_dev, long long ldx, double *residuals, int *nconv_out, int *iterations_out,
-           int *products_out, hipStream_t st, FormW form_w = nullptr) {
+           int *products_out, int *b_products_out, hipStream_t st, FormW form_w = nullptr) {
   using cfs_rt::DevBuf;
   constexpr bool external_w = !std::is_same<FormW, std::nullptr_t>::value;
   static_assert(!external_w || BS == 0, "an external M^-1 reads the raw residuals");
@@ -488,26 +538,31 @@ int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_it
   const long long ld = (n + Vec16<V>::W - 1) / Vec16<V>::W * Vec16<V>::W; // columns 16-byte aligned
   const int mmax = 3 * k;
   const double unit = sizeof(V) == 8 ? 0x1p-53 : 0x1p-24, drop = 64.0 * unit;
-  DevBuf sb, asb, gpart, gout, cdev, nout;
+  DevBuf sb, asb, bsb, gpart, gout, cdev, nout;
   Slots slots;
   Precond<V, BS> pre;
   int rc;
   if ((rc = sb.alloc((size_t)mmax * ld * sizeof(V) + 64)) || (rc = asb.alloc((size_t)mmax * ld * sizeof(V) + 64)) ||
-      (rc = slots.alloc(kLobSlots, st)) || (rc = gpart.alloc(lobpcg_gram_part_bytes(mmax))) ||
-      (rc = gout.alloc((size_t)2 * mmax * mmax * sizeof(double))) || (rc = cdev.alloc((size_t)mmax * 2 * k * sizeof(double))) ||
-      (rc = nout.alloc((size_t)2 * kLobK * sizeof(double))))
+      (GEN && (rc = bsb.alloc((size_t)mmax * ld * sizeof(V) + 64))) || (rc = slots.alloc(kLobSlots, st)) ||
+      (rc = gpart.alloc(lobpcg_gram_part_bytes(mmax))) || (rc = gout.alloc((size_t)2 * mmax * mmax * sizeof(double))) ||
+      (rc = cdev.alloc((size_t)mmax * 2 * k * sizeof(double))) || (rc = nout.alloc((size_t)2 * kLobK * sizeof(double))))
     return rc;
-  V *S = (V *)sb.p, *AS = (V *)asb.p;
+  V *S = (V *)sb.p, *AS = (V *)asb.p, *BSb = GEN ? (V *)bsb.p : nullptr;
   double *part = slots.dev();
   auto col = [&](V *base, int c) { return base + (long long)c * ld; };
   if ((rc = slots.zero())) return rc;
   // the preconditioner; refused before anything else happens
   if ((rc = lobpcg_precond<V, BS>(h, pre, slots))) return rc;
   const V *minv = pre.minv();
-  int products = 0, it = 0;
-  auto product = [&](int c) -> int { // AS[:, c] = A S[:, c]
+  int products = 0, b_products = 0, it = 0;
+  auto product = [&](int c) -> int { // AS[:, c] = A S[:, c]; GEN: and BS[:, c] = B S[:, c]
     ++products;
-    return h->spmv_local(col(AS, c), col(S, c), nullptr, st);
+    if (int r2 = h->spmv_local(col(AS, c), col(S, c), nullptr, st)) return r2;
+    if constexpr (GEN) {
+      ++b_products;
+      return hb->spmv_local(col(BSb, c), col(S, c), nullptr, st);
+    }
+    return 0;
   };
   // X0
   for (int c = 0; c < k; ++c) {
@@ -526,7 +581,7 @@ int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_it
   // steps 1 - 3 on the columns in `cols`
   auto rayleigh_ritz = [&](int *rank) -> int {
     const int m = cols.m;
-    int r2 = lobpcg_gram<V>(S, AS, ld, n, cols, 0, (double *)gpart.p, (double *)gout.p, G.data(), H.data(), st);
+    int r2 = lobpcg_gram<V>(S, AS, BSb, ld, n, cols, 0, (double *)gpart.p, (double *)gout.p, G.data(), H.data(), st);
     if (r2) return r2;
     if (lobpcg_rr(m, G.data(), H.data(), k, drop, theta.data(), C.data(), rank) < 0)
       return cfs_rt::set_err(CFS_HIP_ERR_INTERNAL, "lobpcg: the projected eigenproblem has entries that are not finite, or did not converge");
@@ -534,12 +589,12 @@ int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_it
     const int no = with_p ? 2 * k : k;
     for (int j = 0; j < m; ++j)
       for (int o = 0; o < no; ++o) pack[(size_t)j * no + o] = o < k ? C[(size_t)j * k + o] : (j < k ? 0.0 : C[(size_t)j * k + o - k]);
-    return lobpcg_update<V>(S, AS, ld, n, cols, k, with_p, pack.data(), (double *)cdev.p, st);
+    return lobpcg_update<V>(S, AS, BSb, ld, n, cols, k, with_p, pack.data(), (double *)cdev.p, st);
   };
   // step 4 and the host's look at the norms: res[i] = ||R_i|| / ||X_i||
   auto norms = [&](unsigned wmask) -> int {
-    int r2 = lobpcg_residual<V, BS>((const V *)S, (const V *)AS, col(external_w ? AS : S, k), ld, n, k, theta.data(), wmask, minv, part,
-                                    (double *)nout.p, hn.data(), st);
+    int r2 = lobpcg_residual<V, BS, GEN>((const V *)S, (const V *)AS, (const V *)BSb, col(external_w ? AS : S, k), ld, n, k, theta.data(),
+                                         wmask, minv, part, (double *)nout.p, hn.data(), st);
     if (r2) return r2;
     if constexpr (external_w)
       if (wmask && (r2 = form_w(col(S, k), (const V *)col(AS, k), ld, k, wmask))) return r2;
@@ -561,7 +616,10 @@ int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_it
     int rank = 0;
     if ((rc = rayleigh_ritz(&rank))) return rc;
     if (rank == k) break;
-    if (attempt == 2) return cfs_rt::set_err(CFS_HIP_ERR_ARG, "lobpcg: the start block does not have rank k");
+    if (attempt == 2)
+      return cfs_rt::set_err(CFS_HIP_ERR_ARG, GEN ? "lobpcg_gen: the start block does not have rank k in the B inner product: B may not be "
+                                                    "positive definite"
+                                                  : "lobpcg: the start block does not have rank k");
     for (int c = rank; c < k; ++c) {
       hipLaunchKernelGGL((lobpcg_fill_kernel<V>), dim3(kGrid), dim3(kThreads), 0, st, col(S, c), n, (long long)(k * (attempt + 1) + c) * n);
       if ((rc = product(c))) return rc;
@@ -624,6 +682,7 @@ int lobpcg(Handle *h, int k, double tol, double scale, int maxiter, int debug_it
   if (nconv_out) *nconv_out = nconv;
   if (iterations_out) *iterations_out = it;
   if (products_out) *products_out = products;
+  if (GEN && b_products_out) *b_products_out = b_products;
   return 0;
 }
 

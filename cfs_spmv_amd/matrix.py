@@ -515,6 +515,15 @@ class SymMatrix:
             X = torch.as_strided(X, (self.nrows(), k), (1, ld))
         return w, X, {"nconv": nconv.value, "restarts": restarts.value, "products": products.value, "residuals": res}
 
+    def _pencil_b(self, B):
+        """the B of a pencil (A, B): a SymMatrix of this matrix's n and dtype, else ValueError -- before any device work"""
+        if not isinstance(B, SymMatrix):
+            raise ValueError(f"B must be a SymMatrix (a diagonal B is a handle like any other), not {type(B).__name__}")
+        if B.nrows() != self.nrows() or B.dtype != self.dtype:
+            raise ValueError(f"B must have the n and the dtype of A: B is {B.nrows()} x {B.nrows()} {np.dtype(B.dtype).name}, "
+                             f"A {self.nrows()} x {self.nrows()} {np.dtype(self.dtype).name}")
+        return B
+
     def lobpcg(self, k=6, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, stream=None):
         """the k smallest (algebraic) eigenpairs inside the library (cfs_hip_sym_lobpcg): LOBPCG on blocks of 3 k
         device columns with the preconditioners of pcg() -- precond = "none", "jacobi" or "block_jacobi" (block one
@@ -527,7 +536,22 @@ class SymMatrix:
         precond = G, an Amg of this matrix (self.amg(...)): one column-blocked multigrid cycle per iteration forms W on the
         pairs still active (cfs_hip_sym_lobpcg_amg); info then also has "cycles", the cycles applied, one per column.
         The name "amg" alone is a ValueError here -- this method has no argument for the hierarchy -- and
-        solver.lobpcg_native(A, k, precond="amg", amg=G) is the spelling by name."""
+        solver.lobpcg_native(A, k, precond="amg", amg=G) is the spelling by name.
+        The pencil A x = lambda B x: lobpcg_gen(B, ...) below -- this method keeps its argument list."""
+        return SymMatrix._lobpcg(self, None, k, precond, block, tol, scale, maxiter, x0, stream)
+
+    def lobpcg_gen(self, B, k=6, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, stream=None):
+        """the k smallest eigenpairs of the PENCIL A x = lambda B x (cfs_hip_sym_lobpcg_gen; with precond = G, an Amg of
+        this matrix, cfs_hip_sym_lobpcg_gen_amg) -- K x = lambda M x with a mass matrix.  B: a SymMatrix of the same n and
+        dtype (else ValueError, before any device work), symmetric positive definite; B = self is allowed, and a lumped
+        (diagonal) B is a handle like any other.  Every other argument and the return value as for lobpcg().  Pair i has
+        converged when ||A x_i - theta_i B x_i|| / ||x_i|| <= tol scale (scale still an estimate of ||A||_2); the columns
+        of X are B-orthonormal; the preconditioner is still built from A; info also has "b_products", the products with B
+        ("products" counts those with A).  solver.lobpcg_native(A, k, ..., B=B) is the same call."""
+        return SymMatrix._lobpcg(self, SymMatrix._pencil_b(self, B), k, precond, block, tol, scale, maxiter, x0, stream)
+
+    def _lobpcg(self, B, k, precond, block, tol, scale, maxiter, x0, stream):
+        """lobpcg() (B = None) and lobpcg_gen() behind their argument lists"""
         import torch
         amg = precond if isinstance(precond, Amg) else None
         if amg is not None:
@@ -559,7 +583,21 @@ class SymMatrix:
             x0buf = torch.zeros(k * ld, dtype=tdt, device="cuda")
             torch.as_strided(x0buf, (n, k), (1, ld)).copy_(x0)
         dp = C.POINTER(C.c_double)
-        nconv, iterations, products = C.c_int(), C.c_int(), C.c_int()
+        nconv, iterations, products, b_products = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        if B is not None:
+            before = amg.column_cycles() if amg is not None else 0
+            tail = (float(tol), float(scale), int(maxiter), _ptr(x0buf) if x0buf is not None else None, ld, w.ctypes.data_as(dp),
+                    _ptr(X), ld, res.ctypes.data_as(dp), C.byref(nconv), C.byref(iterations), C.byref(products), C.byref(b_products),
+                    _stream_ptr(stream))
+            if amg is not None:
+                _lib.check(_lib.load().cfs_hip_sym_lobpcg_gen_amg(self._h, B._h, amg._a, k, *tail))
+            else:
+                _lib.check(_lib.load().cfs_hip_sym_lobpcg_gen(self._h, B._h, k, block_rows, *tail))
+            info = {"nconv": nconv.value, "iterations": iterations.value, "products": products.value, "residuals": res,
+                    "b_products": b_products.value}
+            if amg is not None:
+                info["cycles"] = amg.column_cycles() - before
+            return w, torch.as_strided(X, (n, k), (1, ld)), info
         if amg is not None:
             before = amg.column_cycles()
             _lib.check(_lib.load().cfs_hip_sym_lobpcg_amg(
@@ -576,10 +614,12 @@ class SymMatrix:
         X = torch.as_strided(X, (n, k), (1, ld))
         return w, X, {"nconv": nconv.value, "iterations": iterations.value, "products": products.value, "residuals": res}
 
-    def debug_lobpcg(self, k, block_rows, iters, x0=None, stream=None):
+    def debug_lobpcg(self, k, block_rows, iters, x0=None, stream=None, B=None):
         """developer / test: iteration 0 and `iters` more of the solver's own kernels, every pair active
-        (cfs_hip_sym_debug_lobpcg).  Returns (theta, X, resnorms)."""
+        (cfs_hip_sym_debug_lobpcg; with B, the pencil form cfs_hip_sym_debug_lobpcg_gen).  Returns (theta, X, resnorms)."""
         import torch
+        if B is not None:
+            self._pencil_b(B)
         tdt = torch.float64 if self.dtype == np.float64 else torch.float32
         n = self.nrows()
         per = 16 // self.dtype.itemsize
@@ -591,9 +631,12 @@ class SymMatrix:
             x0buf = torch.zeros(k * ld, dtype=tdt, device="cuda")
             torch.as_strided(x0buf, (n, k), (1, ld)).copy_(x0)
         dp = C.POINTER(C.c_double)
-        _lib.check(_lib.load().cfs_hip_sym_debug_lobpcg(
-            self._h, int(k), int(block_rows), _ptr(x0buf) if x0buf is not None else None, ld, int(iters),
-            theta.ctypes.data_as(dp), _ptr(X), ld, res.ctypes.data_as(dp), _stream_ptr(stream)))
+        tail = (int(k), int(block_rows), _ptr(x0buf) if x0buf is not None else None, ld, int(iters), theta.ctypes.data_as(dp), _ptr(X),
+                ld, res.ctypes.data_as(dp), _stream_ptr(stream))
+        if B is not None:
+            _lib.check(_lib.load().cfs_hip_sym_debug_lobpcg_gen(self._h, B._h, *tail))
+        else:
+            _lib.check(_lib.load().cfs_hip_sym_debug_lobpcg(self._h, *tail))
         return theta, torch.as_strided(X, (n, k), (1, ld)), res
 
     def debug_lobpcg_amg(self, amg, k, iters, x0=None, stream=None):

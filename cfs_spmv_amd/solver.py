@@ -663,7 +663,13 @@ def _lobpcg_minv(A, precond, block, amg=None):
     raise ValueError(f"unknown preconditioner {precond!r}: 'none', 'jacobi' or 'block_jacobi'")
 
 
-def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, iters=None, amg=None):
+def _lobpcg_pencil_b(A, B):
+    """the ValueError of a B that is not a SymMatrix of A's n and dtype, before any device work"""
+    if B is not None:
+        A._pencil_b(B)
+
+
+def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, iters=None, amg=None, B=None):
     """the k smallest eigenpairs by LOBPCG, host-driven: the recurrence of cfs_hip_sym_lobpcg (Gram matrices of
     S = [X | W | P_act] in fp64, the Rayleigh-Ritz step with its drop rule, X, P, AX, AP updated implicitly and rounded
     to the value type when stored, W = M^-1 R in fp64, soft locking, the confirm step) with torch operations on A's
@@ -671,10 +677,14 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
     cfs_hip_sym_debug_lobpcg, iteration 0 and `iters` more with every pair active, no convergence test.  Returns
     (w, X, info) like SymMatrix.lobpcg; with iters, info["residuals"] are those of the implicit AX.
     precond="amg", amg=G: the model of cfs_hip_sym_lobpcg_amg -- W_i one cycle of G on the stored R_i, for the pairs the
-    native loop forms it for (those active, as its wmask); info["cycles"] counts them."""
+    native loop forms it for (those active, as its wmask); info["cycles"] counts them.
+    B = a SymMatrix of A's n and dtype: the model of cfs_hip_sym_lobpcg_gen(_amg), the pencil A x = lambda B x -- a third
+    block BS = B S kept by products and updates as AS is, G = S^T BS, R = AX - theta BX, the confirm step recomputes AX and
+    BX; X comes out B-orthonormal; info["b_products"] counts the products with B."""
     import numpy as np
     import torch
     _lobpcg_amg_args(precond, amg)
+    _lobpcg_pencil_b(A, B)
     n = A.nrows()
     tdt = torch.float64 if A.dtype == np.float64 else torch.float32
     unit = 2.0 ** -53 if A.dtype == np.float64 else 2.0 ** -24
@@ -689,13 +699,17 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
     dev = "cuda" if x0 is None else x0.device
     S = torch.zeros((3 * k, n), dtype=tdt, device=dev)   # row c = physical column c: X | W | P
     AS = torch.zeros((3 * k, n), dtype=tdt, device=dev)
+    BS = torch.zeros((3 * k, n), dtype=tdt, device=dev) if B is not None else None
     S[:k] = (torch.from_numpy(default_x0(n, k, A.dtype)).to(dev) if x0 is None else x0.to(tdt)).T
-    products = 0
+    products = b_products = 0
 
     def product(c):
-        nonlocal products
+        nonlocal products, b_products
         A.dense_vector_multiply(AS[c], S[c])          # the hot path
         products += 1
+        if B is not None:
+            B.dense_vector_multiply(BS[c], S[c])
+            b_products += 1
 
     for c in range(k):
         product(c)
@@ -705,7 +719,8 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
         nonlocal theta
         idx = torch.tensor(cols, device=dev)
         Sa, ASa = S[idx].double(), AS[idx].double()
-        G, H = (Sa @ Sa.T).cpu().numpy(), (Sa @ ASa.T).cpu().numpy()
+        BSa = BS[idx].double() if B is not None else Sa
+        G, H = (Sa @ BSa.T).cpu().numpy(), (Sa @ ASa.T).cpu().numpy()
         theta, C, rank = lobpcg_rr(G, H, k, 64.0 * unit)
         Ct = torch.from_numpy(C).to(dev)
         Cp = Ct.clone()
@@ -713,6 +728,10 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
         X, AX = (Ct.T @ Sa).to(tdt), (Ct.T @ ASa).to(tdt)
         if len(cols) > k:
             S[2 * k:], AS[2 * k:] = (Cp.T @ Sa).to(tdt), (Cp.T @ ASa).to(tdt)
+        if B is not None:
+            if len(cols) > k:
+                BS[2 * k:] = (Cp.T @ BSa).to(tdt)
+            BS[:k] = (Ct.T @ BSa).to(tdt)
         S[:k], AS[:k] = X, AX
         return rank
 
@@ -721,7 +740,7 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
     def norms(wcols=None):
         nonlocal cycles
         X, AX = S[:k].double(), AS[:k].double()
-        R = AX - torch.from_numpy(theta).to(dev)[:, None] * X
+        R = AX - torch.from_numpy(theta).to(dev)[:, None] * (BS[:k].double() if B is not None else X)
         if amg is None:
             S[k:2 * k] = apply(R.T).T.to(tdt)
         else:  # (the native loop's wmask: every pair, or those active)
@@ -735,7 +754,8 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
         if rank == k:
             break
         if attempt == 2:
-            raise ValueError("lobpcg: the start block does not have rank k")
+            raise ValueError("lobpcg: the start block does not have rank k" +
+                             (" in the B inner product: B may not be positive definite" if B is not None else ""))
         fill = default_x0(n, k * (attempt + 2), A.dtype)
         for c in range(rank, k):
             S[c] = torch.from_numpy(fill[:, k * (attempt + 1) + c]).to(dev)
@@ -778,17 +798,20 @@ def lobpcg(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, 
     info = {"nconv": nconv, "iterations": it, "products": products, "residuals": res.copy()}
     if amg is not None:
         info["cycles"] = cycles
+    if B is not None:
+        info["b_products"] = b_products
     return theta.copy(), S[:k].T.clone(), info
 
 
-def lobpcg_native(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, amg=None):
+def lobpcg_native(A, k, precond="jacobi", block=3, tol=1e-10, scale=None, maxiter=500, x0=None, amg=None, B=None):
     """the same iteration inside the library (cfs_hip_sym_lobpcg): the Gram matrices by one small-SYRK kernel, the
     update in place, residual and preconditioner in one kernel; two host looks per iteration.  Returns (w, X, info),
-    like lobpcg().  precond="amg", amg=G: cfs_hip_sym_lobpcg_amg, W by one column-blocked cycle of G per iteration."""
+    like lobpcg().  precond="amg", amg=G: cfs_hip_sym_lobpcg_amg, W by one column-blocked cycle of G per iteration.
+    B: the pencil A x = lambda B x (cfs_hip_sym_lobpcg_gen, _gen_amg)."""
     _lobpcg_amg_args(precond, amg)
-    if amg is not None:
-        return A.lobpcg(k=k, precond=amg, block=block, tol=tol, scale=scale, maxiter=maxiter, x0=x0)
-    return A.lobpcg(k=k, precond=precond, block=block, tol=tol, scale=scale, maxiter=maxiter, x0=x0)
+    _lobpcg_pencil_b(A, B)
+    kw = dict(k=k, precond=amg if amg is not None else precond, block=block, tol=tol, scale=scale, maxiter=maxiter, x0=x0)
+    return A.lobpcg(**kw) if B is None else A.lobpcg_gen(B, **kw)
 
 
 def cg_sharded(S, row_splits, b_block, tol=1e-10, maxiter=1000):

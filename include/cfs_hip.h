@@ -1022,6 +1022,68 @@ int cfs_hip_debug_lobpcg_update_cols(void *s_dev, void *as_dev, long long ld, lo
 int cfs_hip_sym_debug_lobpcg_residual(cfs_hip_sym_t h, int block_rows, const void *x_dev, const void *ax_dev, void *w_dev,
                                       long long ld, int k, const double *theta, unsigned active, double *sums,
                                       void *stream);
+/* LOBPCG for the GENERALIZED problem A x = lambda B x: the k <= CFS_HIP_LOBPCG_MAX_K SMALLEST eigenpairs of the pencil
+ * (A, B) -- K x = lambda M x with a mass matrix (vibration), K x = lambda K_g x with a definite geometric stiffness
+ * (buckling).  A (the handle h) is symmetric; B is symmetric POSITIVE DEFINITE and held by a handle of its own, hb, with
+ * h's n, value type and device.  hb == h is allowed (every theta is 1); a diagonal (lumped) B is a handle like any other.
+ * No factorisation of B: B enters by products only, which keeps its sparsity.
+ * This is the iteration of cfs_hip_sym_lobpcg -- the same templates, a compile-time switch and a third block -- on THREE
+ * resident blocks of 3 k columns, S = [X | W | P], AS = A S and BS = B S, all in the value type V, every dot product and
+ * scalar fp64, no contracted multiply-adds:
+ *   1. G = S^T (BS) and H = S^T (AS), upper triangles, in ONE pass over the three blocks: the Gram kernel stages rows
+ *      of all 3 m columns and a G task takes its second operand from the BS part of the row; the same 4 x 4 register
+ *      blocks, task table, fixed-order slice and workgroup sums as cfs_hip_sym_lobpcg.  First host look.
+ *   2. Rayleigh-Ritz on the host, unchanged: it already solves the pencil (H, G).  A column whose G_jj = s_j^T B s_j is
+ *      not finite and > 0 is dropped.
+ *   3. X <- (V)(S C), P <- (V)(S C'), AX, AP and BX <- (V)(BS C), BP <- (V)(BS C') in ONE launch, with the order and
+ *      the rounding of step 3 of cfs_hip_sym_lobpcg for each of the three blocks: BX is carried along implicitly like AX.
+ *   4. R_i = AX_i - theta_i BX_i in fp64 from the stored values; the sums R_i . R_i and X_i . X_i; W_i = (V)(M^-1 R_i)
+ *      with M built from A exactly as cfs_hip_sym_lobpcg builds it (block_rows 0, 1, 2, 3, 4, 6), or by one column-
+ *      blocked multigrid cycle of `a`, a hierarchy of A, on the raw R_i (cfs_hip_sym_lobpcg_gen_amg).  Second host look.
+ *      Pair i has converged when ||A x_i - theta_i B x_i||_2 / ||x_i||_2 <= tol scale; scale: the caller's estimate of
+ *      ||A||_2, as there.  Soft locking as there.
+ *   5. When all k residuals pass, AX = A X and BX = B X are both recomputed (2 k products) and step 4 repeated.
+ *   6. AW_i = A W_i and BW_i = B W_i for the active pairs.
+ * Iteration 0 is steps 1 - 4 on S = X0 with k products of each matrix.  *products counts the products with A,
+ * *b_products those with B (both nullable, as are nconv and iterations).  Device memory held during the call:
+ * (9 k + 1) n values (without the inverse diagonal for block_rows 0 and the multigrid form) plus the scalars.
+ * The returned columns are B-ORTHONORMAL, X^T B X = I up to rounding (not of unit 2-norm).  eigenvalues ascending.
+ * residuals: ||A x_i - theta_i B x_i||_2 / ||x_i||_2 in fp64 from the returned, stored x_i and FRESH products with both
+ * matrices.  All other arguments as for cfs_hip_sym_lobpcg.  The solve is bit-reproducible when both handles are
+ * CFS_HIP_FLAG_DETERMINISTIC.
+ * Refusals, nothing written and the counters zeroed, in this order: those of cfs_hip_sym_lobpcg (of _lobpcg_amg for the
+ * multigrid form) with hb among the null checks; where the handles are first read, CFS_HIP_ERR_ARG for an hb whose n or
+ * value type differs from h's or which lives on another device; CFS_HIP_ERR_UNSUPPORTED for a shard or a multi-device
+ * handle on either side; then the remaining checks of cfs_hip_sym_lobpcg.  A start block that still has rank < k in
+ * the B inner product after the two refills: CFS_HIP_ERR_ARG, "B may not be positive definite" (with B = -I every G_jj
+ * is negative and this is what fires).  An indefinite B is out of scope.
+ * cfs_hip_sym_debug_lobpcg_gen: the counterpart of cfs_hip_sym_debug_lobpcg, resnorms = ||AX_i - theta_i BX_i|| /
+ * ||X_i|| of the implicitly updated blocks.                                                                      */
+int cfs_hip_sym_lobpcg_gen(cfs_hip_sym_t h, cfs_hip_sym_t hb, int k, int block_rows, double tol, double scale,
+                           int maxiter, const void *x0_dev, long long ld0, double *eigenvalues, void *vectors_dev,
+                           long long ld, double *residuals, int *nconv, int *iterations, int *products,
+                           int *b_products, void *stream);
+int cfs_hip_sym_lobpcg_gen_amg(cfs_hip_sym_t h, cfs_hip_sym_t hb, cfs_hip_amg_t a, int k, double tol, double scale,
+                               int maxiter, const void *x0_dev, long long ld0, double *eigenvalues, void *vectors_dev,
+                               long long ld, double *residuals, int *nconv, int *iterations, int *products,
+                               int *b_products, void *stream);
+int cfs_hip_sym_debug_lobpcg_gen(cfs_hip_sym_t h, cfs_hip_sym_t hb, int k, int block_rows, const void *x0_dev,
+                                 long long ld0, int iters, double *theta, void *vectors_dev, long long ld,
+                                 double *resnorms, void *stream);
+/* The three kernels in the forms the pencil solver launches them in; arguments, checks and their order as for the
+ * two-block forms above, with the third block among the null, geometry, overlap and device checks.
+ * cfs_hip_debug_gram3_cols: G = S^T BS and H = S^T AS on the m listed columns of three n x 48 blocks, the solver's
+ * form (upper triangles summed, the lower ones their mirror images).
+ * cfs_hip_debug_lobpcg_update3_cols: step 3 on three blocks of 3 k columns in one launch, the same c and idx for each.
+ * cfs_hip_sym_debug_lobpcg_residual_gen: step 4 with R_i = AX_i - theta_i BX_i; sums[2 i + 1] is still X_i . X_i;
+ * the columns of W overlap none of X, AX, BX.                                                                    */
+int cfs_hip_debug_gram3_cols(const void *s_dev, const void *as_dev, const void *bs_dev, long long ld, long long n, int m,
+                             const int *idx, int value_bytes, double *g, double *hh, void *stream);
+int cfs_hip_debug_lobpcg_update3_cols(void *s_dev, void *as_dev, void *bs_dev, long long ld, long long n, int k, int m,
+                                      const int *idx, int with_p, const double *c, int value_bytes, void *stream);
+int cfs_hip_sym_debug_lobpcg_residual_gen(cfs_hip_sym_t h, int block_rows, const void *x_dev, const void *ax_dev,
+                                          const void *bx_dev, void *w_dev, long long ld, int k, const double *theta,
+                                          unsigned active, double *sums, void *stream);
 
 /* ---- sharded operation: y_block = local rows; contributions to rows owned
  *      by lower ranks are packed into send_buf (device), exchanged by the

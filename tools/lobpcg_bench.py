@@ -24,8 +24,18 @@ interleaved, AMG_ROUNDS = 3 rounds, the best of each, as tools/cg_bench.py does.
 region and its set-up seconds stand beside the numbers.  Separately, one blocked apply of k columns
 (cfs_hip_amg_apply_cols) against k one-column applies on the same hierarchy.  A solve stops at AMG_MAXITER = 2000
 iterations; nconv says whether it got there.  Prints one JSON line and writes it to profiles/lobpcg_amg_bench.json.
+
+--mass: the pencil solver A x = lambda B x (cfs_hip_sym_lobpcg_gen) on its own.  B is the consistent mass matrix
+(lap2dNXxNY: M_ny kron M_nx, M = tridiag(1, 4, 1) / 6; any other matrix: the pattern of A with those weights, mass_of())
+or its lumped diagonal.  Per matrix (default lap2d400x330, pwtk, Flan_1565; fp64) and k = 4, 16, on the SAME handle of A:
+the microseconds per iteration of the pencil solver against the standard solver of the same build (Jacobi, tol = 0, the
+wall time of 2 M iterations minus that of M, M = MASS_M = 20, the best of MASS_ROUNDS = 3 runs each), beside
+1 + nnz(B) / nnz(A) and 1 + the SpMV time of B over that of A; and, with the consistent mass, wall time, iterations and
+products to tol MASS_TOL = 1e-8 with Jacobi, block Jacobi and multigrid, the runs interleaved, the best of the rounds.
+Prints one JSON line and writes it to profiles/lobpcg_gen_bench.json, the run count in it.
 usage: python tools/lobpcg_bench.py [matrix[:scale] ...]
-       python tools/lobpcg_bench.py --amg [--rounds R] [--k 4,16] [matrix[:scale] | lap2dNXxNY ...]"""
+       python tools/lobpcg_bench.py --amg [--rounds R] [--k 4,16] [matrix[:scale] | lap2dNXxNY ...]
+       python tools/lobpcg_bench.py --mass [--rounds R] [--k 4,16] [matrix[:scale] | lap2dNXxNY ...]"""
 import csv, ctypes as C, glob, json, os, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -241,19 +251,119 @@ def main_amg(specs, rounds, ks):
         f.write(line + "\n")
 
 
+MASS_TOL, MASS_ROUNDS, MASS_MAXITER, MASS_M = 1e-8, 3, 2000, 20
+
+
+def mass_of(spec, n, rp, ci, kind):
+    """the mass matrix of the benchmark as CSR: for lap2dNXxNY the consistent mass M_ny kron M_nx, M = tridiag(1, 4, 1) / 6;
+    for any other matrix the PATTERN of A with the same weights -- 1 / 6 off the diagonal and on the diagonal twice the sum
+    of the row's other entries (4 / 6 against 1 / 6 + 1 / 6), at least 1 / 6: strictly dominant, so positive definite.
+    kind = "lumped": the diagonal of its row sums"""
+    import scipy.sparse as sp
+    name = spec.partition(":")[0]
+    if name.startswith("lap2d"):
+        nx, ny = (int(v) for v in name[5:].split("x"))
+        M = lambda k: sp.diags([np.ones(k - 1), 4 * np.ones(k), np.ones(k - 1)], [-1, 0, 1]) / 6.0
+        B = sp.kron(M(ny), M(nx)).tocsr()
+    else:
+        P = sp.csr_matrix((np.ones(len(ci)), ci, rp), shape=(n, n))
+        P = ((P + P.T) > 0).astype(np.float64)  # (the pattern, symmetric whichever triangles the generator stores)
+        P.setdiag(0.0)
+        P.eliminate_zeros()
+        off = np.asarray(P.sum(axis=1)).ravel()
+        B = ((P + sp.diags(np.maximum(2.0 * off, 1.0))) / 6.0).tocsr()
+    if kind == "lumped":
+        B = sp.diags(np.asarray(B.sum(axis=1)).ravel()).tocsr()
+    B.sort_indices()
+    return B.indptr.astype(np.int32), B.indices.astype(np.int32), B.data.astype(np.float64)
+
+
+def main_mass(specs, rounds, ks):
+    """--mass: the pencil solver (cfs_hip_sym_lobpcg_gen) against the standard solver of the same build on the same handle"""
+    out = {"tolerance": MASS_TOL, "rounds": rounds, "maxiter": MASS_MAXITER, "dtype": "float64", "iterations_timed": [MASS_M, 2 * MASS_M]}
+    for spec in specs:
+        n, rp, ci, va = amg_matrix(spec)
+        A = cfs.SymMatrix(n, rp, ci, va)
+        scale = abs(float(A.eigs(k=1, which="LM", tol=1e-3, vectors=False)[0][0]))
+        x = torch.from_numpy(synth.make_x(n, 11)).cuda()
+        y = torch.empty_like(x)
+        spmv_us = lambda H: best(lambda: [H.dense_vector_multiply(y, x) for _ in range(200)], rounds) / 200 * 1e6
+        res = {"n": n, "nnz_a": int(rp[-1]), "scale": scale, "spmv_a_us": round(spmv_us(A), 2)}
+        G = None
+        for kind in ("consistent", "lumped"):
+            brp, bci, bva = mass_of(spec, n, rp, ci, kind)
+            B = cfs.SymMatrix(n, brp, bci, bva)
+            r = {"nnz_b": int(brp[-1]), "one_plus_nnz_ratio": round(1.0 + int(brp[-1]) / int(rp[-1]), 4), "spmv_b_us": round(spmv_us(B), 2)}
+            r["one_plus_spmv_ratio"] = round(1.0 + r["spmv_b_us"] / res["spmv_a_us"], 4)
+            for k in ks:
+                # time per iteration: tol = 0, no pair converges, every iteration carries 3 k columns (and k products of each matrix)
+                per = {}
+                for label, extra in (("standard", {}), ("pencil", {"B": B})):
+                    kw = dict(k=k, precond="jacobi", tol=0.0, scale=1.0, **extra)
+                    t1 = best(lambda: lobpcg_native(A, maxiter=MASS_M, **kw), rounds)
+                    t2 = best(lambda: lobpcg_native(A, maxiter=2 * MASS_M, **kw), rounds)
+                    per[label] = (t2 - t1) / MASS_M * 1e6
+                r[f"k{k}_us_per_iteration"] = {"standard": round(per["standard"], 2), "pencil": round(per["pencil"], 2),
+                                               "pencil_over_standard": round(per["pencil"] / per["standard"], 4)}
+                if kind != "consistent":
+                    continue
+                # time to tolerance of the pencil solver with each preconditioner, the runs interleaved
+                kw = dict(k=k, tol=MASS_TOL, scale=scale, maxiter=MASS_MAXITER)
+                if G is None:
+                    G = A.amg(rp, ci, va)
+                loops = {"jacobi": lambda: A.lobpcg_gen(B, precond="jacobi", **kw)[2],
+                         "block3": lambda: A.lobpcg_gen(B, precond="block_jacobi", block=3, **kw)[2],
+                         "amg": lambda: A.lobpcg_gen(B, precond=G, **kw)[2]}
+                if n % 3:  # (no node blocks of 3 rows)
+                    del loops["block3"]
+                best_of = {}
+                for _ in range(rounds):
+                    for label, fn in loops.items():
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        info = fn()
+                        torch.cuda.synchronize()
+                        t = time.perf_counter() - t0
+                        if t < best_of.get(label, (float("inf"),))[0]:
+                            best_of[label] = (t, info)
+                for label, (t, info) in best_of.items():
+                    r[f"k{k}_{label}"] = {"ms_to_tolerance": round(t * 1e3, 3), "nconv": info["nconv"], "iterations": info["iterations"],
+                                          "products": info["products"], "b_products": info["b_products"], "cycles": info.get("cycles", 0),
+                                          "us_per_iteration": round(t * 1e6 / max(1, info["iterations"]), 2),
+                                          "max_residual_over_scale": float(np.max(info["residuals"]) / scale)}
+            B.close()
+            res[kind] = r
+        if G is not None:
+            G.close()
+        A.close()
+        out[spec] = res
+        print(json.dumps({spec: res}), flush=True)
+    line = json.dumps(out)
+    print(line)
+    with open(os.path.join(ROOT, "profiles", "lobpcg_gen_bench.json"), "w") as f:
+        f.write(line + "\n")
+
+
+def _opts(args, rounds, ks):
+    if "--rounds" in args:
+        i = args.index("--rounds")
+        rounds = int(args[i + 1])
+        del args[i:i + 2]
+    if "--k" in args:
+        i = args.index("--k")
+        ks = tuple(int(v) for v in args[i + 1].split(","))
+        del args[i:i + 2]
+    return args, rounds, ks
+
+
 if __name__ == "__main__":
     if sys.argv[1:2] == ["--child"]:
         child(sys.argv[2], int(sys.argv[3]))
+    elif "--mass" in sys.argv[1:]:
+        args, rounds, ks = _opts([a for a in sys.argv[1:] if a != "--mass"], MASS_ROUNDS, (4, 16))
+        main_mass(args or ["lap2d400x330", "pwtk", "Flan_1565"], rounds, ks)
     elif "--amg" in sys.argv[1:]:
-        args, rounds, ks = [a for a in sys.argv[1:] if a != "--amg"], AMG_ROUNDS, (4, 16)
-        if "--rounds" in args:
-            i = args.index("--rounds")
-            rounds = int(args[i + 1])
-            del args[i:i + 2]
-        if "--k" in args:
-            i = args.index("--k")
-            ks = tuple(int(v) for v in args[i + 1].split(","))
-            del args[i:i + 2]
+        args, rounds, ks = _opts([a for a in sys.argv[1:] if a != "--amg"], AMG_ROUNDS, (4, 16))
         main_amg(args or ["lap2d400x330", "lap2d800x660", "pwtk", "ldoor", "Flan_1565"], rounds, ks)
     else:
         main(sys.argv[1:] or ["pwtk", "ldoor", "Flan_1565"])
